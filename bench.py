@@ -7,9 +7,13 @@ resident in HBM.  One process per GPU (torch.distributed / RCCL only for the bar
 max-over-ranks reduction — worlds are independent, there is no collective on the step path);
 rank r simulates global worlds [r*16000, (r+1)*16000) (weak scaling).
 
-Prints ONE JSON line (rank 0) with the bench contract fields plus
-  "roofline":     dominant kernel vs the HBM roofline (algorithmic bytes / HIP-event kernel time)
-  "cpu_baseline": the CPU oracle (own restatement, NOT the Madrona CPU backend) on the host cores
+Prints ONE JSON line (rank 0) with the bench contract fields.  A plain run does only what that headline needs: set-up,
+warm-up (and the untimed preroll below), the timed steps, and with --dump-outputs DIR the last step's outputs as .npy files.
+--full adds, as separate work:
+  "ms_per_step_percentiles": host wall time of every timed step
+  "roofline":     dominant kernel vs the HBM roofline (algorithmic bytes / HIP-event kernel time of every P-th timed step)
+  "device_status": the simulator's status words, checked for dropped broadphase pairs
+  "cpu_baseline": the CPU oracle (own restatement, NOT the Madrona CPU backend) on the host cores (not with --no-cpu-baseline)
 
 Two ways to get N ranks (the reference is single-GPU, src/mgr.hpp:18 `gpuID`; the ranks are this build's extension):
   * `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` — RANK / LOCAL_RANK / WORLD_SIZE come
@@ -91,6 +95,109 @@ def cpu_baseline(seconds_budget=45.0, steps_of=1920):
             "sample": f"{nworlds} worlds x {steps} of {steps_of} steps (scripts/cpu_benchmark.py args: BASELINE configs[0]"
                       f"{'' if steps >= steps_of else ', cut at the time budget'}), own CPU restatement "
                       f"(oracle/), {cores} threads over worlds; not the Madrona CPU backend"}
+
+
+def roofline_figures(sim, A, N, args, kms, nsamp, P, dt, skip_obs):
+    """--full: the dominant kernel against the HBM roofline, from the HIP-event kernel times of the timed steps."""
+    # Roofline position of the dominant kernel.  A step is two kernels: k_physics (persistent: movement / actions,
+    # 4 XPBD substeps, rewards, per-step reset) and k_observe.  Durations are HIP events on the launch stream
+    # (hs_set_profiling); profiles/ holds the rocprofv3 --kernel-trace --stats summary of this command, whose
+    # per-kernel averages agree with them.  Only kernels that were launched are listed.
+    names = {"physics": "k_physics", "observe": "k_observe"}
+    per_stage = {}
+    for n in kms:
+        avg_ms = kms[n] / max(nsamp, 1)
+        total_bytes, per_world = algorithmic_bytes(sim, A, n)
+        ach = total_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        per_stage[n] = {"kernel": names[n], "avg_ms": avg_ms, "algorithmic_bytes_per_world_step": per_world,
+                        "achieved_GBps": ach, "frac": ach / HBM_PEAK_GBPS}
+        assert 0.0 <= per_stage[n]["frac"] <= 1.0, f"roofline fraction of {n} out of range: {per_stage[n]}"
+    dom = max(kms, key=lambda n: kms[n])
+    # HBM-side traffic cannot be measured inside this process (PMC counters need rocprofv3): it is read from the newest
+    # committed PMC run (tools/pmc.sh + tools/pmc_summary.py) and only when that run was made with THIS build of the
+    # kernels (fingerprint of csrc/); otherwise null.  The source is always named.
+    traffic, traffic_source = None, "none: no profiles/*_traffic.json"
+    tfiles = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json"))
+    if tfiles and N == WORLDS_PER_GPU and args.flags == 0:
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", tfiles[-1])))
+            if tj.get("csrc_sha") == csrc_fingerprint():
+                traffic = tj.get(dom, {}).get("hbm_bytes_per_step")
+                traffic_source = f"profiles/{tfiles[-1]} (rocprofv3 PMC passes of a 40-step run of this build, csrc {tj.get('csrc_sha')}; not this run)"
+            else:
+                traffic_source = f"dropped: profiles/{tfiles[-1]} was measured on other kernel sources (csrc {tj.get('csrc_sha')} != {csrc_fingerprint()})"
+        except Exception as e:
+            traffic_source = f"unreadable profiles/{tfiles[-1]}: {e}"
+    elif tfiles:
+        traffic_source = "none: the committed PMC run is for 16000 worlds, sim_flags 0"
+    # What actually bounds the kernels is VALU issue, not HBM: the instruction counts of the committed SQ-counter run of THIS
+    # build (tools/sqpmc.sh -> profiles/*_sq_counters.txt, same fingerprint rule as the traffic) against the rate at which a
+    # SIMD issues f32 VALU instructions with all its wave slots busy (tools/ubench/pk_rate.hip, measured on the part).
+    valu_issue = None
+    sfiles = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_sq_counters.txt"))
+    if sfiles and N == WORLDS_PER_GPU and args.flags == 0:
+        try:
+            txt = open(os.path.join(ROOT, "profiles", sfiles[-1])).read()
+            if f"csrc_sha {csrc_fingerprint()}" in txt:
+                valu_issue = {"source": f"profiles/{sfiles[-1]} (rocprofv3 SQ counters of a 24-step run of this build, window placed like a short bench run; not this run)",
+                              "simd_count": 1024, "issue_ns_per_instruction_and_simd": 1.2,
+                              "peak_source": "tools/ubench/pk_rate.hip: a SIMD with all wave slots busy issues one f32 VALU instruction per 1.2 ns"}
+                for n in kms:
+                    for line in txt.splitlines():
+                        if line.startswith("sq1") and names[n] in line and "SQ_INSTS_VALU=" in line:
+                            insts = float(line.split("SQ_INSTS_VALU=")[1].split()[0])
+                            floor_ms = insts * 1.2e-9 / 1024 * 1e3
+                            valu_issue[n] = {"valu_wave_instructions_per_launch": insts, "issue_bound_ms": floor_ms,
+                                             "frac": floor_ms / (kms[n] / max(nsamp, 1))}
+        except Exception as e:
+            valu_issue = {"source": f"unreadable profiles/{sfiles[-1]}: {e}"}
+    step_bytes, step_per_world = algorithmic_bytes(sim, A, "physics_only_step" if skip_obs else "step")
+    step_ms = dt / args.steps * 1e3
+    roofline = {"bound": "hbm", "kernel": per_stage[dom]["kernel"], "achieved": per_stage[dom]["achieved_GBps"],
+                "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": per_stage[dom]["frac"], "traffic": traffic,
+                "traffic_source": traffic_source,
+                "avg_kernel_ms": per_stage[dom]["avg_ms"],
+                "algorithmic_bytes_per_world_step": per_stage[dom]["algorithmic_bytes_per_world_step"],
+                "stages": per_stage,
+                # the whole step against the roofline: SURVEY §8(d)'s B per world-step over the wall time per step
+                "step": {"algorithmic_bytes_per_world_step": step_per_world,
+                         "achieved_GBps": step_bytes / (step_ms * 1e-3) / 1e9,
+                         "frac": step_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
+                "kernel_ms_per_step": {n: kms[n] / max(nsamp, 1) for n in kms},
+                "kernel_time_samples": {"every": P, "count": nsamp, "how": "HIP events on the launch stream around the kernels of "
+                                        "every P-th step of the timed region"},
+                "valu_issue": valu_issue,
+                "schedule": "k_physics then k_observe on one stream"}
+    return roofline
+
+
+DUMP_ROLES = ("observations", "rewards", "dones", "pbt_outputs")
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(sim, out_dir):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step — the train interface's
+    observation, reward, done and episode-result tensors — as DIR/<interface name>.npy, float32 (int32 tensors as float64,
+    exact).  When the worlds do not fit in DUMP_BUDGET_BYTES, a fixed seeded sample of them (sorted, the same worlds in
+    every file; an agent row is world * A + slot) is written; DIR/world_index.npy names the worlds either way."""
+    import numpy as np
+    import gpu_hideseek
+    N, A = sim.num_worlds, sim.agents_per_world
+    arrays = {}
+    for name, role, getter in gpu_hideseek.train_interface():
+        if role in DUMP_ROLES:
+            a = getattr(sim, getter)().to_torch().cpu().numpy()
+            if a.shape[0] not in (N, N * A):
+                raise RuntimeError(f"--dump-outputs: {name} has {a.shape[0]} rows, neither {N} worlds nor {N * A} agents")
+            arrays[name] = a.astype(np.float64 if a.dtype.kind in "iu" else np.float32)
+    per_world = 8 + sum(a.nbytes // N for a in arrays.values())             # + its entry in world_index
+    k = min(N, (DUMP_BUDGET_BYTES - 1024 * (len(arrays) + 1)) // per_world)  # 1 KiB per file for the .npy header
+    worlds = np.arange(N) if k == N else np.sort(np.random.default_rng(0).choice(N, size=k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "world_index.npy"), (worlds + sim.world_offset).astype(np.float64))
+    for name, a in arrays.items():
+        r = a.shape[0] // N
+        np.save(os.path.join(out_dir, name + ".npy"), a[(worlds[:, None] * r + np.arange(r)).reshape(-1)])
 
 
 def _free_port():
@@ -185,16 +292,23 @@ def main():
     ap.add_argument("--worlds-per-gpu", type=int, default=WORLDS_PER_GPU,
                     help="16000 = BASELINE configs[1] (default); 16384 = one rank of configs[3] (131072 worlds over 8 GPUs)")
     ap.add_argument("--flags", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel HIP-event times and the roofline, "
+                         "per-step percentiles, the device status check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last step as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-preroll", action="store_true",
                     help="time the steps right after the warm-up even in a run shorter than an episode (a preparation-phase window)")
     ap.add_argument("--cpu-seconds", type=float, default=45.0,
                     help="time budget of the cpu_baseline leg (2000 worlds x 1920 steps take about 25 s on 16 threads)")
     ap.add_argument("--profile-every", type=int, default=0,
-                    help="steps between two steps that carry HIP events (0: 7, or 4 for runs of at most 64 steps)")
+                    help="with --full: steps between two steps that carry HIP events (0: 7, or 4 for runs of at most 64 steps)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     # `bench.py --gpus N` outside a launcher: become the launcher (before anything touches a GPU).
     # (HS_BENCH_FORCE_LAUNCHER=1 sends --gpus 1 through the launcher too: the 1-GPU test of this path)
@@ -271,34 +385,38 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Kernel durations: HIP events on the launch stream around the kernels of every P-th step of the timed region (recording
-    # and resolving them costs 12 us per step, 2.7 % of a step, so they are not put on every step; 7 is coprime to the
-    # 240-step episode, so level-regeneration steps are sampled in proportion).
+    # Kernel durations (--full only): HIP events on the launch stream around the kernels of every P-th step of the timed
+    # region (recording and resolving them costs 12 us per step, 2.7 % of a step, so they are not put on every step; 7 is
+    # coprime to the 240-step episode, so level-regeneration steps are sampled in proportion).
     P = args.profile_every if args.profile_every > 0 else (7 if args.steps > 64 else 4 if args.steps >= 8 else 1)
     nsamp = 0
     sim.set_profiling(False)
     # the kernels a step launches: k_physics (its tail is the per-step reset) and, unless skipped, k_observe
     skip_obs = bool(args.flags & (1 << 16))
     kms = {"physics": 0.0} if skip_obs else {"physics": 0.0, "observe": 0.0}
+    step_s = []                        # host wall time of every step (a step blocks until its kernels are done), --full
     barrier()
     t0 = time.perf_counter()
-    tprev = t0
-    step_s = []                        # host wall time of every step (a step blocks until its kernels are done)
-    for i in range(args.steps):
-        if i % P:
+    if args.full:
+        tprev = t0
+        for i in range(args.steps):
+            if i % P:
+                one_step()
+            else:
+                sim.set_profiling(True)
+                one_step()
+                k = sim.last_step_kernel_ms()
+                sim.set_profiling(False)
+                nsamp += 1
+                kms["physics"] += k["physics"]
+                if not skip_obs:
+                    kms["observe"] += k["observe"]
+            tnow = time.perf_counter()
+            step_s.append(tnow - tprev)
+            tprev = tnow
+    else:
+        for _ in range(args.steps):
             one_step()
-        else:
-            sim.set_profiling(True)
-            one_step()
-            k = sim.last_step_kernel_ms()
-            sim.set_profiling(False)
-            nsamp += 1
-            kms["physics"] += k["physics"]
-            if not skip_obs:
-                kms["observe"] += k["observe"]
-        tnow = time.perf_counter()
-        step_s.append(tnow - tprev)
-        tprev = tnow
     barrier()
     dt = time.perf_counter() - t0
     dt_own = dt
@@ -315,79 +433,14 @@ def main():
         dist.all_gather(g, torch.tensor([dt_own], dtype=torch.float64, device=cdev))
         per_rank_ms = [float(x.item()) / args.steps * 1e3 for x in g]
 
-    # A candidate pair beyond the LDS capacities spills to the slow path (counted), none is ever dropped: say so per run.
-    status = sim.device_status()
-    assert status["dropped_candidate_pairs"] == 0, f"broadphase candidate pairs were dropped: {status}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sim, args.dump_outputs)
 
-    # Roofline position of the dominant kernel.  A step is two kernels: k_physics (persistent: movement / actions,
-    # 4 XPBD substeps, rewards, per-step reset) and k_observe.  Durations are HIP events on the launch stream
-    # (hs_set_profiling); profiles/ holds the rocprofv3 --kernel-trace --stats summary of this command, whose
-    # per-kernel averages agree with them.  Only kernels that were launched are listed.
-    names = {"physics": "k_physics", "observe": "k_observe"}
-    per_stage = {}
-    for n in kms:
-        avg_ms = kms[n] / max(nsamp, 1)
-        total_bytes, per_world = algorithmic_bytes(sim, A, n)
-        ach = total_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        per_stage[n] = {"kernel": names[n], "avg_ms": avg_ms, "algorithmic_bytes_per_world_step": per_world,
-                        "achieved_GBps": ach, "frac": ach / HBM_PEAK_GBPS}
-        assert 0.0 <= per_stage[n]["frac"] <= 1.0, f"roofline fraction of {n} out of range: {per_stage[n]}"
-    dom = max(kms, key=lambda n: kms[n])
-    # HBM-side traffic cannot be measured inside this process (PMC counters need rocprofv3): it is read from the newest
-    # committed PMC run (tools/pmc.sh + tools/pmc_summary.py) and only when that run was made with THIS build of the
-    # kernels (fingerprint of csrc/); otherwise null.  The source is always named.
-    traffic, traffic_source = None, "none: no profiles/*_traffic.json"
-    tfiles = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json"))
-    if tfiles and N == WORLDS_PER_GPU and args.flags == 0:
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", tfiles[-1])))
-            if tj.get("csrc_sha") == csrc_fingerprint():
-                traffic = tj.get(dom, {}).get("hbm_bytes_per_step")
-                traffic_source = f"profiles/{tfiles[-1]} (rocprofv3 PMC passes of a 40-step run of this build, csrc {tj.get('csrc_sha')}; not this run)"
-            else:
-                traffic_source = f"dropped: profiles/{tfiles[-1]} was measured on other kernel sources (csrc {tj.get('csrc_sha')} != {csrc_fingerprint()})"
-        except Exception as e:
-            traffic_source = f"unreadable profiles/{tfiles[-1]}: {e}"
-    elif tfiles:
-        traffic_source = "none: the committed PMC run is for 16000 worlds, sim_flags 0"
-    # What actually bounds the kernels is VALU issue, not HBM: the instruction counts of the committed SQ-counter run of THIS
-    # build (tools/sqpmc.sh -> profiles/*_sq_counters.txt, same fingerprint rule as the traffic) against the rate at which a
-    # SIMD issues f32 VALU instructions with all its wave slots busy (tools/ubench/pk_rate.hip, measured on the part).
-    valu_issue = None
-    sfiles = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_sq_counters.txt"))
-    if sfiles and N == WORLDS_PER_GPU and args.flags == 0:
-        try:
-            txt = open(os.path.join(ROOT, "profiles", sfiles[-1])).read()
-            if f"csrc_sha {csrc_fingerprint()}" in txt:
-                valu_issue = {"source": f"profiles/{sfiles[-1]} (rocprofv3 SQ counters of a 24-step run of this build, window placed like a short bench run; not this run)",
-                              "simd_count": 1024, "issue_ns_per_instruction_and_simd": 1.2,
-                              "peak_source": "tools/ubench/pk_rate.hip: a SIMD with all wave slots busy issues one f32 VALU instruction per 1.2 ns"}
-                for n in kms:
-                    for line in txt.splitlines():
-                        if line.startswith("sq1") and names[n] in line and "SQ_INSTS_VALU=" in line:
-                            insts = float(line.split("SQ_INSTS_VALU=")[1].split()[0])
-                            floor_ms = insts * 1.2e-9 / 1024 * 1e3
-                            valu_issue[n] = {"valu_wave_instructions_per_launch": insts, "issue_bound_ms": floor_ms,
-                                             "frac": floor_ms / (kms[n] / max(nsamp, 1))}
-        except Exception as e:
-            valu_issue = {"source": f"unreadable profiles/{sfiles[-1]}: {e}"}
-    step_bytes, step_per_world = algorithmic_bytes(sim, A, "physics_only_step" if skip_obs else "step")
-    step_ms = dt / args.steps * 1e3
-    roofline = {"bound": "hbm", "kernel": per_stage[dom]["kernel"], "achieved": per_stage[dom]["achieved_GBps"],
-                "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": per_stage[dom]["frac"], "traffic": traffic,
-                "traffic_source": traffic_source,
-                "avg_kernel_ms": per_stage[dom]["avg_ms"],
-                "algorithmic_bytes_per_world_step": per_stage[dom]["algorithmic_bytes_per_world_step"],
-                "stages": per_stage,
-                # the whole step against the roofline: SURVEY §8(d)'s B per world-step over the wall time per step
-                "step": {"algorithmic_bytes_per_world_step": step_per_world,
-                         "achieved_GBps": step_bytes / (step_ms * 1e-3) / 1e9,
-                         "frac": step_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-                "kernel_ms_per_step": {n: kms[n] / max(nsamp, 1) for n in kms},
-                "kernel_time_samples": {"every": P, "count": nsamp, "how": "HIP events on the launch stream around the kernels of "
-                                        "every P-th step of the timed region"},
-                "valu_issue": valu_issue,
-                "schedule": "k_physics then k_observe on one stream"}
+    if args.full:
+        # A candidate pair beyond the LDS capacities spills to the slow path (counted), none is ever dropped: say so per run.
+        status = sim.device_status()
+        assert status["dropped_candidate_pairs"] == 0, f"broadphase candidate pairs were dropped: {status}"
+        roofline = roofline_figures(sim, A, N, args, kms, nsamp, P, dt, skip_obs)
 
     if rank == 0:
         assert stepped == world_size, f"{stepped} of {world_size} ranks stepped"
@@ -399,9 +452,6 @@ def main():
             "n_gpus": stepped, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
             "ms_per_step_per_rank": per_rank_ms,
-            # host wall time per step on rank 0 (a step blocks until its kernels are done): the scatter of the run itself
-            "ms_per_step_percentiles": {k: float(np.percentile(np.asarray(step_s) * 1e3, q))
-                                        for k, q in (("min", 0), ("p10", 10), ("p50", 50), ("p90", 90), ("p99", 99), ("max", 100))},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{N} worlds/GPU x {args.steps} steps, 2 hiders + 2 seekers, sim_flags={args.flags}, "
@@ -422,13 +472,17 @@ def main():
                                        "post-preparation steps are in the episode's own proportion (95 : 145); no level regeneration "
                                        "inside, and the post-preparation steps are the first ones after the seekers' release, when the "
                                        "contact load is still building up: about 7 % faster than whole episodes (32.4 M world-steps/s)")},
-            "roofline": roofline,
         }
-        out["device_status"] = status
-        if not args.no_cpu_baseline and world_size == 1:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-        elif not args.no_cpu_baseline:
-            out["cpu_baseline"] = None
+        if args.full:
+            # host wall time per step on rank 0 (a step blocks until its kernels are done): the scatter of the run itself
+            out["ms_per_step_percentiles"] = {k: float(np.percentile(np.asarray(step_s) * 1e3, q))
+                                              for k, q in (("min", 0), ("p10", 10), ("p50", 50), ("p90", 90), ("p99", 99), ("max", 100))}
+            out["roofline"] = roofline
+            out["device_status"] = status
+            if not args.no_cpu_baseline and world_size == 1:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+            elif not args.no_cpu_baseline:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     del sim
     if dist is not None:

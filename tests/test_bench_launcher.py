@@ -84,7 +84,7 @@ def test_two_ranks_on_a_one_gpu_box_fail_with_device_not_visible():
 @pytest.mark.gpu
 def test_one_rank_through_the_launcher_path():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "16", "--warmup", "2", "--worlds-per-gpu", "2048",
-                        "--no-cpu-baseline"], env=_env(HS_BENCH_FORCE_LAUNCHER="1"), capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], env=_env(HS_BENCH_FORCE_LAUNCHER="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["config"]["total_worlds"] == 2048 and out["value"] > 0
