@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
-#include <cstdlib>
 #include <string>
 #include <vector>
 #include <atomic>
@@ -43,15 +42,10 @@ struct hs_sim {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float last_ms[3] = {0.f, 0.f, 0.f};
     bool initialised = false;
-    bool use_graph = false;                // env HS_GRAPH=1: replay the step as HIP graphs (measured 2 % slower than two direct launches)
-    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};     // physics, observe
     hipStream_t step_stream = nullptr;     // the stream of the open step
-    bool blocking_own_stream = false;      // HS_STREAM=own: hs_step uses the handle's stream as hs_step_begin does
     int step_idx = 0;                      // physics launches mod 3 (SimState::tickSum)
-    int tile = 8;                          // worlds per physics wave: 8 (two waves per SIMD) or 4 (four waves per SIMD); HS_TILE
-    // Load balancing between the physics waves (hs_k_balance.h; HS_BALANCE=0 turns it off, HS_BALANCE_PERIOD sets the steps between deals)
-    bool balance = true;
-    int balance_period = 32, steps_since_balance = 0;
+    // Load balancing between the physics waves (hs_k_balance.h): a deal every kBalancePeriod steps
+    int steps_since_balance = 0;
     int *bal_hist = nullptr, *bal_cursor = nullptr, *bal_new_slot = nullptr;
     void *bal_tmp = nullptr;               // a second arena: the deal copies the columns there and moves them back to their new slots
     void *col_arena = nullptr; size_t col_arena_bytes = 0, col_slots = 0;      // the tiled columns, one after the other
@@ -121,37 +115,7 @@ void launch_observe(hs_sim *s, hipStream_t strm) {
     else hipLaunchKernelGGL(hs::k_observe<320>, dim3(N), dim3(320), 0, strm, S);
 }
 
-// One step = k_physics (movement + actionSystem, 4 XPBD substeps, rewards / dones / episode results, reset: one
-// kernel, a wave per octet of 8 worlds, hs_k_physics.h) and k_observe.  Manager::init = k_reset then k_observe.
-// `stages`: 1 physics, 2 reset (init only), 4 observe.
-int launch_step_eager(hs_sim *s, hipStream_t strm, bool first, bool prof, int stages = 7, bool capture = false) {
-    hs::SimState S = s->S;
-    const int N = S.N, noct = (N + hs::kTile - 1) / hs::kTile;
-    // (a captured launch keeps its arguments for ever: it gets no step index, and the kernel skips the per-wave priority hint)
-    S.stepIdx = capture ? -1 : s->step_idx; if (!capture && !first && (stages & 1)) s->step_idx = (s->step_idx + 1) % 3;
-    if (prof) HS_HIP(hipEventRecord(s->ev[0], strm));
-    if (!first && (stages & 1)) {
-        // rounds of 64 lanes over the tile's bodies: 16 body slots per world with up to 5 agents, 17 with 6
-        const bool six = s->A > hs::kMaxAgents - 1;
-        if (s->tile == 8) {
-            if (six) hipLaunchKernelGGL((hs::k_physics<3, 8>), dim3(noct), dim3(hs::kPhysThreads), hs::kPhysDynLds, strm, S);
-            else hipLaunchKernelGGL((hs::k_physics<2, 8>), dim3(noct), dim3(hs::kPhysThreads), hs::kPhysDynLds, strm, S);
-        } else {
-            if (six) hipLaunchKernelGGL((hs::k_physics<2, 4>), dim3(2 * noct), dim3(hs::kPhysThreads), hs::kPhysDynLds / 2, strm, S);
-            else hipLaunchKernelGGL((hs::k_physics<1, 4>), dim3(2 * noct), dim3(hs::kPhysThreads), hs::kPhysDynLds / 2, strm, S);
-        }
-    }
-    if (prof) HS_HIP(hipEventRecord(s->ev[1], strm));
-    // in a step the reset is the tail of k_physics; only Manager::init launches it on its own
-    if (first && (stages & 2)) hipLaunchKernelGGL(hs::k_reset, dim3((N + 31) / 32), dim3(32), 0, strm, S);     // half-filled waves: the generator diverges per world
-    if (prof) HS_HIP(hipEventRecord(s->ev[2], strm));
-    if (stages & 4) launch_observe(s, strm);
-    if (prof) HS_HIP(hipEventRecord(s->ev[3], strm));
-    HS_HIP(hipGetLastError());
-    return HS_OK;
-}
-
-// Deal the worlds to the octets by contact load (hs_k_balance.h), every balance_period steps: histogram, scan, deal, one copy
+// Deal the worlds to the octets by contact load (hs_k_balance.h), every kBalancePeriod steps: histogram, scan, deal, one copy
 // of the column arena, one move kernel over all columns, commit (six launches and a copy; it was 26 launches and 11 copies).
 int balance_worlds(hs_sim *s, hipStream_t strm) {
     const hs::SimState &S = s->S;
@@ -160,7 +124,7 @@ int balance_worlds(hs_sim *s, hipStream_t strm) {
     const dim3 grid((nfull + 255) / 256), blk(256);
     hipLaunchKernelGGL(hs::k_balance_hist, grid, blk, 0, strm, S, nfull, s->bal_hist);
     hipLaunchKernelGGL(hs::k_balance_scan, dim3(1), dim3(hs::kBalanceBins), 0, strm, s->bal_hist, s->bal_cursor);
-    hipLaunchKernelGGL(hs::k_balance_deal, grid, blk, 0, strm, S, nfull, s->bal_cursor, s->bal_new_slot, s->tile);
+    hipLaunchKernelGGL(hs::k_balance_deal, grid, blk, 0, strm, S, nfull, s->bal_cursor, s->bal_new_slot);
     HS_HIP(hipMemcpyAsync(s->bal_tmp, s->col_arena, s->col_arena_bytes, hipMemcpyDeviceToDevice, strm));
     const size_t n = (size_t)nfull * s->bal_cols.base[hs::kBalanceCols];
     hipLaunchKernelGGL(hs::k_balance_move_all, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, strm, (int *)s->col_arena, (const int *)s->bal_tmp,
@@ -170,45 +134,31 @@ int balance_worlds(hs_sim *s, hipStream_t strm) {
     return HS_OK;
 }
 
-// Optional (HS_GRAPH=1): the step as two HIP graphs (physics, observe), captured once on a private stream (the
-// legacy stream cannot be captured) and replayed on the caller's stream; the profiling events stay ordinary stream
-// events between the graph launches.  It paid off while physics was ~40 launches per step; with the persistent
-// physics kernel a step is two launches and the direct launches are faster.  When capture or instantiation fails
-// the handle falls back to direct launches and hs_get_device_status reports graphs_in_use = 0.
+// One step = k_physics (movement + actionSystem, 4 XPBD substeps, rewards / dones / episode results, reset: one
+// kernel, a wave per octet of 8 worlds, hs_k_physics.h) and k_observe.  Manager::init = k_reset then k_observe.
 int launch_step(hs_sim *s, hipStream_t strm, bool first) {
-    if (!first && s->balance && ++s->steps_since_balance >= s->balance_period) {
+    if (!first && ++s->steps_since_balance >= hs::kBalancePeriod) {
         s->steps_since_balance = 0;
         int rc = balance_worlds(s, strm);
         if (rc != HS_OK) return rc;
     }
-    if (first || !s->use_graph) return launch_step_eager(s, strm, first, s->profiling);
-    const bool skip_obs = (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) != 0;
-    const int ngraphs = skip_obs ? 1 : 2;
-    if (!s->graph_exec[0]) {
-        hipStream_t cap = nullptr;
-        HS_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-        bool ok = true;
-        for (int g = 0; g < ngraphs && ok; ++g) {
-            hipGraph_t gr = nullptr;
-            ok = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) ok = launch_step_eager(s, cap, false, false, g == 0 ? 1 : 4, true) == HS_OK;
-            if (hipStreamEndCapture(cap, &gr) != hipSuccess) ok = false;
-            if (ok) ok = hipGraphInstantiate(&s->graph_exec[g], gr, nullptr, nullptr, 0) == hipSuccess;
-            if (gr) hipGraphDestroy(gr);
-        }
-        hipStreamDestroy(cap);
-        if (!ok) {
-            for (auto &e : s->graph_exec) { if (e) hipGraphExecDestroy(e); e = nullptr; }
-            s->use_graph = false; (void)hipGetLastError();
-            return launch_step_eager(s, strm, first, s->profiling);
-        }
-    }
     const bool prof = s->profiling;
+    hs::SimState S = s->S;
+    const int N = S.N, noct = (N + hs::kTile - 1) / hs::kTile;
+    S.stepIdx = s->step_idx; if (!first) s->step_idx = (s->step_idx + 1) % 3;
     if (prof) HS_HIP(hipEventRecord(s->ev[0], strm));
-    HS_HIP(hipGraphLaunch(s->graph_exec[0], strm));
-    if (prof) { HS_HIP(hipEventRecord(s->ev[1], strm)); HS_HIP(hipEventRecord(s->ev[2], strm)); }
-    if (!skip_obs) HS_HIP(hipGraphLaunch(s->graph_exec[1], strm));
+    if (!first) {
+        // rounds of 64 lanes over the octet's bodies: 16 body slots per world with up to 5 agents, 17 with 6
+        if (s->A > hs::kMaxAgents - 1) hipLaunchKernelGGL(hs::k_physics<3>, dim3(noct), dim3(hs::kPhysThreads), 0, strm, S);
+        else hipLaunchKernelGGL(hs::k_physics<2>, dim3(noct), dim3(hs::kPhysThreads), 0, strm, S);
+    }
+    if (prof) HS_HIP(hipEventRecord(s->ev[1], strm));
+    // in a step the reset is the tail of k_physics; only Manager::init launches it on its own
+    if (first) hipLaunchKernelGGL(hs::k_reset, dim3((N + 31) / 32), dim3(32), 0, strm, S);     // half-filled waves: the generator diverges per world
+    if (prof) HS_HIP(hipEventRecord(s->ev[2], strm));
+    launch_observe(s, strm);
     if (prof) HS_HIP(hipEventRecord(s->ev[3], strm));
+    HS_HIP(hipGetLastError());
     return HS_OK;
 }
 
@@ -311,11 +261,11 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     // (every possible pair of every world: 92 KB per world, 1.5 GB at 16 000 worlds, of which a step touches a few MB)
     { char *p; HS_ALLOC(p, NP * hs::kAllDD * sizeof(hs::ManDD)); S.wsDD = p; HS_ALLOC(p, NP * hs::kAllSC * sizeof(hs::ManS)); S.wsSC = p; }
     HS_ALLOC(S.spPair, NP * (hs::kAllDD + hs::kAllSC)); HS_ALLOC(S.spInfo, NP * hs::kSpInfoWords);
-    HS_ALLOC(S.phaseTicks, hs::phase_ticks_study_base((int)N) + N * hs::kStudyWords);   // + k_observe's section counters + the per-world work counters
+    HS_ALLOC(S.phaseTicks, hs::phase_ticks_obs_base((int)N) + 16 * 1024 + 16);   // + k_observe's section counters + the convex tests' counters
     HS_ALLOC(S.slotOfWorld, N); HS_ALLOC(S.worldOfSlot, NP); HS_ALLOC(S.loadAcc, N); HS_ALLOC(S.wallHist, N);
     if ((rc = s->dalloc(&S.slotHdr, NP, 0xFF)) != HS_OK) { hs_destroy(s); return rc; }      // world id -1: empty slot
     HS_ALLOC(S.lidarSinCos, 60);
-    HS_ALLOC(S.octTicks, NP / 4); HS_ALLOC(S.tickSum, 3);
+    HS_ALLOC(S.octTicks, NP / hs::kTile); HS_ALLOC(S.tickSum, 3);
     HS_ALLOC(s->bal_hist, hs::kBalanceBins); HS_ALLOC(s->bal_cursor, hs::kBalanceBins); HS_ALLOC(s->bal_new_slot, N);
     HS_ALLOC(S.status, 4);
 #undef HS_ALLOC
@@ -334,11 +284,6 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     for (auto &e : s->ev) {
         if (hipEventCreate(&e) != hipSuccess) { hs_destroy(s); return fail(HS_ERR_HIP, "hipEventCreate failed"); }
     }
-    if (const char *e = getenv("HS_GRAPH")) s->use_graph = atoi(e) != 0;
-    if (const char *e = getenv("HS_STREAM")) s->blocking_own_stream = std::strcmp(e, "own") == 0;
-    if (const char *e = getenv("HS_TILE")) { const int v = atoi(e); if (v == 4 || v == 8) s->tile = v; }
-    if (const char *e = getenv("HS_BALANCE")) s->balance = atoi(e) != 0;
-    if (const char *e = getenv("HS_BALANCE_PERIOD")) { const int v = atoi(e); if (v > 0) s->balance_period = v; }
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&s->evIn, hipEventDisableTiming) != hipSuccess) { hs_destroy(s); return fail(HS_ERR_HIP, "stream/event creation failed"); }
     S.wbeg = 0; S.wcnt = (int)N;
@@ -385,7 +330,6 @@ void hs_destroy(hs_sim *s) {
     for (auto &e : s->ev) if (e) hipEventDestroy(e);
     if (s->evIn) hipEventDestroy(s->evIn);
     if (s->stream) hipStreamDestroy(s->stream);
-    for (auto &e : s->graph_exec) if (e) hipGraphExecDestroy(e);
     delete s;
 }
 
@@ -448,7 +392,7 @@ int32_t hs_step_end(hs_sim *s) {
 }
 
 int32_t hs_step(hs_sim *s) {
-    int rc = step_begin(s, s && s->blocking_own_stream);
+    int rc = step_begin(s, false);
     return rc != HS_OK ? rc : hs_step_end(s);
 }
 
@@ -653,19 +597,10 @@ int32_t hs_xla_last_status(int32_t clear) { return clear ? g_xla_status.exchange
 int32_t hs_debug_phase_ticks(hs_sim *s, int64_t *out, int32_t max_groups) {
     if (!s || !out) return fail(HS_ERR_INVALID_ARG, "null argument");
     HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int nb = (s->S.N + hs::kTile - 1) / hs::kTile * (hs::kTile / s->tile);          // one workgroup (wave) per tile
+    int nb = (s->S.N + hs::kTile - 1) / hs::kTile;          // one workgroup (wave) per octet
     if (nb > max_groups) nb = max_groups;
     HS_HIP(hipMemcpy(out, s->S.phaseTicks, (size_t)nb * 10 * sizeof(int64_t), hipMemcpyDeviceToHost));
     return nb;
-}
-
-// Per-world work counters (HS_LOAD_STUDY builds): [worlds][8], see hs_state.h phase_ticks_study_base.
-int32_t hs_debug_load_study(hs_sim *s, int64_t *out, int32_t max_worlds) {
-    if (!s || !out) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    const int n = s->S.N < max_worlds ? s->S.N : max_worlds;
-    HS_HIP(hipMemcpy(out, s->S.phaseTicks + hs::phase_ticks_study_base(s->S.N), (size_t)n * hs::kStudyWords * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return n;
 }
 
 // The same for k_observe: ticks per section summed over all waves (HS_PHASE_TIMING builds).
@@ -852,7 +787,7 @@ int32_t hs_get_device_status(hs_sim *s, hs_device_status *out) {
     out->spilled_static_pairs = st[1];
     out->dropped_dd_pairs = 0;             // nothing can overflow the spill lists (hs_k_physics.h: sized for every pair)
     out->dropped_static_pairs = 0;
-    out->graphs_in_use = (s->use_graph && s->graph_exec[0]) ? 1 : 0;
+    out->graphs_in_use = 0;                // (HIP-graph replay was removed)
     out->reserved = 0;
     return HS_OK;
 }

@@ -14,6 +14,7 @@
 
 namespace hs {
 
+constexpr int kBalancePeriod = 32;     // steps between deals
 constexpr int kBalanceBins = 1024;
 
 // 1. histogram of the load classes (descending: class 0 = busiest)
@@ -38,14 +39,13 @@ __global__ void __launch_bounds__(kBalanceBins) k_balance_scan(int *hist, int *c
     hist[t] = 0;
 }
 // 3. rank of every world (order inside a class does not matter), its new slot; the load counters start over
-// (`tile`: worlds per physics wave, 8 or 4 — the groups the load is equalised over)
-__global__ void __launch_bounds__(256) k_balance_deal(SimState S, int nfull, int *cursor, int *newSlot, int tile) {
+__global__ void __launch_bounds__(256) k_balance_deal(SimState S, int nfull, int *cursor, int *newSlot) {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= nfull) return;
     const int r = atomicAdd(&cursor[load_class(S.loadAcc[w])], 1);
-    const int noct = nfull / tile;
+    const int noct = nfull / kTile;
     const int row = r / noct, col = r - row * noct;
-    newSlot[w] = ((row & 1) ? noct - 1 - col : col) * tile + row;
+    newSlot[w] = ((row & 1) ? noct - 1 - col : col) * kTile + row;
     S.loadAcc[w] = 0;
 }
 // 4. every row of every tiled column moves from the old slot to the new one, in ONE launch: the columns are consecutive

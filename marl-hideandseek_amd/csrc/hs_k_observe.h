@@ -25,17 +25,9 @@
 
 namespace hs {
 
-// Timing probes (development aid, results are wrong when set): -DHS_OBS_SKIP=<bits> leaves sections of k_observe out:
-// 1 walls, 2 hull cull (no pairs), 4 exact hull tests, 8 observation rows, 16 ray results, 32 everything after staging.
-#ifndef HS_OBS_SKIP
-#define HS_OBS_SKIP 0
-#endif
-
 // waves per SIMD the register allocation of k_observe aims at (8 needs 48 bytes of scratch per lane: 1 % faster, but the
 // spills show up as 60 % more HBM write traffic)
-#ifndef HS_OBS_WAVES
-#define HS_OBS_WAVES 7
-#endif
+constexpr int kObsWaves = 7;
 
 constexpr int kRaysPerAgent = 46;                          // 30 lidar + 16 visibility targets
 // Lane layout of the rays: the A*30 lidar rays first (ray = agent * 30 + k), the A*16 visibility rays from the next
@@ -103,7 +95,7 @@ constexpr unsigned kKeyMiss = 0xffffffffu;
 
 // NT = threads per world = obs_threads(A) (192 for the 4-agent benchmark): a lane per ray.
 template <int NT>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_WAVES, HS_OBS_WAVES))) k_observe(SimState S) {
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWaves, kObsWaves))) k_observe(SimState S) {
     __shared__ ObsShared<NT> sh;
     const int tid = threadIdx.x;
 #ifdef HS_PHASE_TIMING
@@ -137,7 +129,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_
     __syncthreads();
     const WorldGeom &g = sh.g;
     const int nAgents = cnt_agents(counts), nBoxes = cnt_boxes(counts), nRamps = cnt_ramps(counts);
-    if (HS_OBS_SKIP & 32) return;
     HS_OTICK(0)
     for (int item = tid; item < nAgents * kNumDSlots; item += NT) {
         const int i = item / kNumDSlots, b = item % kNumDSlots;
@@ -192,7 +183,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_
         // static geometry: same order and arithmetic as trace_ray
         int hit = -1; float best = tmax;
         const V3 inv = {1.f / d.x, 1.f / d.y, 1.f / d.z};
-        const int nw = (HS_OBS_SKIP & 1) ? 0 : g.numWalls;
+        const int nw = g.numWalls;
         const WallZ wz = ray_wall_z(o.z, d.z, inv.z);          // the z slab is the same for every wall
         // (a ray with an exactly zero x or y component takes the general form; decided per wave)
         if (__ballot(d.x == 0.f || d.y == 0.f) == 0) {
@@ -228,7 +219,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_
         // origin (origin - centre is exactly 0), and a ray that starts inside a hull never hits it (every slab's entry
         // is negative).
         const float dd2 = dot(d, d);
-        const unsigned others = __builtin_amdgcn_readfirstlane(sh.present) & ((HS_OBS_SKIP & 2) ? 0u : ~0u);
+        const unsigned others = __builtin_amdgcn_readfirstlane(sh.present);
         const float *relI = &sh.rel[i][0][0];
         constexpr unsigned kRampBits = ((1u << kMaxRamps) - 1u) << kRampSlot0;
         const int wv = tid >> 6;
@@ -267,7 +258,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_
         int np2 = 0, nr2 = 0;
 #pragma unroll
         for (int v = 0; v < NW; ++v) { np2 += sh.nPairs[v]; nr2 += sh.nRampPairs[v]; }
-        if (HS_OBS_SKIP & 4) { np2 = 0; nr2 = 0; }
         for (int p = tid; p < np2; p += NT) {
             int q = p, v = 0;                                     // p-th pair of the concatenated regions
 #pragma unroll
@@ -300,7 +290,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_
     __syncthreads();
     HS_OTICK(6)
     // ---------------- pass 3: ray results -> exported columns ----------------
-    for (int r = tid; r < ((HS_OBS_SKIP & 16) ? 0 : NT); r += NT) {
+    for (int r = tid; r < NT; r += NT) {
         const RayId rid = ray_id(r, visBase);
         const int i = rid.agent, k = rid.k;
         if (i >= nAgents) continue;
@@ -332,7 +322,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(HS_OBS_
     // ---------------- collectObservationsSystem rows + globalPositionsDebugSystem ----------------
     // items: A*16 (agent, other entity) rows first — a whole wave of the same work for 4 agents —, then the A self rows,
     // then the debug positions
-    const int nRel = A * 16, nObs = (HS_OBS_SKIP & 8) ? -1 : nRel + A;
+    const int nRel = A * 16, nObs = nRel + A;
     for (int item = tid; item < nObs + 1; item += NT) {
         if (item < nObs) {
             const int i = item < nRel ? item >> 4 : item - nRel, e = item < nRel ? 1 + (item & 15) : 0;

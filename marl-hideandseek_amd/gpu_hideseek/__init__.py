@@ -295,7 +295,7 @@ class HideAndSeekSimulator:
 
     def device_status(self):
         """hs_get_device_status: sticky device-side counters — candidate pairs that took the spill path of the physics
-        kernel (beyond its LDS capacities; results unaffected), dropped pairs (always 0) — and whether graphs are in use."""
+        kernel (beyond its LDS capacities; results unaffected), dropped pairs (always 0); graphs_in_use is always False."""
         st = _native.HsDeviceStatus()
         _check(self._L.hs_get_device_status(self._h, C.byref(st)))
         return {"dropped_dd_pairs": int(st.dropped_dd_pairs), "dropped_static_pairs": int(st.dropped_static_pairs),

@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import gpu_hideseek
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 16000
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 240
-period = int(os.environ.get("HS_BALANCE_PERIOD", "32"))
+period = 32                      # steps between deals (hs_k_balance.h kBalancePeriod)
 sim = gpu_hideseek.HideAndSeekSimulator(exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=0, num_worlds=N, sim_flags=0, rand_seed=0,
     min_hiders=2, max_hiders=2, min_seekers=2, max_seekers=2, num_pbt_policies=1)
 act = sim.action_tensor().to_torch()
