@@ -1,6 +1,6 @@
 """ORACLE — TEST INFRASTRUCTURE ONLY.
 
-ctypes driver for the CPU restatement (oracle/_build/libhs_ref.so).  Imported only by tests/,
+ctypes driver for the CPU restatement (oracle/_build/libhs_ref.so).  Imported only by tests/, lockstep.py,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg; never by the product package.
 PARITY UNPINNED against the real reference (engine source absent) — see DESIGN.md.
 """

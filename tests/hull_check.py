@@ -11,8 +11,8 @@ import json
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hulls.npz")
 OBJECT_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "object_table.json")
 # SimObject id -> collision mesh, as the reference's loadPhysicsObjects assigns them (tests/golden/object_table.json)
-NAMES = {o["id"]: o["mesh"].replace("_collision.obj", "") for o in json.load(open(OBJECT_TABLE))["objects"].values() if o["mesh"]}
-assert NAMES == {2: "cube", 3: "wall", 4: "agent", 5: "agent", 6: "ramp", 7: "elongated"}
+MESHES = {o["id"]: o["mesh"].replace("_collision.obj", "") for o in json.load(open(OBJECT_TABLE))["objects"].values() if o["mesh"]}
+assert MESHES == {2: "cube", 3: "wall", 4: "agent", 5: "agent", 6: "ramp", 7: "elongated"}
 
 
 def check_object_params(obj, params):
@@ -46,7 +46,7 @@ def canon_loop(points):
 
 def check_hull(obj, verts, faces, normals, edges):
     g = np.load(GOLDEN)
-    name = NAMES[obj]
+    name = MESHES[obj]
     gv, gf = g[f"{name}_v"], g[f"{name}_f"]
     verts = np.asarray(verts, np.float32)
     assert {tuple(v) for v in verts.tolist()} == {tuple(v) for v in gv.tolist()}, f"{name}: vertex set"

@@ -3,6 +3,8 @@ of scripts/benchmark.py (restated here — the reference tree does not exist on 
 import numpy as np
 import pytest
 
+from lockstep import Pair
+
 pytestmark = pytest.mark.gpu
 
 
@@ -112,25 +114,13 @@ def test_skip_observations_extension_leaves_physics_unchanged(oracle=None):
 def test_world_count_with_a_partial_octet_matches_the_oracle(oracle):
     """301 worlds = 37 octets + 5 worlds: the padding slots of the last octet must stay inert.  Moves, turns, grabs and
     locks, 30 steps, every body and the exported tensors against the oracle."""
-    import torch
-    n = 301
-    sim = _sim(n, rand_seed=3, min_hiders=2, max_hiders=3, min_seekers=1, max_seekers=3)
-    ref = oracle.RefSim(n, rand_seed=3, min_hiders=2, max_hiders=3, min_seekers=1, max_seekers=3, threads=8)
-    sim.init(); ref.init()
-    act = sim.action_tensor().to_torch()
-    g = np.arange(act.shape[0], dtype=np.int64)
-    for s in range(30):
-        a = np.stack([(g * 7 + s) % 11, (g * 3 + 2 * s) % 11, (g + s) % 11, ((g + s) % 13 == 0), ((g * 2 + s) % 17 == 0)],
-                     axis=1).astype(np.int32)
-        ref.tensor("action")[:] = a
-        act.copy_(torch.from_numpy(a).to(act.device))
-        sim.step(); ref.step()
-    gb, gm = sim.debug_bodies()
-    rb, rm = ref.bodies()
-    assert np.array_equal(gm, rm) and np.array_equal(gb.view(np.int32), rb.view(np.int32))
-    for k in ("lidar", "reward", "self_data", "box_data", "visible_agents_mask", "global_positions", "action"):
-        got = getattr(sim, k + "_tensor")().to_torch().cpu().numpy().reshape(ref.tensor(k).shape)
-        assert np.array_equal(np.ascontiguousarray(got).view(np.int32), ref.tensor(k).view(np.int32)), k
+    def moves_turns_grabs_locks(s, rows):
+        g = np.arange(rows, dtype=np.int64)
+        return np.stack([(g * 7 + s) % 11, (g * 3 + 2 * s) % 11, (g + s) % 11, ((g + s) % 13 == 0),
+                         ((g * 2 + s) % 17 == 0)], axis=1)
+    p = Pair(301, seed=3, hiders=(2, 3), seekers=(1, 3))
+    p.drive(30, moves_turns_grabs_locks, every=30, walls=False,
+            names=("lidar", "reward", "self_data", "box_data", "visible_agents_mask", "global_positions", "action"))
 
 
 def test_headless_cpp_driver_runs():

@@ -4,7 +4,7 @@ behind sim.jax() (src/mgr.cpp:362-436): HIP path through the C ABI vs the CPU or
 import numpy as np
 import pytest
 
-from test_gpu_parity import NAMES, assert_equal_state, bits, drive, make_pair
+from lockstep import NAMES, OBS, Pair, bits
 
 pytestmark = pytest.mark.gpu
 
@@ -17,8 +17,8 @@ def _ckpt_views(sim):
 
 def test_checkpoint_tensor_contract(oracle):
     import torch
-    sim, ref, gt = make_pair(oracle, 8)
-    ctrl, ck = _ckpt_views(sim)
+    p = Pair(8)                       # the views do not own their memory: keep the simulator alive
+    ctrl, ck = _ckpt_views(p.sim)
     assert ctrl.dtype == torch.uint8 and tuple(ctrl.shape) == (8, 4)          # mgr.cpp:1209-1217
     assert ck.dtype == torch.uint8 and tuple(ck.shape) == (8, 1392)           # mgr.cpp:1219-1227
     assert int(ctrl.sum()) == 0                                               # Sim::Sim sim.cpp:1391-1393
@@ -31,9 +31,10 @@ def test_save_load_parity_with_oracle(oracle, cfg):
     trajectory after a restore all match the oracle."""
     import torch
     n = cfg["n"]
-    sim, ref, gt = make_pair(oracle, n, flags=cfg["flags"], seed=cfg["seed"], hiders=cfg["hiders"], seekers=cfg["seekers"])
+    p = Pair(n, flags=cfg["flags"], seed=cfg["seed"], hiders=cfg["hiders"], seekers=cfg["seekers"])
+    sim, ref = p.sim, p.ref
     ctrl, ck = _ckpt_views(sim)
-    drive(sim, ref, gt, 60, "full", check_every=20, seed=1)
+    p.drive(60, "full", every=20, seed=1)
     # --- save every world
     ctrl.view(torch.int32)[:] = 1
     ref.tensor("ckpt_ctrl")[:] = 1
@@ -46,25 +47,27 @@ def test_save_load_parity_with_oracle(oracle, cfg):
     grab_idx = rec[:, 5 + 13::29][:, :6]                            # agents[i].grabIdx
     assert (grab_idx >= 0).any(), "no live grab joint in the fixture: weak test"
     # --- move on, then restore half of the worlds
-    drive(sim, ref, gt, 15, "full", check_every=15, seed=2)
+    p.drive(15, "full", every=15, seed=2)
     trig = (np.arange(n) % 2 == 0).astype(np.int32)
     ctrl.view(torch.int32)[:, 0] = torch.from_numpy(trig).to(ctrl.device)
     ref.tensor("ckpt_ctrl")[:, 0] = trig
     sim.load_checkpoints(); ref.load_checkpoints()
     assert np.array_equal(ctrl.view(torch.int32).cpu().numpy().ravel(), trig)     # trigger stays 1 (sim.cpp:963)
-    assert_equal_state(sim, ref, gt, "after load")
+    p.check("after load")
     _, info = sim.debug_walls()
     assert (info[trig == 1, 6] == 60).all() and (info[trig == 0, 6] == 75).all()
     # --- the restored worlds keep simulating identically (joints, locks, RNG state restored)
     ctrl.zero_(); ref.tensor("ckpt_ctrl")[:] = 0
-    drive(sim, ref, gt, 40, "full", check_every=10, seed=3)
+    p.drive(40, "full", every=10, seed=3)
 
 
 def test_restore_replays_the_same_trajectory(oracle):
     """Size-independent property: save, run k steps, load, re-run the same actions -> identical outputs."""
     import torch
-    sim, ref, gt = make_pair(oracle, 512, seed=21)
-    ref.close()
+    p = Pair(512, seed=21)
+    p.ref.close()
+    sim = p.sim
+    gt = {k: p.gpu.view(k) for k in NAMES}
     ctrl, ck = _ckpt_views(sim)
     rng = np.random.default_rng(5)
     acts = torch.from_numpy(rng.integers(0, 11, size=(30, 512 * 4, 3)).astype(np.int32)).cuda()
@@ -94,18 +97,19 @@ def test_restore_replays_the_same_trajectory(oracle):
 
 def test_single_world_save_and_load(oracle):
     import torch
-    sim, ref, gt = make_pair(oracle, 16, seed=2)
+    p = Pair(16, seed=2)
+    sim, ref = p.sim, p.ref
     ctrl, ck = _ckpt_views(sim)
-    drive(sim, ref, gt, 5, "bench", check_every=5)
+    p.drive(5, "bench", every=5)
     sim.save_checkpoint(3)
     rec = ck.cpu().numpy()
     assert rec[3].any() and not rec[np.arange(16) != 3].any()
     ref.tensor("ckpt_ctrl")[3] = 1; ref.save_checkpoints()
     assert np.array_equal(rec, ref.tensor("ckpt"))
-    drive(sim, ref, gt, 5, "bench", check_every=5)
+    p.drive(5, "bench", every=5)
     sim.load_checkpoint(3)
     ref.tensor("ckpt_ctrl")[3] = 1; ref.load_checkpoints()
-    assert_equal_state(sim, ref, gt, "single-world load")
+    p.check("single-world load")
     with pytest.raises(ValueError):
         sim.save_checkpoint(16)
 
@@ -119,16 +123,14 @@ def test_stream_entry_points_match_blocking_api(oracle):
               min_hiders=2, max_hiders=2, min_seekers=2, max_seekers=2, num_pbt_policies=1)
     a = gpu_hideseek.HideAndSeekSimulator(**kw)
     b = gpu_hideseek.HideAndSeekSimulator(**kw)
-    obs_names = ["prep_counter", "self_data", "self_type", "self_mask", "lidar", "agent_data", "box_data", "ramp_data",
-                 "visible_agents_mask", "visible_boxes_mask", "visible_ramps_mask"]
     at = {k: getattr(a, k + "_tensor")().to_torch() for k in NAMES}
     bt = {k: getattr(b, k + "_tensor")().to_torch() for k in NAMES}
-    obs = [torch.zeros_like(bt[k]) for k in obs_names]
+    obs = [torch.zeros_like(bt[k]) for k in OBS]
     rew, done, epres = torch.zeros_like(bt["reward"]), torch.zeros_like(bt["done"]), torch.zeros_like(bt["episode_result"])
     strm = torch.cuda.Stream()
     a.init()
     b.stream_init(strm.cuda_stream, obs)
-    for k, o in zip(obs_names, obs):
+    for k, o in zip(OBS, obs):
         assert torch.equal(o.view(torch.int32), at[k].view(torch.int32)), k
     rng = np.random.default_rng(0)
     for t in range(6):
@@ -143,7 +145,7 @@ def test_stream_entry_points_match_blocking_api(oracle):
         strm.wait_stream(torch.cuda.current_stream())
         b.stream_step(strm.cuda_stream, [act, resets, pol] + obs + [rew, done, epres])
         strm.synchronize()
-        for k, o in zip(obs_names + ["reward", "done", "episode_result"], obs + [rew, done, epres]):
+        for k, o in zip(OBS + ["reward", "done", "episode_result"], obs + [rew, done, epres]):
             assert torch.equal(o.view(torch.int32), at[k].view(torch.int32)), (t, k)
     # checkpoints through the stream functions
     ctrl = torch.ones(64, 1, dtype=torch.int32, device="cuda")
@@ -157,7 +159,7 @@ def test_stream_entry_points_match_blocking_api(oracle):
     b.stream_load_checkpoints(strm.cuda_stream, [ctrl, ckpts] + obs); strm.synchronize()
     a.ckpt_ctrl_tensor().to_torch().view(torch.int32)[:] = 1
     a.load_checkpoints()
-    for k, o in zip(obs_names, obs):
+    for k, o in zip(OBS, obs):
         assert torch.equal(o.view(torch.int32), at[k].view(torch.int32)), k
     assert np.array_equal(bits(a.debug_bodies()[0]), bits(b.debug_bodies()[0]))
     with pytest.raises(ValueError):
@@ -244,8 +246,10 @@ def test_replay_log_round_trip(oracle, tmp_path):
     import gpu_hideseek
     from gpu_hideseek import replay
     n = 24
-    sim, ref, gt = make_pair(oracle, n, seed=6)
-    ref.close()
+    p = Pair(n, seed=6)
+    p.ref.close()
+    sim = p.sim
+    gt = {k: p.gpu.view(k) for k in ("action", "self_data", "lidar", "global_positions")}
     path = tmp_path / "run.log"
     rng = np.random.default_rng(3)
     seen = []
@@ -276,9 +280,10 @@ def test_unbounded_episode_step_does_not_corrupt_the_prep_counter(oracle):
     the reference does after step 96 (src/sim.cpp:461-463), instead of wrapping into the preparation phase again."""
     import torch
     n = 16
-    sim, ref, gt = make_pair(oracle, n, flags=2, seed=4)
+    p = Pair(n, flags=2, seed=4)
+    sim, ref = p.sim, p.ref
     ctrl, ck = _ckpt_views(sim)
-    drive(sim, ref, gt, 3, "bench", check_every=3)
+    p.drive(3, "bench", every=3)
     ctrl.view(torch.int32)[:] = 1
     ref.tensor("ckpt_ctrl")[:] = 1
     sim.save_checkpoints(); ref.save_checkpoints()
@@ -290,7 +295,7 @@ def test_unbounded_episode_step_does_not_corrupt_the_prep_counter(oracle):
         ref.tensor("ckpt_ctrl")[:] = 1
         sim.load_checkpoints(); ref.load_checkpoints()
         ctrl.zero_(); ref.tensor("ckpt_ctrl")[:] = 0
-        assert_equal_state(sim, ref, gt, f"loaded at step {step}")
-        drive(sim, ref, gt, 2, "bench", check_every=1)
+        p.check(f"loaded at step {step}")
+        p.drive(2, "bench", every=1)
         _, info = sim.debug_walls()
         assert (info[:, 6] == step + 2).all()

@@ -5,34 +5,9 @@ reference snapshot; what the image must show follows from first-party source in 
 import numpy as np
 import pytest
 
-from test_gpu_parity import NAMES, bits, drive
+from lockstep import EXT_RENDER, Pair
 
 pytestmark = pytest.mark.gpu
-
-EXT_RENDER = 1 << 17
-
-
-def make(oracle, n, flags, seed, hiders, seekers, W, H, render=True):
-    import gpu_hideseek
-    sim = gpu_hideseek.HideAndSeekSimulator(
-        exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=0, num_worlds=n, sim_flags=flags, rand_seed=seed,
-        min_hiders=hiders[0], max_hiders=hiders[1], min_seekers=seekers[0], max_seekers=seekers[1],
-        num_pbt_policies=1, enable_batch_renderer=render, batch_render_width=W, batch_render_height=H)
-    ref = oracle.RefSim(n, sim_flags=flags & 0xffff, rand_seed=seed, min_hiders=hiders[0], max_hiders=hiders[1],
-                        min_seekers=seekers[0], max_seekers=seekers[1], threads=8)
-    gt = {k: getattr(sim, k + "_tensor")().to_torch() for k in NAMES}
-    sim.init(); ref.init()
-    return sim, ref, gt
-
-
-def assert_views_equal(sim, ref, W, H, tag):
-    d = sim.depth_tensor().to_torch().cpu().numpy()
-    c = sim.rgb_tensor().to_torch().cpu().numpy()
-    rd, rc = ref.render(W, H)
-    assert d.shape == rd.shape and c.shape == rc.shape and c.dtype == np.uint8
-    assert np.array_equal(c, rc), f"{tag}: rgb differs in {np.argwhere(c != rc)[:3]}"
-    assert np.array_equal(bits(d), bits(rd)), f"{tag}: depth differs in {np.argwhere(bits(d) != bits(rd))[:3]}"
-    return d, c
 
 
 @pytest.mark.parametrize("cfg", [
@@ -43,18 +18,19 @@ def assert_views_equal(sim, ref, W, H, tag):
 def test_render_on_request_matches_oracle(oracle, cfg):
     """sim.render() after init and after driven steps (boxes pushed around, ramps, locked / grabbed bodies)."""
     W, H = cfg["W"], cfg["H"]
-    sim, ref, gt = make(oracle, cfg["n"], cfg["flags"], cfg["seed"], cfg["hiders"], cfg["seekers"], W, H)
+    p = Pair(cfg["n"], cfg["flags"], cfg["seed"], cfg["hiders"], cfg["seekers"], render=(W, H))
+    sim = p.sim
     # with the reference scripts' arguments the outputs exist and stay unwritten (scripts/benchmark.py:32,47)
     assert not sim.depth_tensor().to_torch().any() and not sim.rgb_tensor().to_torch().any()
     sim.render()
-    d, c = assert_views_equal(sim, ref, W, H, "init")
+    d, c = p.check_views(W, H, "init")
     assert d.any() and (c[..., 3] == 255).any()
     for chunk in range(3):
-        drive(sim, ref, gt, 40, cfg["mode"], seed=chunk, check_every=40)
+        p.drive(40, cfg["mode"], seed=chunk, every=40)
         sim.render()
-        assert_views_equal(sim, ref, W, H, f"chunk {chunk}")
+        p.check_views(W, H, f"chunk {chunk}")
     if cfg["hiders"][0] != cfg["hiders"][1]:
-        mask = ref.tensor("self_mask").reshape(-1)
+        mask = p.ref.tensor("self_mask").reshape(-1)
         d = sim.depth_tensor().to_torch().cpu().numpy()
         assert (mask == 0).any() and not d[mask == 0].any()
 
@@ -62,35 +38,32 @@ def test_render_on_request_matches_oracle(oracle, cfg):
 def test_render_every_step_under_the_extension_flag(oracle):
     """SimFlags.ExtRender: init and every step leave the views of the new state in the tensors — across an episode end
     (level regeneration) and a host-triggered reset — also through the stream entry point."""
-    import torch
     W, H = 32, 32
-    sim, ref, gt = make(oracle, 12, EXT_RENDER, 2, (2, 2), (2, 2), W, H)
-    assert_views_equal(sim, ref, W, H, "init")
+    p = Pair(12, EXT_RENDER, 2, render=(W, H))
+    sim, ref = p.sim, p.ref
+    p.check_views(W, H, "init")
     rng = np.random.default_rng(0)
     for t in range(245):
-        act = ref.tensor("action").copy()
-        act[:, 0:3] = rng.integers(0, 11, size=(act.shape[0], 3))
-        ref.tensor("action")[:] = act
-        gt["action"].copy_(torch.from_numpy(act).cuda())
+        p.act(rng.integers(0, 11, size=(p.rows, 3)), cols=(0, 1, 2))
         if t == 100:
-            ref.tensor("reset")[3] = 1; gt["reset"][3] = 1
+            ref.tensor("reset")[3] = 1; p.gpu.view("reset")[3] = 1
         if t % 2:
             sim.step()
         else:
             sim.step_begin(); sim.step_end()
         ref.step()
         if t % 40 == 0 or t in (100, 101, 239, 240, 241):
-            assert_views_equal(sim, ref, W, H, f"step {t}")
+            p.check_views(W, H, f"step {t}")
 
 
 def test_flag_needs_the_renderer_and_default_stays_dummy(oracle):
     """ExtRender without enable_batch_renderer renders nothing; the tensors can still be taken (cpu_benchmark.py:38
     asks for rgb with the renderer off) and render() fills them on request."""
-    sim, ref, gt = make(oracle, 4, EXT_RENDER, 1, (2, 2), (2, 2), 64, 64, render=False)
-    sim.step(); ref.step()
-    assert not sim.rgb_tensor().to_torch().any()
-    sim.render()
-    assert_views_equal(sim, ref, 64, 64, "on request")
+    p = Pair(4, EXT_RENDER, 1)
+    p.step()
+    assert not p.sim.rgb_tensor().to_torch().any()
+    p.sim.render()
+    p.check_views(64, 64, "on request")
 
 
 def test_view_culls_lose_no_hit_over_many_worlds(oracle):
@@ -98,9 +71,9 @@ def test_view_culls_lose_no_hit_over_many_worlds(oracle):
     rays leave the walls' height range; the oracle tests every ray against everything.  1 536 views of 384 different
     levels at two moments of the episode, every pixel equal."""
     W, H = 40, 24
-    sim, ref, gt = make(oracle, 384, 0, 77, (2, 2), (2, 2), W, H)
-    sim.render()
-    assert_views_equal(sim, ref, W, H, "init")
-    drive(sim, ref, gt, 130, "bench", seed=5, check_every=130)
-    sim.render()
-    assert_views_equal(sim, ref, W, H, "step 130")
+    p = Pair(384, 0, 77, render=(W, H))
+    p.sim.render()
+    p.check_views(W, H, "init")
+    p.drive(130, "bench", seed=5, every=130)
+    p.sim.render()
+    p.check_views(W, H, "step 130")

@@ -36,34 +36,19 @@ print("STATUS", st["spilled_dd_pairs"], st["spilled_static_pairs"], int(st["grap
 # the physics feeds and the body state, bit for bit, at several steps.  hiders / seekers 3 + 3 with grab / lock actions
 # exercises joints, locked (static) boxes and the third round of bodies together with the spill path.
 PARITY_LOOP = """
-import sys, hashlib, numpy as np, torch, gpu_hideseek
+import numpy as np
 sys.path.insert(0, %r)
-import hs_ref
+import lockstep
 N, H, K, FLAGS, STEPS = %d, %d, %d, %d, %d
-sim = gpu_hideseek.HideAndSeekSimulator(exec_mode=1, gpu_id=0, num_worlds=N, sim_flags=FLAGS, rand_seed=21, min_hiders=1,
-      max_hiders=H, min_seekers=1, max_seekers=K, num_pbt_policies=1)
-ref = hs_ref.RefSim(N, sim_flags=FLAGS, rand_seed=21, min_hiders=1, max_hiders=H, min_seekers=1, max_seekers=K, threads=8)
-sim.init(); ref.init()
-act = sim.action_tensor().to_torch()
 rng = np.random.default_rng(4)
-h = hashlib.sha256()
-for s in range(STEPS):
-    a = ref.tensor("action")
-    lo, hi = (0, 5) if FLAGS & 8 else (0, 11)
-    a[:, 0:3] = rng.integers(lo, hi, size=(a.shape[0], 3)); a[:, 3:5] = rng.integers(0, 2, size=(a.shape[0], 2)) * (rng.random((a.shape[0], 2)) < 0.2)
-    act.copy_(torch.from_numpy(a.copy()).to(act.device))
-    sim.step(); ref.step()
-    if s %% 6 == 5 or s == STEPS - 1:
-        gb, gm = sim.debug_bodies(); rb, rm = ref.bodies()
-        assert np.array_equal(gm, rm), ("meta", s)
-        bad = np.argwhere(gb.view(np.int32) != rb.view(np.int32))
-        assert bad.size == 0, ("bodies", s, bad[:5].tolist())
-        for n in ("self_data", "agent_data", "box_data", "ramp_data", "lidar", "reward", "done", "visible_boxes_mask", "global_positions"):
-            g = getattr(sim, n + "_tensor")().to_torch().cpu().numpy().reshape(ref.tensor(n).shape)
-            assert np.array_equal(g.view(np.int32), ref.tensor(n).view(np.int32)), (n, s)
-        h.update(gb.tobytes())
-st = sim.device_status()
-print("PARITY", h.hexdigest(), st["spilled_dd_pairs"], st["spilled_static_pairs"], st["dropped_candidate_pairs"])
+hi = 5 if FLAGS & 8 else 11
+act = lambda s, rows: np.concatenate([rng.integers(0, hi, size=(rows, 3)),
+                                      rng.integers(0, 2, size=(rows, 2)) * (rng.random((rows, 2)) < 0.2)], axis=1)
+p = lockstep.Pair(N, flags=FLAGS, seed=21, hiders=(1, H), seekers=(1, K))
+digest = p.drive(STEPS, act, every=6, walls=False, digest=True, names=("self_data", "agent_data", "box_data", "ramp_data", "lidar",
+                 "reward", "done", "visible_boxes_mask", "global_positions"))
+st = p.sim.device_status()
+print("PARITY", digest, st["spilled_dd_pairs"], st["spilled_static_pairs"], st["dropped_candidate_pairs"])
 """
 
 

@@ -147,7 +147,7 @@ def test_train_interface_names_roles_and_order(hideseek_lib):
     for _, _, g in tab:
         assert g is None or callable(getattr(gpu_hideseek.HideAndSeekSimulator, g))
     # the observation block is also the buffer order of the stream entry points (mgr.cpp:183-197, 351-362)
-    from test_gpu_configs import OBS
+    from lockstep import OBS
     assert [by[n][1][:-len("_tensor")] for n in OBS_NAMES] == OBS
 
 
