@@ -270,9 +270,6 @@ int32_t hs_debug_phase_ticks(hs_sim *sim, int64_t *out, int32_t max_groups);
 /* The same for k_observe: ticks per section, summed over all waves: stage (incl. the schedule's wait), per-agent table,
  * ray setup, walls, planes, hull cull, exact hull tests, ray results, observation rows. */
 int32_t hs_debug_observe_ticks(hs_sim *sim, int64_t out[16]);
-/* ... and the work counters of the convex tests, summed over all waves and substeps: calls, box-shaped items, wedge
- * items, rounds of 32 pairs, colliding pairs, contact-generation rounds. */
-int32_t hs_debug_sat_counters(hs_sim *sim, int64_t out[16]);
 
 /* The DEVICE's hull tables for one SimObject (src/sim.hpp:78-88; 3 = wall, unit size), evaluated by a one-lane kernel through
  * the very functions the convex tests use (csrc/hs_collide.h: packed topology, closed-form vertices) at the identity

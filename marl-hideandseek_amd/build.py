@@ -51,8 +51,8 @@ def build_smallcap(force=False):
 TIMING_LIB = os.path.join(HERE, "lib", "libhideseek_timing.so")
 
 
-def build_timing(force=False, counters=False):
-    return build_lib(force=force, out=TIMING_LIB, defines=("HS_PHASE_TIMING",) + (("HS_SAT_COUNTERS",) if counters else ()))
+def build_timing(force=False):
+    return build_lib(force=force, out=TIMING_LIB, defines=("HS_PHASE_TIMING",))
 
 
 def build_headless():
@@ -71,4 +71,4 @@ if __name__ == "__main__":
     print(build_headless())
     print(build_smallcap(force="--force" in sys.argv))
     if "--timing" in sys.argv:
-        print(build_timing(force="--force" in sys.argv, counters="--sat-counters" in sys.argv))
+        print(build_timing(force="--force" in sys.argv))

@@ -261,7 +261,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     // (every possible pair of every world: 92 KB per world, 1.5 GB at 16 000 worlds, of which a step touches a few MB)
     { char *p; HS_ALLOC(p, NP * hs::kAllDD * sizeof(hs::ManDD)); S.wsDD = p; HS_ALLOC(p, NP * hs::kAllSC * sizeof(hs::ManS)); S.wsSC = p; }
     HS_ALLOC(S.spPair, NP * (hs::kAllDD + hs::kAllSC)); HS_ALLOC(S.spInfo, NP * hs::kSpInfoWords);
-    HS_ALLOC(S.phaseTicks, hs::phase_ticks_obs_base((int)N) + 16 * 1024 + 16);   // + k_observe's section counters + the convex tests' counters
+    HS_ALLOC(S.phaseTicks, hs::phase_ticks_obs_base((int)N) + 16 * 1024);   // + k_observe's section counters
     HS_ALLOC(S.slotOfWorld, N); HS_ALLOC(S.worldOfSlot, NP); HS_ALLOC(S.loadAcc, N); HS_ALLOC(S.wallHist, N);
     if ((rc = s->dalloc(&S.slotHdr, NP, 0xFF)) != HS_OK) { hs_destroy(s); return rc; }      // world id -1: empty slot
     HS_ALLOC(S.lidarSinCos, 60);
@@ -611,13 +611,6 @@ int32_t hs_debug_observe_ticks(hs_sim *s, int64_t out[16]) {
     HS_HIP(hipMemcpy(part.data(), s->S.phaseTicks + hs::phase_ticks_obs_base(s->S.N), part.size() * sizeof(int64_t),
                      hipMemcpyDeviceToHost));
     for (int i = 0; i < 16; ++i) { out[i] = 0; for (int b = 0; b < 1024; ++b) out[i] += part[(size_t)b * 16 + i]; }
-    return HS_OK;
-}
-// ... and the work counters of the convex tests: calls, box items, wedge items, rounds, colliding pairs, contact rounds.
-int32_t hs_debug_sat_counters(hs_sim *s, int64_t out[16]) {
-    if (!s || !out) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    HS_HIP(hipMemcpy(out, s->S.phaseTicks + hs::phase_ticks_obs_base(s->S.N) + 16 * 1024, 16 * sizeof(int64_t), hipMemcpyDeviceToHost));
     return HS_OK;
 }
 

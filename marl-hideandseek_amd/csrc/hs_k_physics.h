@@ -457,8 +457,28 @@ HSD ItemCounts phase_detect(const SimState &S, OctRes &R, int NS) {
 }
 
 // ------------------------------------------------------------------------------------------
+// One static manifold `m` (a wall or an extra plane) of body `me`, for wall_round and spill_static: the position pass hands
+// each point's new normal multiplier to set_lam(j, value), the velocity pass reads them.  UNROLL 4: `m` is a copy in
+// registers.  UNROLL 1: `m` is the record in the global workspace, read field by field (cold code: a private copy indexed
+// by j would live in scratch memory).
+template <bool POS, int UNROLL, typename SetLam>
+HSD void static_manifold(BodyS &me, const ManS &m, SetLam set_lam) {
+    BodyS none;
+    body_refresh_inertia(me);
+    const V3 n = ld3(m.n);
+    const int np = m.np;
+    const float mu = POS ? m.muS : m.muD;
+#pragma unroll UNROLL
+    for (int j = 0; j < 4; ++j)
+        if (j < np) {
+            const float lamj = m.lam[j];
+            if (POS) set_lam(j, lamj + solve_point_position<false>(me, none, n, ld3(m.rA[j]), V3{0.f, 0.f, 0.f}, m.offB[j], mu));
+            else solve_point_velocity<false>(me, none, n, ld3(m.rA[j]), V3{0.f, 0.f, 0.f}, lamj, mu);
+        }
+}
+
+// ------------------------------------------------------------------------------------------
 // The SPILL PATH: candidate pairs beyond the LDS capacities.  Cold code behind wave-uniform branches.
-// (Template parameter SPILL of the phases: false compiles the spill path out — the register report of the fast path alone.)
 #define HS_COLD __device__ __forceinline__
 struct SpillCtx {
     const float *walls, *planes;         // the tiled columns (hs_state.h Col)
@@ -601,46 +621,18 @@ HS_COLD void spill_static(SpillCtx c, OctRes *Rp, int NS) {
         const int info = c.spInfo[(size_t)w * kSpInfoWords + 1 + slot];
         const int first = info & 0xffff, cnt = info >> 16;
         if (cnt == 0) continue;
-        BodyS me, none;
+        BodyS me;
         rbody_load(R, g, slot, me);
 #pragma unroll 1
         for (int k = first; k < first + cnt; ++k) {
-            ManS *const m = c.wsSC + (size_t)w * kAllSC + k;
-            const int np = m->np;
-            if (np <= 0) continue;
-            body_refresh_inertia(me);
-            const V3 n = ld3(m->n);
-            const float mu = POS ? m->muS : m->muD;
-#pragma unroll 1
-            for (int j = 0; j < np; ++j) {
-                const float lamj = m->lam[j];
-                if (POS) m->lam[j] = lamj + solve_point_position<false>(me, none, n, ld3(m->rA[j]), V3{0.f, 0.f, 0.f}, m->offB[j], mu);
-                else solve_point_velocity<false>(me, none, n, ld3(m->rA[j]), V3{0.f, 0.f, 0.f}, lamj, mu);
-            }
+            ManS &m = c.wsSC[(size_t)w * kAllSC + k];
+            if (m.np <= 0) continue;
+            static_manifold<POS, 1>(me, m, [&](int j, float v) { m.lam[j] = v; });
         }
         if (POS) rbody_store_pose(R, g, slot, me); else rbody_store_vel(R, g, slot, me);
     }
 }
 
-#ifdef HS_PHASE_TIMING
-#define HS_TICK_PARAMS , long long &tk, long long (&acc)[10]
-#define HS_TICK_ARGS , tk, acc
-#define HS_TICK(i) { const long long now_ = wall_clock64(); acc[i] += now_ - tk; tk = now_; }
-#else
-#define HS_TICK_PARAMS
-#define HS_TICK_ARGS
-#define HS_TICK(i)
-#endif
-// HS_FINE_TIMING (with HS_PHASE_TIMING; development aid): the ten slots are re-assigned to look inside the convex tests —
-// 0 everything before them, 1 axis search of the box rounds, 2 of the wedge rounds, 3 pending-list upkeep, 4 contact
-// generation, 5 manifold records, 6 dd_pos, 7 static position passes, 8 the rest of the substep, 9 post / load / store.
-#ifdef HS_FINE_TIMING
-#define HS_FTICK(i) HS_TICK(i)
-#define HS_CTICK(i, j) HS_TICK(j)
-#else
-#define HS_FTICK(i)
-#define HS_CTICK(i, j) HS_TICK(i)
-#endif
 // ------------------------------------------------------------------------------------------
 // Exact convex tests, in two stages (hs_collide.h).  Stage 1 — the separating-axis search — runs over all the
 // octet's candidate pairs, two lanes per pair (2k and 2k + 1), 32 pairs per round; the pairs that collide are appended
@@ -655,7 +647,7 @@ HSD HullSrc sat_hull_b(const SimState &S, const OctRes &R, int g, int w, bool is
 }
 // stage 2 for the first `npend` pending pairs: lane i < 32 takes pair i.  `last`: this is the substep's last round,
 // whose manifolds stay in LDS (in the lane's own clip column); returns whether a manifold went to global memory.
-HSD bool sat_flush(const SimState &S, OctRes &R, int npend, bool last HS_TICK_PARAMS) {
+HSD bool sat_flush(const SimState &S, OctRes &R, int npend, bool last) {
     const int lane = hs_lane() & 63;
     const bool toLds = last && lane < OctRes::kSlots;
     bool wroteGlobal = false;
@@ -722,7 +714,6 @@ HSD bool sat_flush(const SimState &S, OctRes &R, int npend, bool last HS_TICK_PA
     }
     // every lane is done with its clipping scratch: the slots may overwrite it
     wave_sync(); __builtin_amdgcn_wave_barrier();
-    HS_FTICK(4)
     if (mkind != 0) {
         int4 *dst = reinterpret_cast<int4 *>(R.u.sat.clip + lane * kManWords);
 #pragma unroll
@@ -736,31 +727,22 @@ HSD bool sat_flush(const SimState &S, OctRes &R, int npend, bool last HS_TICK_PA
         }
     }
     wave_sync();
-    HS_FTICK(5)
     return __ballot(wroteGlobal) != 0ull;
 }
 // Returns whether any manifold of the substep lies in the global workspace (wave-uniform): only then do the solver
 // phases have to wait for global memory at all.
-template <bool SPILL>
-HSD bool phase_sat(const SimState &S, OctRes &R, ItemCounts ic HS_TICK_PARAMS) {
+HSD bool phase_sat(const SimState &S, OctRes &R, ItemCounts ic) {
     const int wedge0 = (ic.nbox + 31) / 32 * 32;
     const int lane = hs_lane() & 63;
     const bool hi = (lane & 1) != 0;                  // the second lane of a pair (box rounds: lanes 2k, 2k + 1)
     int npend = 0;
     bool usedGlobal = false;
-    int nhit_total = 0, nflush = 0;      // (counters of the HS_PHASE_TIMING build)
-#ifdef HS_SAT_COUNTERS
-    long long tflush = 0, twedge = 0; const long long tsat0 = wall_clock64();
-#define HS_SAT_T(x) x
-#else
-#define HS_SAT_T(x)
-#endif
     // rounds over the box-only items, 2 lanes per pair and 32 pairs per round, then over the items with a wedge, 16 lanes
     // per pair and 4 pairs per round (sat_axes_wide); `lead`: the lane of a pair that files its result
     const int boxRounds = (ic.nbox + OctRes::kSatPairs - 1) / OctRes::kSatPairs, wedgeRounds = (ic.nwedge + 3) / 4;
     // (pairs beyond the LDS capacities, if any world of the octet has them: tested and turned into manifolds first, while
     // the clip buffers are free)
-    if (SPILL && __builtin_expect(ic.anySpill, 0)) { spill_sat(spill_ctx(S), &R); usedGlobal = true; }
+    if (__builtin_expect(ic.anySpill, 0)) { spill_sat(spill_ctx(S), &R); usedGlobal = true; }
     // The axis-search rounds and the contact rounds alternate as two plain loops — as many axis-search rounds as the pending
     // list (OctRes::kClip entries) is sure to hold, then one contact round — instead of a contact round nested inside the
     // axis-search loop: the two bodies never share registers.  (A round files at most as many pairs as it has items.)
@@ -768,7 +750,6 @@ HSD bool phase_sat(const SimState &S, OctRes &R, ItemCounts ic HS_TICK_PARAMS) {
     int round = 0;
     while (round < totalRounds) {
     for (; round < totalRounds; ++round) {
-        HS_SAT_T(const long long tr0_ = wall_clock64();)
         const bool wide = round >= boxRounds;
         {
             const int itemsHere = wide ? min(4, wedge0 + ic.nwedge - (wedge0 + (round - boxRounds) * 4)) : min(OctRes::kSatPairs, ic.nbox - round * OctRes::kSatPairs);
@@ -796,36 +777,21 @@ HSD bool phase_sat(const SimState &S, OctRes &R, ItemCounts ic HS_TICK_PARAMS) {
                 res = sat_axes(sat_hull_a(R, g, a), sat_hull_b(S, R, g, w, isdd, bsel), hi);
             }
         }
-        HS_SAT_T(if (wide) twedge += wall_clock64() - tr0_;)
-#ifdef HS_FINE_TIMING
-        if (wide) HS_TICK(2) else HS_TICK(1)
-#endif
         // the colliding pairs of this round join the pending list (their lead lanes file the results)
         const bool hit = lead && res.code != 0;
         const unsigned long long m = __ballot(hit);
         const int nhit = __popcll(m);
-        nhit_total += nhit;
         if (hit) {
             const int pos = npend + __popcll(m & ((1ull << lane) - 1ull));
             R.u.sat.pend[0][pos] = item | (res.code << 16);         // (item < 2^9, axis code < 2^12)
             R.u.sat.pend[1][pos] = __float_as_int(res.ax.x); R.u.sat.pend[2][pos] = __float_as_int(res.ax.y); R.u.sat.pend[3][pos] = __float_as_int(res.ax.z);
         }
         npend += nhit;
-        HS_FTICK(3)
     }
     wave_sync();
-    if (npend > 0) { HS_SAT_T(const long long t0_ = wall_clock64();) usedGlobal |= sat_flush(S, R, npend, round >= totalRounds HS_TICK_ARGS); HS_SAT_T(tflush += wall_clock64() - t0_;) ++nflush; npend = 0; }
+    if (npend > 0) { usedGlobal |= sat_flush(S, R, npend, round >= totalRounds); npend = 0; }
     }
     if (usedGlobal) mem_sync();          // the manifolds in global memory are complete for the lanes that solve them
-#ifdef HS_SAT_COUNTERS
-    if (lane == 0) {      // work counters of the convex tests (tools/phase_timing.py; their atomics disturb the phase times)
-        unsigned long long *c = (unsigned long long *)S.phaseTicks + phase_ticks_obs_base(S.N) + 16 * 1024;
-        atomicAdd(&c[0], 1ull); atomicAdd(&c[1], (unsigned long long)ic.nbox); atomicAdd(&c[2], (unsigned long long)ic.nwedge);
-        atomicAdd(&c[3], (unsigned long long)(boxRounds + wedgeRounds)); atomicAdd(&c[4], (unsigned long long)nhit_total);
-        atomicAdd(&c[5], (unsigned long long)nflush);
-        atomicAdd(&c[6], (unsigned long long)tflush); atomicAdd(&c[7], (unsigned long long)(wall_clock64() - tsat0)); atomicAdd(&c[8], (unsigned long long)twedge);
-    }
-#endif
     return usedGlobal;
 }
 
@@ -956,7 +922,7 @@ HSD void pair_point_velocity(BodyS &me, bool isA, V3 n, V3 rl, float lamN, float
     else { me.lin = nmadd(me.lin, p, me.invM); me.ang = me.ang - da; }
 }
 
-template <bool POS, bool SPILL>
+template <bool POS>
 HSD void phase_dd(const SimState &S, OctRes &R, bool anySpill) {
     constexpr int GL = kWorldLanes, PAIRS = GL / 2;               // lanes per world; manifolds of a world in flight at once
     const int L = hs_lane(), g = L / GL, q = L % GL;
@@ -966,7 +932,7 @@ HSD void phase_dd(const SimState &S, OctRes &R, bool anySpill) {
     const int w = S.wbeg + g;                                     // the world's slot in the tiled columns
     const int ndd = R.ndd[g];
     const bool grab = R.hasGrab[g] != 0;
-    if (!(SPILL && anySpill) && __ballot(R.ddAcc[g] != 0u || (POS && grab)) == 0ull) return;        // nothing to do in the whole octet
+    if (!anySpill && __ballot(R.ddAcc[g] != 0u || (POS && grab)) == 0ull) return;        // nothing to do in the whole octet
     if (POS && grab && q == 0) {
         const int teams = S.teams[R.wid[g]];
         for (int a = 0; a < kMaxAgents; ++a) {
@@ -1058,7 +1024,7 @@ HSD void phase_dd(const SimState &S, OctRes &R, bool anySpill) {
     }
     wave_sync();
     // (the world's SPILLED body-body pairs come after every pair above in pair order)
-    if (SPILL && __builtin_expect(anySpill, 0)) { spill_dd<POS>(spill_ctx(S), &R); wave_sync(); }
+    if (__builtin_expect(anySpill, 0)) { spill_dd<POS>(spill_ctx(S), &R); wave_sync(); }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1128,7 +1094,7 @@ HSD void wall_round(const SimState &S, OctRes &R, int first, int nwb) {
         const int bsc = sci & 0xff, asc = sci >> 8;
         const unsigned acc = R.scAcc[g];
         ManS *const wsSC = (ManS *)S.wsSC + (size_t)(S.wbeg + g) * kAllSC;
-        BodyS me, none;
+        BodyS me;
         rbody_load(R, g, slot, me);
         // the body's ACCEPTED candidates in candidate order, a lane at its own pace: a trip of the loop is a whole manifold
         // solve for the wave, so the trips are the largest number of manifolds any listed body has (mostly one), not
@@ -1141,20 +1107,9 @@ HSD void wall_round(const SimState &S, OctRes &R, int first, int nwb) {
             const int loc = pair_loc(R.scPair[k][g]);
             ManS m;
             if (loc != kLocGlobal) man_lds_load(R.u.sat.clip, loc, m); else m = wsSC[k];
-            body_refresh_inertia(me);
-            const V3 n = ld3(m.n);
-            if (POS) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < m.np) {
-                        const float lam = m.lam[j] + solve_point_position<false>(me, none, n, ld3(m.rA[j]), V3{0.f, 0.f, 0.f}, m.offB[j], m.muS);
-                        if (loc != kLocGlobal) man_lds_set_lam<ManS>(R.u.sat.clip, loc, j, lam); else wsSC[k].lam[j] = lam;
-                    }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < m.np) solve_point_velocity<false>(me, none, n, ld3(m.rA[j]), V3{0.f, 0.f, 0.f}, m.lam[j], m.muD);
-            }
+            static_manifold<POS, 4>(me, m, [&](int j, float v) {
+                if (loc != kLocGlobal) man_lds_set_lam<ManS>(R.u.sat.clip, loc, j, v); else wsSC[k].lam[j] = v;
+            });
         }
         if (POS) rbody_store_pose(R, g, slot, me); else rbody_store_vel(R, g, slot, me);
     }
@@ -1431,18 +1386,28 @@ HSD void static_passes(const SimState &S, OctRes &R, BodyReg (&br)[ROUNDS], int 
     wave_sync();
 }
 
+// HS_PHASE_TIMING (development aid): wall-clock ticks of the ten phases of include/hideseek.h hs_debug_phase_ticks.
+#ifdef HS_PHASE_TIMING
+#define HS_TICK_PARAMS , long long &tk, long long (&acc)[10]
+#define HS_TICK_ARGS , tk, acc
+#define HS_TICK(i) { const long long now_ = wall_clock64(); acc[i] += now_ - tk; tk = now_; }
+#else
+#define HS_TICK_PARAMS
+#define HS_TICK_ARGS
+#define HS_TICK(i)
+#endif
 // What follows the broadphase in a substep: convex tests -> body-body position solve -> static position passes ->
 // velocities from the pose change -> body-body and static velocity passes (-> integration for the next substep).
 #define HS_BODY(r) const bool valid = (r) * 64 + L < nbodies; const int t_ = valid ? R.bodies[(r) * 64 + L] : 0; \
                    const int slot = t_ >> 3, g = t_ & 7; const int meta = valid ? R.meta[slot][g] : 0;
-template <int ROUNDS, bool SPILL>
+template <int ROUNDS>
 HSD void substep_rest(const SimState &S, OctRes &R, BodyReg (&br)[ROUNDS], int nbodies, int NS, ItemCounts ic, bool integrateNext,
                       const float *aforce HS_TICK_PARAMS) {
     const int L = hs_lane();
-    const bool manGlobal = phase_sat<SPILL>(S, R, ic HS_TICK_ARGS);
-    HS_CTICK(3, 3)
-    phase_dd<true, SPILL>(S, R, ic.anySpill);
-    HS_CTICK(4, 6)
+    const bool manGlobal = phase_sat(S, R, ic);
+    HS_TICK(3)
+    phase_dd<true>(S, R, ic.anySpill);
+    HS_TICK(4)
     // (with 6 agents a third round exists for up to 136 bodies, but an octet rarely holds more than 128: then round 1 is
     // the last one that holds bodies, and the passes are two, not three)
     constexpr int kShortLastR = ROUNDS - 2;
@@ -1454,23 +1419,23 @@ HSD void substep_rest(const SimState &S, OctRes &R, BodyReg (&br)[ROUNDS], int n
     if (shortLast) static_passes<ROUNDS, kShortLastR, true>(S, R, br, nbodies, nLast, nMerged);
     else static_passes<ROUNDS, ROUNDS - 1, true>(S, R, br, nbodies, nLast, nMerged);
     if (wl.nwb > nMerged) { wall_round<true>(S, R, nMerged, wl.nwb); wave_sync(); }
-    if (SPILL && __builtin_expect(ic.anySpill, 0)) { spill_static<true>(spill_ctx(S), &R, NS); wave_sync(); }
+    if (__builtin_expect(ic.anySpill, 0)) { spill_static<true>(spill_ctx(S), &R, NS); wave_sync(); }
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) { HS_BODY(r) if (valid) derive_body_velocity(R, slot, g, meta); }
     if (manGlobal) mem_sync(); else wave_sync();   // (the multipliers of manifolds in the global workspace, for the velocity pass)
-    HS_CTICK(5, 7)
-    phase_dd<false, SPILL>(S, R, ic.anySpill);
-    HS_CTICK(6, 8)
+    HS_TICK(5)
+    phase_dd<false>(S, R, ic.anySpill);
+    HS_TICK(6)
     if (shortLast) static_passes<ROUNDS, kShortLastR, false>(S, R, br, nbodies, nLast, nMerged);
     else static_passes<ROUNDS, ROUNDS - 1, false>(S, R, br, nbodies, nLast, nMerged);
     if (wl.nwb > nMerged) { wall_round<false>(S, R, nMerged, wl.nwb); wave_sync(); }
-    if (SPILL && __builtin_expect(ic.anySpill, 0)) { spill_static<false>(spill_ctx(S), &R, NS); wave_sync(); }
+    if (__builtin_expect(ic.anySpill, 0)) { spill_static<false>(spill_ctx(S), &R, NS); wave_sync(); }
     if (integrateNext) {
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) { HS_BODY(r) if (valid) integrate_body(R, br[r], slot, g, meta, aforce); }
         wave_sync();
     }
-    HS_CTICK(7, 8)
+    HS_TICK(7)
 }
 
 // ROUNDS = rounds of 64 lanes that cover the octet's bodies: 2 up to 16 body slots per world (<= 5 agents), 3 with
@@ -1561,7 +1526,7 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
         if (valid) integrate_body(R, b, slot, g, meta, aforce);
     }
     wave_sync();
-    HS_CTICK(1, 0)
+    HS_TICK(1)
     // The substeps.  (The spill path — pairs beyond the LDS capacities, a handful in millions of world-steps — sits behind
     // wave-uniform branches on ic.anySpill inside the phases.  While the kernel kept its lane constants alive across all
     // phases it sat at its 256-register budget and this code cost the hot path 12 spilled registers whichever way it was
@@ -1572,7 +1537,7 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
     for (int sub = 0; sub < kNumSubsteps; ++sub) {
         const ItemCounts ic = phase_detect<ROUNDS>(S, R, NS);
         HS_TICK(2)
-        substep_rest<ROUNDS, true>(S, R, br, nbodies, NS, ic, sub + 1 < kNumSubsteps, aforce HS_TICK_ARGS);
+        substep_rest<ROUNDS>(S, R, br, nbodies, NS, ic, sub + 1 < kNumSubsteps, aforce HS_TICK_ARGS);
     }
 #undef HS_BODY
     phase_post(S, R);
@@ -1582,7 +1547,7 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
     copy_out_vel(S.blin, p0, &R.u.vel.lin[0][0][0], R); copy_out_vel(S.bang, p0, &R.u.vel.ang[0][0][0], R);
     copy_out(S.bmeta, p0, &R.meta[0][0]);
     mem_sync();                           // the write-back is complete before a regenerated level overwrites it
-    HS_CTICK(8, 9)
+    HS_TICK(8)
     // resetSystem, one lane per world: step counter, or a whole new level on the 240th step / on request
     // (the generator works in the LDS the octet no longer needs: hs_k_reset.h GenScratch)
     {

@@ -92,8 +92,8 @@ struct SimState {
     int *spInfo;              // [slots][18] totals (body-body | body-static << 16), per body: first spilled static | count << 16
     int *status;           // [4] sticky counters: body-body / body-static candidate pairs that took the spill path, -, -
                            // (include/hideseek.h hs_device_status); bumped only when something happens
-    long long *phaseTicks; // [physics waves][10] accumulated per-phase ticks, then k_observe's sections and the convex tests'
-                           // counters from phase_ticks_obs_base() on (HS_PHASE_TIMING builds only)
+    long long *phaseTicks; // [physics waves][10] accumulated per-phase ticks, then k_observe's sections from
+                           // phase_ticks_obs_base() on (HS_PHASE_TIMING builds only)
 };
 
 // phaseTicks: the physics waves' part, one wave per octet
