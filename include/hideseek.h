@@ -157,6 +157,27 @@ int32_t hs_step_async(hs_sim *sim, void *hip_stream);
  * object (src/mgr.cpp:621-647, textures not reproduced) x (0.3 + 0.7 Lambert term of the light of :657-659), alpha 255.
  * Blocking.  Madrona's renderer is absent from the reference snapshot: the image is this build's own. */
 int32_t hs_render(hs_sim *sim);
+
+/* Spectator cameras (the function of the reference's src/viewer.cpp without a window): render any world of this handle
+ * from any pose.  Axes as the agent camera's: local +y forward, +x right, +z up; rot = w,x,y,z, used as given (no
+ * normalisation).  A pixel is hs_render's pixel with tan_half_fov_y in place of tan(50 degrees): a camera at an agent's
+ * pose + (0, 0, 0.5) with tan_half_fov_y = tan(50 degrees) reproduces that agent's view bit for bit. */
+typedef struct hs_camera {
+    int32_t world;                /* local world index of this handle */
+    float pos[3];
+    float rot[4];
+    float tan_half_fov_y;
+} hs_camera;
+enum { HS_SPECTATE_NO_CULL = 1 };  /* test every pixel against everything (the culls are conservative: same output) */
+/* Render `n` cameras (`cams`: host memory) at width x height into caller-owned device buffers of this handle's GPU:
+ * depth [n,H,W] f32 (0: nothing hit), rgba [n,H,W,4] u8 (alpha 255, black sky), hit [n,H,W] i32 (0-16 movable body
+ * slot, 100+k wall k, 200+p plane p, -1 nothing or nearer than z-near).  Any output may be null, not all three; each
+ * must be 4-byte aligned.  Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written):
+ * world in [0, num_worlds), 1 <= width, height <= 4096, n >= 1, a finite pose, |rot|^2 in [0.99, 1.01], tan_half_fov_y
+ * finite and > 0.  Refused before hs_init and inside an open step; ordered after the device's legacy default stream;
+ * blocking.  Writes no simulator state; works without enable_batch_renderer and under HS_FLAG_EXT_SKIP_OBSERVATIONS. */
+int32_t hs_render_cameras(hs_sim *sim, const hs_camera *cams, int32_t n, int32_t width, int32_t height, uint32_t flags,
+                          float *depth, uint8_t *rgba, int32_t *hit);
 /* The 21 Manager::*Tensor() getters + policyAssignmentsTensor / episodeResultTensor
  * (src/mgr.cpp:1062-1336). */
 int32_t hs_get_tensor(hs_sim *sim, int32_t export_id, hs_tensor_desc *out);

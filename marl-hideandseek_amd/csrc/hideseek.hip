@@ -7,12 +7,16 @@
 #include <string>
 #include <vector>
 #include <atomic>
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
 
 #include "../../include/hideseek.h"
 #include "hs_state.h"
 #include "hs_k_reset.h"
 #include "hs_k_observe.h"
 #include "hs_k_render.h"
+#include "hs_k_spectate.h"
 #include "hs_k_physics.h"
 #include "hs_k_balance.h"
 #include "hs_solver.h"
@@ -54,6 +58,8 @@ struct hs_sim {
     hipEvent_t evIn = nullptr;             // orders `stream` after the device's legacy default stream (torch's writes to `action`)
     bool step_open = false;                // hs_step_begin without its hs_step_end
     std::atomic<int32_t> async_error{0};   // a failed XLA custom call on this handle (hs_xla_*: the ABI has no status channel; XLA's thread)
+    hs::SpectateCam *cams = nullptr;       // hs_render_cameras: the device copy of the cameras, grown on demand
+    int cam_cap = 0;
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -327,6 +333,7 @@ void hs_destroy(hs_sim *s) {
     if (!s) return;
     hipDeviceSynchronize();
     for (void *p : s->allocs) hipFree(p);
+    if (s->cams) hipFree(s->cams);
     for (auto &e : s->ev) if (e) hipEventDestroy(e);
     if (s->evIn) hipEventDestroy(s->evIn);
     if (s->stream) hipStreamDestroy(s->stream);
@@ -426,6 +433,55 @@ int32_t hs_render(hs_sim *s) {
     if (rc == HS_OK) rc = order_after_default_stream(s);
     if (rc != HS_OK) return rc;
     launch_render(s, s->stream);
+    HS_HIP(hipGetLastError());
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+static_assert(sizeof(hs_camera) == sizeof(hs::SpectateCam) && offsetof(hs_camera, rot) == offsetof(hs::SpectateCam, rot) &&
+              offsetof(hs_camera, tan_half_fov_y) == offsetof(hs::SpectateCam, tanHalfFovY), "hs_camera layout");
+static_assert((int)HS_SPECTATE_NO_CULL == (int)hs::kSpectateNoCull, "HS_SPECTATE_NO_CULL");
+
+int32_t hs_render_cameras(hs_sim *s, const hs_camera *cams, int32_t n, int32_t W, int32_t H, uint32_t flags, float *depth,
+                          uint8_t *rgba, int32_t *hit) {
+    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras inside an open step");
+    if (!cams || n < 1) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras: need at least one camera");
+    if (W < 1 || W > 4096 || H < 1 || H > 4096) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras: width / height outside [1, 4096]");
+    if (flags & ~(uint32_t)HS_SPECTATE_NO_CULL) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras: unknown flags");
+    if (!depth && !rgba && !hit) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras: every output is null");
+    if (((uintptr_t)depth | (uintptr_t)rgba | (uintptr_t)hit) & 3u) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras: outputs must be 4-byte aligned");
+    for (int32_t i = 0; i < n; ++i) {
+        const hs_camera &c = cams[i];
+        auto at = [i] { return "hs_render_cameras: camera " + std::to_string(i) + ": "; };
+        if (c.world < 0 || c.world >= s->S.N) return fail(HS_ERR_INVALID_ARG, at() + "world index out of range");
+        bool finite = std::isfinite(c.tan_half_fov_y);
+        for (float v : c.pos) finite = finite && std::isfinite(v);
+        for (float v : c.rot) finite = finite && std::isfinite(v);
+        if (!finite) return fail(HS_ERR_INVALID_ARG, at() + "non-finite pose or field of view");
+        const double q2 = (double)c.rot[0] * c.rot[0] + (double)c.rot[1] * c.rot[1] + (double)c.rot[2] * c.rot[2] + (double)c.rot[3] * c.rot[3];
+        if (!(q2 >= 0.99 && q2 <= 1.01)) return fail(HS_ERR_INVALID_ARG, at() + "rotation is not a unit quaternion (|q|^2 outside [0.99, 1.01])");
+        if (!(c.tan_half_fov_y > 0.f)) return fail(HS_ERR_INVALID_ARG, at() + "tan_half_fov_y must be > 0");
+    }
+    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    if (n > s->cam_cap) {
+        if (s->cams) { HS_HIP(hipStreamSynchronize(s->stream)); HS_HIP(hipFree(s->cams)); s->cams = nullptr; s->cam_cap = 0; }
+        HS_HIP(hipMalloc(&s->cams, (size_t)n * sizeof(hs::SpectateCam)));
+        s->cam_cap = n;
+    }
+    int rc = order_after_default_stream(s);
+    if (rc != HS_OK) return rc;
+    HS_HIP(hipMemcpyAsync(s->cams, cams, (size_t)n * sizeof(hs_camera), hipMemcpyHostToDevice, s->stream));
+    const int tilesX = (W + hs::kSpectateTileW - 1) / hs::kSpectateTileW, tilesY = (H + hs::kSpectateTileH - 1) / hs::kSpectateTileH;
+    const int tilesPerCam = tilesX * tilesY;
+    const int perLaunch = std::max(1, (1 << 22) / tilesPerCam);      // cameras per launch: the grid stays far below 2^32 threads
+    for (int c0 = 0; c0 < n; c0 += perLaunch) {
+        const int nc = std::min(perLaunch, n - c0);
+        hipLaunchKernelGGL(hs::k_spectate, dim3((unsigned)(nc * tilesPerCam)), dim3(hs::kSpectateThreads), 0, s->stream, s->S,
+                           (const hs::SpectateCam *)s->cams, c0, (int)W, (int)H, tilesX, tilesPerCam, (unsigned)flags, depth,
+                           (unsigned *)rgba, (int *)hit);
+    }
     HS_HIP(hipGetLastError());
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;

@@ -121,6 +121,14 @@ class HideAndSeekSimulator:
         Manager::step's batchRender(), src/mgr.cpp:894-901).  Per step instead: SimFlags.ExtRender."""
         _check(self._L.hs_render(self._h))
 
+    def spectate(self, cameras, width, height, *, depth=True, rgb=True, hit=False, out=None, exact=False):
+        """Render spectator cameras (gpu_hideseek.spectate: Camera, look_at, top_down, agent_camera) of this handle's
+        worlds at width x height (hs_render_cameras): {"depth": [V,H,W] f32, "rgb": [V,H,W,4] u8, "hit": [V,H,W] i32}
+        for the requested outputs, as new tensors or in the preallocated ones of `out`.  `exact` turns the kernel's
+        culls off (same output).  Writes no simulator state."""
+        from . import spectate
+        return spectate.render(self, cameras, width, height, depth, rgb, hit, out, exact)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -31,6 +31,13 @@ class HsDeviceStatus(C.Structure):
                 ("spilled_dd_pairs", C.c_int64), ("spilled_static_pairs", C.c_int64)]
 
 
+class HsCamera(C.Structure):
+    """hs_camera: a spectator camera (hs_render_cameras)."""
+    _fields_ = [("world", C.c_int32), ("pos", C.c_float * 3), ("rot", C.c_float * 4), ("tan_half_fov_y", C.c_float)]
+
+
+HS_SPECTATE_NO_CULL = 1
+
 # XLA custom-call targets (include/hideseek.h hs_xla_*): the key `sim.jax()` files each one under -> native symbol
 XLA_TARGETS = {"init": "hs_xla_init", "step": "hs_xla_step", "save_ckpts": "hs_xla_save_checkpoints",
                "load_ckpts": "hs_xla_load_checkpoints"}
@@ -76,6 +83,9 @@ def load():
     L.hs_step_async.restype = C.c_int32
     L.hs_get_tensor.argtypes = [C.c_void_p, C.c_int32, C.POINTER(HsTensorDesc)]
     L.hs_get_tensor.restype = C.c_int32
+    L.hs_render_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
+    L.hs_render_cameras.restype = C.c_int32
     L.hs_trigger_reset.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.hs_trigger_reset.restype = C.c_int32
     L.hs_set_action.argtypes = [C.c_void_p] + [C.c_int32] * 6

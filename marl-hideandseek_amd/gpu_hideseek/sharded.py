@@ -139,6 +139,12 @@ class ShardedSimulator:
         shard, local = locate(self.ranges, int(agent_idx) // A)
         self.shards[shard].set_action(local * A + int(agent_idx) % A, x, y, r, g, l)
 
+    def spectate(self, cameras, width, height, *, depth=True, rgb=True, hit=False, out=None, exact=False):
+        """HideAndSeekSimulator.spectate with GLOBAL world ids: each camera is rendered by the shard that owns its world;
+        the images come back in the caller's camera order, on the first shard's device (or in `out`)."""
+        from . import spectate
+        return spectate.render_sharded(self, cameras, width, height, depth, rgb, hit, out, exact)
+
     def device_status(self):
         out = {}
         for s in self.shards:
