@@ -69,7 +69,8 @@ HSD void store_posvel(float *o, V3 p, V3 e, V3 l, V3 a) {
     o[6] = l.x; o[7] = l.y; o[8] = l.z; o[9] = a.x; o[10] = a.y; o[11] = a.z;
 }
 
-// Cooperative load of one world's geometry from the SoA columns into LDS.
+// Cooperative load of one world's geometry from the SoA columns into LDS: stage_geom (hs_rays.h) fused with the loads of
+// the velocities and the grab state (the counts come with the slot header).
 template <int NT>
 HSD void stage_world(const SimState &S, int ps, ObsShared<NT> &sh, int tid) {
     for (int i = tid; i < kNumDSlots; i += NT) sh.g.meta[i] = S.bmeta(i, ps);
@@ -135,15 +136,15 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
         const int m = g.meta[b];
         if (m == 0) continue;
         if (i == 0) atomicOr(&sh.present, 1u << b);
-        const V3 mo = geom_pos(g, kAgentSlot0 + i) - geom_pos(g, b);
-        const V3 ol = qrot(qinv(geom_rot(g, b)), mo);
-        float *e = sh.rel[i][b];
+        const V3 mo = g.g_pos(kAgentSlot0 + i) - g.g_pos(b);
+        const V3 ol = qrot(qinv(g.g_rot(b)), mo);
+        float *e = sh.rel[i][b];                               // (the row of PixelView::set_hull, hs_k_render.h)
         e[0] = mo.x; e[1] = mo.y; e[2] = mo.z;
         e[3] = dot(mo, mo) - obj_bound_r2(meta_obj(m));
         e[4] = ol.x; e[5] = ol.y; e[6] = ol.z;
     }
     for (int i = tid - (NT - 8); i >= 0 && i < nAgents; i += NT) {          // (the last lanes: they have no table item)
-        const Q rot = geom_rot(g, kAgentSlot0 + i);
+        const Q rot = g.g_rot(kAgentSlot0 + i);
         const V3 f = qrot(rot, {0.f, 1.f, 0.f}), rt = qrot(rot, {1.f, 0.f, 0.f});
         sh.fwd[i][0] = f.x; sh.fwd[i][1] = f.y; sh.fwd[i][2] = f.z;
         sh.right[i][0] = rt.x; sh.right[i][1] = rt.y; sh.right[i][2] = rt.z;
@@ -157,7 +158,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
         sh.rayKey[r] = ray_key(-1.f, kKeyMiss);               // "no ray" (visibility ray not cast)
         if (i >= nAgents) continue;                            // (also the padding lanes between the two kinds)
         const int slot = kAgentSlot0 + i;
-        const V3 o = geom_pos(g, slot);
+        const V3 o = g.g_pos(slot);
         const V3 fwd = {sh.fwd[i][0], sh.fwd[i][1], sh.fwd[i][2]};
         V3 d; float tmax;
         if (k < 30) {
@@ -174,13 +175,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
             else if (e < kMaxBoxes + kMaxRamps) { tslot = kRampSlot0 + (e - kMaxBoxes); present = (e - kMaxBoxes) < nRamps; }
             else { const int jj = e - kMaxBoxes - kMaxRamps; const int j = jj < i ? jj : jj + 1; tslot = kAgentSlot0 + j; present = j < nAgents; }
             if (!present) continue;
-            d = geom_pos(g, tslot) - o;
+            d = g.g_pos(tslot) - o;
             if (dot(normalize(d), fwd) < kCosFovHalf) continue;
             tmax = 1.f;
         }
         sh.rayD[r][0] = d.x; sh.rayD[r][1] = d.y; sh.rayD[r][2] = d.z;
         HS_OTICK(2)
-        // static geometry: same order and arithmetic as trace_ray
+        // static geometry: same order and arithmetic as trace_ray (cast_pixel, hs_k_render.h, has this walls block over a
+        // view's wall list and the plane loop: an edit here is an edit there)
         int hit = -1; float best = tmax;
         const V3 inv = {1.f / d.x, 1.f / d.y, 1.f / d.z};
         const int nw = g.numWalls;
@@ -267,7 +269,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
             const int i = ray_id(r, visBase).agent;
             const float *e = sh.rel[i][b];
             const V3 ol = {e[4], e[5], e[6]};
-            const V3 dl = qrot(qinv(geom_rot(g, b)), {sh.rayD[r][0], sh.rayD[r][1], sh.rayD[r][2]});
+            const V3 dl = qrot(qinv(g.g_rot(b)), {sh.rayD[r][0], sh.rayD[r][1], sh.rayD[r][2]});
             const V3 he = obj_half_extents(meta_obj(g.meta[b]));
             const float tmax = r < visBase ? 200.f : 1.f;
             const float t = __ballot(dl.x == 0.f || dl.y == 0.f || dl.z == 0.f) == 0 ? ray_box_local_nz(ol, dl, he) : ray_box_local(ol, dl, he);
@@ -281,7 +283,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
             const int r = pr >> 5, b = pr & 31;
             const int i = ray_id(r, visBase).agent;
             const float *e = sh.rel[i][b];
-            const V3 dl = qrot(qinv(geom_rot(g, b)), {sh.rayD[r][0], sh.rayD[r][1], sh.rayD[r][2]});
+            const V3 dl = qrot(qinv(g.g_rot(b)), {sh.rayD[r][0], sh.rayD[r][1], sh.rayD[r][2]});
             const float tmax = r < visBase ? 200.f : 1.f;
             const float t = ray_wedge_local({e[4], e[5], e[6]}, dl);
             if (t >= 0.f && t <= tmax) atomicMin(&sh.rayKey[r], ray_key(t, b));
@@ -329,8 +331,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
             if (i >= nAgents) continue;
             const int row = w * A + i;
             const int slot = kAgentSlot0 + i;
-            const V3 mpos = geom_pos(g, slot);
-            const Q mrot = geom_rot(g, slot);
+            const V3 mpos = g.g_pos(slot);
+            const Q mrot = g.g_rot(slot);
             const V3 mlin = {sh.lin[slot][0], sh.lin[slot][1], sh.lin[slot][2]};
             const V3 mang = {sh.ang[slot][0], sh.ang[slot][1], sh.ang[slot][2]};
             const Q toF = qinv(mrot);
@@ -356,8 +358,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
             }
             if (!present) { for (int k = 0; k < width; ++k) o[k] = 0.f; continue; }
             // computeRelativePosVelObs (sim.cpp:401-420)
-            const V3 x = geom_pos(g, tslot);
-            const Q q = geom_rot(g, tslot);
+            const V3 x = g.g_pos(tslot);
+            const Q q = g.g_rot(tslot);
             const V3 lin = {sh.lin[tslot][0], sh.lin[tslot][1], sh.lin[tslot][2]};
             const V3 ang = {sh.ang[tslot][0], sh.ang[tslot][1], sh.ang[tslot][2]};
             V3 p = qrot(toF, x - mpos);

@@ -5,7 +5,8 @@
 // view, z-near 0.001, offset 0.5 up; src/sim.cpp:1400-1403), the interface entity taking its agent's pose in
 // updateCameraSystem (:943-954) — the base colours per object type and one directional light (src/mgr.cpp:621-660).
 // This kernel is a ray caster over the same flat per-world geometry the lidar uses (hs_rays.h): one workgroup per
-// view, a lane per pixel, closest hit per pixel.
+// view, a lane per pixel, closest hit per pixel.  The pixel (cast_pixel) and what a view's pixels share (PixelView) are
+// also k_spectate's (hs_k_spectate.h), which renders from any pose.
 //   depth  view-space depth of the hit (distance along the camera's forward axis), 0 where nothing is hit
 //   rgb    base colour of the hit object x (0.3 ambient + 0.7 Lambert term of the light), alpha 255; black sky
 // The reference's textures (floor grid, the agents' faces) are not reproduced; the seeker's red face texture is stood
@@ -75,42 +76,87 @@ HSD unsigned render_shade(V3 base, V3 n) {
     return (unsigned)(r * 255.f + 0.5f) | ((unsigned)(gch * 255.f + 0.5f) << 8) | ((unsigned)(b * 255.f + 0.5f) << 16) | 0xff000000u;
 }
 
-// The camera of one view and, per movable hull, what all rays of the view share (as k_observe's per-agent table):
-// camera origin - hull centre, its squared length minus the bounding radius, the origin in the hull's frame.
-struct RenderView {
+// What the pixels of one view (k_render) or one tile (k_spectate) share: the camera, per movable hull what all rays
+// share (set_hull), the hulls and the walls that may be hit.  NEAR = kMaxWalls adds a lower bound of each listed wall's
+// view depth for cast_pixel's per-wave skip, NEAR = 0 nothing (a trailing member, not a derived struct: it follows
+// wallId without padding, 784 / 640 bytes).
+template <int NEAR>
+struct PixelView {
+    static constexpr bool kWallNear = NEAR > 0;
     float fwd[3], right[3], up[3], o[3];
     alignas(16) float rel[kNumDSlots][8];
-    unsigned others;                     // bit b: hull b exists, is not the viewer's own and may be in view
-    // Walls that may be in view, ascending, each with a lower bound of the view depth of any point on it.  For a camera
-    // that only yaws (every agent: inverse inertia x, y = 0) a wall wholly behind the camera or wholly outside the
-    // horizontal field of view is left out, and a wall farther than the depth at which a ray leaves the walls' height
-    // range [0, 2.5] is skipped per wave — conservative tests with a centimetre of margin, so no hit is ever lost.
+    unsigned others;                     // bit b: hull b exists and may be in view
     int nWalls;
-    unsigned char wallId[kMaxWalls];
-    float wallNear[kMaxWalls];
-};
+    unsigned char wallId[kMaxWalls];     // ascending
+    float wallNear[NEAR];
 
-// One pixel: the closest hit over walls, planes and hulls under trace_ray's rule (closest entry with 0 <= t <= far; ties
-// keep the lower id — hulls < walls < planes, the order trace_ray visits them in), evaluated in an order that suits the
-// wave: the walls by the branch-free scan of hs_rays.h, the hulls behind the conservative bounding-sphere cull with the
-// origin-side terms taken from the view's table.  Same expressions as trace_ray for every candidate, so the same bits.
-HSD void render_pixel(const WorldGeom &g, const RenderView &vw, int px, int py, int W, int H, float *depth, unsigned *rgba) {
+    HSD void set_camera(V3 f, V3 r, V3 u, V3 org) {
+        fwd[0] = f.x; fwd[1] = f.y; fwd[2] = f.z; right[0] = r.x; right[1] = r.y; right[2] = r.z;
+        up[0] = u.x; up[1] = u.y; up[2] = u.z; o[0] = org.x; o[1] = org.y; o[2] = org.z;
+    }
+    // Hull b's row (meta word m) for the camera origin org: org - centre, its squared length - the bounding radius^2
+    // (the origin-side terms of trace_ray's cull), org in the hull's frame; k_observe fills the same rows per agent.
+    // Returns org - centre.
+    HSD V3 set_hull(const WorldGeom &g, int b, int m, V3 org) {
+        const V3 mo = org - g.g_pos(b);
+        const V3 ol = qrot(qinv(g.g_rot(b)), mo);
+        float *e = rel[b];
+        const float r2 = obj_bound_r2(meta_obj(m));
+        e[0] = mo.x; e[1] = mo.y; e[2] = mo.z; e[3] = dot(mo, mo) - r2;
+        e[4] = ol.x; e[5] = ol.y; e[6] = ol.z; e[7] = 0.f;
+        return mo;
+    }
+    // Called by all 64 lanes of a wave, lane b for hull b / lane q for wall q (lead: its first lane): the kept ones.
+    HSD void set_hulls(bool keep, bool lead) {
+        const unsigned long long pm = __ballot(keep);
+        if (lead) others = (unsigned)pm;
+    }
+    HSD void set_walls(bool keep, int q, bool lead, float nearest = 0.f) {
+        const unsigned long long km = __ballot(keep);
+        if (keep) {
+            const int k = __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0u));
+            wallId[k] = (unsigned char)q;
+            if constexpr (kWallNear) wallNear[k] = nearest;
+        }
+        if (lead) nWalls = __builtin_popcountll(km);
+    }
+};
+// k_render's view.  For a camera that only yaws (every agent: inverse inertia x, y = 0) a hull or a wall wholly behind
+// the camera or wholly outside the horizontal field of view is left out, and a wall farther than the depth at which a
+// ray leaves the walls' height range [0, 2.5] is skipped per wave (wallNear) — conservative tests with a centimetre of
+// margin, so no hit is ever lost.
+using RenderView = PixelView<kMaxWalls>;
+
+// The ray of pixel centre (px, py) is (fwd + right u) + up v: forward component 1, so t is the view-space depth.
+HSD float pixel_u(int px, int W, float tanHalfFov, float aspect) { return ((((float)px + 0.5f) / (float)W) * 2.f - 1.f) * (tanHalfFov * aspect); }
+HSD float pixel_v(int py, int H, float tanHalfFov) { return (1.f - (((float)py + 0.5f) / (float)H) * 2.f) * tanHalfFov; }
+
+// One pixel of k_render and k_spectate: depth and colour of the closest hit, whose id is returned (-1, depth 0 and
+// black for the sky and for a hit before the near plane).  The closest hit over walls, planes and hulls follows
+// trace_ray's rule (closest entry with 0 <= t <= far; ties keep the lower id — hulls < walls < planes, the order
+// trace_ray visits them in), evaluated in an order that suits the wave: the view's walls by the branch-free scan of
+// hs_rays.h, the view's hulls behind the conservative bounding-sphere cull (not if exact) with the origin-side terms
+// taken from the view's table.  Same expressions as trace_ray for every candidate, so the same bits.
+template <class VIEW>
+HSD int cast_pixel(const WorldGeom &g, const VIEW &vw, int px, int py, int W, int H, float tanHalfFov, bool exact,
+                   float *depth, unsigned *rgba) {
     const V3 fwd = {vw.fwd[0], vw.fwd[1], vw.fwd[2]}, right = {vw.right[0], vw.right[1], vw.right[2]}, up = {vw.up[0], vw.up[1], vw.up[2]};
     const V3 o = {vw.o[0], vw.o[1], vw.o[2]};
     const float aspect = (float)W / (float)H;
-    const float u = ((((float)px + 0.5f) / (float)W) * 2.f - 1.f) * (kTanHalfFov * aspect);
-    const float v = (1.f - (((float)py + 0.5f) / (float)H) * 2.f) * kTanHalfFov;
-    const V3 d = (fwd + right * u) + up * v;            // forward component 1: t is the view-space depth
+    const float u = pixel_u(px, W, tanHalfFov, aspect);
+    const float v = pixel_v(py, H, tanHalfFov);
+    const V3 d = (fwd + right * u) + up * v;
     const float tmax = kCamFar;
     int hit = -1; float best = tmax;
-    // walls
+    // walls (as k_observe's pass 1, over the view's list)
     const V3 inv = {1.f / d.x, 1.f / d.y, 1.f / d.z};
     const WallZ wz = ray_wall_z(o.z, d.z, inv.z);
     const int nw = vw.nWalls;
     if (__ballot(d.x == 0.f || d.y == 0.f) == 0) {
         WallScan ws(tmax, wz, o.x, o.y, inv);
         for (int k = 0; k < nw; ++k) {
-            if (__ballot(wz.tf >= vw.wallNear[k]) == 0ull) continue;      // every ray of the wave has left [0, 2.5] before it
+            if constexpr (VIEW::kWallNear)
+                if (__ballot(wz.tf >= vw.wallNear[k]) == 0ull) continue;      // every ray of the wave has left [0, 2.5] before it
             const int q = vw.wallId[k];
             const f32x2 *wq = reinterpret_cast<const f32x2 *>(g.wall[q]);
             ws.wall(wq[0], wq[1], kHitWallBase + q);
@@ -124,7 +170,7 @@ HSD void render_pixel(const WorldGeom &g, const RenderView &vw, int px, int py, 
             if (t >= 0.f && t <= best && (hit < 0 || t < best)) { best = t; hit = kHitWallBase + q; }
         }
     }
-    // planes
+    // planes (trace_ray's loop; k_observe has a copy)
     const int np = g.numPlanes;
     for (int p = 0; p < np; ++p) {
         const V3 n = {g.plane[p][0], g.plane[p][1], g.plane[p][2]};
@@ -143,21 +189,22 @@ HSD void render_pixel(const WorldGeom &g, const RenderView &vw, int px, int py, 
         if (!((others >> b) & 1u)) continue;
         const float4 e = *reinterpret_cast<const float4 *>(vw.rel[b]);
         const float bb = (e.x * d.x + e.y * d.y) + e.z * d.z, cc = e.w;
-        const bool culled = cc > 0.f && (bb > 0.f || bb * bb < dd2 * cc * 0.999f);
+        const bool culled = !exact && cc > 0.f && (bb > 0.f || bb * bb < dd2 * cc * 0.999f);
         if (__ballot(!culled) == 0ull) continue;
         if (!culled) {
             const int obj = meta_obj(g.meta[b]);
             const V3 ol = {vw.rel[b][4], vw.rel[b][5], vw.rel[b][6]};
-            const V3 dl = qrot(qinv(geom_rot(g, b)), d);
+            const V3 dl = qrot(qinv(g.g_rot(b)), d);
             const float t = obj == OBJ_RAMP ? ray_wedge_local(ol, dl) : ray_box_local(ol, dl, obj_half_extents(obj));
             if (t >= 0.f && t <= tmax && (t < best || (t == best && b < hit) || hit < 0)) { best = t; hit = b; }
         }
     }
-    if (hit < 0 || best < kCamNear) { *depth = 0.f; *rgba = 0xff000000u; return; }
+    if (hit < 0 || best < kCamNear) { *depth = 0.f; *rgba = 0xff000000u; return -1; }
     const V3 p = o + d * best;
     const int obj = hit < kNumDSlots ? meta_obj(g.meta[hit]) : OBJ_NONE;
     *depth = best;
     *rgba = render_shade(render_base_colour(obj, hit), hit_normal(g, hit, p));
+    return hit;
 }
 
 // One workgroup per view (world slot, agent); views of inactive agents are zero-filled.
@@ -169,12 +216,7 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(SimState S, float *de
     const int ps = blockIdx.x / A_, agent = blockIdx.x % A_;        // slot of the tiled columns, agent index
     const int w = S.worldOfSlot[ps];
     if (w < 0) return;                                              // (padding slot of the last octet)
-    for (int i = tid; i < kNumDSlots; i += kRenderThreads) g.meta[i] = S.bmeta(i, ps);
-    for (int i = tid; i < kNumDSlots * 3; i += kRenderThreads) g.pos[i % kNumDSlots][i / kNumDSlots] = S.bpos(i, ps);
-    for (int i = tid; i < kNumDSlots * 4; i += kRenderThreads) g.rot[i % kNumDSlots][i / kNumDSlots] = S.brot(i, ps);
-    for (int i = tid; i < 4 * kMaxWalls; i += kRenderThreads) g.wall[i % kMaxWalls][i / kMaxWalls] = S.walls(i, ps);
-    for (int i = tid; i < 4 * kMaxPlanes; i += kRenderThreads) g.plane[i % kMaxPlanes][i / kMaxPlanes] = S.planes(i, ps);
-    if (tid == 0) { g.numWalls = S.numWalls[w]; g.numPlanes = S.numPlanes[w]; }
+    stage_geom(S, ps, w, g, tid, kRenderThreads);
     __syncthreads();
     const int aslot = kAgentSlot0 + agent;
     const size_t view = (size_t)w * A_ + agent;
@@ -186,8 +228,8 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(SimState S, float *de
         return;
     }
     // the view's camera, per-hull table and wall list
-    const V3 o = geom_pos(g, aslot) + V3{0.f, 0.f, kCamUp};
-    const Q crot = geom_rot(g, aslot);
+    const V3 o = g.g_pos(aslot) + V3{0.f, 0.f, kCamUp};
+    const Q crot = g.g_rot(aslot);
     const V3 cf = qrot(crot, {0.f, 1.f, 0.f}), cr = qrot(crot, {1.f, 0.f, 0.f}), cu = qrot(crot, {0.f, 0.f, 1.f});
     // horizontal culls only for a camera that yaws and nothing else (then a ray's x, y direction is fwd + u right)
     const bool yawOnly = cu.x == 0.f && cu.y == 0.f && cf.z == 0.f && cr.z == 0.f;
@@ -195,23 +237,17 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(SimState S, float *de
     const float kMargin = 0.01f;
     if (tid < 64) {
         const int m = tid < kNumDSlots ? g.meta[tid] : 0;
-        bool keep = m != 0 && tid != aslot;
+        bool keep = m != 0 && tid != aslot;                             // (not the viewer's own hull)
         if (keep) {
-            const V3 mo = o - geom_pos(g, tid);
-            const V3 ol = qrot(qinv(geom_rot(g, tid)), mo);
-            float *e = vw.rel[tid];
-            const float r2 = obj_bound_r2(meta_obj(m));
-            e[0] = mo.x; e[1] = mo.y; e[2] = mo.z; e[3] = dot(mo, mo) - r2;
-            e[4] = ol.x; e[5] = ol.y; e[6] = ol.z; e[7] = 0.f;
+            const V3 mo = vw.set_hull(g, tid, m, o);
             if (yawOnly) {
                 // bounding sphere against the two vertical side planes of the view and the plane through the camera
-                const float R = sqrtf(r2) + kMargin, side = sqrtf(1.f + umax * umax);
+                const float R = sqrtf(obj_bound_r2(meta_obj(m))) + kMargin, side = sqrtf(1.f + umax * umax);
                 const float f = -(mo.x * cf.x + mo.y * cf.y), r = -(mo.x * cr.x + mo.y * cr.y);
                 if (f < -R || r - umax * f > R * side || -r - umax * f > R * side) keep = false;
             }
         }
-        const unsigned long long pm = __ballot(keep);
-        if (tid == 0) vw.others = (unsigned)pm;
+        vw.set_hulls(keep, tid == 0);
     } else if (tid < 128) {
         const int q = tid - 64;
         bool keep = q < g.numWalls;
@@ -230,20 +266,14 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(SimState S, float *de
             if (fmax < -kMargin || allRight || allLeft) keep = false;
             nearest = fmin - kMargin;
         }
-        const unsigned long long km = __ballot(keep);
-        if (keep) {
-            const int k = __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0u));
-            vw.wallId[k] = (unsigned char)q; vw.wallNear[k] = nearest;
-        }
-        if (tid == 64) vw.nWalls = __builtin_popcountll(km);
+        vw.set_walls(keep, q, tid == 64, nearest);
     } else if (tid == 128) {
-        vw.fwd[0] = cf.x; vw.fwd[1] = cf.y; vw.fwd[2] = cf.z; vw.right[0] = cr.x; vw.right[1] = cr.y; vw.right[2] = cr.z;
-        vw.up[0] = cu.x; vw.up[1] = cu.y; vw.up[2] = cu.z; vw.o[0] = o.x; vw.o[1] = o.y; vw.o[2] = o.z;
+        vw.set_camera(cf, cr, cu, o);
     }
     __syncthreads();
     for (int i = tid; i < W * H; i += kRenderThreads) {
         float d; unsigned c;
-        render_pixel(g, vw, i % W, i / W, W, H, &d, &c);
+        cast_pixel(g, vw, i % W, i / W, W, H, kTanHalfFov, false, &d, &c);
         dv[i] = d; cv[i] = c;
     }
 }

@@ -3,9 +3,9 @@
 // a window.
 //
 // A camera is {world, pos, rot (w,x,y,z), tan_half_fov_y} with the agent camera's axes: local +y forward, +x right,
-// +z up.  A pixel is k_render's pixel (hs_k_render.h render_pixel) with the camera's tan_half_fov_y in place of
-// kTanHalfFov: ray (fwd + right u) + up v, trace_ray's hit rule (closest entry with 0 <= t <= 1000, ties to the lower
-// id, no hit on a hull the ray starts inside), the same z-near, sky, hit_normal and render_shade.  The quaternion is
+// +z up.  A pixel is k_render's pixel, the same function (hs_k_render.h cast_pixel) with the camera's tan_half_fov_y
+// in place of kTanHalfFov: ray (fwd + right u) + up v, trace_ray's hit rule (closest entry with 0 <= t <= 1000, ties to
+// the lower id, no hit on a hull the ray starts inside), z-near, sky, hit_normal and render_shade.  The quaternion is
 // used as given.  So a camera at an agent's pose + (0, 0, 0.5) with fov 100 degrees reproduces that agent's view bit
 // for bit: its own hull drops out by the inside-start rule.
 //
@@ -14,7 +14,9 @@
 // worlds between slots) and culls per tile: a hull's bounding sphere or a wall's box (z in [0, 2.5]) that lies wholly
 // outside one of the four side planes of the pyramid of the tile's pixel-centre rays, or behind the plane through the
 // camera across the tile's centre ray, is left out.  The culls keep a centimetre of margin plus 1e-4 of the distance,
-// so they are conservative; HS_SPECTATE_NO_CULL turns them all off (every pixel against everything).
+// so they are conservative; HS_SPECTATE_NO_CULL turns them and cast_pixel's per-ray sphere cull off (every pixel
+// against everything).  The view's set-up shares k_render's vocabulary (stage_geom, PixelView); the culls, the tiling
+// and the camera's source are what differs.
 #pragma once
 #include "hs_state.h"
 #include "hs_rays.h"
@@ -34,18 +36,7 @@ struct SpectateCam {
     float tanHalfFovY;
 };
 
-// What a tile's pixels share: the camera, the hulls that may be hit with their origin-side terms (as RenderView), and
-// the walls that may be hit, ascending.
-struct SpectateTile {
-    float fwd[3], right[3], up[3], o[3];
-    alignas(16) float rel[kNumDSlots][8];
-    unsigned others;
-    int nWalls;
-    unsigned char wallId[kMaxWalls];
-};
-
-HSD float spectate_u(int px, int W, float tanh, float aspect) { return ((((float)px + 0.5f) / (float)W) * 2.f - 1.f) * (tanh * aspect); }
-HSD float spectate_v(int py, int H, float tanh) { return (1.f - (((float)py + 0.5f) / (float)H) * 2.f) * tanh; }
+using SpectateTile = PixelView<0>;      // what a tile's pixels share: no per-wall depth bounds
 
 // The cull planes of one tile, through the camera origin, with unit inward normals; a degenerate plane gets n = 0 and
 // keeps everything.  The tile's rays d = (f + u r) + v up, u in [u0, u1], v in [v1, v0], are convex combinations of its
@@ -96,74 +87,6 @@ struct TileCull {
     }
 };
 
-// One pixel: render_pixel's expressions with the camera's field of view and the tile's lists; hit -1 for the sky.
-HSD void spectate_pixel(const WorldGeom &g, const SpectateTile &tl, int px, int py, int W, int H, float tanh, bool exact,
-                        float *depth_out, unsigned *rgba_out, int *hit_out) {
-    const V3 fwd = {tl.fwd[0], tl.fwd[1], tl.fwd[2]}, right = {tl.right[0], tl.right[1], tl.right[2]}, up = {tl.up[0], tl.up[1], tl.up[2]};
-    const V3 o = {tl.o[0], tl.o[1], tl.o[2]};
-    const float aspect = (float)W / (float)H;
-    const float u = spectate_u(px, W, tanh, aspect);
-    const float v = spectate_v(py, H, tanh);
-    const V3 d = (fwd + right * u) + up * v;
-    const float tmax = kCamFar;
-    int hit = -1; float best = tmax;
-    // walls
-    const V3 inv = {1.f / d.x, 1.f / d.y, 1.f / d.z};
-    const WallZ wz = ray_wall_z(o.z, d.z, inv.z);
-    const int nw = tl.nWalls;
-    if (__ballot(d.x == 0.f || d.y == 0.f) == 0) {
-        WallScan ws(tmax, wz, o.x, o.y, inv);
-        for (int k = 0; k < nw; ++k) {
-            const int q = tl.wallId[k];
-            const f32x2 *wq = reinterpret_cast<const f32x2 *>(g.wall[q]);
-            ws.wall(wq[0], wq[1], kHitWallBase + q);
-        }
-        ws.finish(tmax);
-        best = ws.best; hit = ws.hit;
-    } else {
-        for (int k = 0; k < nw; ++k) {
-            const int q = tl.wallId[k];
-            const float t = ray_wall_xy(o.x - g.wall[q][0], o.y - g.wall[q][1], d, inv, g.wall[q][2], g.wall[q][3], wz);
-            if (t >= 0.f && t <= best && (hit < 0 || t < best)) { best = t; hit = kHitWallBase + q; }
-        }
-    }
-    // planes
-    const int np = g.numPlanes;
-    for (int p = 0; p < np; ++p) {
-        const V3 n = {g.plane[p][0], g.plane[p][1], g.plane[p][2]};
-        const float dn = dot(n, d);
-        if (!(dn < 0.f)) continue;
-        const float dist = dot(n, o) - g.plane[p][3];
-        if (dist < 0.f) continue;
-        const float t = -dist / dn;
-        if (t >= 0.f && t <= best && (hit < 0 || t < best)) { best = t; hit = kHitPlaneBase + p; }
-    }
-    // hulls (lower ids than the static geometry: a hull wins a tie)
-    const float dd2 = dot(d, d);
-    const unsigned others = __builtin_amdgcn_readfirstlane(tl.others);
-#pragma unroll 1
-    for (int b = 0; b < kNumDSlots; ++b) {
-        if (!((others >> b) & 1u)) continue;
-        const float4 e = *reinterpret_cast<const float4 *>(tl.rel[b]);
-        const float bb = (e.x * d.x + e.y * d.y) + e.z * d.z, cc = e.w;
-        const bool culled = !exact && cc > 0.f && (bb > 0.f || bb * bb < dd2 * cc * 0.999f);
-        if (__ballot(!culled) == 0ull) continue;
-        if (!culled) {
-            const int obj = meta_obj(g.meta[b]);
-            const V3 ol = {tl.rel[b][4], tl.rel[b][5], tl.rel[b][6]};
-            const V3 dl = qrot(qinv(geom_rot(g, b)), d);
-            const float t = obj == OBJ_RAMP ? ray_wedge_local(ol, dl) : ray_box_local(ol, dl, obj_half_extents(obj));
-            if (t >= 0.f && t <= tmax && (t < best || (t == best && b < hit) || hit < 0)) { best = t; hit = b; }
-        }
-    }
-    if (hit < 0 || best < kCamNear) { *depth_out = 0.f; *rgba_out = 0xff000000u; *hit_out = -1; return; }
-    const V3 p = o + d * best;
-    const int obj = hit < kNumDSlots ? meta_obj(g.meta[hit]) : OBJ_NONE;
-    *depth_out = best;
-    *rgba_out = render_shade(render_base_colour(obj, hit), hit_normal(g, hit, p));
-    *hit_out = hit;
-}
-
 // One workgroup per (camera, tile) of cameras [cam0, cam0 + gridDim.x / tilesPerCam).  Outputs [V][H][W] (rgba packed
 // r, g, b, a), each may be null.  The host has validated the cameras (world in range, finite pose).
 __global__ void __launch_bounds__(kSpectateThreads) k_spectate(SimState S, const SpectateCam *cams, int cam0, int W, int H,
@@ -177,12 +100,7 @@ __global__ void __launch_bounds__(kSpectateThreads) k_spectate(SimState S, const
     const SpectateCam &C = cams[cam];
     const int w = C.world;
     const int ps = S.slotOfWorld[w];
-    for (int i = tid; i < kNumDSlots; i += kSpectateThreads) g.meta[i] = S.bmeta(i, ps);
-    for (int i = tid; i < kNumDSlots * 3; i += kSpectateThreads) g.pos[i % kNumDSlots][i / kNumDSlots] = S.bpos(i, ps);
-    for (int i = tid; i < kNumDSlots * 4; i += kSpectateThreads) g.rot[i % kNumDSlots][i / kNumDSlots] = S.brot(i, ps);
-    for (int i = tid; i < 4 * kMaxWalls; i += kSpectateThreads) g.wall[i % kMaxWalls][i / kMaxWalls] = S.walls(i, ps);
-    for (int i = tid; i < 4 * kMaxPlanes; i += kSpectateThreads) g.plane[i % kMaxPlanes][i / kMaxPlanes] = S.planes(i, ps);
-    if (tid == 0) { g.numWalls = S.numWalls[w]; g.numPlanes = S.numPlanes[w]; }
+    stage_geom(S, ps, w, g, tid, kSpectateThreads);
     const V3 o = {C.pos[0], C.pos[1], C.pos[2]};
     const Q crot = {C.rot[0], C.rot[1], C.rot[2], C.rot[3]};
     const float tanh = C.tanHalfFovY;
@@ -193,37 +111,25 @@ __global__ void __launch_bounds__(kSpectateThreads) k_spectate(SimState S, const
     const V3 cf = qrot(crot, {0.f, 1.f, 0.f}), cr = qrot(crot, {1.f, 0.f, 0.f}), cu = qrot(crot, {0.f, 0.f, 1.f});
     if (tid < 128) {
         const float aspect = (float)W / (float)H;
-        const TileCull cull(cf, cr, cu, spectate_u(x0, W, tanh, aspect), spectate_u(x1, W, tanh, aspect),
-                            spectate_v(y0, H, tanh), spectate_v(y1, H, tanh));
+        const TileCull cull(cf, cr, cu, pixel_u(x0, W, tanh, aspect), pixel_u(x1, W, tanh, aspect),
+                            pixel_v(y0, H, tanh), pixel_v(y1, H, tanh));
         if (tid < 64) {
             const int m = tid < kNumDSlots ? g.meta[tid] : 0;
             bool keep = m != 0;
             if (keep) {
-                const V3 mo = o - geom_pos(g, tid);
-                const V3 ol = qrot(qinv(geom_rot(g, tid)), mo);
-                float *e = tl.rel[tid];
-                const float r2 = obj_bound_r2(meta_obj(m));
-                e[0] = mo.x; e[1] = mo.y; e[2] = mo.z; e[3] = dot(mo, mo) - r2;
-                e[4] = ol.x; e[5] = ol.y; e[6] = ol.z; e[7] = 0.f;
-                if (!exact) keep = cull.sphere(V3{0.f, 0.f, 0.f} - mo, sqrtf(r2));
+                const V3 mo = tl.set_hull(g, tid, m, o);
+                if (!exact) keep = cull.sphere(V3{0.f, 0.f, 0.f} - mo, sqrtf(obj_bound_r2(meta_obj(m))));
             }
-            const unsigned long long pm = __ballot(keep);
-            if (tid == 0) tl.others = (unsigned)pm;
+            tl.set_hulls(keep, tid == 0);
         } else {
             const int q = tid - 64;
             bool keep = q < g.numWalls;
             if (keep && !exact)
                 keep = cull.box(V3{g.wall[q][0] - o.x, g.wall[q][1] - o.y, 1.25f - o.z}, V3{g.wall[q][2], g.wall[q][3], 1.25f});
-            const unsigned long long km = __ballot(keep);
-            if (keep) {
-                const int k = __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0u));
-                tl.wallId[k] = (unsigned char)q;
-            }
-            if (tid == 64) tl.nWalls = __builtin_popcountll(km);
+            tl.set_walls(keep, q, tid == 64);
         }
     } else if (tid == 128) {
-        tl.fwd[0] = cf.x; tl.fwd[1] = cf.y; tl.fwd[2] = cf.z; tl.right[0] = cr.x; tl.right[1] = cr.y; tl.right[2] = cr.z;
-        tl.up[0] = cu.x; tl.up[1] = cu.y; tl.up[2] = cu.z; tl.o[0] = o.x; tl.o[1] = o.y; tl.o[2] = o.z;
+        tl.set_camera(cf, cr, cu, o);
     }
     __syncthreads();
     // a wave per tile row, 64 lanes along it; lanes right of the image shade its last column and store nothing
@@ -231,8 +137,8 @@ __global__ void __launch_bounds__(kSpectateThreads) k_spectate(SimState S, const
     const int px = x0 + lane;
     const bool inx = px <= x1;
     for (int py = y0 + wave; py <= y1; py += kSpectateThreads / 64) {
-        float dv; unsigned cv; int hv;
-        spectate_pixel(g, tl, inx ? px : x1, py, W, H, tanh, exact, &dv, &cv, &hv);
+        float dv; unsigned cv;
+        const int hv = cast_pixel(g, tl, inx ? px : x1, py, W, H, tanh, exact, &dv, &cv);
         if (inx) {
             const size_t i = ((size_t)cam * H + py) * (size_t)W + px;
             if (depth) depth[i] = dv;

@@ -7,7 +7,7 @@
 // 0 <= t <= t_max in units of |d|; a ray starting inside a hull does not hit that hull; ties keep
 // the lower body id.  Body ids: 0..16 movable slots, 100+k walls, 200+p planes, -1 miss.
 #pragma once
-#include "hs_dev.h"
+#include "hs_state.h"
 
 namespace hs {
 
@@ -22,7 +22,7 @@ struct WorldGeom {
     float wall[kMaxWalls][4];     // cx, cy, hx, hy
     float plane[kMaxPlanes][4];   // nx, ny, nz, d
     // the geometry-view interface of trace_ray (the physics kernel has a second implementation over its
-    // LDS-resident columns, hs_k_pipeline.h ResGeom)
+    // LDS-resident columns, hs_k_physics.h ResGeom)
     HSD int g_meta(int i) const { return meta[i]; }
     HSD V3 g_pos(int i) const { return {pos[i][0], pos[i][1], pos[i][2]}; }
     HSD Q g_rot(int i) const { return {rot[i][0], rot[i][1], rot[i][2], rot[i][3]}; }
@@ -32,8 +32,16 @@ struct WorldGeom {
     HSD float g_plane(int p, int c) const { return plane[p][c]; }
 };
 
-HSD V3 geom_pos(const WorldGeom &g, int i) { return {g.pos[i][0], g.pos[i][1], g.pos[i][2]}; }
-HSD Q geom_rot(const WorldGeom &g, int i) { return {g.rot[i][0], g.rot[i][1], g.rot[i][2], g.rot[i][3]}; }
+// Cooperative load of world w, which lives in slot ps of the SoA columns, into LDS by nt threads (k_observe's
+// stage_world is the same fused with the velocity loads).
+HSD void stage_geom(const SimState &S, int ps, int w, WorldGeom &g, int tid, int nt) {
+    for (int i = tid; i < kNumDSlots; i += nt) g.meta[i] = S.bmeta(i, ps);
+    for (int i = tid; i < kNumDSlots * 3; i += nt) g.pos[i % kNumDSlots][i / kNumDSlots] = S.bpos(i, ps);
+    for (int i = tid; i < kNumDSlots * 4; i += nt) g.rot[i % kNumDSlots][i / kNumDSlots] = S.brot(i, ps);
+    for (int i = tid; i < 4 * kMaxWalls; i += nt) g.wall[i % kMaxWalls][i / kMaxWalls] = S.walls(i, ps);
+    for (int i = tid; i < 4 * kMaxPlanes; i += nt) g.plane[i % kMaxPlanes][i / kMaxPlanes] = S.planes(i, ps);
+    if (tid == 0) { g.numWalls = S.numWalls[w]; g.numPlanes = S.numPlanes[w]; }
+}
 
 HSD float ray_box_local(V3 o, V3 d, V3 e) {
     float tn = -3.0e38f, tf = 3.0e38f;
@@ -185,7 +193,7 @@ HSD int trace_ray(const G &g, V3 o, V3 d, float tmax, float *t_out) {
         float t = ray_wall(ol, d, inv, {g.g_wall(k, 2), g.g_wall(k, 3), 1.25f});
         if (t >= 0.f && t <= best && (hit < 0 || t < best)) { best = t; hit = kHitWallBase + k; }
     }
-    const int np = g.g_num_planes();
+    const int np = g.g_num_planes();                       // (copies of this loop: k_observe pass 1, cast_pixel)
     for (int p = 0; p < np; ++p) {
         V3 n = {g.g_plane(p, 0), g.g_plane(p, 1), g.g_plane(p, 2)};
         float dn = dot(n, d);
