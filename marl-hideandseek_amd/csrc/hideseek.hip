@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <memory>
+#include <type_traits>
 
 #include "../../include/hideseek.h"
 #include "hs_state.h"
@@ -32,6 +34,17 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
         hipError_t e_ = (expr);                                                               \
         if (e_ != hipSuccess)                                                                 \
             return fail(HS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+    } while (0)
+#define HS_TRY(expr)                                                                          \
+    do {                                                                                      \
+        const int rc_ = (expr);                                                               \
+        if (rc_ != HS_OK) return rc_;                                                         \
+    } while (0)
+// How every entry point opens: its arguments are there, and the handle's device is the current one.
+#define HS_ENTER(args_ok, msg)                                                                \
+    do {                                                                                      \
+        if (!(args_ok)) return fail(HS_ERR_INVALID_ARG, msg);                                 \
+        HS_HIP(hipSetDevice(s->cfg.gpu_id));                                                  \
     } while (0)
 
 }  // namespace
@@ -73,29 +86,63 @@ struct hs_sim {
 
 namespace {
 
-void set_desc(hs_sim *s, int id, void *ptr, int dtype, std::initializer_list<int64_t> dims) {
+// The exported tensors (ExportID, src/sim.hpp:45-68; mgr.cpp:1062-1336), one row per HS_EXPORT_* id in id order: element
+// type, rows per world or per agent, trailing dims (0: absent), and the SimState field the kernels reach it through.
+// hs_create allocates and describes them from here, and every byte count of a stream copy is that of a descriptor
+// (bytes_of).  The two renderer outputs are not rows: their dims come from the config and they are allocated on first need.
+struct ExportRow { int32_t id, dtype; bool per_agent; int64_t tail[2]; size_t field; };
+static_assert(std::is_standard_layout<hs::SimState>::value, "offsetof(hs::SimState, ...)");
+#define HS_X(f) offsetof(hs::SimState, f)
+constexpr ExportRow kExports[] = {
+    {HS_EXPORT_RESET, HS_DTYPE_I32, false, {1}, HS_X(xReset)},
+    {HS_EXPORT_PREP_COUNTER, HS_DTYPE_I32, true, {1}, HS_X(xPrep)},
+    {HS_EXPORT_ACTION, HS_DTYPE_I32, true, {5}, HS_X(xAction)},
+    {HS_EXPORT_SELF_OBS, HS_DTYPE_F32, true, {13}, HS_X(xSelfObs)},
+    {HS_EXPORT_SELF_TYPE, HS_DTYPE_I32, true, {1}, HS_X(xSelfType)},
+    {HS_EXPORT_SELF_MASK, HS_DTYPE_F32, true, {1}, HS_X(xSelfMask)},
+    {HS_EXPORT_AGENT_OBS, HS_DTYPE_F32, true, {5, 14}, HS_X(xAgentObs)},
+    {HS_EXPORT_BOX_OBS, HS_DTYPE_F32, true, {9, 17}, HS_X(xBoxObs)},
+    {HS_EXPORT_RAMP_OBS, HS_DTYPE_F32, true, {2, 14}, HS_X(xRampObs)},
+    {HS_EXPORT_AGENT_VIS_MASKS, HS_DTYPE_F32, true, {5, 1}, HS_X(xVisAgents)},
+    {HS_EXPORT_BOX_VIS_MASKS, HS_DTYPE_F32, true, {9, 1}, HS_X(xVisBoxes)},
+    {HS_EXPORT_RAMP_VIS_MASKS, HS_DTYPE_F32, true, {2, 1}, HS_X(xVisRamps)},
+    {HS_EXPORT_LIDAR, HS_DTYPE_F32, true, {30}, HS_X(xLidar)},
+    {HS_EXPORT_SEED, HS_DTYPE_I32, true, {2}, HS_X(xSeed)},
+    {HS_EXPORT_REWARD, HS_DTYPE_F32, true, {1}, HS_X(xReward)},
+    {HS_EXPORT_DONE, HS_DTYPE_I32, true, {1}, HS_X(xDone)},
+    {HS_EXPORT_GLOBAL_DEBUG_POSITIONS, HS_DTYPE_F32, false, {17, 2}, HS_X(xGlobalPos)},
+    {HS_EXPORT_AGENT_POLICY, HS_DTYPE_I32, true, {1}, HS_X(xPolicy)},
+    {HS_EXPORT_EPISODE_RESULT, HS_DTYPE_F32, false, {2}, HS_X(xEpisodeResult)},
+    // raw bytes, as the reference exports them (mgr.cpp:1209-1227)
+    {HS_EXPORT_CHECKPOINT_CONTROL, HS_DTYPE_U8, false, {sizeof(int32_t)}, HS_X(xCkptCtrl)},
+    {HS_EXPORT_CHECKPOINT, HS_DTYPE_U8, false, {sizeof(hs_checkpoint)}, HS_X(xCkpt)},
+};
+#undef HS_X
+static_assert(sizeof(kExports) / sizeof(kExports[0]) == HS_EXPORT_DEPTH, "a row per export below the renderer outputs");
+
+size_t bytes_of(const hs_sim *s, int id) {
+    const hs_tensor_desc &d = s->exports[id];
+    return (size_t)(d.dims[0] * d.dims[1] * d.dims[2] * d.dims[3]) * (d.dtype == HS_DTYPE_U8 ? 1 : 4);
+}
+// Describe export `id` and allocate it, zero-filled: a dim of 0 is absent, the rest of dims[] is padded with 1.
+int alloc_export(hs_sim *s, int id, int dtype, std::initializer_list<int64_t> dims) {
     hs_tensor_desc &d = s->exports[id];
-    d.ptr = ptr; d.dtype = dtype; d.ndim = (int32_t)dims.size(); d.gpu_id = s->cfg.gpu_id;
-    int i = 0;
-    for (int64_t v : dims) d.dims[i++] = v;
-    for (; i < 4; ++i) d.dims[i] = 1;
+    d.dtype = dtype; d.ndim = 0; d.gpu_id = s->cfg.gpu_id;
+    for (int64_t v : dims) if (v) d.dims[d.ndim++] = v;
+    for (int i = d.ndim; i < 4; ++i) d.dims[i] = 1;
+    uint8_t *p;
+    HS_TRY(s->dalloc(&p, bytes_of(s, id)));
+    d.ptr = p;
+    return HS_OK;
 }
 
 // The renderer outputs (Manager::depthTensor / rgbTensor, src/mgr.cpp:1241-1263): allocated on first need, zero-filled.
 int ensure_render_buffers(hs_sim *s) {
-    if (s->exports[HS_EXPORT_RGB].ptr && s->exports[HS_EXPORT_DEPTH].ptr) return HS_OK;
     const int64_t r = (int64_t)s->S.N * s->A;
     const int64_t H = s->cfg.batch_render_height > 0 ? s->cfg.batch_render_height : 64;
     const int64_t Wd = s->cfg.batch_render_width > 0 ? s->cfg.batch_render_width : 64;
-    int rc;
-    if (!s->exports[HS_EXPORT_RGB].ptr) {
-        uint8_t *p; if ((rc = s->dalloc(&p, (size_t)(r * H * Wd * 4))) != HS_OK) return rc;
-        set_desc(s, HS_EXPORT_RGB, p, HS_DTYPE_U8, {r, H, Wd, 4});
-    }
-    if (!s->exports[HS_EXPORT_DEPTH].ptr) {
-        float *p; if ((rc = s->dalloc(&p, (size_t)(r * H * Wd))) != HS_OK) return rc;
-        set_desc(s, HS_EXPORT_DEPTH, p, HS_DTYPE_F32, {r, H, Wd, 1});
-    }
+    if (!s->exports[HS_EXPORT_RGB].ptr) HS_TRY(alloc_export(s, HS_EXPORT_RGB, HS_DTYPE_U8, {r, H, Wd, 4}));
+    if (!s->exports[HS_EXPORT_DEPTH].ptr) HS_TRY(alloc_export(s, HS_EXPORT_DEPTH, HS_DTYPE_F32, {r, H, Wd, 1}));
     return HS_OK;
 }
 // k_render over every view (hs_k_render.h); the buffers exist (ensure_render_buffers).
@@ -220,7 +267,9 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     if (cfg->gpu_id < 0 || cfg->gpu_id >= ndev) return fail(HS_ERR_INVALID_ARG, "gpu_id out of range");
     HS_HIP(hipSetDevice(cfg->gpu_id));
 
-    hs_sim *s = new hs_sim();
+    struct Destroy { void operator()(hs_sim *p) const { hs_destroy(p); } };
+    std::unique_ptr<hs_sim, Destroy> guard(new hs_sim());      // any return before the release below frees everything
+    hs_sim *s = guard.get();
     s->cfg = *cfg;
     s->A = A;
     hs::SimState &S = s->S;
@@ -232,8 +281,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     S.minSeekers = cfg->min_seekers; S.maxSeekers = cfg->max_seekers;
     S.worldOffset = cfg->world_offset;
     const int D = hs::kNumDSlots, AG = hs::kMaxAgents;
-    int rc = HS_OK;
-#define HS_ALLOC(ptr, n) if ((rc = s->dalloc(&(ptr), (n))) != HS_OK) { hs_destroy(s); return rc; }
+#define HS_ALLOC(ptr, ...) HS_TRY(s->dalloc(&(ptr), __VA_ARGS__))
     // tiled columns (hs_state.h Col): whole octets, the padding worlds stay zero = empty slots
     const size_t NP = (N + hs::kTile - 1) / hs::kTile * hs::kTile;
     // the tiled columns are consecutive pieces of ONE arena (so that the periodic deal moves them in one launch): all have
@@ -257,19 +305,19 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(S.numWalls, N); HS_ALLOC(S.numPlanes, N);
     HS_ALLOC(S.curWorldEpisode, N); HS_ALLOC(S.rngKeyA, N); HS_ALLOC(S.rngKeyB, N); HS_ALLOC(S.rngCount, N);
     HS_ALLOC(S.curEpisodeStep, N); HS_ALLOC(S.hiderTeamReward, N); HS_ALLOC(S.counts, N); HS_ALLOC(S.teams, N);
-    HS_ALLOC(S.epKeyA, N); HS_ALLOC(S.epKeyB, N); HS_ALLOC(S.xCkptCtrl, N); HS_ALLOC(S.xCkpt, N * sizeof(hs_checkpoint));
-    HS_ALLOC(S.xReset, N); HS_ALLOC(S.xPrep, R); HS_ALLOC(S.xAction, R * 5); HS_ALLOC(S.xSelfType, R);
-    HS_ALLOC(S.xSeed, R * 2); HS_ALLOC(S.xDone, R); HS_ALLOC(S.xPolicy, R);
-    HS_ALLOC(S.xSelfObs, R * 13); HS_ALLOC(S.xSelfMask, R); HS_ALLOC(S.xAgentObs, R * 5 * 14);
-    HS_ALLOC(S.xBoxObs, R * 9 * 17); HS_ALLOC(S.xRampObs, R * 2 * 14); HS_ALLOC(S.xVisAgents, R * 5);
-    HS_ALLOC(S.xVisBoxes, R * 9); HS_ALLOC(S.xVisRamps, R * 2); HS_ALLOC(S.xLidar, R * 30);
-    HS_ALLOC(S.xReward, R); HS_ALLOC(S.xGlobalPos, N * 34); HS_ALLOC(S.xEpisodeResult, N * 2);
+    HS_ALLOC(S.epKeyA, N); HS_ALLOC(S.epKeyB, N);
+    // the exported tensors (kExports): descriptor, allocation, and the kernels' pointer to it
+    std::memset(s->exports, 0, sizeof(s->exports));
+    for (const ExportRow &e : kExports) {
+        HS_TRY(alloc_export(s, e.id, e.dtype, {(int64_t)(e.per_agent ? R : N), e.tail[0], e.tail[1]}));
+        std::memcpy((char *)&S + e.field, &s->exports[e.id].ptr, sizeof(void *));
+    }
     // (every possible pair of every world: 92 KB per world, 1.5 GB at 16 000 worlds, of which a step touches a few MB)
     { char *p; HS_ALLOC(p, NP * hs::kAllDD * sizeof(hs::ManDD)); S.wsDD = p; HS_ALLOC(p, NP * hs::kAllSC * sizeof(hs::ManS)); S.wsSC = p; }
     HS_ALLOC(S.spPair, NP * (hs::kAllDD + hs::kAllSC)); HS_ALLOC(S.spInfo, NP * hs::kSpInfoWords);
     HS_ALLOC(S.phaseTicks, hs::phase_ticks_obs_base((int)N) + 16 * 1024);   // + k_observe's section counters
     HS_ALLOC(S.slotOfWorld, N); HS_ALLOC(S.worldOfSlot, NP); HS_ALLOC(S.loadAcc, N); HS_ALLOC(S.wallHist, N);
-    if ((rc = s->dalloc(&S.slotHdr, NP, 0xFF)) != HS_OK) { hs_destroy(s); return rc; }      // world id -1: empty slot
+    HS_ALLOC(S.slotHdr, NP, 0xFF);                                                          // world id -1: empty slot
     HS_ALLOC(S.lidarSinCos, 60);
     HS_ALLOC(S.octTicks, NP / hs::kTile); HS_ALLOC(S.tickSum, 3);
     HS_ALLOC(s->bal_hist, hs::kBalanceBins); HS_ALLOC(s->bal_cursor, hs::kBalanceBins); HS_ALLOC(s->bal_new_slot, N);
@@ -282,50 +330,22 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
         if (hipMemcpy(S.slotOfWorld, ident.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(S.worldOfSlot, ident.data(), NP * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(S.xReset, ones.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(S.grabOther.p, neg.data(), AG * NP * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            hs_destroy(s);
+            hipMemcpy(S.grabOther.p, neg.data(), AG * NP * 4, hipMemcpyHostToDevice) != hipSuccess)
             return fail(HS_ERR_HIP, "initial upload failed");
-        }
     }
-    for (auto &e : s->ev) {
-        if (hipEventCreate(&e) != hipSuccess) { hs_destroy(s); return fail(HS_ERR_HIP, "hipEventCreate failed"); }
-    }
+    for (auto &e : s->ev)
+        if (hipEventCreate(&e) != hipSuccess) return fail(HS_ERR_HIP, "hipEventCreate failed");
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s->evIn, hipEventDisableTiming) != hipSuccess) { hs_destroy(s); return fail(HS_ERR_HIP, "stream/event creation failed"); }
+        hipEventCreateWithFlags(&s->evIn, hipEventDisableTiming) != hipSuccess) return fail(HS_ERR_HIP, "stream/event creation failed");
     S.wbeg = 0; S.wcnt = (int)N;
     hipLaunchKernelGGL(hs::k_lidar_table, dim3(1), dim3(64), 0, s->stream, S);
-    if (hipStreamSynchronize(s->stream) != hipSuccess) { hs_destroy(s); return fail(HS_ERR_HIP, "k_lidar_table failed"); }
-    std::memset(s->exports, 0, sizeof(s->exports));
-    const int64_t n = (int64_t)N, r = (int64_t)R;
-    set_desc(s, HS_EXPORT_RESET, S.xReset, HS_DTYPE_I32, {n, 1});
-    set_desc(s, HS_EXPORT_PREP_COUNTER, S.xPrep, HS_DTYPE_I32, {r, 1});
-    set_desc(s, HS_EXPORT_ACTION, S.xAction, HS_DTYPE_I32, {r, 5});
-    set_desc(s, HS_EXPORT_SELF_OBS, S.xSelfObs, HS_DTYPE_F32, {r, 13});
-    set_desc(s, HS_EXPORT_SELF_TYPE, S.xSelfType, HS_DTYPE_I32, {r, 1});
-    set_desc(s, HS_EXPORT_SELF_MASK, S.xSelfMask, HS_DTYPE_F32, {r, 1});
-    set_desc(s, HS_EXPORT_AGENT_OBS, S.xAgentObs, HS_DTYPE_F32, {r, 5, 14});
-    set_desc(s, HS_EXPORT_BOX_OBS, S.xBoxObs, HS_DTYPE_F32, {r, 9, 17});
-    set_desc(s, HS_EXPORT_RAMP_OBS, S.xRampObs, HS_DTYPE_F32, {r, 2, 14});
-    set_desc(s, HS_EXPORT_AGENT_VIS_MASKS, S.xVisAgents, HS_DTYPE_F32, {r, 5, 1});
-    set_desc(s, HS_EXPORT_BOX_VIS_MASKS, S.xVisBoxes, HS_DTYPE_F32, {r, 9, 1});
-    set_desc(s, HS_EXPORT_RAMP_VIS_MASKS, S.xVisRamps, HS_DTYPE_F32, {r, 2, 1});
-    set_desc(s, HS_EXPORT_LIDAR, S.xLidar, HS_DTYPE_F32, {r, 30});
-    set_desc(s, HS_EXPORT_SEED, S.xSeed, HS_DTYPE_I32, {r, 2});
-    set_desc(s, HS_EXPORT_REWARD, S.xReward, HS_DTYPE_F32, {r, 1});
-    set_desc(s, HS_EXPORT_DONE, S.xDone, HS_DTYPE_I32, {r, 1});
-    set_desc(s, HS_EXPORT_GLOBAL_DEBUG_POSITIONS, S.xGlobalPos, HS_DTYPE_F32, {n, 17, 2});
-    set_desc(s, HS_EXPORT_AGENT_POLICY, S.xPolicy, HS_DTYPE_I32, {r, 1});
-    set_desc(s, HS_EXPORT_EPISODE_RESULT, S.xEpisodeResult, HS_DTYPE_F32, {n, 2});
-    // raw bytes, as the reference exports them (mgr.cpp:1209-1227)
-    set_desc(s, HS_EXPORT_CHECKPOINT_CONTROL, S.xCkptCtrl, HS_DTYPE_U8, {n, (int64_t)sizeof(int32_t)});
-    set_desc(s, HS_EXPORT_CHECKPOINT, S.xCkpt, HS_DTYPE_U8, {n, (int64_t)sizeof(hs_checkpoint)});
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(HS_ERR_HIP, "k_lidar_table failed");
     if ((S.flags & hs::FLAG_EXT_RENDER) && cfg->enable_batch_renderer) {      // rendered by every init / step
-        const int rc = ensure_render_buffers(s);
-        if (rc != HS_OK) { hs_destroy(s); return rc; }
+        HS_TRY(ensure_render_buffers(s));
     } else {
         s->S.flags &= ~(uint32_t)hs::FLAG_EXT_RENDER;                         // (the flag needs the renderer switched on)
     }
-    *out = s;
+    *out = guard.release();
     return HS_OK;
 }
 
@@ -350,15 +370,18 @@ int order_after_default_stream(hs_sim *s) {
     HS_HIP(hipStreamWaitEvent(s->stream, s->evIn, 0));
     return HS_OK;
 }
+// A blocking call: `launch(s, stream)` on the handle's own stream, after the default stream's work, and waited for.
+int run_blocking(hs_sim *s, int (*launch)(hs_sim *, hipStream_t)) {
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch(s, s->stream));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
 }  // namespace
 
 int32_t hs_init(hs_sim *s) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = order_after_default_stream(s);
-    if (rc == HS_OK) rc = launch_step(s, s->stream, true);
-    if (rc != HS_OK) return rc;
-    HS_HIP(hipStreamSynchronize(s->stream));
+    HS_ENTER(s, "null sim");
+    HS_TRY(run_blocking(s, [](hs_sim *s, hipStream_t strm) { return launch_step(s, strm, true); }));
     s->initialised = true;
     return HS_OK;
 }
@@ -369,14 +392,11 @@ namespace {
 // waits for it anyway.  hs_step_begin / hs_step_end use the handle's own stream, so that the steps of several handles
 // (one per GPU) run side by side.
 int step_begin(hs_sim *s, bool own_stream) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
+    HS_ENTER(s, "null sim");
     if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_step_begin: the previous step was not ended");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = HS_OK;
     s->step_stream = own_stream ? s->stream : nullptr;
-    if (own_stream) rc = order_after_default_stream(s);
-    if (rc == HS_OK) rc = launch_step(s, s->step_stream, false);
-    if (rc != HS_OK) return rc;
+    if (own_stream) HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_step(s, s->step_stream, false));
     s->step_open = true;
     return HS_OK;
 }
@@ -385,10 +405,9 @@ int step_begin(hs_sim *s, bool own_stream) {
 int32_t hs_step_begin(hs_sim *s) { return step_begin(s, true); }
 
 int32_t hs_step_end(hs_sim *s) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
+    HS_ENTER(s, "null sim");
     if (!s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_step_end without hs_step_begin");
     s->step_open = false;
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
     HS_HIP(hipStreamSynchronize(s->step_stream));
     if (s->profiling) {
         HS_HIP(hipEventElapsedTime(&s->last_ms[0], s->ev[0], s->ev[1]));
@@ -399,15 +418,14 @@ int32_t hs_step_end(hs_sim *s) {
 }
 
 int32_t hs_step(hs_sim *s) {
-    int rc = step_begin(s, false);
-    return rc != HS_OK ? rc : hs_step_end(s);
+    HS_TRY(step_begin(s, false));
+    return hs_step_end(s);
 }
 
 int32_t hs_step_async(hs_sim *s, void *hip_stream) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = poll_status(s);               // a failure of an earlier asynchronous step surfaces here
-    return rc != HS_OK ? rc : launch_step(s, (hipStream_t)hip_stream, false);
+    HS_ENTER(s, "null sim");
+    HS_TRY(poll_status(s));                // a failure of an earlier asynchronous step surfaces here
+    return launch_step(s, (hipStream_t)hip_stream, false);
 }
 
 int32_t hs_get_tensor(hs_sim *s, int32_t id, hs_tensor_desc *out) {
@@ -417,25 +435,22 @@ int32_t hs_get_tensor(hs_sim *s, int32_t id, hs_tensor_desc *out) {
         // renderer outputs are allocated on first request; written only by hs_render / under HS_FLAG_EXT_RENDER
         if (id != HS_EXPORT_RGB && id != HS_EXPORT_DEPTH) return fail(HS_ERR_INVALID_ARG, "export not available");
         HS_HIP(hipSetDevice(s->cfg.gpu_id));
-        const int rc = ensure_render_buffers(s);
-        if (rc != HS_OK) return rc;
+        HS_TRY(ensure_render_buffers(s));
     }
     *out = s->exports[id];
     return HS_OK;
 }
 
 int32_t hs_render(hs_sim *s) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
+    HS_ENTER(s, "null sim");
     if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_render before hs_init");
     if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_render inside an open step");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = ensure_render_buffers(s);
-    if (rc == HS_OK) rc = order_after_default_stream(s);
-    if (rc != HS_OK) return rc;
-    launch_render(s, s->stream);
-    HS_HIP(hipGetLastError());
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
+    HS_TRY(ensure_render_buffers(s));
+    return run_blocking(s, [](hs_sim *s, hipStream_t strm) -> int {
+        launch_render(s, strm);
+        HS_HIP(hipGetLastError());
+        return HS_OK;
+    });
 }
 
 static_assert(sizeof(hs_camera) == sizeof(hs::SpectateCam) && offsetof(hs_camera, rot) == offsetof(hs::SpectateCam, rot) &&
@@ -444,7 +459,7 @@ static_assert((int)HS_SPECTATE_NO_CULL == (int)hs::kSpectateNoCull, "HS_SPECTATE
 
 int32_t hs_render_cameras(hs_sim *s, const hs_camera *cams, int32_t n, int32_t W, int32_t H, uint32_t flags, float *depth,
                           uint8_t *rgba, int32_t *hit) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
+    HS_ENTER(s, "null sim");
     if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras before hs_init");
     if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras inside an open step");
     if (!cams || n < 1) return fail(HS_ERR_INVALID_ARG, "hs_render_cameras: need at least one camera");
@@ -464,14 +479,12 @@ int32_t hs_render_cameras(hs_sim *s, const hs_camera *cams, int32_t n, int32_t W
         if (!(q2 >= 0.99 && q2 <= 1.01)) return fail(HS_ERR_INVALID_ARG, at() + "rotation is not a unit quaternion (|q|^2 outside [0.99, 1.01])");
         if (!(c.tan_half_fov_y > 0.f)) return fail(HS_ERR_INVALID_ARG, at() + "tan_half_fov_y must be > 0");
     }
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
     if (n > s->cam_cap) {
         if (s->cams) { HS_HIP(hipStreamSynchronize(s->stream)); HS_HIP(hipFree(s->cams)); s->cams = nullptr; s->cam_cap = 0; }
         HS_HIP(hipMalloc(&s->cams, (size_t)n * sizeof(hs::SpectateCam)));
         s->cam_cap = n;
     }
-    int rc = order_after_default_stream(s);
-    if (rc != HS_OK) return rc;
+    HS_TRY(order_after_default_stream(s));
     HS_HIP(hipMemcpyAsync(s->cams, cams, (size_t)n * sizeof(hs_camera), hipMemcpyHostToDevice, s->stream));
     const int tilesX = (W + hs::kSpectateTileW - 1) / hs::kSpectateTileW, tilesY = (H + hs::kSpectateTileH - 1) / hs::kSpectateTileH;
     const int tilesPerCam = tilesX * tilesY;
@@ -488,15 +501,13 @@ int32_t hs_render_cameras(hs_sim *s, const hs_camera *cams, int32_t n, int32_t W
 }
 
 int32_t hs_trigger_reset(hs_sim *s, int32_t world, int32_t level) {
-    if (!s || world < 0 || world >= s->S.N) return fail(HS_ERR_INVALID_ARG, "world index out of range");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && world >= 0 && world < s->S.N, "world index out of range");
     HS_HIP(hipMemcpy(s->S.xReset + world, &level, sizeof(int32_t), hipMemcpyHostToDevice));
     return HS_OK;
 }
 
 int32_t hs_set_action(hs_sim *s, int32_t agent, int32_t x, int32_t y, int32_t r, int32_t g, int32_t l) {
-    if (!s || agent < 0 || agent >= s->S.N * s->A) return fail(HS_ERR_INVALID_ARG, "agent index out of range");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && agent >= 0 && agent < s->S.N * s->A, "agent index out of range");
     int32_t a[5] = {x, y, r, g ? 1 : 0, l ? 1 : 0};
     HS_HIP(hipMemcpy(s->S.xAction + (size_t)agent * 5, a, sizeof(a), hipMemcpyHostToDevice));
     return HS_OK;
@@ -524,34 +535,22 @@ int set_ckpt_trigger(hs_sim *s, int32_t world) {
 }  // namespace
 
 int32_t hs_save_checkpoints(hs_sim *s) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = order_after_default_stream(s);
-    if (rc == HS_OK) rc = launch_save_ckpts(s, s->stream);
-    if (rc != HS_OK) return rc;
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
+    HS_ENTER(s, "null sim");
+    return run_blocking(s, launch_save_ckpts);
 }
 int32_t hs_load_checkpoints(hs_sim *s) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = order_after_default_stream(s);
-    if (rc == HS_OK) rc = launch_load_ckpts(s, s->stream);
-    if (rc != HS_OK) return rc;
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
+    HS_ENTER(s, "null sim");
+    return run_blocking(s, launch_load_ckpts);
 }
 int32_t hs_save_checkpoint(hs_sim *s, int32_t world) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = set_ckpt_trigger(s, world);
-    return rc != HS_OK ? rc : hs_save_checkpoints(s);
+    HS_ENTER(s, "null sim");
+    HS_TRY(set_ckpt_trigger(s, world));
+    return run_blocking(s, launch_save_ckpts);
 }
 int32_t hs_load_checkpoint(hs_sim *s, int32_t world) {
-    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
-    int rc = set_ckpt_trigger(s, world);
-    return rc != HS_OK ? rc : hs_load_checkpoints(s);
+    HS_ENTER(s, "null sim");
+    HS_TRY(set_ckpt_trigger(s, world));
+    return run_blocking(s, launch_load_ckpts);
 }
 
 // ---- stream entry points with the reference's JAX buffer order (mgr.cpp:168-201, 362-436) ----
@@ -562,70 +561,77 @@ int copy_dd(void *dst, const void *src, size_t bytes, hipStream_t strm) {
     HS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, strm));
     return HS_OK;
 }
-// copyOutObservations (mgr.cpp:340-360); returns the advanced buffer cursor through *pp
+// One operand or result of a stream entry point: the caller's buffer into / out of export `id`, all of its bytes.
+int copy_in(hs_sim *s, int id, const void *src, hipStream_t strm) { return copy_dd(s->exports[id].ptr, src, bytes_of(s, id), strm); }
+int copy_out(hs_sim *s, int id, void *dst, hipStream_t strm) { return copy_dd(dst, s->exports[id].ptr, bytes_of(s, id), strm); }
+
+// Manager::trainInterface (mgr.cpp:1338-1375), in its order (hs_train_interface)
+const hs_iface_entry kTrainInterface[] = {
+    {"actions", HS_ROLE_ACTION, HS_EXPORT_ACTION},
+    {"resets", HS_ROLE_RESET, HS_EXPORT_RESET},
+    {"sim_ctrl", HS_ROLE_SIM_CTRL, -1},
+    {"policy_assignments", HS_ROLE_PBT_INPUT, HS_EXPORT_AGENT_POLICY},
+    {"prep_counter", HS_ROLE_OBSERVATION, HS_EXPORT_PREP_COUNTER},
+    {"self_data", HS_ROLE_OBSERVATION, HS_EXPORT_SELF_OBS},
+    {"self_type", HS_ROLE_OBSERVATION, HS_EXPORT_SELF_TYPE},
+    {"self_mask", HS_ROLE_OBSERVATION, HS_EXPORT_SELF_MASK},
+    {"self_lidar", HS_ROLE_OBSERVATION, HS_EXPORT_LIDAR},
+    {"agent_data", HS_ROLE_OBSERVATION, HS_EXPORT_AGENT_OBS},
+    {"box_data", HS_ROLE_OBSERVATION, HS_EXPORT_BOX_OBS},
+    {"ramp_data", HS_ROLE_OBSERVATION, HS_EXPORT_RAMP_OBS},
+    {"vis_agents_mask", HS_ROLE_OBSERVATION, HS_EXPORT_AGENT_VIS_MASKS},
+    {"vis_boxes_mask", HS_ROLE_OBSERVATION, HS_EXPORT_BOX_VIS_MASKS},
+    {"vis_ramps_mask", HS_ROLE_OBSERVATION, HS_EXPORT_RAMP_VIS_MASKS},
+    {"rewards", HS_ROLE_REWARD, HS_EXPORT_REWARD},
+    {"dones", HS_ROLE_DONE, HS_EXPORT_DONE},
+    {"episode_results", HS_ROLE_PBT_OUTPUT, HS_EXPORT_EPISODE_RESULT},
+    {"checkpoint_data", HS_ROLE_CHECKPOINT, HS_EXPORT_CHECKPOINT},
+};
+// copyOutObservations (mgr.cpp:340-360): the observation rows of the interface, in its order; returns the advanced
+// buffer cursor through *pp
 int copy_out_observations(hs_sim *s, hipStream_t strm, void ***pp) {
-    const hs::SimState &S = s->S;
-    const size_t R = (size_t)S.N * s->A;
-    const struct { const void *src; size_t bytes; } obs[11] = {
-        {S.xPrep, R * 4}, {S.xSelfObs, R * 13 * 4}, {S.xSelfType, R * 4}, {S.xSelfMask, R * 4}, {S.xLidar, R * 30 * 4},
-        {S.xAgentObs, R * 5 * 14 * 4}, {S.xBoxObs, R * 9 * 17 * 4}, {S.xRampObs, R * 2 * 14 * 4},
-        {S.xVisAgents, R * 5 * 4}, {S.xVisBoxes, R * 9 * 4}, {S.xVisRamps, R * 2 * 4}};
-    for (const auto &o : obs) {
-        int rc = copy_dd(*(*pp)++, o.src, o.bytes, strm);
-        if (rc != HS_OK) return rc;
-    }
+    for (const hs_iface_entry &e : kTrainInterface)
+        if (e.role == HS_ROLE_OBSERVATION) HS_TRY(copy_out(s, e.export_id, *(*pp)++, strm));
     return HS_OK;
 }
 }  // namespace
 
 int32_t hs_jax_init(hs_sim *s, void *hip_stream, void **buffers) {
-    if (!s || !buffers) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && buffers, "null argument");
     hipStream_t strm = (hipStream_t)hip_stream;
-    int rc = launch_step(s, strm, true);
-    if (rc == HS_OK) rc = copy_out_observations(s, strm, &buffers);
-    if (rc != HS_OK) return rc;
+    HS_TRY(launch_step(s, strm, true));
+    HS_TRY(copy_out_observations(s, strm, &buffers));
     HS_HIP(hipStreamSynchronize(strm));          // gpuStreamInit synchronises (mgr.cpp:376)
     s->initialised = true;
     return HS_OK;
 }
 int32_t hs_jax_step(hs_sim *s, void *hip_stream, void **buffers) {
-    if (!s || !buffers) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && buffers, "null argument");
     hipStream_t strm = (hipStream_t)hip_stream;
-    const hs::SimState &S = s->S;
-    const size_t N = (size_t)S.N, R = N * s->A;
-    int rc = poll_status(s);               // a failure of an earlier asynchronous step surfaces here
-    if (rc == HS_OK) rc = copy_dd(S.xAction, *buffers++, R * 5 * 4, strm);
-    if (rc == HS_OK) rc = copy_dd(S.xReset, *buffers++, N * 4, strm);
-    if (rc == HS_OK) rc = copy_dd(S.xPolicy, *buffers++, R * 4, strm);
-    if (rc == HS_OK) rc = launch_step(s, strm, false);
-    if (rc == HS_OK) rc = copy_out_observations(s, strm, &buffers);
-    if (rc == HS_OK) rc = copy_dd(*buffers++, S.xReward, R * 4, strm);
-    if (rc == HS_OK) rc = copy_dd(*buffers++, S.xDone, R * 4, strm);
-    if (rc == HS_OK) rc = copy_dd(*buffers++, S.xEpisodeResult, N * 2 * 4, strm);
-    return rc;
+    HS_TRY(poll_status(s));                // a failure of an earlier asynchronous step surfaces here
+    HS_TRY(copy_in(s, HS_EXPORT_ACTION, *buffers++, strm));
+    HS_TRY(copy_in(s, HS_EXPORT_RESET, *buffers++, strm));
+    HS_TRY(copy_in(s, HS_EXPORT_AGENT_POLICY, *buffers++, strm));
+    HS_TRY(launch_step(s, strm, false));
+    HS_TRY(copy_out_observations(s, strm, &buffers));
+    HS_TRY(copy_out(s, HS_EXPORT_REWARD, *buffers++, strm));
+    HS_TRY(copy_out(s, HS_EXPORT_DONE, *buffers++, strm));
+    return copy_out(s, HS_EXPORT_EPISODE_RESULT, *buffers++, strm);
 }
 int32_t hs_jax_save_checkpoints(hs_sim *s, void *hip_stream, void **buffers) {
-    if (!s || !buffers) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && buffers, "null argument");
     hipStream_t strm = (hipStream_t)hip_stream;
-    const size_t N = (size_t)s->S.N;
-    int rc = copy_dd(s->S.xCkptCtrl, buffers[0], N * 4, strm);
-    if (rc == HS_OK) rc = launch_save_ckpts(s, strm);
-    if (rc == HS_OK) rc = copy_dd(buffers[1], s->S.xCkpt, N * sizeof(hs_checkpoint), strm);
-    return rc;
+    HS_TRY(copy_in(s, HS_EXPORT_CHECKPOINT_CONTROL, buffers[0], strm));
+    HS_TRY(launch_save_ckpts(s, strm));
+    return copy_out(s, HS_EXPORT_CHECKPOINT, buffers[1], strm);
 }
 int32_t hs_jax_load_checkpoints(hs_sim *s, void *hip_stream, void **buffers) {
-    if (!s || !buffers) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && buffers, "null argument");
     hipStream_t strm = (hipStream_t)hip_stream;
-    const size_t N = (size_t)s->S.N;
-    int rc = copy_dd(s->S.xCkptCtrl, *buffers++, N * 4, strm);
-    if (rc == HS_OK) rc = copy_dd(s->S.xCkpt, *buffers++, N * sizeof(hs_checkpoint), strm);
-    if (rc == HS_OK) rc = launch_load_ckpts(s, strm);
-    if (rc == HS_OK) rc = copy_out_observations(s, strm, &buffers);
-    return rc;
+    HS_TRY(copy_in(s, HS_EXPORT_CHECKPOINT_CONTROL, *buffers++, strm));
+    HS_TRY(copy_in(s, HS_EXPORT_CHECKPOINT, *buffers++, strm));
+    HS_TRY(launch_load_ckpts(s, strm));
+    return copy_out_observations(s, strm, &buffers);
 }
 
 // ---- XLA custom-call targets (the original, status-less GPU custom-call ABI) ----
@@ -651,8 +657,7 @@ int32_t hs_xla_last_status(int32_t clear) { return clear ? g_xla_status.exchange
 
 // Development aid (HS_PHASE_TIMING builds): accumulated wall-clock ticks per phase per workgroup of k_physics.
 int32_t hs_debug_phase_ticks(hs_sim *s, int64_t *out, int32_t max_groups) {
-    if (!s || !out) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && out, "null argument");
     int nb = (s->S.N + hs::kTile - 1) / hs::kTile;          // one workgroup (wave) per octet
     if (nb > max_groups) nb = max_groups;
     HS_HIP(hipMemcpy(out, s->S.phaseTicks, (size_t)nb * 10 * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -661,8 +666,7 @@ int32_t hs_debug_phase_ticks(hs_sim *s, int64_t *out, int32_t max_groups) {
 
 // The same for k_observe: ticks per section summed over all waves (HS_PHASE_TIMING builds).
 int32_t hs_debug_observe_ticks(hs_sim *s, int64_t out[16]) {
-    if (!s || !out) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && out, "null argument");
     std::vector<int64_t> part(16 * 1024);
     HS_HIP(hipMemcpy(part.data(), s->S.phaseTicks + hs::phase_ticks_obs_base(s->S.N), part.size() * sizeof(int64_t),
                      hipMemcpyDeviceToHost));
@@ -671,8 +675,7 @@ int32_t hs_debug_observe_ticks(hs_sim *s, int64_t out[16]) {
 }
 
 int32_t hs_debug_dump_bodies(hs_sim *s, float *bodies, int32_t *meta) {
-    if (!s || !bodies || !meta) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && bodies && meta, "null argument");
     HS_HIP(hipDeviceSynchronize());
     const size_t N = s->S.N, D = hs::kNumDSlots;
     HostCol<float, 3 * hs::kNumDSlots> pos, lin, ang; HostCol<float, 4 * hs::kNumDSlots> rot; HostCol<int, hs::kNumDSlots> m;
@@ -696,8 +699,7 @@ int32_t hs_debug_dump_bodies(hs_sim *s, float *bodies, int32_t *meta) {
 }
 
 int32_t hs_debug_dump_walls(hs_sim *s, float *walls, int32_t *info) {
-    if (!s || !walls || !info) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && walls && info, "null argument");
     HS_HIP(hipDeviceSynchronize());
     const size_t N = s->S.N, K = hs::kMaxWalls;
     HostCol<float, 4 * hs::kMaxWalls> wl;
@@ -800,35 +802,12 @@ int32_t hs_debug_object_params(int32_t obj, float *out) {
 void hs_dlpack_noop_deleter(void *) {}
 
 int32_t hs_train_interface(const hs_iface_entry **entries) {
-    // Manager::trainInterface (mgr.cpp:1338-1375), in its order
-    static const hs_iface_entry table[] = {
-        {"actions", HS_ROLE_ACTION, HS_EXPORT_ACTION},
-        {"resets", HS_ROLE_RESET, HS_EXPORT_RESET},
-        {"sim_ctrl", HS_ROLE_SIM_CTRL, -1},
-        {"policy_assignments", HS_ROLE_PBT_INPUT, HS_EXPORT_AGENT_POLICY},
-        {"prep_counter", HS_ROLE_OBSERVATION, HS_EXPORT_PREP_COUNTER},
-        {"self_data", HS_ROLE_OBSERVATION, HS_EXPORT_SELF_OBS},
-        {"self_type", HS_ROLE_OBSERVATION, HS_EXPORT_SELF_TYPE},
-        {"self_mask", HS_ROLE_OBSERVATION, HS_EXPORT_SELF_MASK},
-        {"self_lidar", HS_ROLE_OBSERVATION, HS_EXPORT_LIDAR},
-        {"agent_data", HS_ROLE_OBSERVATION, HS_EXPORT_AGENT_OBS},
-        {"box_data", HS_ROLE_OBSERVATION, HS_EXPORT_BOX_OBS},
-        {"ramp_data", HS_ROLE_OBSERVATION, HS_EXPORT_RAMP_OBS},
-        {"vis_agents_mask", HS_ROLE_OBSERVATION, HS_EXPORT_AGENT_VIS_MASKS},
-        {"vis_boxes_mask", HS_ROLE_OBSERVATION, HS_EXPORT_BOX_VIS_MASKS},
-        {"vis_ramps_mask", HS_ROLE_OBSERVATION, HS_EXPORT_RAMP_VIS_MASKS},
-        {"rewards", HS_ROLE_REWARD, HS_EXPORT_REWARD},
-        {"dones", HS_ROLE_DONE, HS_EXPORT_DONE},
-        {"episode_results", HS_ROLE_PBT_OUTPUT, HS_EXPORT_EPISODE_RESULT},
-        {"checkpoint_data", HS_ROLE_CHECKPOINT, HS_EXPORT_CHECKPOINT},
-    };
-    if (entries) *entries = table;
-    return (int32_t)(sizeof(table) / sizeof(table[0]));
+    if (entries) *entries = kTrainInterface;
+    return (int32_t)(sizeof(kTrainInterface) / sizeof(kTrainInterface[0]));
 }
 
 int32_t hs_get_device_status(hs_sim *s, hs_device_status *out) {
-    if (!s || !out) return fail(HS_ERR_INVALID_ARG, "null argument");
-    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    HS_ENTER(s && out, "null argument");
     HS_HIP(hipDeviceSynchronize());
     int st[4];
     HS_HIP(hipMemcpy(st, s->S.status, sizeof(st), hipMemcpyDeviceToHost));

@@ -47,6 +47,25 @@ _EXPORTS = dict(reset=0, prep_counter=1, action=2, self_data=3, self_type=4, sel
 
 
 _EXPORT_NAMES = {v: k for k, v in _EXPORTS.items()}
+# getter -> export: the 21 getters of bindings.cpp:76-96 and Manager::episodeResultTensor / policyAssignmentsTensor
+# (mgr.cpp:1312-1331; JAX interface only) are <export>_tensor()
+_GETTERS = {name: name for name in _EXPORTS}
+# scripts/cpu_benchmark.py:77 calls a getter the reference binding lacks
+_GETTERS["agent_mask"] = "self_mask"
+
+
+def _tensor_getters(cls):
+    """Class decorator: a <getter>_tensor() method for every entry of _GETTERS, returning cls._tensor(<export>)."""
+    def make(getter, export):
+        def method(self):
+            return self._tensor(export)
+        method.__name__ = getter + "_tensor"
+        method.__qualname__ = f"{cls.__name__}.{getter}_tensor"
+        method.__doc__ = f"The `{export}` tensor of the simulator (export id {_EXPORTS[export]}, include/hideseek.h)."
+        return method
+    for getter, export in _GETTERS.items():
+        setattr(cls, getter + "_tensor", make(getter, export))
+    return cls
 _ROLES = {0: "actions", 1: "resets", 2: "sim_ctrl", 3: "pbt_inputs", 4: "observations", 5: "rewards", 6: "dones",
           7: "pbt_outputs", 8: "checkpoint_data"}
 
@@ -77,6 +96,7 @@ def _close_all():
         s.close()
 
 
+@_tensor_getters
 class HideAndSeekSimulator:
     """gpu_hideseek.HideAndSeekSimulator (src/bindings.cpp:31-118)."""
 
@@ -149,33 +169,7 @@ class HideAndSeekSimulator:
             t = self._tensors[name] = Tensor(weakref.proxy(self), d)
         return t
 
-    # the 21 getters of bindings.cpp:76-96
-    def reset_tensor(self): return self._tensor("reset")
-    def done_tensor(self): return self._tensor("done")
-    def prep_counter_tensor(self): return self._tensor("prep_counter")
-    def action_tensor(self): return self._tensor("action")
-    def reward_tensor(self): return self._tensor("reward")
-    def self_data_tensor(self): return self._tensor("self_data")
-    def self_type_tensor(self): return self._tensor("self_type")
-    def self_mask_tensor(self): return self._tensor("self_mask")
-    def agent_data_tensor(self): return self._tensor("agent_data")
-    def box_data_tensor(self): return self._tensor("box_data")
-    def ramp_data_tensor(self): return self._tensor("ramp_data")
-    def visible_agents_mask_tensor(self): return self._tensor("visible_agents_mask")
-    def visible_boxes_mask_tensor(self): return self._tensor("visible_boxes_mask")
-    def visible_ramps_mask_tensor(self): return self._tensor("visible_ramps_mask")
-    def global_positions_tensor(self): return self._tensor("global_positions")
-    def depth_tensor(self): return self._tensor("depth")
-    def rgb_tensor(self): return self._tensor("rgb")
-    def lidar_tensor(self): return self._tensor("lidar")
-    def seed_tensor(self): return self._tensor("seed")
-    def ckpt_ctrl_tensor(self): return self._tensor("ckpt_ctrl")
-    def ckpt_tensor(self): return self._tensor("ckpt")
-    # scripts/cpu_benchmark.py:77 calls a getter the reference binding lacks
-    def agent_mask_tensor(self): return self._tensor("self_mask")
-    # Manager::episodeResultTensor / policyAssignmentsTensor (mgr.cpp:1312-1331; JAX interface only)
-    def episode_result_tensor(self): return self._tensor("episode_result")
-    def policy_assignments_tensor(self): return self._tensor("policy_assignments")
+    # reset_tensor(), action_tensor(), ...: _tensor_getters
 
     def trigger_reset(self, world_idx, level_idx):
         _check(self._L.hs_trigger_reset(self._h, int(world_idx), int(level_idx)))

@@ -13,12 +13,7 @@ Tensors: `sim.action_tensor()` etc. return a ShardedTensor — `.shards` are the
 `.gather()` concatenates them into ONE pinned host tensor (rows in global world order), `.scatter(t)` writes a
 host tensor of that shape back to the devices (actions, resets).
 """
-from . import madrona
-
-_GETTERS = ["reset", "done", "prep_counter", "action", "reward", "self_data", "self_type", "self_mask", "agent_data",
-            "box_data", "ramp_data", "visible_agents_mask", "visible_boxes_mask", "visible_ramps_mask",
-            "global_positions", "depth", "rgb", "lidar", "seed", "ckpt_ctrl", "ckpt", "agent_mask", "episode_result",
-            "policy_assignments"]
+from . import _tensor_getters, madrona
 
 
 def shard_ranges(num_worlds, num_shards):
@@ -92,6 +87,7 @@ class ShardedTensor:
         return self.shards[0].to_torch() if len(self.shards) == 1 else self.gather()
 
 
+@_tensor_getters
 class ShardedSimulator:
     def __init__(self, gpu_ids, num_worlds, **kw):
         from . import HideAndSeekSimulator
@@ -155,14 +151,3 @@ class ShardedSimulator:
     def close(self):
         for s in self.shards:
             s.close()
-
-
-def _make_getter(name):
-    def getter(self):
-        return self._tensor(name)
-    getter.__name__ = name + "_tensor"
-    return getter
-
-
-for _n in _GETTERS:
-    setattr(ShardedSimulator, _n + "_tensor", _make_getter(_n))

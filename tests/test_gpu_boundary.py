@@ -39,6 +39,30 @@ def test_tensor_shapes_dtypes_and_device():
         assert tuple(t.shape) == shape and t.dtype == dt and t.is_cuda and t.is_contiguous(), name
 
 
+@pytest.mark.parametrize("hiders, seekers", [(2, 2), (3, 3)])
+def test_every_export_matches_the_oracles_table(hiders, seekers):
+    """The library's export table (csrc/hideseek.hip kExports, as the getters report it) against the oracle's independent
+    statement of the same tensors (hs_ref.TENSORS): export id, dtype, and shape with N rows for a per-world entry and
+    N * A for a per-agent one.  ckpt_ctrl is exported as raw bytes, u8 [N, 4], where the oracle says i32 [N, 1]
+    (mgr.cpp:1209-1217): rows and bytes per row must agree."""
+    import gpu_hideseek
+    import hs_ref
+    import torch
+    N, A = 24, hiders + seekers
+    sim = _sim(N, min_hiders=hiders, max_hiders=hiders, min_seekers=seekers, max_seekers=seekers)
+    assert sim.agents_per_world == A
+    torch_dtype = {np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
+    for name, (eid, dt, tail, per_agent) in hs_ref.TENSORS.items():
+        assert gpu_hideseek._EXPORTS[name] == eid, name
+        t = getattr(sim, name + "_tensor")().to_torch()
+        shape = (N * A if per_agent else N,) + tail
+        if name == "ckpt_ctrl":
+            assert t.dtype == torch.uint8 and tuple(t.shape) == (N, 4), name
+            assert t.shape[0] == shape[0] and t[0].numel() * t.element_size() == int(np.prod(tail)) * np.dtype(dt).itemsize
+        else:
+            assert tuple(t.shape) == shape and t.dtype == torch_dtype[dt], name
+
+
 def test_tensors_alias_simulator_memory():
     """The scripts mutate action/reset in place (benchmark.py:64-65,82-84): views must be zero-copy
     and persistent."""

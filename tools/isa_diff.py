@@ -11,7 +11,7 @@ def kernels(path):
     out, name = {}, None
     for l in open(path):
         l = re.sub(r"\s*(;|//).*", "", l).strip()
-        m = re.match(r"(_Z\w+):$", l)
+        m = re.match(r"((?:_Z|k_)\w+):$", l)      # mangled names, and the extern "C" kernels of hideseek.hip
         if m:
             name = m.group(1)
             out[name] = []
