@@ -95,7 +95,8 @@ enum {
     HS_NUM_EXPORTS = 23
 };
 
-enum { HS_DTYPE_I32 = 0, HS_DTYPE_F32 = 1, HS_DTYPE_U8 = 2 };
+/* Element types.  HS_DTYPE_BF16 / HS_DTYPE_F16 are output types of hs_pack_policy_inputs only: no export has them. */
+enum { HS_DTYPE_I32 = 0, HS_DTYPE_F32 = 1, HS_DTYPE_U8 = 2, HS_DTYPE_BF16 = 3, HS_DTYPE_F16 = 4 };
 
 /* madrona::py::Tensor (src/mgr.cpp:824-842): pointer, element type, dimensions, device. */
 typedef struct hs_tensor_desc {
@@ -198,6 +199,38 @@ int32_t hs_load_checkpoint(hs_sim *sim, int32_t world_idx);
 int32_t hs_load_checkpoints(hs_sim *sim);
 /* CUDAImpl::saveCheckpoints (src/mgr.cpp:316-319): run the SaveCheckpoints graph for the current triggers. */
 int32_t hs_save_checkpoints(hs_sim *sim);
+
+/* Policy inputs: what the reference's policy makes of the observation exports before its network sees them
+ * (scripts/jax_policy.py:84-98 extract_self_obs, :262-280 the actor's tables, :372-390 the critic's), as one row of
+ * HS_PACK_ROW features per agent row (world * A + slot), written in the learner's element type into the learner's memory:
+ *   column 0        (float)prep_counter / 96.0f              (jax_policy.py:86)
+ *   columns 1-13    self_data;  14: (float)self_type;  15-44: lidar       (the "self" row, jax_policy.py:88-98)
+ *   columns 45-114  agent_data [5][14];  115-267: box_data [9][17];  268-295: ramp_data [2][14]
+ * critic: the data as exported (jax_policy.py:372-390).  actor: columns 45-295 are data * visibility mask of the entity,
+ * an IEEE f32 multiplication (jax_policy.py:262-280: agent_data * vis_agents_mask, ...).  HS_DTYPE_BF16 / HS_DTYPE_F16
+ * round the f32 value to nearest even (jnp.astype, jax_policy.py:84; f16 subnormals kept, beyond 65504: infinity).
+ * moments [HS_PACK_MOMENTS] f64, for an observation normaliser: with m = self_mask of the row (1.0 or 0.0,
+ * src/level_gen.cpp:21, 332) and x the f32 critic value of column c: [c] = sum m x, [HS_PACK_ROW + c] = sum m x x,
+ * [2 HS_PACK_ROW] = sum m, over all rows.  Summed without atomics in an order that depends on the row count alone: the
+ * same state gives the same bits on every call.  The partial sums go through a workspace of the handle, so two calls
+ * with moments on one handle must not overlap.
+ * Outputs are caller-owned device memory of the handle's GPU: contiguous [rows][HS_PACK_ROW], 16-byte aligned.  Any may
+ * be null, not all three.  Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written):
+ * null request, every output null, unknown dtype, misaligned pointer.  HS_ERR_INVALID_ARG before hs_init and inside an
+ * open step; HS_ERR_UNSUPPORTED under HS_FLAG_EXT_SKIP_OBSERVATIONS (there are no observations).  Writes no simulator
+ * state.  hs_pack_policy_inputs is ordered after the device's legacy default stream and blocking;
+ * hs_pack_policy_inputs_async enqueues on the caller's hipStream_t without synchronising, as hs_jax_step does (the
+ * caller orders it after the step that wrote the observations). */
+enum { HS_PACK_ROW = 296, HS_PACK_MOMENTS = 593 };
+typedef struct hs_pack_request {
+    void *actor;                  /* [rows][HS_PACK_ROW] of actor_dtype, or null */
+    int32_t actor_dtype;          /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    void *critic;
+    int32_t critic_dtype;
+    double *moments;              /* [HS_PACK_MOMENTS], or null */
+} hs_pack_request;
+int32_t hs_pack_policy_inputs(hs_sim *sim, const hs_pack_request *req);
+int32_t hs_pack_policy_inputs_async(hs_sim *sim, void *hip_stream, const hs_pack_request *req);
 
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.

@@ -21,6 +21,7 @@
 #include "hs_k_spectate.h"
 #include "hs_k_physics.h"
 #include "hs_k_balance.h"
+#include "hs_k_pack.h"
 #include "hs_solver.h"
 
 namespace {
@@ -73,6 +74,7 @@ struct hs_sim {
     std::atomic<int32_t> async_error{0};   // a failed XLA custom call on this handle (hs_xla_*: the ABI has no status channel; XLA's thread)
     hs::SpectateCam *cams = nullptr;       // hs_render_cameras: the device copy of the cameras, grown on demand
     int cam_cap = 0;
+    double *pack_partials = nullptr;       // hs_pack_policy_inputs: the moments of each workgroup, [pack_grid][HS_PACK_MOMENTS]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -119,6 +121,18 @@ constexpr ExportRow kExports[] = {
 };
 #undef HS_X
 static_assert(sizeof(kExports) / sizeof(kExports[0]) == HS_EXPORT_DEPTH, "a row per export below the renderer outputs");
+
+// k_pack's row (hs_k_pack.h) is made of these exports, with their widths
+constexpr bool pack_table(int id, int64_t t0, int64_t t1, int32_t dtype = HS_DTYPE_F32) {
+    return kExports[id].id == id && kExports[id].per_agent && kExports[id].dtype == dtype && kExports[id].tail[0] == t0 && kExports[id].tail[1] == t1;
+}
+static_assert(pack_table(HS_EXPORT_PREP_COUNTER, 1, 0, HS_DTYPE_I32) && pack_table(HS_EXPORT_SELF_TYPE, 1, 0, HS_DTYPE_I32) &&
+              pack_table(HS_EXPORT_SELF_MASK, 1, 0) && pack_table(HS_EXPORT_SELF_OBS, hs::kPackSelfW, 0) &&
+              pack_table(HS_EXPORT_LIDAR, hs::kPackLidarW, 0) && pack_table(HS_EXPORT_AGENT_OBS, hs::kPackAgentN, hs::kPackAgentW) &&
+              pack_table(HS_EXPORT_BOX_OBS, hs::kPackBoxN, hs::kPackBoxW) && pack_table(HS_EXPORT_RAMP_OBS, hs::kPackRampN, hs::kPackRampW) &&
+              pack_table(HS_EXPORT_AGENT_VIS_MASKS, hs::kPackAgentN, 1) && pack_table(HS_EXPORT_BOX_VIS_MASKS, hs::kPackBoxN, 1) &&
+              pack_table(HS_EXPORT_RAMP_VIS_MASKS, hs::kPackRampN, 1), "k_pack's widths are those of kExports");
+static_assert(HS_PACK_ROW == hs::kPackRow && HS_PACK_MOMENTS == hs::kPackMoments, "hs_pack_request layout");
 
 size_t bytes_of(const hs_sim *s, int id) {
     const hs_tensor_desc &d = s->exports[id];
@@ -226,6 +240,53 @@ int poll_status(hs_sim *s) {
 
 }  // namespace
 
+// ---- policy inputs (hs_k_pack.h) ----
+namespace {
+template <typename TA, typename TC, bool MOM> void launch_pack_as(const hs::PackArgs &a, hipStream_t strm) {
+    if constexpr (std::is_same<TA, hs::PackAbsent>::value && std::is_same<TC, hs::PackAbsent>::value && !MOM) return;
+    else hipLaunchKernelGGL((hs::k_pack<TA, TC, MOM>), dim3(hs::pack_grid(a.rows)), dim3(hs::kPackThreads), 0, strm, a);
+}
+// f(tag) with the element type of output `p` of type `dtype` as tag's type
+template <typename F> void with_pack_type(const void *p, int32_t dtype, F f) {
+    if (!p) f(hs::PackAbsent{});
+    else if (dtype == HS_DTYPE_F32) f(float{});
+    else if (dtype == HS_DTYPE_BF16) f(hs::PackBf16{});
+    else f(hs::PackF16{});
+}
+bool pack_dtype_ok(int32_t d) { return d == HS_DTYPE_F32 || d == HS_DTYPE_BF16 || d == HS_DTYPE_F16; }
+
+int check_pack(hs_sim *s, const hs_pack_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: null request");
+    if (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)
+        return fail(HS_ERR_UNSUPPORTED, "hs_pack_policy_inputs: HS_FLAG_EXT_SKIP_OBSERVATIONS leaves no observations to pack");
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs inside an open step");
+    if (!r->actor && !r->critic && !r->moments) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: every output is null");
+    if ((r->actor && !pack_dtype_ok(r->actor_dtype)) || (r->critic && !pack_dtype_ok(r->critic_dtype)))
+        return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: output dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (((uintptr_t)r->actor | (uintptr_t)r->critic) & 15u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: outputs must be 16-byte aligned");
+    if ((uintptr_t)r->moments & 7u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: moments must be 8-byte aligned");
+    return HS_OK;
+}
+// One k_pack over every agent row (the request has passed check_pack), then the fixed-order sum of the moments.
+int launch_pack(hs_sim *s, hipStream_t strm, const hs_pack_request *r) {
+    const hs::SimState &S = s->S;
+    const hs::PackArgs a = {S.xPrep, S.xSelfType, S.xSelfObs, S.xSelfMask, S.xLidar, S.xAgentObs, S.xBoxObs, S.xRampObs,
+                            S.xVisAgents, S.xVisBoxes, S.xVisRamps, r->actor, r->critic, s->pack_partials, S.N * s->A};
+    with_pack_type(r->actor, r->actor_dtype, [&](auto ta) {
+        with_pack_type(r->critic, r->critic_dtype, [&](auto tc) {
+            if (r->moments) launch_pack_as<decltype(ta), decltype(tc), true>(a, strm);
+            else launch_pack_as<decltype(ta), decltype(tc), false>(a, strm);
+        });
+    });
+    if (r->moments)
+        hipLaunchKernelGGL(hs::k_pack_moments_sum<>, dim3((hs::kPackMoments + hs::kPackThreads / hs::kPackSumSegs - 1) / (hs::kPackThreads / hs::kPackSumSegs)),
+                           dim3(hs::kPackThreads), 0, strm, (const double *)s->pack_partials, hs::pack_grid(a.rows), r->moments);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -322,6 +383,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(S.octTicks, NP / hs::kTile); HS_ALLOC(S.tickSum, 3);
     HS_ALLOC(s->bal_hist, hs::kBalanceBins); HS_ALLOC(s->bal_cursor, hs::kBalanceBins); HS_ALLOC(s->bal_new_slot, N);
     HS_ALLOC(S.status, 4);
+    if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -632,6 +694,21 @@ int32_t hs_jax_load_checkpoints(hs_sim *s, void *hip_stream, void **buffers) {
     HS_TRY(copy_in(s, HS_EXPORT_CHECKPOINT, *buffers++, strm));
     HS_TRY(launch_load_ckpts(s, strm));
     return copy_out_observations(s, strm, &buffers);
+}
+
+// ---- policy inputs (hs_k_pack.h; check_pack / launch_pack above) ----
+int32_t hs_pack_policy_inputs_async(hs_sim *s, void *hip_stream, const hs_pack_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_pack(s, req));
+    return launch_pack(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_pack_policy_inputs(hs_sim *s, const hs_pack_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_pack(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_pack(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
 }
 
 // ---- XLA custom-call targets (the original, status-less GPU custom-call ABI) ----

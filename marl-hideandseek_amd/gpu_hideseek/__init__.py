@@ -149,6 +149,16 @@ class HideAndSeekSimulator:
         from . import spectate
         return spectate.render(self, cameras, width, height, depth, rgb, hit, out, exact)
 
+    def pack_policy_inputs(self, actor=None, critic=None, moments=None, *, dtype=None, stream=None):
+        """Pack the observation exports into policy-input rows [num_worlds * agents_per_world, 296] in one kernel
+        (gpu_hideseek.policy_inputs: LAYOUT, views, moments_to_mean_var; hs_pack_policy_inputs).  `actor` (entity tables
+        times their visibility masks) and `critic` (unmasked) are each True (a new tensor of `dtype`: float32, bfloat16
+        or float16), a preallocated tensor (its dtype is taken; a slot buf[t] of a [T, R, 296] rollout buffer will do) or
+        None; `moments` likewise, [593] float64.  stream=None blocks; a torch.cuda.Stream or raw handle enqueues there
+        without synchronising (the caller orders it after the step).  Returns {name: tensor} of what was written."""
+        from . import policy_inputs
+        return policy_inputs.pack(self, actor, critic, moments, dtype, stream)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

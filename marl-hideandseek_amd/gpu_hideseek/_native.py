@@ -86,6 +86,10 @@ def load():
     L.hs_render_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     L.hs_render_cameras.restype = C.c_int32
+    L.hs_pack_policy_inputs.argtypes = [C.c_void_p, C.c_void_p]                 # (sim, const hs_pack_request *)
+    L.hs_pack_policy_inputs.restype = C.c_int32
+    L.hs_pack_policy_inputs_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]   # (sim, hipStream_t, request)
+    L.hs_pack_policy_inputs_async.restype = C.c_int32
     L.hs_trigger_reset.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.hs_trigger_reset.restype = C.c_int32
     L.hs_set_action.argtypes = [C.c_void_p] + [C.c_int32] * 6

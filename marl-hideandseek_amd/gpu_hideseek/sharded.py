@@ -141,6 +141,13 @@ class ShardedSimulator:
         from . import spectate
         return spectate.render_sharded(self, cameras, width, height, depth, rgb, hit, out, exact)
 
+    def pack_policy_inputs(self, actor=None, critic=None, moments=None, *, dtype=None, stream=None):
+        """HideAndSeekSimulator.pack_policy_inputs per shard: a list of the shards' results, each on its own device.
+        Every argument is True / None for all shards or a list with one entry per shard; every shard's pack is enqueued
+        before any is waited for."""
+        from . import policy_inputs
+        return policy_inputs.pack_sharded(self, actor, critic, moments, dtype, stream)
+
     def device_status(self):
         out = {}
         for s in self.shards:
