@@ -334,7 +334,7 @@ int32_t hs_debug_dump_hull(int32_t obj, float *verts, int32_t *faces, int32_t *c
                            float *local);
 
 /* The DEVICE's object table for one SimObject: out[6] = inverse mass, static / dynamic friction coefficient, inverse inertia x y z
- * (object frame) as the kernels use them (csrc/hs_dev.h).  tests/test_gpu_hulls.py pins the first three and the zeroed
+ * (object frame) as the kernels use them (csrc/hs_core.h, the scalar core the CPU oracle reads too).  tests/test_gpu_hulls.py pins the first three and the zeroed
  * inertia axes of the agents to tests/golden/object_table.json (src/mgr.cpp:441-588). */
 int32_t hs_debug_object_params(int32_t obj, float *out);
 

@@ -12,7 +12,6 @@
 namespace hs {
 
 struct Seg { float x1, y1, x2, y2; };
-struct AABB { V3 lo, hi; };
 
 HSD Seg seg_make(float ax, float ay, float bx, float by) {     // geo_gen.cpp:60-65
     if (ax > bx || ay > by) return {bx, by, ax, ay};
@@ -188,10 +187,6 @@ HSD AABB object_aabb(int obj) {
     if (obj == OBJ_RAMP) return {{-1.f, -2.f, -1.f}, {1.f, 1.f, 1.f}};
     if (obj == OBJ_BOX) return {{-4.f, -0.75f, -1.f}, {4.f, 0.75f, 1.f}};
     return {{-1.f, -1.f, -1.f}, {1.f, 1.f, 1.f}};
-}
-HSD bool aabb_overlaps(const AABB &a, const AABB &b) {
-    return a.lo.x < b.hi.x && b.lo.x < a.hi.x && a.lo.y < b.hi.y && b.lo.y < a.hi.y &&
-           a.lo.z < b.hi.z && b.lo.z < a.hi.z;
 }
 
 // Per-lane working copy of the world being generated.

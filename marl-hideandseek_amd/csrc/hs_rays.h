@@ -11,9 +11,6 @@
 
 namespace hs {
 
-constexpr int kHitWallBase = 100;
-constexpr int kHitPlaneBase = 200;
-
 struct WorldGeom {
     int meta[kNumDSlots];
     float pos[kNumDSlots][3];
@@ -43,39 +40,7 @@ HSD void stage_geom(const SimState &S, int ps, int w, WorldGeom &g, int tid, int
     if (tid == 0) { g.numWalls = S.numWalls[w]; g.numPlanes = S.numPlanes[w]; }
 }
 
-HSD float ray_box_local(V3 o, V3 d, V3 e) {
-    float tn = -3.0e38f, tf = 3.0e38f;
-    const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, ee[3] = {e.x, e.y, e.z};
-    bool miss = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (dd[k] == 0.f) { if (oo[k] < -ee[k] || oo[k] > ee[k]) miss = true; continue; }
-        // slab in centre / extent form: entry = -o/d - e/|d|, exit = -o/d + e/|d| (no near/far swap)
-        float inv = 1.f / dd[k];
-        const float r = ee[k] * fabsf(inv);                 // entry = -o/d - e/|d|, exit = -o/d + e/|d|, each one fused multiply-add
-        tn = fmaxf(tn, hs_fma(-oo[k], inv, -r)); tf = fminf(tf, hs_fma(-oo[k], inv, r));
-    }
-    if (miss || tn > tf || tn < 0.f) return -1.f;
-    return tn;
-}
-
-HSD float ray_wedge_local(V3 o, V3 d) {
-    float tn = -3.0e38f, tf = 3.0e38f;
-    const float fn[5][3] = {{0, 0, -1}, {0, 1, 0}, {0, -0.554700196f, 0.832050294f}, {1, 0, 0}, {-1, 0, 0}};
-    const float off[5] = {1.f, 1.f, 0.277350098f, 1.f, 1.f};
-    bool miss = false;
-#pragma unroll
-    for (int f = 0; f < 5; ++f) {
-        V3 n = {fn[f][0], fn[f][1], fn[f][2]};
-        float dist = dot(n, o) - off[f];
-        float dn = dot(n, d);
-        if (dn == 0.f) { if (dist > 0.f) miss = true; continue; }
-        float t = -dist / dn;
-        if (dn < 0.f) tn = fmaxf(tn, t); else tf = fminf(tf, t);
-    }
-    if (miss || tn > tf || tn < 0.f) return -1.f;
-    return tn;
-}
+// (ray_box_local / ray_wedge_local, the ray against one hull in its own frame: hs_core.h)
 
 // Axis-aligned wall box with the per-ray reciprocal direction hoisted out of the wall loop (the same
 // quotients 1/d[k] the generic slab test computes, so results are bit-identical).

@@ -17,27 +17,9 @@ static_assert(sizeof(ManDD) == 144 && sizeof(ManS) == 112, "manifold layout");
 
 HSD bool has_mass_i(float invM, V3 invI) { return invM != 0.f || invI.z != 0.f || invI.x != 0.f || invI.y != 0.f; }
 
-// World-space inverse inertia R diag(invI) R^T (symmetric): evaluated once per manifold / joint from the
-// body's rotation at that moment and kept while the manifold's contact points are solved.
-struct Sym3 { float xx, xy, xz, yy, yz, zz; };
+// (Sym3, the world-space inverse inertia R diag(invI) R^T, and world_inv_inertia / sym_mul / quat_add_rotation: hs_core.h)
 struct BodyS { V3 pos; Q rot; V3 ppos; Q prot; V3 lin, ang; float invM; V3 invI; Sym3 Iw; };
 
-HSD Sym3 world_inv_inertia(Q q, V3 invI) {
-    M3 m = m3_from_quat(q);
-    V3 r0 = m.c0 * invI.x, r1 = m.c1 * invI.y, r2 = m.c2 * invI.z;
-    Sym3 s;
-    s.xx = hs_fma(r2.x, m.c2.x, hs_fma(r1.x, m.c1.x, r0.x * m.c0.x));
-    s.xy = hs_fma(r2.x, m.c2.y, hs_fma(r1.x, m.c1.y, r0.x * m.c0.y));
-    s.xz = hs_fma(r2.x, m.c2.z, hs_fma(r1.x, m.c1.z, r0.x * m.c0.z));
-    s.yy = hs_fma(r2.y, m.c2.y, hs_fma(r1.y, m.c1.y, r0.y * m.c0.y));
-    s.yz = hs_fma(r2.y, m.c2.z, hs_fma(r1.y, m.c1.z, r0.y * m.c0.z));
-    s.zz = hs_fma(r2.z, m.c2.z, hs_fma(r1.z, m.c1.z, r0.z * m.c0.z));
-    return s;
-}
-HSD V3 sym_mul(const Sym3 &s, V3 v) {
-    return {hs_fma(s.xz, v.z, hs_fma(s.xy, v.y, s.xx * v.x)), hs_fma(s.yz, v.z, hs_fma(s.yy, v.y, s.xy * v.x)),
-            hs_fma(s.zz, v.z, hs_fma(s.yz, v.y, s.xz * v.x))};
-}
 // call at the start of every manifold / joint (the oracle re-evaluates body_mass there)
 HSD void body_refresh_inertia(BodyS &b) {
     b.Iw = has_mass_i(b.invM, b.invI) ? world_inv_inertia(b.rot, b.invI) : Sym3{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -58,16 +40,6 @@ HSD float gen_inv_mass_sq(const BodyS &b, V3 r, V3 d, float d2) {
 HSD float gen_inv_mass(const BodyS &b, V3 r, V3 n) {
     V3 rn = cross(r, n);
     return dot_add(rn, sym_mul(b.Iw, rn), b.invM);
-}
-// q += 0.5 * (0,dth) * q, then one Newton step of 1/sqrt(|q|^2) from 1 (DESIGN.md "Engine decisions")
-HSD Q quat_add_rotation(Q q, V3 dth) {
-    Q dq = qmul(Q{0.f, dth.x, dth.y, dth.z}, q);
-    Q r = {hs_fma(0.5f, dq.w, q.w), hs_fma(0.5f, dq.x, q.x), hs_fma(0.5f, dq.y, q.y), hs_fma(0.5f, dq.z, q.z)};
-    const float n2 = hs_fma(r.z, r.z, hs_fma(r.y, r.y, hs_fma(r.x, r.x, r.w * r.w)));
-    // small updates (|dth| < 0.2 rad: every contact correction, ordinary integration); a joint that snaps a badly
-    // misaligned body round can turn it by radians in one go and gets the exact normalisation
-    const float k = n2 < 1.01f ? hs_fma(-0.5f, n2, 1.5f) : 1.f / sqrtf(n2);
-    return {r.w * k, r.x * k, r.y * k, r.z * k};
 }
 HSD bool has_mass(const BodyS &b) { return b.invM != 0.f || b.invI.z != 0.f || b.invI.x != 0.f || b.invI.y != 0.f; }
 

@@ -75,7 +75,7 @@ def quat_from_axes(right, fwd, up):
 
 
 def qrot(q, v):
-    """The kernels' quaternion rotation (csrc/hs_dev.h qrot), float64: the axes a camera's quaternion gives."""
+    """The kernels' quaternion rotation (csrc/hs_core.h qrot), float64: the axes a camera's quaternion gives."""
     w, p, v = float(q[0]), np.asarray(q[1:], np.float64), np.asarray(v, np.float64)
     return (2 * w * w - 1) * v + 2 * np.dot(p, v) * p + 2 * w * np.cross(p, v)
 

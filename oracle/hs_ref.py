@@ -16,6 +16,7 @@ _LIB_PATH = os.path.join(_HERE, "_build", "libhs_ref.so")
 
 def build(force=False):
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".hpp", ".cpp"))]
+    srcs.append(os.path.join(_HERE, "..", "marl-hideandseek_amd", "csrc", "hs_core.h"))   # the scalar core shared with the kernels
     if (not force and os.path.exists(_LIB_PATH)
             and os.path.getmtime(_LIB_PATH) >= max(os.path.getmtime(s) for s in srcs)):
         return _LIB_PATH

@@ -97,10 +97,10 @@ void hsref_threefry(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t
     RandKey r = threefry2x32({k0, k1}, c0, c1); out[0] = r.a; out[1] = r.b;
 }
 void hsref_rng_draws(uint32_t k0, uint32_t k1, int32_t n, uint32_t *bits_out) {
-    RNG r(RandKey{k0, k1});
+    RNG r{RandKey{k0, k1}, 0};
     for (int i = 0; i < n; ++i) bits_out[i] = r.bits32();
 }
-int32_t hsref_sample_i32(uint32_t k0, uint32_t k1, int32_t a, int32_t b) { RNG r(RandKey{k0, k1}); return r.sampleI32(a, b); }
+int32_t hsref_sample_i32(uint32_t k0, uint32_t k1, int32_t a, int32_t b) { RNG r{RandKey{k0, k1}, 0}; return r.sampleI32(a, b); }
 void hsref_sincos(float x, float *s, float *c) { hs_sincosf(x, s, c); }
 float hsref_atan2(float y, float x) { return hs_atan2f(y, x); }
 float hsref_asin(float x) { return hs_asinf(x); }

@@ -80,7 +80,7 @@ static inline void load_checkpoint_system(World &w, Exports &ex, int wi, const C
     trigger = 1;
     reset_environment(w, 0, init_key, false);
     w.curEpisodeRNDCounter = {ck.episodeRNDKey[0], ck.episodeRNDKey[1]};
-    w.rng = RNG(rand_split_i(init_key, ck.episodeRNDKey[0], ck.episodeRNDKey[1]));
+    w.rng = RNG{rand_split_i(init_key, ck.episodeRNDKey[0], ck.episodeRNDKey[1]), 0};
     w.runningScores[0] = ck.runningScores[0]; w.runningScores[1] = ck.runningScores[1];
     w.curEpisodeStep = ck.episodeStep;
     // "HACK, need to burn RNG state to get same result in generateEnv" (:976-980)

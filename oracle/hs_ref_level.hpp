@@ -395,7 +395,7 @@ static inline void generate_debug_level(World &wd, Exports &ex, int world, int l
 // generateEnvironment (level_gen.cpp:312-334)
 static inline void generate_environment(World &wd, Exports &ex, int world, RandKey level_key,
                                         int level, uint32_t flags, int num_hiders, int num_seekers) {
-    RNG level_rng(level_key);
+    RNG level_rng{level_key, 0};
     if (level == 1) generate_training_level(wd, ex, world, level_rng, flags, num_hiders, num_seekers);
     else generate_debug_level(wd, ex, world, level);
     for (int i = wd.numActiveAgents; i < ex.A; ++i) {

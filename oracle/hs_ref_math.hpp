@@ -1,162 +1,32 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.  Nothing under oracle/ is shipped or called by the
 // product path (marl-hideandseek_amd/); only tests/, __graft_entry__.smoke() and bench.py's
-// cpu_baseline leg may build/load it.
+// cpu_baseline leg may build/load it.  The dependency runs one way: the oracle reads the product's
+// scalar core, the product never includes anything from oracle/.
 //
 // PARITY UNPINNED: the reference's arithmetic for vectors/quaternions/AABBs lives in the
 // Madrona engine (external/madrona, an empty submodule directory in the reference snapshot,
-// pinned commit unknown).  This file is a clean-room restatement of the semantics visible at
-// the call sites (src/sim.cpp, src/level_gen.cpp).  All float code here must be compiled
-// with -ffp-contract=off: the HIP product evaluates the same expression trees in the same
-// order so results agree bit for bit.  The vector / quaternion helpers below use FUSED
-// multiply-adds, written out one by one (hs_fma: one rounding, the same on both machines) —
-// as a CUDA build of the reference does by default (nvcc --fmad=true), though which of its
-// operations that fuses is as unknowable as the rest of the engine's arithmetic.
+// pinned commit unknown).  The scalar core (csrc/hs_core.h: V3 / Q / M3 and their fused
+// multiply-adds, the trigonometry, the RNG, the constants, enums and object tables, the
+// ray-against-one-hull tests) is ONE file read by both compilers, so a leaf expression cannot
+// differ between the two sides; it is pinned from first principles (known-answer vectors, libm,
+// the reference's meshes), not by comparing the sides.  Everything above it — level generation,
+// narrowphase, solver scheduling, observations, rendering — is restated here separately from the
+// kernels, against the semantics visible at the call sites (src/sim.cpp, src/level_gen.cpp).
+// All float code must be compiled with -ffp-contract=off: the HIP product evaluates the same
+// expression trees in the same order so results agree bit for bit.  The fused multiply-adds are
+// written out one by one (hs_fma) — as a CUDA build of the reference fuses by default (nvcc
+// --fmad=true), though which of its operations that fuses is as unknowable as the rest of the
+// engine's arithmetic.
 #pragma once
-#include <cstdint>
-#include <cmath>
+#include "../marl-hideandseek_amd/csrc/hs_core.h"
 
 namespace hsref {
+using namespace hs;
 
-struct V3 { float x, y, z; };
+// ---- helpers only the oracle uses ----
 struct V2 { float x, y; };
-struct Q  { float w, x, y, z; };
-
-static inline V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-static inline V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-static inline V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-static inline V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
-static inline V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 static inline V3 operator*(float s, V3 a) { return {a.x * s, a.y * s, a.z * s}; }
-static inline V3 mulc(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
-static inline float hs_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-static inline float dot(V3 a, V3 b) { return hs_fma(a.z, b.z, hs_fma(a.y, b.y, a.x * b.x)); }
-static inline V3 cross(V3 a, V3 b) {
-    return {hs_fma(a.y, b.z, -(a.z * b.y)), hs_fma(a.z, b.x, -(a.x * b.z)), hs_fma(a.x, b.y, -(a.y * b.x))};
-}
-// a + b * s and a - b * s, each component one fused multiply-add
-static inline V3 madd(V3 a, V3 b, float s) { return {hs_fma(b.x, s, a.x), hs_fma(b.y, s, a.y), hs_fma(b.z, s, a.z)}; }
-static inline V3 nmadd(V3 a, V3 b, float s) { return {hs_fma(-b.x, s, a.x), hs_fma(-b.y, s, a.y), hs_fma(-b.z, s, a.z)}; }
-// a . b + c and a x b + c with every product fused
-static inline float dot_add(V3 a, V3 b, float c) { return hs_fma(a.z, b.z, hs_fma(a.y, b.y, hs_fma(a.x, b.x, c))); }
-static inline V3 cross_add(V3 a, V3 b, V3 c) {
-    return {hs_fma(a.y, b.z, hs_fma(-a.z, b.y, c.x)), hs_fma(a.z, b.x, hs_fma(-a.x, b.z, c.y)), hs_fma(a.x, b.y, hs_fma(-a.y, b.x, c.z))};
-}
-static inline float len2(V3 a) { return dot(a, a); }
-static inline float len(V3 a) { return sqrtf(dot(a, a)); }
-// (madrona Vector3::normalize, used at sim.cpp:591,733,786) — v * (1/len)
-static inline V3 normalize(V3 a) { float inv = 1.f / len(a); return a * inv; }
 static inline float getc(V3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
-
-// ---- quaternions (w,x,y,z), madrona::math::Quat call sites sim.cpp:225,350,408-409,469 ----
-static inline Q qmul(Q a, Q b) {
-    return {
-        hs_fma(-a.z, b.z, hs_fma(-a.y, b.y, hs_fma(-a.x, b.x, a.w * b.w))),
-        hs_fma(-a.z, b.y, hs_fma(a.y, b.z, hs_fma(a.x, b.w, a.w * b.x))),
-        hs_fma(a.z, b.x, hs_fma(a.y, b.w, hs_fma(-a.x, b.z, a.w * b.y))),
-        hs_fma(a.z, b.w, hs_fma(-a.y, b.x, hs_fma(a.x, b.y, a.w * b.z))),
-    };
-}
-static inline Q qinv(Q q) { return {q.w, -q.x, -q.y, -q.z}; }  // unit quaternions: conjugate
-static inline Q qnormalize(Q q) {
-    float n2 = hs_fma(q.z, q.z, hs_fma(q.y, q.y, hs_fma(q.x, q.x, q.w * q.w)));
-    float inv = 1.f / sqrtf(n2);
-    return {q.w * inv, q.x * inv, q.y * inv, q.z * inv};
-}
-// v' = 2(p.v)p + (2w^2-1)v + 2w(p x v)
-static inline V3 qrot(Q q, V3 v) {
-    V3 p = {q.x, q.y, q.z};
-    float s = q.w;
-    float d2 = 2.f * dot(p, v);
-    float s2 = 2.f * s;
-    float k = hs_fma(s2, s, -1.f);
-    V3 c = cross(p, v);
-    return {hs_fma(s2, c.x, hs_fma(d2, p.x, k * v.x)), hs_fma(s2, c.y, hs_fma(d2, p.y, k * v.y)),
-            hs_fma(s2, c.z, hs_fma(d2, p.z, k * v.z))};
-}
-
-// ---- deterministic transcendental functions (shared formulas with the HIP product) ----
-// sin/cos: Cody-Waite reduction by pi/2 + cephes single-precision minimax polynomials.
-static inline void hs_sincosf(float x, float *s_out, float *c_out) {
-    const float two_over_pi = 0.63661977236758134308f;
-    const float pio2_hi = 1.5707962512969970703125f;     // pi/2 split: hi + lo
-    const float pio2_lo = 7.54978995489188216e-8f;
-    float kf = x * two_over_pi;
-    int k = (int)(kf + (kf >= 0.f ? 0.5f : -0.5f));
-    float fk = (float)k;
-    float r = (x - fk * pio2_hi) - fk * pio2_lo;
-    float z = r * r;
-    float sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
-    float cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z
-               - 0.5f * z + 1.f;
-    float s, c;
-    switch (k & 3) {
-    case 0: s = sp; c = cp; break;
-    case 1: s = cp; c = -sp; break;
-    case 2: s = -sp; c = -cp; break;
-    default: s = -cp; c = sp; break;
-    }
-    *s_out = s; *c_out = c;
-}
-
-static inline float hs_atanf(float xin) {
-    float sign = xin < 0.f ? -1.f : 1.f;
-    float x = fabsf(xin);
-    float y;
-    if (x > 2.414213562373095f) { y = 1.5707963267948966f; x = -(1.f / x); }
-    else if (x > 0.4142135623730950f) { y = 0.7853981633974483f; x = (x - 1.f) / (x + 1.f); }
-    else { y = 0.f; }
-    float z = x * x;
-    y = y + ((((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z
-              - 3.33329491539e-1f) * z * x + x);
-    return sign * y;
-}
-
-static inline float hs_atan2f(float y, float x) {
-    const float pi = 3.14159265358979323846f;
-    if (x == 0.f) {
-        if (y > 0.f) return 0.5f * pi;
-        if (y < 0.f) return -0.5f * pi;
-        return 0.f;
-    }
-    float a = hs_atanf(y / x);
-    if (x < 0.f) { a = (y >= 0.f) ? a + pi : a - pi; }
-    return a;
-}
-
-static inline float hs_asinf(float xin) {
-    float sign = xin < 0.f ? -1.f : 1.f;
-    float a = fabsf(xin);
-    float z, x;
-    bool flag = a > 0.5f;
-    if (flag) { z = 0.5f * (1.f - a); x = sqrtf(z); }
-    else { x = a; z = x * x; }
-    float p = ((((4.2163199048e-2f * z + 2.4181311049e-2f) * z + 4.5470025998e-2f) * z
-                + 7.4953002686e-2f) * z + 1.6666752422e-1f) * z * x + x;
-    if (flag) { p = p + p; p = 1.5707963267948966f - p; }
-    return sign * p;
-}
-
-// Quat::angleAxis(angle, {0,0,1}) (level_gen.cpp:139,179,215,277)
-static inline Q quat_angle_axis_z(float angle) {
-    float s, c;
-    hs_sincosf(angle * 0.5f, &s, &c);
-    return {c, 0.f, 0.f, s};
-}
-
-// ---- 3x3 rotation (columns) from a unit quaternion ----
-struct M3 { V3 c0, c1, c2; };
-static inline M3 m3_from_quat(Q q) {
-    float y2 = q.y * q.y, z2 = q.z * q.z;
-    float xy = q.x * q.y, xz = q.x * q.z, yz = q.y * q.z;
-    M3 m;
-    m.c0 = {hs_fma(-2.f, hs_fma(q.y, q.y, z2), 1.f), 2.f * hs_fma(q.w, q.z, xy), 2.f * hs_fma(-q.w, q.y, xz)};
-    m.c1 = {2.f * hs_fma(-q.w, q.z, xy), hs_fma(-2.f, hs_fma(q.x, q.x, z2), 1.f), 2.f * hs_fma(q.w, q.x, yz)};
-    m.c2 = {2.f * hs_fma(q.w, q.y, xz), 2.f * hs_fma(-q.w, q.x, yz), hs_fma(-2.f, hs_fma(q.x, q.x, y2), 1.f)};
-    return m;
-}
-
-// ---- AABB (madrona::math::AABB call sites level_gen.cpp:104-121,142-143) ----
-struct AABB { V3 lo, hi; };
 
 // Real-Time Collision Detection 4.2.6 style transformed AABB: M = R * diag(scale).
 static inline AABB aabb_apply_trs(AABB b, V3 t, Q r, V3 s) {
@@ -173,10 +43,6 @@ static inline AABB aabb_apply_trs(AABB b, V3 t, Q r, V3 s) {
         }
     }
     return {{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
-}
-static inline bool aabb_overlaps(const AABB &a, const AABB &b) {
-    return a.lo.x < b.hi.x && b.lo.x < a.hi.x && a.lo.y < b.hi.y && b.lo.y < a.hi.y &&
-           a.lo.z < b.hi.z && b.lo.z < a.hi.z;
 }
 
 }  // namespace hsref

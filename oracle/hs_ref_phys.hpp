@@ -18,47 +18,15 @@
 
 namespace hsref {
 
-constexpr float kSubstepH = (1.f / 30.f) / 4.f;
-constexpr float kInvSubstepH = 120.f;
-constexpr float kGravityZ = -9.8f;            // sim.cpp:1360
 // Candidate pairs per world per substep (pairs whose AABBs overlap) are bounded only by the body counts, as in the
 // reference (src/sim.cpp:1356-1361 sizes for every entity): 17 movable bodies give at most 136 body-body pairs, and a
 // body meets at most 36 walls + 2 extra planes.  No pair is ever dropped.  (The HIP kernels keep the first 16 / 24
 // candidates of a world in LDS and spill the rest to a global list — same pairs, same order, same results.)
 constexpr int kMaxDDCand = kNumDSlots * (kNumDSlots - 1) / 2;          // 136 body-body candidate pairs
 constexpr int kMaxSCand = kNumDSlots * (kMaxWalls + kMaxPlanes - 1);   // body-(wall | plane>=1) candidate pairs
-constexpr float kMaxDepenVel = 3.f;         // m/s, rate limit for pre-existing overlap
 
-// mgr.cpp:476-559 — inverse mass and friction per SimObject
-static inline float obj_inv_mass(int32_t o) {
-    switch (o) {
-    case OBJ_CUBE: case OBJ_RAMP: case OBJ_BOX: return 0.5f;
-    case OBJ_HIDER: case OBJ_SEEKER: case OBJ_SPHERE: return 1.f;   // (no level ever makes a sphere; the table has it)
-    default: return 0.f;
-    }
-}
-static inline float obj_mu_s(int32_t o) { return o == OBJ_PLANE ? 2.f : 0.5f; }
-static inline float obj_mu_d(int32_t o) {
-    switch (o) {
-    case OBJ_PLANE: return 2.f;
-    case OBJ_CUBE: case OBJ_WALL: return 2.f;
-    case OBJ_HIDER: case OBJ_SEEKER: return 16.f;
-    case OBJ_RAMP: return 1.f;
-    case OBJ_BOX: return 4.f;
-    default: return 0.5f;
-    }
-}
-// Diagonal inverse inertia in the object frame (uniform density solids; the wedge's product of
-// inertia and centre-of-mass offset are dropped — DESIGN.md).  Agents: x,y zeroed (mgr.cpp:577-584).
-static inline V3 obj_inv_inertia(int32_t o) {
-    switch (o) {
-    case OBJ_CUBE: return {0.75f, 0.75f, 0.75f};                       // m=2, 2x2x2
-    case OBJ_BOX: return {0.96f, 0.088235294f, 0.090566038f};          // m=2, 8x1.5x2
-    case OBJ_RAMP: return {0.692307692f, 0.9f, 0.6f};                  // m=2 wedge
-    case OBJ_HIDER: case OBJ_SEEKER: return {0.f, 0.f, 1.5f};          // m=1, 2x2x2, yaw only
-    default: return {0.f, 0.f, 0.f};
-    }
-}
+// (kSubstepH, kGravityZ, kMaxDepenVel — m/s, the rate limit for pre-existing overlap — and the object tables obj_inv_mass,
+// obj_mu_s / obj_mu_d, obj_inv_inertia, obj_half_extents: csrc/hs_core.h)
 
 // ----------------------------------------------------------------------------------------
 // World-space convex hulls: boxes (8 v / 6 f / 3 edge directions) and the ramp wedge
@@ -133,10 +101,6 @@ static inline void hull_wedge(Hull &h, V3 c, const M3 &m) {
     h.ed[3] = (m.c0 * kWedgeSlant[0] + m.c1 * kWedgeSlant[1]) + m.c2 * kWedgeSlant[2];
     for (int i = 0; i < 9; ++i) { h.e0[i] = kWedgeEdges[i][0]; h.e1[i] = kWedgeEdges[i][1]; h.edir[i] = kWedgeEdges[i][2]; }
     hull_finish(h);
-}
-
-static inline V3 obj_half_extents(int32_t o) {
-    return o == OBJ_BOX ? V3{4.f, 0.75f, 1.f} : V3{1.f, 1.f, 1.f};
 }
 
 static inline void hull_from_body(Hull &h, int32_t obj, V3 pos, Q rot) {
@@ -353,26 +317,7 @@ static inline bool collide_hulls(const Hull &A, const Hull &B, RawManifold &m) {
 // ----------------------------------------------------------------------------------------
 // XPBD solver
 // ----------------------------------------------------------------------------------------
-// World-space inverse inertia R diag(invI) R^T (symmetric, 6 values).  It is evaluated once per
-// manifold (and per joint) from the body's rotation at that moment and kept while the manifold's
-// contact points are solved.
-struct Sym3 { float xx, xy, xz, yy, yz, zz; };
-static inline Sym3 world_inv_inertia(Q q, V3 invI) {
-    M3 m = m3_from_quat(q);
-    V3 r0 = m.c0 * invI.x, r1 = m.c1 * invI.y, r2 = m.c2 * invI.z;
-    Sym3 s;
-    s.xx = hs_fma(r2.x, m.c2.x, hs_fma(r1.x, m.c1.x, r0.x * m.c0.x));
-    s.xy = hs_fma(r2.x, m.c2.y, hs_fma(r1.x, m.c1.y, r0.x * m.c0.y));
-    s.xz = hs_fma(r2.x, m.c2.z, hs_fma(r1.x, m.c1.z, r0.x * m.c0.z));
-    s.yy = hs_fma(r2.y, m.c2.y, hs_fma(r1.y, m.c1.y, r0.y * m.c0.y));
-    s.yz = hs_fma(r2.y, m.c2.z, hs_fma(r1.y, m.c1.z, r0.y * m.c0.z));
-    s.zz = hs_fma(r2.z, m.c2.z, hs_fma(r1.z, m.c1.z, r0.z * m.c0.z));
-    return s;
-}
-static inline V3 sym_mul(const Sym3 &s, V3 v) {
-    return {hs_fma(s.xz, v.z, hs_fma(s.xy, v.y, s.xx * v.x)), hs_fma(s.yz, v.z, hs_fma(s.yy, v.y, s.xy * v.x)),
-            hs_fma(s.zz, v.z, hs_fma(s.yz, v.y, s.xz * v.x))};
-}
+// (Sym3, world_inv_inertia, sym_mul and quat_add_rotation are the scalar core's, csrc/hs_core.h)
 struct BodyMass { float invM; V3 invI; Sym3 Iw; };
 
 static inline BodyMass body_mass(const DBody &b) {
@@ -391,20 +336,6 @@ static inline float gen_inv_mass_sq(const BodyMass &bm, V3 r, V3 d, float d2) {
 static inline float gen_inv_mass(const BodyMass &bm, V3 r, V3 n) {
     V3 rn = cross(r, n);
     return dot_add(rn, sym_mul(bm.Iw, rn), bm.invM);
-}
-// q += 0.5 * (0,dth) * q, then — for small updates — ONE Newton step of 1/sqrt(|q|^2) from 1 instead of an exact
-// normalisation:
-// |q|^2 = 1 + |dth|^2/4 after the update, so the step leaves a norm error of 3/8 (|dth|^2/4)^2 (< 2e-5 even for a
-// body tumbling at 20 rad/s) that the next update corrects again; it costs 4 multiplies instead of sqrt + divide
-// in the innermost loop of the solver.
-static inline Q quat_add_rotation(Q q, V3 dth) {
-    Q dq = qmul(Q{0.f, dth.x, dth.y, dth.z}, q);
-    Q r = {hs_fma(0.5f, dq.w, q.w), hs_fma(0.5f, dq.x, q.x), hs_fma(0.5f, dq.y, q.y), hs_fma(0.5f, dq.z, q.z)};
-    const float n2 = hs_fma(r.z, r.z, hs_fma(r.y, r.y, hs_fma(r.x, r.x, r.w * r.w)));
-    // small updates (|dth| < 0.2 rad: every contact correction, ordinary integration); a joint that snaps a badly
-    // misaligned body round can turn it by radians in one go and gets the exact normalisation
-    const float k = n2 < 1.01f ? hs_fma(-0.5f, n2, 1.5f) : 1.f / sqrtf(n2);
-    return {r.w * k, r.x * k, r.y * k, r.z * k};
 }
 // positional impulse p applied at rA (on A, gets -p) and rB (on B, gets +p); r's are world offsets
 static inline void apply_pos_impulse(DBody *A, const BodyMass &ma, V3 rA, DBody *B, const BodyMass &mb,
@@ -740,39 +671,7 @@ static inline void physics_substep(World &w) {
 // starts inside a hull does not hit that hull (the agents' own cubes: sim.cpp:579,720).
 // Returns the body id: D-slot (0..16), 100+wall, 200+plane, or -1.
 // ----------------------------------------------------------------------------------------
-constexpr int kHitWallBase = 100;
-constexpr int kHitPlaneBase = 200;
-
-// slab test against a box given in its own frame (origin o, dir d local); entry t or -1
-static inline float ray_box_local(V3 o, V3 d, V3 e) {
-    float tn = -3.0e38f, tf = 3.0e38f;
-    const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, ee[3] = {e.x, e.y, e.z};
-    for (int k = 0; k < 3; ++k) {
-        if (dd[k] == 0.f) { if (oo[k] < -ee[k] || oo[k] > ee[k]) return -1.f; continue; }
-        // slab in centre / extent form: entry = -o/d - e/|d|, exit = -o/d + e/|d| (no near/far swap)
-        float inv = 1.f / dd[k];
-        const float r = ee[k] * fabsf(inv);
-        tn = fmaxf(tn, hs_fma(-oo[k], inv, -r)); tf = fminf(tf, hs_fma(-oo[k], inv, r));
-    }
-    if (tn > tf || tn < 0.f) return -1.f;
-    return tn;
-}
-static inline float ray_wedge_local(V3 o, V3 d) {
-    float tn = -3.0e38f, tf = 3.0e38f;
-    // plane offsets of the wedge faces in its own frame: n.p = off
-    const float off[5] = {1.f, 1.f, 0.277350098f, 1.f, 1.f};
-    for (int f = 0; f < 5; ++f) {
-        V3 n = {kWedgeFN[f][0], kWedgeFN[f][1], kWedgeFN[f][2]};
-        float dist = dot(n, o) - off[f];
-        float dn = dot(n, d);
-        if (dn == 0.f) { if (dist > 0.f) return -1.f; continue; }
-        float t = -dist / dn;
-        if (dn < 0.f) tn = fmaxf(tn, t); else tf = fminf(tf, t);
-    }
-    if (tn > tf || tn < 0.f) return -1.f;
-    return tn;
-}
-
+// (kHitWallBase / kHitPlaneBase and ray_box_local / ray_wedge_local, the ray against one hull in its own frame: csrc/hs_core.h)
 static inline int trace_ray(const World &w, V3 o, V3 d, float tmax, float *t_out) {
     int hit = -1; float best = tmax;
     for (int i = 0; i < kNumDSlots; ++i) {

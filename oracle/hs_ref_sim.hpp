@@ -29,7 +29,7 @@ static inline void reset_environment(World &w, uint32_t world_id, RandKey init_k
     if (update_rng) {
         RandKey ctr = {w.curWorldEpisode++, world_id};
         w.curEpisodeRNDCounter = ctr;
-        w.rng = RNG(rand_split_i(init_key, ctr.a, ctr.b));
+        w.rng = RNG{rand_split_i(init_key, ctr.a, ctr.b), 0};
     }
 }
 
@@ -127,8 +127,6 @@ static inline void agent_zero_vel_system(World &w) {
     }
 }
 
-constexpr float kCosFovHalf = 0.382683426f;   // cosf(toRadians(135/2)) sim.cpp:582,767
-
 // ---- rewardsVisSystem sim.cpp:763-804
 static inline void rewards_vis_system(World &w, int A) {
     for (int i = 0; i < A; ++i) {
@@ -178,19 +176,6 @@ static inline void update_episode_results_system(World &w, Exports &ex, int wi) 
         else if (w.runningScores[0] < w.runningScores[1]) { res[0] = 0.f; res[1] = 1.f; }
         else { res[0] = 0.5f; res[1] = 0.5f; }
     }
-}
-
-// ---- quatToEuler sim.cpp:372-399
-static inline V3 quat_to_euler(Q q) {
-    float sinr = 2.f * (q.w * q.x + q.y * q.z);
-    float cosr = 1.f - 2.f * (q.x * q.x + q.y * q.y);
-    float roll = hs_atan2f(sinr, cosr);
-    float sinp = 2.f * (q.w * q.y - q.z * q.x);
-    float pitch = fabsf(sinp) >= 1.f ? copysignf(3.14159265358979323846f / 2.f, sinp) : hs_asinf(sinp);
-    float siny = 2.f * (q.w * q.z + q.x * q.y);
-    float cosy = 1.f - 2.f * (q.y * q.y + q.z * q.z);
-    float yaw = hs_atan2f(siny, cosy);
-    return {roll, pitch, yaw};
 }
 
 // ---- computeRelativePosVelObs sim.cpp:401-420 ; writes 12 floats

@@ -7,44 +7,10 @@
 
 namespace hsref {
 
-// src/sim.hpp:39-41
-constexpr int kMaxBoxes = 9;
-constexpr int kMaxRamps = 2;
-constexpr int kMaxAgents = 6;
-// src/sim.cpp:14-17
-constexpr float kDeltaT = 1.f / 30.f;
-constexpr int kNumSubsteps = 4;
-constexpr int kNumPrepSteps = 96;
-constexpr int kEpisodeLen = 240;
-
-// src/sim.hpp:78-88
-enum SimObject : int32_t {
-    OBJ_SPHERE = 0, OBJ_PLANE = 1, OBJ_CUBE = 2, OBJ_WALL = 3, OBJ_HIDER = 4, OBJ_SEEKER = 5,
-    OBJ_RAMP = 6, OBJ_BOX = 7, OBJ_NONE = -1,
-};
-// src/sim.hpp:127-132
-enum OwnerTeam : int32_t { OWNER_NONE = 0, OWNER_SEEKER = 1, OWNER_HIDER = 2, OWNER_UNOWNABLE = 3 };
-// madrona::phys::ResponseType (enum values are the build's own)
-enum ResponseType : int32_t { RESP_DYNAMIC = 0, RESP_KINEMATIC = 1, RESP_STATIC = 2 };
-// src/sim.hpp:138-141
-enum AgentType : int32_t { AGENT_SEEKER = 0, AGENT_HIDER = 1 };
-// src/sim_flags.hpp:7-13
-enum SimFlags : uint32_t {
-    FLAG_DEFAULT = 0, FLAG_USE_FIXED_WORLD = 1, FLAG_IGNORE_EPISODE_LENGTH = 2,
-    FLAG_RANDOM_FLIP_TEAMS = 4, FLAG_ZERO_AGENT_VELOCITY = 8,
-};
-
-// Slot layout of movable ("D") bodies: boxes, then ramps, then agents.
-constexpr int kBoxSlot0 = 0;
-constexpr int kRampSlot0 = kMaxBoxes;                 // 9
-constexpr int kAgentSlot0 = kMaxBoxes + kMaxRamps;    // 11
-constexpr int kNumDSlots = kAgentSlot0 + kMaxAgents;  // 17
-// Static bodies: axis-aligned walls and infinite planes.
-// Reference worst case is 34 walls (geo_gen.cpp:429-462; its TmpArray holds 33 and the
-// overflow is only asserted in debug builds, geo_gen.cpp:24,144-147).  We hold 36.
-constexpr int kMaxWalls = 36;
-constexpr int kMaxPlanes = 3;
-constexpr int kMaxStatics = kMaxWalls + kMaxPlanes;   // 39
+// Capacities, the slot layout of movable ("D") bodies (boxes, then ramps, then agents) and the SimObject / OwnerTeam /
+// ResponseType / AgentType / SimFlags values are the scalar core's (csrc/hs_core.h).
+// The reference's worst case is 34 walls (geo_gen.cpp:429-462; its TmpArray holds 33 and the
+// overflow is only asserted in debug builds, geo_gen.cpp:24,144-147); kMaxWalls holds 36.
 
 struct DBody {
     int32_t objType;       // SimObject or OBJ_NONE when the slot is empty
