@@ -15,13 +15,7 @@ import pytest
 
 from conftest import GOLDEN
 
-BODY = [("pos", "<f4", 3), ("rot", "<f4", 4), ("lin", "<f4", 3), ("ang", "<f4", 3)]
-OBJ = np.dtype(BODY + [("team", "<u4"), ("locked", "u1"), ("pad", "u1", 3)])
-AGENT = np.dtype(BODY + [("grab_idx", "<i4"), ("r1", "<f4", 3), ("r2", "<f4", 3), ("att1", "<f4", 4), ("att2", "<f4", 4),
-                         ("sep", "<f4")])
-CKPT = np.dtype([("key", "<u4", 2), ("scores", "<i4", 2), ("step", "<i4"), ("agents", AGENT, 6), ("boxes", OBJ, 9),
-                 ("ramps", OBJ, 2), ("nh", "<i4"), ("ns", "<i4"), ("nb", "<i4"), ("nr", "<i4")])
-assert CKPT.itemsize == 1392
+from scenes import CKPT            # the Checkpoint record dtype (oracle/scenes.py)
 
 CUBE, RAMP, BOX = 2, 6, 7            # SimObject (src/sim.hpp:78-88)
 FIXED_NO_EPISODE_END = 1 | 2         # UseFixedWorld | IgnoreEpisodeLength
