@@ -95,7 +95,8 @@ enum {
     HS_NUM_EXPORTS = 23
 };
 
-/* Element types.  HS_DTYPE_BF16 / HS_DTYPE_F16 are output types of hs_pack_policy_inputs only: no export has them. */
+/* Element types.  HS_DTYPE_BF16 / HS_DTYPE_F16 are output types of hs_pack_policy_inputs and logits types of
+ * hs_sample_actions only: no export has them. */
 enum { HS_DTYPE_I32 = 0, HS_DTYPE_F32 = 1, HS_DTYPE_U8 = 2, HS_DTYPE_BF16 = 3, HS_DTYPE_F16 = 4 };
 
 /* madrona::py::Tensor (src/mgr.cpp:824-842): pointer, element type, dimensions, device. */
@@ -231,6 +232,59 @@ typedef struct hs_pack_request {
 } hs_pack_request;
 int32_t hs_pack_policy_inputs(hs_sim *sim, const hs_pack_request *req);
 int32_t hs_pack_policy_inputs_async(hs_sim *sim, void *hip_stream, const hs_pack_request *req);
+
+/* Action sampling: the leg after the network.  The actor's logits of every agent row (world * A + slot) become the
+ * [rows][HS_SAMPLE_HEADS] i32 action the next hs_step reads, with the log-probability and the entropy a PPO learner
+ * stores, in one kernel (csrc/hs_k_sample.h) — a multi-discrete actor head as the reference's learner has it
+ * (scripts/jax_train.py:146-148, actions_num_buckets = [5, 5, 5, 2, 2]).
+ * A row has L = sum of buckets[h] logits, head after head, at logits + row * logits_stride (in elements) of
+ * logits_dtype (HS_DTYPE_F32 | _BF16 | _F16; narrow types are widened to f32 exactly, all arithmetic is IEEE f32
+ * without contraction, expf / logf are the accurate library functions).  Head h with K = buckets[h] logits l_0 .. l_{K-1}:
+ *   m = max l_i;   e_i = expf(l_i - m);   c_i = ((e_0 + e_1) + ...) + e_i, added in index order;   S = c_{K-1}
+ *   log_prob_h = (l_a - m) - logf(S)
+ *   entropy_h  = logf(S) - (sum_i e_i * (l_i - m)) / S     summed in index order; a term with e_i == 0 is exactly 0
+ * A logit of -inf masks its bucket (e_i = 0) and produces no NaN; a head needs one finite logit, +inf and NaN are not
+ * supported.  The action a of the head:
+ *   HS_SAMPLE_DRAW      the smallest index with u * S < c_a (an f32 product); if there is none, the last index with
+ *                       e_i > 0.  A bucket with e_i == 0 is never drawn.
+ *   HS_SAMPLE_GREEDY    the first index of the maximum logit.
+ *   HS_SAMPLE_EVALUATE  the value stored in the action buffer, clamped into [0, K) for the lookup; the action buffer
+ *                       is only read.
+ * The uniform u of (row, head h): with g = (world_offset + world) * A + slot, the global agent row,
+ *   k = threefry2x32(key = {seed[0], seed[1]}, c0 = g, c1 = counter)         (Threefry-2x32-20)
+ *   {x0, x1} = threefry2x32(key = k, c0 = h, c1 = 0);   u = (float)((x0 ^ x1) >> 8) * 2^-24      in [0, 1)
+ * so a draw depends on seed, counter and the global row alone: handles that split the worlds between them
+ * (world_offset) draw what one handle over all of them draws.  Use a fresh counter (or seed) for every call of a rollout.
+ * Row outputs: log_prob = (((lp_0 + lp_1) + lp_2) + lp_3) + lp_4 and entropy likewise, in this order; head_log_prob
+ * holds the five lp_h.  HS_SAMPLE_ZERO_INACTIVE: a row whose self_mask export is 0 gets action 0 in every head and 0 in
+ * log_prob, entropy and head_log_prob (in HS_SAMPLE_EVALUATE its action is left as it is).
+ * action, log_prob, entropy, head_log_prob: contiguous device memory of the handle's GPU, 4-byte aligned; logits
+ * aligned to their element size.  Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing
+ * written): null request or logits, unknown dtype, mode or flag bit, a bucket count outside [1, HS_SAMPLE_MAX_BUCKETS],
+ * more than HS_SAMPLE_MAX_LOGITS logits per row, logits_stride below the sum of the buckets, a misaligned pointer,
+ * HS_SAMPLE_EVALUATE with every output null, a call before hs_init or inside an open step.  HS_SAMPLE_ZERO_INACTIVE
+ * under HS_FLAG_EXT_SKIP_OBSERVATIONS: HS_ERR_UNSUPPORTED (no self_mask); without that flag the call works there.
+ * Writes no simulator state but the action export, and that only with a null `action` outside HS_SAMPLE_EVALUATE.
+ * hs_sample_actions is ordered after the device's legacy default stream and blocking, so a following hs_step sees the
+ * actions; hs_sample_actions_async enqueues on the caller's hipStream_t without synchronising. */
+enum { HS_SAMPLE_HEADS = 5, HS_SAMPLE_MAX_BUCKETS = 16, HS_SAMPLE_MAX_LOGITS = 64 };
+enum { HS_SAMPLE_DRAW = 0, HS_SAMPLE_GREEDY = 1, HS_SAMPLE_EVALUATE = 2 };
+enum { HS_SAMPLE_ZERO_INACTIVE = 1 };
+typedef struct hs_sample_request {
+    const void *logits;           /* [rows][logits_stride] of logits_dtype; the first sum-of-buckets columns are read */
+    int32_t logits_dtype;         /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t logits_stride;        /* elements, >= sum of buckets */
+    int32_t buckets[HS_SAMPLE_HEADS];     /* each in [1, HS_SAMPLE_MAX_BUCKETS] */
+    int32_t mode;
+    uint32_t flags;
+    uint32_t seed[2];
+    uint32_t counter;
+    int32_t *action;              /* [rows][5]; null = the simulator's own action export, written in place */
+    float *log_prob, *entropy;    /* [rows], either may be null */
+    float *head_log_prob;         /* [rows][5] or null */
+} hs_sample_request;
+int32_t hs_sample_actions(hs_sim *sim, const hs_sample_request *req);
+int32_t hs_sample_actions_async(hs_sim *sim, void *hip_stream, const hs_sample_request *req);
 
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.

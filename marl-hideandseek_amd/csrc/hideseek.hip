@@ -22,6 +22,7 @@
 #include "hs_k_physics.h"
 #include "hs_k_balance.h"
 #include "hs_k_pack.h"
+#include "hs_k_sample.h"
 #include "hs_solver.h"
 
 namespace {
@@ -282,6 +283,64 @@ int launch_pack(hs_sim *s, hipStream_t strm, const hs_pack_request *r) {
     if (r->moments)
         hipLaunchKernelGGL(hs::k_pack_moments_sum<>, dim3((hs::kPackMoments + hs::kPackThreads / hs::kPackSumSegs - 1) / (hs::kPackThreads / hs::kPackSumSegs)),
                            dim3(hs::kPackThreads), 0, strm, (const double *)s->pack_partials, hs::pack_grid(a.rows), r->moments);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
+// ---- action sampling (hs_k_sample.h) ----
+namespace {
+static_assert(HS_SAMPLE_HEADS == hs::kSampleHeads && HS_SAMPLE_MAX_BUCKETS == hs::kSampleMaxBuckets && HS_SAMPLE_MAX_LOGITS == hs::kSampleMaxLogits &&
+              HS_SAMPLE_DRAW == hs::kSampleDraw && HS_SAMPLE_GREEDY == hs::kSampleGreedy && HS_SAMPLE_EVALUATE == hs::kSampleEvaluate,
+              "hs_sample_request and k_sample agree");
+static_assert(kExports[HS_EXPORT_ACTION].tail[0] == HS_SAMPLE_HEADS && kExports[HS_EXPORT_ACTION].dtype == HS_DTYPE_I32, "k_sample writes the action export's rows");
+
+int sample_logits(const hs_sample_request *r) {
+    int L = 0;
+    for (int h = 0; h < HS_SAMPLE_HEADS; ++h) L += r->buckets[h];
+    return L;
+}
+
+int check_sample(hs_sim *s, const hs_sample_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: null request");
+    if (!r->logits) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: null logits");
+    if (!pack_dtype_ok(r->logits_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: logits dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->mode != HS_SAMPLE_DRAW && r->mode != HS_SAMPLE_GREEDY && r->mode != HS_SAMPLE_EVALUATE) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: unknown mode");
+    if (r->flags & ~(uint32_t)HS_SAMPLE_ZERO_INACTIVE) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: unknown flag");
+    for (int h = 0; h < HS_SAMPLE_HEADS; ++h)
+        if (r->buckets[h] < 1 || r->buckets[h] > HS_SAMPLE_MAX_BUCKETS) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: a bucket count must be in [1, HS_SAMPLE_MAX_BUCKETS]");
+    if (sample_logits(r) > HS_SAMPLE_MAX_LOGITS) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: more than HS_SAMPLE_MAX_LOGITS logits per row");
+    if (r->logits_stride < sample_logits(r)) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: logits_stride is below the sum of the buckets");
+    if ((uintptr_t)r->logits & (r->logits_dtype == HS_DTYPE_F32 ? 3u : 1u)) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: logits must be aligned to their element size");
+    if (((uintptr_t)r->action | (uintptr_t)r->log_prob | (uintptr_t)r->entropy | (uintptr_t)r->head_log_prob) & 3u)
+        return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: action, log_prob, entropy and head_log_prob must be 4-byte aligned");
+    if (r->mode == HS_SAMPLE_EVALUATE && !r->log_prob && !r->entropy && !r->head_log_prob)
+        return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: HS_SAMPLE_EVALUATE with every output null");
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions inside an open step");
+    if ((r->flags & HS_SAMPLE_ZERO_INACTIVE) && (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS))
+        return fail(HS_ERR_UNSUPPORTED, "hs_sample_actions: HS_SAMPLE_ZERO_INACTIVE needs self_mask, which HS_FLAG_EXT_SKIP_OBSERVATIONS leaves unwritten");
+    return HS_OK;
+}
+// One k_sample over every agent row (the request has passed check_sample).
+int launch_sample(hs_sim *s, hipStream_t strm, const hs_sample_request *r) {
+    const hs::SimState &S = s->S;
+    hs::SampleArgs a = {};
+    a.logits = r->logits;
+    a.actionIn = a.action = r->action ? r->action : S.xAction;
+    a.selfMask = (r->flags & HS_SAMPLE_ZERO_INACTIVE) ? S.xSelfMask : nullptr;
+    a.logProb = r->log_prob; a.entropy = r->entropy; a.headLogProb = r->head_log_prob;
+    for (int h = 0, off = 0; h < HS_SAMPLE_HEADS; off += r->buckets[h++]) {
+        a.bucketK |= (uint64_t)r->buckets[h] << (8 * h);
+        a.bucketOff |= (uint64_t)off << (8 * h);
+    }
+    a.rows = S.N * s->A; a.stride = r->logits_stride; a.L = sample_logits(r); a.mode = r->mode;
+    a.seed0 = r->seed[0]; a.seed1 = r->seed[1]; a.counter = r->counter;
+    a.row0Global = (uint32_t)S.worldOffset * (uint32_t)s->A;
+    const dim3 grid(hs::sample_grid(a.rows)), blk(hs::kSampleThreads);
+    if (r->logits_dtype == HS_DTYPE_F32) hipLaunchKernelGGL(hs::k_sample<float>, grid, blk, 0, strm, a);
+    else if (r->logits_dtype == HS_DTYPE_BF16) hipLaunchKernelGGL(hs::k_sample<hs::SampleBf16>, grid, blk, 0, strm, a);
+    else hipLaunchKernelGGL(hs::k_sample<hs::SampleF16>, grid, blk, 0, strm, a);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -707,6 +766,21 @@ int32_t hs_pack_policy_inputs(hs_sim *s, const hs_pack_request *req) {
     HS_TRY(check_pack(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_pack(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- action sampling (hs_k_sample.h; check_sample / launch_sample above) ----
+int32_t hs_sample_actions_async(hs_sim *s, void *hip_stream, const hs_sample_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_sample(s, req));
+    return launch_sample(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_sample_actions(hs_sim *s, const hs_sample_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_sample(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_sample(s, s->stream, req));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

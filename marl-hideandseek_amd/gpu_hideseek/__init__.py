@@ -159,6 +159,22 @@ class HideAndSeekSimulator:
         from . import policy_inputs
         return policy_inputs.pack(self, actor, critic, moments, dtype, stream)
 
+    def sample_actions(self, logits, *, buckets=(5, 5, 5, 2, 2), mode="draw", seed=(0, 0), counter=0, action=None,
+                       log_prob=None, entropy=None, head_log_prob=None, zero_inactive=False, stream=None):
+        """Turn the actor's logits [num_worlds * agents_per_world, W >= sum(buckets)] (float32, bfloat16 or float16,
+        contiguous in the last dimension) into the five action heads of every agent row in one kernel
+        (gpu_hideseek.action_sampling; hs_sample_actions).  mode "draw" samples with the uniforms keyed by (seed,
+        counter, global agent row), "greedy" takes the first maximum, "evaluate" scores the actions already stored.
+        `action` is None (in place: action_tensor(), ready for the next step) or an int32 [rows, 5] tensor; `log_prob`,
+        `entropy` [rows] and `head_log_prob` [rows, 5] are each True (a new float32 tensor), a preallocated tensor (a
+        slot buf[t] of a rollout buffer will do) or None.  zero_inactive zeroes the rows whose self_mask is 0.
+        stream=None blocks; a torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns
+        {name: tensor} of the action and what was written."""
+        from . import action_sampling
+        return action_sampling.sample(self, logits, stream, buckets=buckets, mode=mode, seed=seed, counter=counter,
+                                      action=action, log_prob=log_prob, entropy=entropy, head_log_prob=head_log_prob,
+                                      zero_inactive=zero_inactive)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -90,6 +90,10 @@ def load():
     L.hs_pack_policy_inputs.restype = C.c_int32
     L.hs_pack_policy_inputs_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]   # (sim, hipStream_t, request)
     L.hs_pack_policy_inputs_async.restype = C.c_int32
+    L.hs_sample_actions.argtypes = [C.c_void_p, C.c_void_p]                     # (sim, const hs_sample_request *)
+    L.hs_sample_actions.restype = C.c_int32
+    L.hs_sample_actions_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]       # (sim, hipStream_t, request)
+    L.hs_sample_actions_async.restype = C.c_int32
     L.hs_trigger_reset.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.hs_trigger_reset.restype = C.c_int32
     L.hs_set_action.argtypes = [C.c_void_p] + [C.c_int32] * 6

@@ -148,6 +148,16 @@ class ShardedSimulator:
         from . import policy_inputs
         return policy_inputs.pack_sharded(self, actor, critic, moments, dtype, stream)
 
+    def sample_actions(self, logits, *, buckets=(5, 5, 5, 2, 2), mode="draw", seed=(0, 0), counter=0, action=None,
+                       log_prob=None, entropy=None, head_log_prob=None, zero_inactive=False, stream=None):
+        """HideAndSeekSimulator.sample_actions per shard: `logits` has one tensor per shard, on the shard's device; a
+        list of the shards' results.  Every output (and `stream`) is True / None for all shards or a list with one entry
+        per shard.  The draws are keyed by the global agent row, so they do not depend on the number of shards."""
+        from . import action_sampling
+        return action_sampling.sample_sharded(self, logits, stream, action, log_prob, entropy, head_log_prob,
+                                              buckets=buckets, mode=mode, seed=seed, counter=counter,
+                                              zero_inactive=zero_inactive)
+
     def device_status(self):
         out = {}
         for s in self.shards:
