@@ -95,8 +95,8 @@ enum {
     HS_NUM_EXPORTS = 23
 };
 
-/* Element types.  HS_DTYPE_BF16 / HS_DTYPE_F16 are output types of hs_pack_policy_inputs and logits types of
- * hs_sample_actions only: no export has them. */
+/* Element types.  HS_DTYPE_BF16 / HS_DTYPE_F16 are output types of hs_pack_policy_inputs, logits types of
+ * hs_sample_actions and value types of hs_compute_gae only: no export has them. */
 enum { HS_DTYPE_I32 = 0, HS_DTYPE_F32 = 1, HS_DTYPE_U8 = 2, HS_DTYPE_BF16 = 3, HS_DTYPE_F16 = 4 };
 
 /* madrona::py::Tensor (src/mgr.cpp:824-842): pointer, element type, dimensions, device. */
@@ -285,6 +285,52 @@ typedef struct hs_sample_request {
 } hs_sample_request;
 int32_t hs_sample_actions(hs_sim *sim, const hs_sample_request *req);
 int32_t hs_sample_actions_async(hs_sim *sim, void *hip_stream, const hs_sample_request *req);
+
+/* Advantages and value targets: the leg after the last step of a rollout.  Generalised advantage estimation as the
+ * reference trains with it (scripts/jax_train.py:45,152-153: gamma 0.998, gae_lambda 0.95, 40 steps per update) over the
+ * rewards, dones and critic values of T steps, in one kernel (csrc/hs_k_gae.h).  Every array is [T][rows], rows =
+ * num_worlds * A of the handle (row = world * A + slot), contiguous; every pointer is device memory of the handle's GPU.
+ * The arithmetic is the contract.  Narrow values (HS_DTYPE_BF16 / _F16) are widened to f32 exactly; everything is IEEE
+ * f32, unfused, in exactly this order.  Per row, with gl = gamma * lambda (an f32 product) and carry = 0, for t = T-1
+ * down to 0:
+ *   v      = value[t];   vn = (t == T-1) ? bootstrap : value[t+1]
+ *   active = mask == null || mask[t] != 0;      ended = done[t] != 0
+ *   if !active:  adv = +0.0, ret = +0.0, carry = +0.0        (selects: reward / value / vn of this step are not used, a
+ *                                                             NaN there reaches no output)
+ *   else:        delta = ended ? (reward[t] - v) : ((reward[t] + gamma * vn) - v)
+ *                adv   = ended ? delta : (delta + gl * carry)
+ *                ret   = adv + v;   carry = adv
+ *   advantage[t] = adv;  returns[t] = ret
+ * On an ended step vn and carry are selected away, not multiplied by zero: a NaN in the next episode's first value does
+ * not leak backwards.  The done of the 240-step episode limit is terminal, as the reference treats it.
+ * moments [HS_GAE_MOMENTS] f64, over the active (t, row) pairs: [0] = sum adv, [1] = sum adv^2, [2] = sum ret,
+ * [3] = sum ret^2, [4] = their count; each term is the f64 of the f32 value, the square is taken in f64.  Summed without
+ * atomics in an order that depends on (rows, T) alone: the same inputs give the same bits on every call.  The partial
+ * sums go through a workspace of the handle, so two calls with moments on one handle must not overlap.
+ * advantage, returns and moments may each be null, not all three; only what is requested is written.  Everything is
+ * validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request;
+ * a null reward, done, value or bootstrap; every output null; an unknown value_dtype; steps outside
+ * [1, HS_GAE_MAX_STEPS]; gamma or lambda not finite or outside [0, 1]; a pointer not aligned to its element size
+ * (moments: 8 bytes); an output range that overlaps an input range or another output; a call before hs_init or inside an
+ * open step.  It reads no export itself, so it works under HS_FLAG_EXT_SKIP_OBSERVATIONS, and writes no simulator state.
+ * hs_compute_gae is ordered after the device's legacy default stream and blocking; hs_compute_gae_async enqueues on the
+ * caller's hipStream_t without synchronising. */
+enum { HS_GAE_MAX_STEPS = 4096, HS_GAE_MOMENTS = 5 };
+typedef struct hs_gae_request {
+    const float   *reward;        /* [T][rows] f32: the reward export of step t */
+    const int32_t *done;          /* [T][rows] i32: the done export of step t; nonzero = the episode ended with step t */
+    const void    *value;         /* [T][rows] of value_dtype: V(observation the action of step t was chosen from) */
+    const void    *bootstrap;     /* [rows] of value_dtype: V(observation after step T-1) */
+    const float   *mask;          /* [T][rows] f32 (the self_mask export at step t: 1.0 / 0.0), or null = all active */
+    int32_t value_dtype;          /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t steps;                /* T, 1 .. HS_GAE_MAX_STEPS */
+    float gamma, lambda;          /* each finite, in [0, 1] */
+    float  *advantage;            /* [T][rows] f32 or null */
+    float  *returns;              /* [T][rows] f32 or null */
+    double *moments;              /* [HS_GAE_MOMENTS] f64 or null */
+} hs_gae_request;                 /* 80 bytes */
+int32_t hs_compute_gae(hs_sim *sim, const hs_gae_request *req);
+int32_t hs_compute_gae_async(hs_sim *sim, void *hip_stream, const hs_gae_request *req);
 
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.

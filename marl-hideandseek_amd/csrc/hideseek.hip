@@ -23,6 +23,7 @@
 #include "hs_k_balance.h"
 #include "hs_k_pack.h"
 #include "hs_k_sample.h"
+#include "hs_k_gae.h"
 #include "hs_solver.h"
 
 namespace {
@@ -76,6 +77,7 @@ struct hs_sim {
     hs::SpectateCam *cams = nullptr;       // hs_render_cameras: the device copy of the cameras, grown on demand
     int cam_cap = 0;
     double *pack_partials = nullptr;       // hs_pack_policy_inputs: the moments of each workgroup, [pack_grid][HS_PACK_MOMENTS]
+    double *gae_partials = nullptr;        // hs_compute_gae: the moments of each workgroup, [gae_grid][HS_GAE_MOMENTS]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -346,6 +348,66 @@ int launch_sample(hs_sim *s, hipStream_t strm, const hs_sample_request *r) {
 }
 }  // namespace
 
+// ---- advantages and value targets (hs_k_gae.h) ----
+namespace {
+static_assert(HS_GAE_MAX_STEPS == hs::kGaeMaxSteps && HS_GAE_MOMENTS == hs::kGaeMoments, "hs_gae_request and k_gae agree");
+static_assert(sizeof(hs_gae_request) == 80 && offsetof(hs_gae_request, value_dtype) == 40 && offsetof(hs_gae_request, gamma) == 48 &&
+              offsetof(hs_gae_request, advantage) == 56 && offsetof(hs_gae_request, moments) == 72, "hs_gae_request layout (gpu_hideseek/advantages.py mirrors it)");
+static_assert(kExports[HS_EXPORT_REWARD].dtype == HS_DTYPE_F32 && kExports[HS_EXPORT_DONE].dtype == HS_DTYPE_I32 && kExports[HS_EXPORT_SELF_MASK].dtype == HS_DTYPE_F32 &&
+              kExports[HS_EXPORT_REWARD].per_agent && kExports[HS_EXPORT_DONE].per_agent && kExports[HS_EXPORT_SELF_MASK].per_agent,
+              "k_gae reads copies of the reward, done and self_mask exports");
+
+struct GaeRange { const char *name; uintptr_t lo, hi; };
+bool gae_overlap(const GaeRange &a, const GaeRange &b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
+
+int check_gae(hs_sim *s, const hs_gae_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null request");
+    if (!r->reward) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null reward");
+    if (!r->done) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null done");
+    if (!r->value) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null value");
+    if (!r->bootstrap) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null bootstrap");
+    if (!r->advantage && !r->returns && !r->moments) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: every output is null");
+    if (!pack_dtype_ok(r->value_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: value dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->steps < 1 || r->steps > HS_GAE_MAX_STEPS) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: steps must be in [1, HS_GAE_MAX_STEPS]");
+    if (!(r->gamma >= 0.f && r->gamma <= 1.f)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: gamma must be finite and in [0, 1]");
+    if (!(r->lambda >= 0.f && r->lambda <= 1.f)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: lambda must be finite and in [0, 1]");
+    const uintptr_t vsize = r->value_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if (((uintptr_t)r->reward | (uintptr_t)r->done | (uintptr_t)r->mask | (uintptr_t)r->advantage | (uintptr_t)r->returns) & 3u)
+        return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: reward, done, mask, advantage and returns must be 4-byte aligned");
+    if (((uintptr_t)r->value | (uintptr_t)r->bootstrap) & (vsize - 1)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: value and bootstrap must be aligned to their element size");
+    if ((uintptr_t)r->moments & 7u) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: moments must be 8-byte aligned");
+    const uintptr_t rows = (uintptr_t)s->S.N * (uintptr_t)s->A, n = rows * (uintptr_t)r->steps;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange in[] = {range("reward", r->reward, n * 4), range("done", r->done, n * 4), range("value", r->value, n * vsize),
+                           range("bootstrap", r->bootstrap, rows * vsize), range("mask", r->mask, n * 4)};
+    const GaeRange out[] = {range("advantage", r->advantage, n * 4), range("returns", r->returns, n * 4),
+                            range("moments", r->moments, HS_GAE_MOMENTS * sizeof(double))};
+    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
+        for (const GaeRange &x : in)
+            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_compute_gae: ") + out[i].name + " overlaps " + x.name);
+        for (size_t j = 0; j < i; ++j)
+            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_compute_gae: ") + out[i].name + " overlaps " + out[j].name);
+    }
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae inside an open step");
+    return HS_OK;
+}
+// One k_gae over every agent row (the request has passed check_gae), then the fixed-order sum of the moments.
+int launch_gae(hs_sim *s, hipStream_t strm, const hs_gae_request *r) {
+    const hs::GaeArgs a = {r->reward, r->done, r->value, r->bootstrap, r->mask, r->advantage, r->returns,
+                           r->moments ? s->gae_partials : nullptr, s->S.N * s->A, r->steps, r->gamma, r->lambda};
+    const dim3 grid(hs::gae_grid(a.rows)), blk(hs::kGaeThreads);
+    if (r->value_dtype == HS_DTYPE_F32) hipLaunchKernelGGL(hs::k_gae<float>, grid, blk, 0, strm, a);
+    else if (r->value_dtype == HS_DTYPE_BF16) hipLaunchKernelGGL(hs::k_gae<hs::SampleBf16>, grid, blk, 0, strm, a);
+    else hipLaunchKernelGGL(hs::k_gae<hs::SampleF16>, grid, blk, 0, strm, a);
+    if (r->moments)
+        hipLaunchKernelGGL(hs::k_gae_moments_sum<>, dim3(1), dim3(hs::kGaeMoments * hs::kGaeSumSegs), 0, strm, (const double *)s->gae_partials,
+                           hs::gae_grid(a.rows), r->moments);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -443,6 +505,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->bal_hist, hs::kBalanceBins); HS_ALLOC(s->bal_cursor, hs::kBalanceBins); HS_ALLOC(s->bal_new_slot, N);
     HS_ALLOC(S.status, 4);
     if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
+    HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -781,6 +844,21 @@ int32_t hs_sample_actions(hs_sim *s, const hs_sample_request *req) {
     HS_TRY(check_sample(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_sample(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- advantages and value targets (hs_k_gae.h; check_gae / launch_gae above) ----
+int32_t hs_compute_gae_async(hs_sim *s, void *hip_stream, const hs_gae_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_gae(s, req));
+    return launch_gae(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_compute_gae(hs_sim *s, const hs_gae_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_gae(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_gae(s, s->stream, req));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

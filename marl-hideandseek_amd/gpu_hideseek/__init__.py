@@ -175,6 +175,22 @@ class HideAndSeekSimulator:
                                       action=action, log_prob=log_prob, entropy=entropy, head_log_prob=head_log_prob,
                                       zero_inactive=zero_inactive)
 
+    def compute_advantages(self, rewards, dones, values, bootstrap, *, gamma=0.998, gae_lambda=0.95, mask=None,
+                           advantages=True, returns=True, moments=None, stream=None):
+        """GAE advantages and value targets of a rollout in one kernel (gpu_hideseek.advantages; hs_compute_gae, whose
+        header comment states the arithmetic: IEEE f32 in a fixed order, the same bits on every call).  `rewards`
+        (float32), `dones` (int32: nonzero = the episode ended with step t), `values` (float32, bfloat16 or float16: the
+        critic's value of the observation the action of step t was chosen from) and `mask` (float32 self_mask of step t,
+        or None: every row active) are contiguous [T, rows], [T, rows, 1] or [T, num_worlds, agents_per_world];
+        `bootstrap` [rows] is the value of the observation after the last step, in the dtype of `values`.
+        `advantages` and `returns` are each True (a new float32 tensor shaped like `rewards`), a preallocated tensor or
+        None; `moments` likewise, [5] float64: sum and sum of squares of the advantages and of the returns and the count,
+        over the active steps (advantages.moments_to_mean_std).  stream=None blocks; a torch.cuda.Stream or raw handle
+        enqueues there without synchronising.  Returns {name: tensor} of what was written."""
+        from . import advantages as _advantages
+        return _advantages.compute(self, rewards, dones, values, bootstrap, stream, gamma=gamma, gae_lambda=gae_lambda,
+                                   mask=mask, advantages=advantages, returns=returns, moments=moments)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

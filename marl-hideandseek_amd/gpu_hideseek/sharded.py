@@ -158,6 +158,16 @@ class ShardedSimulator:
                                               buckets=buckets, mode=mode, seed=seed, counter=counter,
                                               zero_inactive=zero_inactive)
 
+    def compute_advantages(self, rewards, dones, values, bootstrap, *, gamma=0.998, gae_lambda=0.95, mask=None,
+                           advantages=True, returns=True, moments=None, stream=None):
+        """HideAndSeekSimulator.compute_advantages per shard: `rewards`, `dones`, `values` and `bootstrap` have one
+        tensor per shard, on the shard's device; a list of the shards' results.  `mask`, every output and `stream` are
+        True / None for all shards or a list with one entry per shard.  A row's results depend on that row alone, so
+        they do not depend on the number of shards."""
+        from . import advantages as _advantages
+        return _advantages.compute_sharded(self, rewards, dones, values, bootstrap, stream, mask, advantages, returns,
+                                           moments, gamma=gamma, gae_lambda=gae_lambda)
+
     def device_status(self):
         out = {}
         for s in self.shards:
