@@ -96,7 +96,7 @@ enum {
 };
 
 /* Element types.  HS_DTYPE_BF16 / HS_DTYPE_F16 are output types of hs_pack_policy_inputs, logits types of
- * hs_sample_actions and value types of hs_compute_gae only: no export has them. */
+ * hs_sample_actions, value types of hs_compute_gae and the types of hs_ppo_loss only: no export has them. */
 enum { HS_DTYPE_I32 = 0, HS_DTYPE_F32 = 1, HS_DTYPE_U8 = 2, HS_DTYPE_BF16 = 3, HS_DTYPE_F16 = 4 };
 
 /* madrona::py::Tensor (src/mgr.cpp:824-842): pointer, element type, dimensions, device. */
@@ -331,6 +331,81 @@ typedef struct hs_gae_request {
 } hs_gae_request;                 /* 80 bytes */
 int32_t hs_compute_gae(hs_sim *sim, const hs_gae_request *req);
 int32_t hs_compute_gae_async(hs_sim *sim, void *hip_stream, const hs_gae_request *req);
+
+/* The PPO loss and its gradients: the leg after the network's forward pass of a minibatch.  Over n samples (a sample is
+ * one (step, agent row) pair; n is free, it is not tied to the handle's rows, which supplies the device and a workspace)
+ * one kernel (csrc/hs_k_ppo.h) reads the new logits and value, the stored action, old log-probability, advantage and
+ * return once and writes d loss / d logits, d loss / d value and the sums behind the loss statistics once: the clipped
+ * surrogate, the (optionally clipped) value loss and the entropy bonus as the reference's learner has them
+ * (scripts/jax_train.py:41-45), with their closed-form gradients, so that the learner calls backward on the network's
+ * outputs with these gradients and no autograd graph of the loss exists.
+ * The arithmetic is the contract.  Narrow logits and values are widened to f32 exactly; everything is IEEE f32, unfused,
+ * in exactly this order; expf / logf are the accurate library functions.  sum5(x) = (((x_0 + x_1) + x_2) + x_3) + x_4.
+ * Head h of a sample, with K = buckets[h] logits l_i and the action a_h clamped into [0, K): m, e_i = expf(l_i - m), S,
+ * log_prob_h and entropy_h exactly as hs_sample_actions defines them (HS_SAMPLE_EVALUATE), and logS = logf(S).
+ *   lp = sum5(log_prob_h);  ent = sum5(entropy_h)       the bits hs_sample_actions returns under the same logits
+ *   A  = advantage, or with adv_moments M (the moments of hs_compute_gae): (advantage - mean) / (std + 1e-8f), where in
+ *        f64 mu = M[0] / M[4], mean = (float)mu, std = (float)sqrt(max(M[1] / M[4] - mu * mu, 0)); both 0 when M[4] == 0
+ *   dlp = lp - old_log_prob;  ratio = expf(dlp);  s1 = ratio * A;  s2 = min(max(ratio, 1.f - c), 1.f + c) * A
+ *   pg = s1 <= s2 ? -s1 : -s2;     g_lp = s1 <= s2 ? -s1 : +0;     kl = (ratio - 1.f) - dlp          (c = clip_coef)
+ *   with value (v the new value, R = returns):  dv = v - R
+ *     old_value == null:  vl = 0.5f * (dv * dv);  g_v = dv
+ *     else (vo = old_value):  dvo = v - vo;  dvc = |dvo| <= c ? dv : (vo + (dvo < 0 ? -c : c)) - R     (inside the clip
+ *                         range the clipped value is v itself, not vo + (v - vo) with its rounding: u2 == u1 there)
+ *                         u1 = dv * dv;  u2 = dvc * dvc;  vl = 0.5f * (u1 >= u2 ? u1 : u2);   g_v = u1 >= u2 ? dv : +0
+ *   active = mask == null || mask != 0;   cnt = the number of active samples, counted on the device before the
+ *   gradients are made;   w = grad_scale / (float)cnt
+ *   bucket i of head h:  d = l_i - m;  p = e_i / S;  t = p * ((d - logS) + entropy_h)
+ *                        x = g_lp * ((i == a_h ? 1.f : 0.f) - p) + entropy_coef * t;   y = w * x
+ *                        grad_logits = (active && e_i > 0 && y != 0) ? y : +0
+ *   grad_value:          y = w * (value_loss_coef * g_v);   grad_value = (active && y != 0) ? y : +0
+ * These are selects: an inactive sample gets +0 everywhere whatever its inputs hold (a NaN there reaches no output), a
+ * bucket without e_i > 0, such as one masked with -inf, gets exactly +0 (autograd through log_softmax gives NaN there), and
+ * a zero of either sign is stored as +0.  As for hs_sample_actions a head needs one finite logit and +inf and NaN logits
+ * are not supported; a head whose logits are all -inf has e_i = NaN and so gets +0 in every bucket, but the sample's
+ * log-probability, and with it the gradients of its other heads and its terms of the statistics, are NaN.  grad_logits is rounded to grad_dtype to nearest even; only columns 0 .. L-1
+ * of a row of grad_stride elements are written.  grad_value has value_dtype.  With cnt == 0 every gradient is +0.
+ * stats [HS_PPO_STATS] f64, sums over the active samples of the f64 of the f32 per-sample values: [0] = sum pg,
+ * [1] = sum vl (0 without value), [2] = sum ent, [3] = sum kl, [4] = the count of s2 < s1 (policy-clipped), [5] = the
+ * count of u2 > u1 (value-clipped), [6] = cnt.  Summed without atomics in an order that depends on n alone: the same
+ * inputs give the same bits on every call.  The gradients are those of
+ *   loss = grad_scale * (stats[0] - entropy_coef * stats[2] + value_loss_coef * stats[1]) / cnt.
+ * The count and the partial sums go through a workspace of the handle: two calls on one handle must not overlap.
+ * grad_logits, grad_value and stats may each be null, not all three; only what is requested is written.  Everything is
+ * validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request,
+ * logits, action, old_log_prob or advantage; every output null; grad_value without value; value without returns; an
+ * unknown dtype; a bucket count outside [1, HS_SAMPLE_MAX_BUCKETS] or more than HS_SAMPLE_MAX_LOGITS logits; a stride
+ * below the sum of the buckets; n < 1 or n * stride >= 2^31; a coefficient that is not finite or clip_coef <= 0; a
+ * pointer not aligned to its element size (adv_moments, stats: 8 bytes); an output range that overlaps an input range or
+ * another output; a call before hs_init or inside an open step.  It reads no export and writes no simulator state, so it
+ * works under HS_FLAG_EXT_SKIP_OBSERVATIONS.  hs_ppo_loss is ordered after the device's legacy default stream and
+ * blocking; hs_ppo_loss_async enqueues on the caller's hipStream_t without synchronising. */
+enum { HS_PPO_STATS = 7 };
+typedef struct hs_ppo_request {
+    const void    *logits;        /* [n][logits_stride] of logits_dtype: the new policy's logits */
+    const int32_t *action;        /* [n][HS_SAMPLE_HEADS] i32: the stored actions */
+    const float   *old_log_prob;  /* [n] f32: log_prob of hs_sample_actions when the action was drawn */
+    const float   *advantage;     /* [n] f32 */
+    const double  *adv_moments;   /* [HS_GAE_MOMENTS] f64 on the device (hs_compute_gae's moments), or null = as given */
+    const float   *mask;          /* [n] f32 (self_mask: 1.0 / 0.0), or null = all active */
+    const void    *value;         /* [n] of value_dtype: the new critic's value, or null = no value term */
+    const float   *returns;       /* [n] f32; required iff value is given */
+    const float   *old_value;     /* [n] f32, or null = the value loss is not clipped */
+    int32_t n;                    /* samples, n >= 1 and n * stride < 2^31 */
+    int32_t logits_dtype;         /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t logits_stride;        /* elements, >= sum of buckets */
+    int32_t grad_dtype;           /* of grad_logits */
+    int32_t grad_stride;          /* elements, >= sum of buckets */
+    int32_t value_dtype;          /* of value and grad_value */
+    int32_t buckets[HS_SAMPLE_HEADS];     /* as hs_sample_request */
+    float clip_coef;              /* c > 0 */
+    float value_loss_coef, entropy_coef, grad_scale;      /* finite */
+    void   *grad_logits;          /* [n][grad_stride] of grad_dtype, or null */
+    void   *grad_value;           /* [n] of value_dtype, or null */
+    double *stats;                /* [HS_PPO_STATS] f64, or null */
+} hs_ppo_request;                 /* 160 bytes */
+int32_t hs_ppo_loss(hs_sim *sim, const hs_ppo_request *req);
+int32_t hs_ppo_loss_async(hs_sim *sim, void *hip_stream, const hs_ppo_request *req);
 
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.

@@ -24,6 +24,7 @@
 #include "hs_k_pack.h"
 #include "hs_k_sample.h"
 #include "hs_k_gae.h"
+#include "hs_k_ppo.h"
 #include "hs_solver.h"
 
 namespace {
@@ -78,6 +79,8 @@ struct hs_sim {
     int cam_cap = 0;
     double *pack_partials = nullptr;       // hs_pack_policy_inputs: the moments of each workgroup, [pack_grid][HS_PACK_MOMENTS]
     double *gae_partials = nullptr;        // hs_compute_gae: the moments of each workgroup, [gae_grid][HS_GAE_MOMENTS]
+    double *ppo_partials = nullptr;        // hs_ppo_loss: the statistics of each workgroup, [kPpoMaxGrid][HS_PPO_STATS]
+    int32_t *ppo_counts = nullptr;         // hs_ppo_loss: the active samples each workgroup of k_ppo_count saw, [kPpoCountGrid]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -408,6 +411,107 @@ int launch_gae(hs_sim *s, hipStream_t strm, const hs_gae_request *r) {
 }
 }  // namespace
 
+// ---- the PPO loss and its gradients (hs_k_ppo.h) ----
+namespace {
+static_assert(HS_PPO_STATS == hs::kPpoStats && HS_GAE_MOMENTS == hs::kGaeMoments, "hs_ppo_request and k_ppo agree");
+static_assert(sizeof(hs_ppo_request) == 160 && offsetof(hs_ppo_request, n) == 72 && offsetof(hs_ppo_request, buckets) == 96 &&
+              offsetof(hs_ppo_request, clip_coef) == 116 && offsetof(hs_ppo_request, grad_logits) == 136 && offsetof(hs_ppo_request, stats) == 152,
+              "hs_ppo_request layout (gpu_hideseek/ppo_loss.py mirrors it)");
+
+int check_ppo(hs_sim *s, const hs_ppo_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null request");
+    if (!r->logits) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null logits");
+    if (!r->action) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null action");
+    if (!r->old_log_prob) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null old_log_prob");
+    if (!r->advantage) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null advantage");
+    if (!r->grad_logits && !r->grad_value && !r->stats) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: every output is null");
+    if (r->grad_value && !r->value) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: grad_value without value");
+    if (r->value && !r->returns) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: value without returns");
+    if (!r->value && (r->returns || r->old_value)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: returns or old_value without value");
+    if (!pack_dtype_ok(r->logits_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: logits dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->grad_logits && !pack_dtype_ok(r->grad_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: grad dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->value && !pack_dtype_ok(r->value_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: value dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    int L = 0;
+    for (int h = 0; h < HS_SAMPLE_HEADS; ++h) {
+        if (r->buckets[h] < 1 || r->buckets[h] > HS_SAMPLE_MAX_BUCKETS) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: a bucket count must be in [1, HS_SAMPLE_MAX_BUCKETS]");
+        L += r->buckets[h];
+    }
+    if (L > HS_SAMPLE_MAX_LOGITS) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: more than HS_SAMPLE_MAX_LOGITS logits per sample");
+    if (r->logits_stride < L) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: logits_stride is below the sum of the buckets");
+    if (r->grad_logits && r->grad_stride < L) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: grad_stride is below the sum of the buckets");
+    if (r->n < 1 || (int64_t)r->n * r->logits_stride >= (int64_t)1 << 31 || (r->grad_logits && (int64_t)r->n * r->grad_stride >= (int64_t)1 << 31))
+        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: n must be at least 1 and n * stride below 2^31");
+    if (!std::isfinite(r->clip_coef) || !(r->clip_coef > 0.f)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: clip_coef must be finite and above 0");
+    if (!std::isfinite(r->value_loss_coef) || !std::isfinite(r->entropy_coef) || !std::isfinite(r->grad_scale))
+        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: value_loss_coef, entropy_coef and grad_scale must be finite");
+    const uintptr_t lsize = r->logits_dtype == HS_DTYPE_F32 ? 4u : 2u, gsize = r->grad_dtype == HS_DTYPE_F32 ? 4u : 2u, vsize = r->value_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if (((uintptr_t)r->action | (uintptr_t)r->old_log_prob | (uintptr_t)r->advantage | (uintptr_t)r->mask | (uintptr_t)r->returns | (uintptr_t)r->old_value) & 3u)
+        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: action, old_log_prob, advantage, mask, returns and old_value must be 4-byte aligned");
+    if (((uintptr_t)r->logits & (lsize - 1)) || (r->grad_logits && ((uintptr_t)r->grad_logits & (gsize - 1))) ||
+        (r->value && (((uintptr_t)r->value | (uintptr_t)r->grad_value) & (vsize - 1))))
+        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: logits, grad_logits, value and grad_value must be aligned to their element size");
+    if (((uintptr_t)r->adv_moments | (uintptr_t)r->stats) & 7u) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: adv_moments and stats must be 8-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange in[] = {range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + L) * lsize), range("action", r->action, n * HS_SAMPLE_HEADS * 4),
+                           range("old_log_prob", r->old_log_prob, n * 4), range("advantage", r->advantage, n * 4),
+                           range("adv_moments", r->adv_moments, HS_GAE_MOMENTS * sizeof(double)), range("mask", r->mask, n * 4),
+                           range("value", r->value, n * vsize), range("returns", r->returns, n * 4), range("old_value", r->old_value, n * 4)};
+    const GaeRange out[] = {range("grad_logits", r->grad_logits, r->grad_logits ? ((n - 1) * (uintptr_t)r->grad_stride + L) * gsize : 0),
+                            range("grad_value", r->grad_value, n * vsize), range("stats", r->stats, HS_PPO_STATS * sizeof(double))};
+    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
+        for (const GaeRange &x : in)
+            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_ppo_loss: ") + out[i].name + " overlaps " + x.name);
+        for (size_t j = 0; j < i; ++j)
+            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_ppo_loss: ") + out[i].name + " overlaps " + out[j].name);
+    }
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss inside an open step");
+    return HS_OK;
+}
+
+// f(tag) with the element type of array `p` of type `dtype` as tag's type
+template <typename F> void with_ppo_type(const void *p, int32_t dtype, F f) {
+    if (!p) f(hs::PpoAbsent{});
+    else if (dtype == HS_DTYPE_F32) f(float{});
+    else if (dtype == HS_DTYPE_BF16) f(hs::SampleBf16{});
+    else f(hs::SampleF16{});
+}
+// With a mask the count of the active samples, then one k_ppo over the samples (the request has passed check_ppo), then
+// the fixed-order sum of the statistics.
+int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
+    hs::PpoArgs a = {};
+    a.logits = r->logits; a.action = r->action; a.oldLogProb = r->old_log_prob; a.advantage = r->advantage;
+    a.advMoments = r->adv_moments; a.mask = r->mask; a.value = r->value; a.returns = r->returns; a.oldValue = r->old_value;
+    a.gradLogits = r->grad_logits; a.gradValue = r->grad_value; a.partials = r->stats ? s->ppo_partials : nullptr;
+    a.counts = s->ppo_counts;
+    for (int h = 0, off = 0; h < HS_SAMPLE_HEADS; off += r->buckets[h++]) {
+        a.bucketK |= (uint64_t)r->buckets[h] << (8 * h);
+        a.bucketOff |= (uint64_t)off << (8 * h);
+        a.L = off + r->buckets[h];
+    }
+    a.n = r->n; a.stride = r->logits_stride; a.gradStride = r->grad_stride; a.countParts = hs::ppo_count_grid(a.n);
+    a.clip = r->clip_coef; a.valueCoef = r->value_loss_coef; a.entropyCoef = r->entropy_coef; a.gradScale = r->grad_scale;
+    const dim3 grid(hs::ppo_grid(a.n)), blk(hs::kPpoThreads);
+    if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), blk, 0, strm, r->mask, a.n, s->ppo_counts);
+    auto with_logits = [&](auto tl) {
+        with_ppo_type(r->grad_logits, r->grad_dtype, [&](auto tg) {
+            with_ppo_type(r->value, r->value_dtype, [&](auto tv) {
+                hipLaunchKernelGGL((hs::k_ppo<decltype(tl), decltype(tg), decltype(tv)>), grid, blk, 0, strm, a);
+            });
+        });
+    };
+    if (r->logits_dtype == HS_DTYPE_F32) with_logits(float{});
+    else if (r->logits_dtype == HS_DTYPE_BF16) with_logits(hs::SampleBf16{});
+    else with_logits(hs::SampleF16{});
+    if (r->stats)
+        hipLaunchKernelGGL(hs::k_ppo_stats_sum<>, dim3(1), dim3(hs::kPpoStats * hs::kPpoSumSegs), 0, strm, (const double *)s->ppo_partials,
+                           hs::ppo_grid(a.n), r->stats);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -506,6 +610,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(S.status, 4);
     if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
     HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
+    HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -859,6 +964,21 @@ int32_t hs_compute_gae(hs_sim *s, const hs_gae_request *req) {
     HS_TRY(check_gae(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_gae(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- the PPO loss and its gradients (hs_k_ppo.h; check_ppo / launch_ppo above) ----
+int32_t hs_ppo_loss_async(hs_sim *s, void *hip_stream, const hs_ppo_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_ppo(s, req));
+    return launch_ppo(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_ppo_loss(hs_sim *s, const hs_ppo_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_ppo(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_ppo(s, s->stream, req));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

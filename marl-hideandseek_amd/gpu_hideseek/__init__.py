@@ -191,6 +191,26 @@ class HideAndSeekSimulator:
         return _advantages.compute(self, rewards, dones, values, bootstrap, stream, gamma=gamma, gae_lambda=gae_lambda,
                                    mask=mask, advantages=advantages, returns=returns, moments=moments)
 
+    def ppo_loss(self, logits, action, old_log_prob, advantage, *, buckets=(5, 5, 5, 2, 2), adv_moments=None, mask=None, value=None,
+                 returns=None, old_value=None, clip_coef=0.2, value_loss_coef=0.5, entropy_coef=0.01, grad_scale=1.0,
+                 grad_logits=True, grad_value=None, stats=True, grad_dtype=None, stream=None):
+        """The PPO loss of a minibatch and its gradients in one kernel (gpu_hideseek.ppo_loss; hs_ppo_loss, whose header
+        comment states the arithmetic: IEEE f32 in a fixed order).  Over the n = logits.shape[0] samples: `logits`
+        [n, W >= sum(buckets)] (float32, bfloat16 or float16, contiguous in the last dimension: pass logits.detach()),
+        `action` [n, 5] int32, `old_log_prob` and `advantage` [n] float32; optional `adv_moments` (the moments of
+        compute_advantages: the advantage is normalised on the device), `mask` [n] float32, `value` [n] or [n, 1] with
+        `returns` [n] float32 and, for the clipped value loss, `old_value` [n] float32.  `grad_logits`, `grad_value` and
+        `stats` are each True (a new tensor: grad_logits shaped like `logits` in `grad_dtype`, by default the logits'
+        dtype; grad_value like `value`; stats [7] float64), a preallocated tensor or None; grad_value=None means True
+        with a value.  A bucket masked with -inf and an inactive sample get gradients of exactly 0.  stream=None blocks;
+        a torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {name: tensor} of what was
+        written, plus "coefficients" for ppo_loss.attach / stats_to_metrics."""
+        from . import ppo_loss as _ppo_loss
+        return _ppo_loss.compute(self, logits, action, old_log_prob, advantage, stream, buckets=buckets, adv_moments=adv_moments,
+                                 mask=mask, value=value, returns=returns, old_value=old_value, clip_coef=clip_coef,
+                                 value_loss_coef=value_loss_coef, entropy_coef=entropy_coef, grad_scale=grad_scale,
+                                 grad_logits=grad_logits, grad_value=grad_value, stats=stats, grad_dtype=grad_dtype)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -168,6 +168,19 @@ class ShardedSimulator:
         return _advantages.compute_sharded(self, rewards, dones, values, bootstrap, stream, mask, advantages, returns,
                                            moments, gamma=gamma, gae_lambda=gae_lambda)
 
+    def ppo_loss(self, logits, action, old_log_prob, advantage, *, buckets=(5, 5, 5, 2, 2), adv_moments=None, mask=None, value=None,
+                 returns=None, old_value=None, clip_coef=0.2, value_loss_coef=0.5, entropy_coef=0.01, grad_scale=1.0,
+                 grad_logits=True, grad_value=None, stats=True, grad_dtype=None, stream=None):
+        """HideAndSeekSimulator.ppo_loss per shard: `logits`, `action`, `old_log_prob` and `advantage` have one tensor
+        per shard, on the shard's device; a list of the shards' results.  Every other tensor argument, every output and
+        `stream` are True / None for all shards or a list with one entry per shard.  A sample's gradients depend on that
+        sample and on its shard's count of active samples (ppo_loss.compute_sharded)."""
+        from . import ppo_loss as _ppo_loss
+        return _ppo_loss.compute_sharded(self, logits, action, old_log_prob, advantage, stream, buckets=buckets, adv_moments=adv_moments,
+                                 mask=mask, value=value, returns=returns, old_value=old_value, clip_coef=clip_coef,
+                                 value_loss_coef=value_loss_coef, entropy_coef=entropy_coef, grad_scale=grad_scale,
+                                 grad_logits=grad_logits, grad_value=grad_value, stats=stats, grad_dtype=grad_dtype)
+
     def device_status(self):
         out = {}
         for s in self.shards:
