@@ -233,6 +233,62 @@ typedef struct hs_pack_request {
 int32_t hs_pack_policy_inputs(hs_sim *sim, const hs_pack_request *req);
 int32_t hs_pack_policy_inputs_async(hs_sim *sim, void *hip_stream, const hs_pack_request *req);
 
+/* Observation normaliser: the exponential moving average that the reference's policy wraps around its network
+ * (scripts/jax_policy.py:372-390, ObservationsEMANormalizer.create(decay = 0.99999, ...)), kept on the device between a
+ * rollout and the next pack.  It normalises every column of the row but HS_NORM_SKIP_PREP_COUNTER and
+ * HS_NORM_SKIP_SELF_TYPE (jax_policy.py:382-389 leaves prep_counter, self_type and the masks alone; the masks are not
+ * columns of the row).  madrona_learn is not available, so the update rule below is this project's contract and is not
+ * pinned to the reference's.
+ * state [HS_NORM_STATE] f64, caller-owned device memory: m1[c] = [c] the running first moment of column c,
+ * m2[c] = [HS_PACK_ROW + c] the running second raw moment, N = [2 HS_PACK_ROW] the bias-correction weight.  All zeros is
+ * a fresh normaliser.
+ * table [HS_NORM_TABLE] f32, caller-owned device memory, 16-byte aligned: mu[c] = [c], inv[c] = [HS_PACK_ROW + c]; what
+ * hs_pack_policy_inputs_normalized reads.
+ * hs_obs_norm_update, one kernel (csrc/hs_k_norm.h).  The num_moments vectors of `moments` (each as
+ * hs_pack_policy_inputs writes it: several shards, or the T steps of a rollout) form one batch.  IEEE f64, unfused, in
+ * exactly this order:
+ *   s1[c], s2[c], n = the sums of the vectors' [c], [HS_PACK_ROW + c], [2 HS_PACK_ROW], added in index order starting
+ *                     from the first vector
+ *   if n > 0, with a = 1.0 - decay:    m1[c] = decay * m1[c] + a * (s1[c] / n)
+ *                                      m2[c] = decay * m2[c] + a * (s2[c] / n)
+ *                                      N     = decay * N + a                   (two products and one addition each)
+ *   otherwise the state is unchanged.
+ *   The table is always rewritten from the resulting state.  A normalised column with N > 0:
+ *       mu = m1[c] / N;   v = m2[c] / N - mu * mu;   v = v < 0 ? 0 : v        (a select)
+ *       table[c] = (float)mu;   table[HS_PACK_ROW + c] = (float)(1.0 / sqrt(v + eps))
+ *   A skipped column, or N == 0:  table[c] = +0.0f;   table[HS_PACK_ROW + c] = 1.0f.
+ * No atomics: the result depends on the inputs alone.  Everything is validated before anything is launched
+ * (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request; null moments, state or table;
+ * num_moments outside [1, HS_NORM_MAX_MOMENTS]; decay outside [0, 1) or NaN; eps not finite or <= 0; moments or state
+ * not 8-byte aligned, a table not 16-byte aligned; state or table overlapping moments or each other; a call before
+ * hs_init or inside an open step.  It reads no export and writes no simulator state; the handle supplies the device.
+ * hs_obs_norm_update is ordered after the device's legacy default stream and blocking; hs_obs_norm_update_async enqueues
+ * on the caller's hipStream_t without synchronising. */
+enum { HS_NORM_STATE = 593, HS_NORM_TABLE = 592, HS_NORM_MAX_MOMENTS = 4096 };
+enum { HS_NORM_SKIP_PREP_COUNTER = 0, HS_NORM_SKIP_SELF_TYPE = 14 };      /* the columns that are not normalised */
+typedef struct hs_obs_norm_request {
+    const double *moments;        /* [num_moments][HS_PACK_MOMENTS] f64, contiguous */
+    int32_t num_moments;          /* 1 .. HS_NORM_MAX_MOMENTS */
+    double decay;                 /* in [0, 1) */
+    double eps;                   /* finite, > 0 */
+    double *state;                /* [HS_NORM_STATE] f64, read and written */
+    float *table;                 /* [HS_NORM_TABLE] f32, written */
+} hs_obs_norm_request;            /* 48 bytes */
+int32_t hs_obs_norm_update(hs_sim *sim, const hs_obs_norm_request *req);
+int32_t hs_obs_norm_update_async(hs_sim *sim, void *hip_stream, const hs_obs_norm_request *req);
+
+/* hs_pack_policy_inputs with the normaliser's table (one kernel, k_pack_norm).  Everything hs_pack_policy_inputs
+ * specifies still holds; in addition every element of the critic row is y = (x - mu[c]) * inv[c], one IEEE f32
+ * subtraction then one f32 multiplication, unfused, on the f32 value x of the un-normalised critic row; the actor row is
+ * y * mask in columns 45-295 (normalise, then mask, as the reference's obs_preprocess runs before ActorNet); the cast to
+ * the output type comes last.  The moments stay those of the raw x, so one launch normalises with the current table
+ * and collects the statistics of the next update.  With the table of a fresh state, (x - 0) * 1, the outputs have the
+ * bits of hs_pack_policy_inputs, -0 included.  Validation, ordering and streams as hs_pack_policy_inputs; a null or
+ * not 16-byte aligned table is refused with HS_ERR_INVALID_ARG before anything is launched.  The table is read by the
+ * kernel: an hs_obs_norm_update that rewrites it must be ordered before or after the pack. */
+int32_t hs_pack_policy_inputs_normalized(hs_sim *sim, const hs_pack_request *req, const float *table);
+int32_t hs_pack_policy_inputs_normalized_async(hs_sim *sim, void *hip_stream, const hs_pack_request *req, const float *table);
+
 /* Action sampling: the leg after the network.  The actor's logits of every agent row (world * A + slot) become the
  * [rows][HS_SAMPLE_HEADS] i32 action the next hs_step reads, with the log-probability and the entropy a PPO learner
  * stores, in one kernel (csrc/hs_k_sample.h) — a multi-discrete actor head as the reference's learner has it

@@ -25,6 +25,7 @@
 #include "hs_k_sample.h"
 #include "hs_k_gae.h"
 #include "hs_k_ppo.h"
+#include "hs_k_norm.h"
 #include "hs_solver.h"
 
 namespace {
@@ -274,22 +275,32 @@ int check_pack(hs_sim *s, const hs_pack_request *r) {
     if ((uintptr_t)r->moments & 7u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: moments must be 8-byte aligned");
     return HS_OK;
 }
+// The fixed-order sum of the workgroups' moments, after a k_pack or k_pack_norm that wrote them.  A template, so that
+// k_pack_moments_sum is instantiated after the k_pack kernels of launch_pack, as it was when launch_pack launched it.
+template <int kSegs = hs::kPackSumSegs>
+int launch_pack_moments_sum(hs_sim *s, hipStream_t strm, const hs_pack_request *r, int rows) {
+    constexpr int kCols = hs::kPackThreads / kSegs;
+    if (r->moments)
+        hipLaunchKernelGGL(hs::k_pack_moments_sum<kSegs>, dim3((hs::kPackMoments + kCols - 1) / kCols), dim3(hs::kPackThreads), 0, strm,
+                           (const double *)s->pack_partials, hs::pack_grid(rows), r->moments);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+hs::PackArgs pack_args(hs_sim *s, const hs_pack_request *r) {
+    const hs::SimState &S = s->S;
+    return {S.xPrep, S.xSelfType, S.xSelfObs, S.xSelfMask, S.xLidar, S.xAgentObs, S.xBoxObs, S.xRampObs,
+            S.xVisAgents, S.xVisBoxes, S.xVisRamps, r->actor, r->critic, s->pack_partials, S.N * s->A};
+}
 // One k_pack over every agent row (the request has passed check_pack), then the fixed-order sum of the moments.
 int launch_pack(hs_sim *s, hipStream_t strm, const hs_pack_request *r) {
-    const hs::SimState &S = s->S;
-    const hs::PackArgs a = {S.xPrep, S.xSelfType, S.xSelfObs, S.xSelfMask, S.xLidar, S.xAgentObs, S.xBoxObs, S.xRampObs,
-                            S.xVisAgents, S.xVisBoxes, S.xVisRamps, r->actor, r->critic, s->pack_partials, S.N * s->A};
+    const hs::PackArgs a = pack_args(s, r);
     with_pack_type(r->actor, r->actor_dtype, [&](auto ta) {
         with_pack_type(r->critic, r->critic_dtype, [&](auto tc) {
             if (r->moments) launch_pack_as<decltype(ta), decltype(tc), true>(a, strm);
             else launch_pack_as<decltype(ta), decltype(tc), false>(a, strm);
         });
     });
-    if (r->moments)
-        hipLaunchKernelGGL(hs::k_pack_moments_sum<>, dim3((hs::kPackMoments + hs::kPackThreads / hs::kPackSumSegs - 1) / (hs::kPackThreads / hs::kPackSumSegs)),
-                           dim3(hs::kPackThreads), 0, strm, (const double *)s->pack_partials, hs::pack_grid(a.rows), r->moments);
-    HS_HIP(hipGetLastError());
-    return HS_OK;
+    return launch_pack_moments_sum<>(s, strm, r, a.rows);
 }
 }  // namespace
 
@@ -509,6 +520,66 @@ int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
                            hs::ppo_grid(a.n), r->stats);
     HS_HIP(hipGetLastError());
     return HS_OK;
+}
+}  // namespace
+
+// ---- observation normaliser (hs_k_norm.h); after the other launchers, so that its kernels are instantiated last ----
+namespace {
+static_assert(HS_NORM_STATE == hs::kNormState && HS_NORM_TABLE == hs::kNormTable && HS_NORM_MAX_MOMENTS == hs::kNormMaxMoments &&
+              HS_NORM_STATE == HS_PACK_MOMENTS, "hs_obs_norm_request and k_norm_update agree");
+static_assert(hs::norm_skipped(HS_NORM_SKIP_PREP_COUNTER) && hs::norm_skipped(HS_NORM_SKIP_SELF_TYPE) && HS_NORM_SKIP_SELF_TYPE == hs::kPackColType,
+              "the skipped columns are prep_counter and self_type");
+static_assert(sizeof(hs_obs_norm_request) == 48 && offsetof(hs_obs_norm_request, num_moments) == 8 && offsetof(hs_obs_norm_request, decay) == 16 &&
+              offsetof(hs_obs_norm_request, eps) == 24 && offsetof(hs_obs_norm_request, state) == 32 && offsetof(hs_obs_norm_request, table) == 40,
+              "hs_obs_norm_request layout (gpu_hideseek/policy_inputs.py mirrors it)");
+
+int check_norm_update(hs_sim *s, const hs_obs_norm_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null request");
+    if (!r->moments) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null moments");
+    if (!r->state) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null state");
+    if (!r->table) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null table");
+    if (r->num_moments < 1 || r->num_moments > HS_NORM_MAX_MOMENTS) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: num_moments must be in [1, HS_NORM_MAX_MOMENTS]");
+    if (!(r->decay >= 0.0 && r->decay < 1.0)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: decay must be in [0, 1)");
+    if (!std::isfinite(r->eps) || !(r->eps > 0.0)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: eps must be finite and above 0");
+    if (((uintptr_t)r->moments | (uintptr_t)r->state) & 7u) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: moments and state must be 8-byte aligned");
+    if ((uintptr_t)r->table & 15u) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: table must be 16-byte aligned");
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange moments = range("moments", r->moments, (uintptr_t)r->num_moments * HS_PACK_MOMENTS * sizeof(double));
+    const GaeRange state = range("state", r->state, HS_NORM_STATE * sizeof(double)), table = range("table", r->table, HS_NORM_TABLE * sizeof(float));
+    if (gae_overlap(state, moments)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: state overlaps moments");
+    if (gae_overlap(table, moments)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: table overlaps moments");
+    if (gae_overlap(table, state)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: table overlaps state");
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update inside an open step");
+    return HS_OK;
+}
+int launch_norm_update(hipStream_t strm, const hs_obs_norm_request *r) {
+    const hs::NormArgs a = {r->moments, r->num_moments, r->decay, r->eps, r->state, r->table};
+    hipLaunchKernelGGL(hs::k_norm_update<>, dim3(1), dim3(hs::kNormThreads), 0, strm, a);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+int check_pack_norm(hs_sim *s, const hs_pack_request *r, const float *table) {
+    HS_TRY(check_pack(s, r));
+    if (!table) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs_normalized: null table");
+    if ((uintptr_t)table & 15u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs_normalized: table must be 16-byte aligned");
+    return HS_OK;
+}
+// One k_pack_norm over every agent row (the request has passed check_pack_norm), then the fixed-order sum of the moments.
+// With no rows requested the moments alone are those of hs_pack_policy_inputs: the table is not read.
+int launch_pack_norm(hs_sim *s, hipStream_t strm, const hs_pack_request *r, const float *table) {
+    if (!r->actor && !r->critic) return launch_pack(s, strm, r);
+    const hs::PackArgs a = pack_args(s, r);
+    const dim3 grid(hs::pack_grid(a.rows)), blk(hs::kPackThreads);
+    with_pack_type(r->actor, r->actor_dtype, [&](auto ta) {
+        with_pack_type(r->critic, r->critic_dtype, [&](auto tc) {
+            if constexpr (std::is_same<decltype(ta), hs::PackAbsent>::value && std::is_same<decltype(tc), hs::PackAbsent>::value) return;
+            else if (r->moments) hipLaunchKernelGGL((hs::k_pack_norm<decltype(ta), decltype(tc), true>), grid, blk, 0, strm, a, table);
+            else hipLaunchKernelGGL((hs::k_pack_norm<decltype(ta), decltype(tc), false>), grid, blk, 0, strm, a, table);
+        });
+    });
+    return launch_pack_moments_sum<>(s, strm, r, a.rows);
 }
 }  // namespace
 
@@ -979,6 +1050,34 @@ int32_t hs_ppo_loss(hs_sim *s, const hs_ppo_request *req) {
     HS_TRY(check_ppo(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_ppo(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- observation normaliser (hs_k_norm.h; check_norm_update / launch_pack_norm above) ----
+int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_norm_update(s, req));
+    return launch_norm_update((hipStream_t)hip_stream, req);
+}
+int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_norm_update(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_norm_update(s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+int32_t hs_pack_policy_inputs_normalized_async(hs_sim *s, void *hip_stream, const hs_pack_request *req, const float *table) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_pack_norm(s, req, table));
+    return launch_pack_norm(s, (hipStream_t)hip_stream, req, table);
+}
+int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_pack_norm(s, req, table));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_pack_norm(s, s->stream, req, table));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

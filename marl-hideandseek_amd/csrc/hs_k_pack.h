@@ -138,16 +138,37 @@ HSD void pack_store16(PackF16 *dst, const float (&v)[8]) {
 }
 
 // The block's rows to out (rows of kPackRow T from row0 on), 16 bytes per lane and pass; MASKED: the actor's rows.
-template <typename T, bool MASKED> HSD void pack_write(T *out, size_t row0, int nrows, const PackImage &im) {
+// NORM: y = (x - mu[c]) * inv[c] first, an f32 subtraction and an f32 multiplication, with mu | inv the two halves of
+// `table` (hs_k_norm.h).  A piece starts at a column that is a multiple of K, so its mu and inv are aligned 16-byte
+// vectors of the table, loaded from global memory (2.4 KB, cache-resident) ahead of the ds_read they meet.
+template <typename T, bool MASKED, bool NORM> HSD void pack_write(T *out, size_t row0, int nrows, const PackImage &im, const float *__restrict__ table) {
     constexpr int K = 16 / (int)sizeof(T), kPerRow = kPackRow / K;
     T *dst = out + row0 * kPackRow;
     const int n = nrows * kPerRow;
     for (int q = threadIdx.x; q < n; q += kPackThreads) {
         float v[K];
+        [[maybe_unused]] float4 mu[K / 4], inv[K / 4];
+        if (NORM) {
+            const int c0 = (q % kPerRow) * K;
+#pragma unroll
+            for (int k = 0; k < K / 4; ++k) {
+                mu[k] = *(const float4 *)(table + c0 + 4 * k);
+                inv[k] = *(const float4 *)(table + kPackRow + c0 + 4 * k);
+            }
+        }
 #pragma unroll
         for (int k = 0; k < K; k += 4) {
             const float4 x = *(const float4 *)(im.row + q * K + k);
             v[k] = x.x; v[k + 1] = x.y; v[k + 2] = x.z; v[k + 3] = x.w;
+        }
+        if (NORM) {
+#pragma unroll
+            for (int k = 0; k < K; k += 4) {
+                v[k] = (v[k] - mu[k / 4].x) * inv[k / 4].x;
+                v[k + 1] = (v[k + 1] - mu[k / 4].y) * inv[k / 4].y;
+                v[k + 2] = (v[k + 2] - mu[k / 4].z) * inv[k / 4].z;
+                v[k + 3] = (v[k + 3] - mu[k / 4].w) * inv[k / 4].w;
+            }
         }
         if (MASKED) {
             const int r = q / kPerRow, c0 = (q - r * kPerRow) * K;
@@ -161,8 +182,10 @@ template <typename T, bool MASKED> HSD void pack_write(T *out, size_t row0, int 
     }
 }
 
-template <typename TA, typename TC, bool MOM>
-__global__ __launch_bounds__(kPackThreads) void k_pack(PackArgs a) {
+// The body of k_pack and of k_pack_norm (hs_k_norm.h), one instantiation per kernel, so the image is that kernel's LDS:
+// the row blocks of one workgroup staged, written as the actor's and the critic's rows, and the moments of the raw image.
+template <typename TA, typename TC, bool MOM, bool NORM>
+HSD void pack_blocks(const PackArgs a, const float *__restrict__ table) {
     constexpr bool kActor = !std::is_same<TA, PackAbsent>::value;
     __shared__ PackImage im;
     if (kActor)
@@ -181,8 +204,8 @@ __global__ __launch_bounds__(kPackThreads) void k_pack(PackArgs a) {
         if (nrows == kPackRows) pack_load<true>(a, row0, nrows, im, kActor, MOM);
         else pack_load<false>(a, row0, nrows, im, kActor, MOM);
         __syncthreads();
-        if constexpr (kActor) pack_write<TA, true>((TA *)a.actor, row0, nrows, im);
-        if constexpr (!std::is_same<TC, PackAbsent>::value) pack_write<TC, false>((TC *)a.critic, row0, nrows, im);
+        if constexpr (kActor) pack_write<TA, true, NORM>((TA *)a.actor, row0, nrows, im, table);
+        if constexpr (!std::is_same<TC, PackAbsent>::value) pack_write<TC, false, NORM>((TC *)a.critic, row0, nrows, im, table);
         if (MOM) {
 #pragma unroll
             for (int j = 0; j < kOwn; ++j) {
@@ -207,6 +230,11 @@ __global__ __launch_bounds__(kPackThreads) void k_pack(PackArgs a) {
         }
         if (threadIdx.x == 0) p[2 * kPackRow] = cnt;
     }
+}
+
+template <typename TA, typename TC, bool MOM>
+__global__ __launch_bounds__(kPackThreads) void k_pack(PackArgs a) {
+    pack_blocks<TA, TC, MOM, false>(a, nullptr);
 }
 
 // out[c] = sum of partials[0 .. nparts)[c], always in the same order: kPackSumSegs lanes per column each add a

@@ -149,15 +149,18 @@ class HideAndSeekSimulator:
         from . import spectate
         return spectate.render(self, cameras, width, height, depth, rgb, hit, out, exact)
 
-    def pack_policy_inputs(self, actor=None, critic=None, moments=None, *, dtype=None, stream=None):
+    def pack_policy_inputs(self, actor=None, critic=None, moments=None, *, dtype=None, stream=None, normaliser=None):
         """Pack the observation exports into policy-input rows [num_worlds * agents_per_world, 296] in one kernel
         (gpu_hideseek.policy_inputs: LAYOUT, views, moments_to_mean_var; hs_pack_policy_inputs).  `actor` (entity tables
         times their visibility masks) and `critic` (unmasked) are each True (a new tensor of `dtype`: float32, bfloat16
         or float16), a preallocated tensor (its dtype is taken; a slot buf[t] of a [T, R, 296] rollout buffer will do) or
         None; `moments` likewise, [593] float64.  stream=None blocks; a torch.cuda.Stream or raw handle enqueues there
-        without synchronising (the caller orders it after the step).  Returns {name: tensor} of what was written."""
+        without synchronising (the caller orders it after the step).  `normaliser`, a policy_inputs.ObsNormaliser or its
+        float32 [592] table, normalises every element as (x - mean) * inv_std before the actor's masks and the cast
+        (hs_pack_policy_inputs_normalized); the moments stay those of the raw rows.  Returns {name: tensor} of what was
+        written."""
         from . import policy_inputs
-        return policy_inputs.pack(self, actor, critic, moments, dtype, stream)
+        return policy_inputs.pack(self, actor, critic, moments, dtype, stream, normaliser)
 
     def sample_actions(self, logits, *, buckets=(5, 5, 5, 2, 2), mode="draw", seed=(0, 0), counter=0, action=None,
                        log_prob=None, entropy=None, head_log_prob=None, zero_inactive=False, stream=None):

@@ -90,6 +90,14 @@ def load():
     L.hs_pack_policy_inputs.restype = C.c_int32
     L.hs_pack_policy_inputs_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]   # (sim, hipStream_t, request)
     L.hs_pack_policy_inputs_async.restype = C.c_int32
+    L.hs_pack_policy_inputs_normalized.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]      # (sim, request, const float *table)
+    L.hs_pack_policy_inputs_normalized.restype = C.c_int32
+    L.hs_pack_policy_inputs_normalized_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]    # (sim, hipStream_t, request, table)
+    L.hs_pack_policy_inputs_normalized_async.restype = C.c_int32
+    L.hs_obs_norm_update.argtypes = [C.c_void_p, C.c_void_p]                    # (sim, const hs_obs_norm_request *)
+    L.hs_obs_norm_update.restype = C.c_int32
+    L.hs_obs_norm_update_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]      # (sim, hipStream_t, request)
+    L.hs_obs_norm_update_async.restype = C.c_int32
     L.hs_sample_actions.argtypes = [C.c_void_p, C.c_void_p]                     # (sim, const hs_sample_request *)
     L.hs_sample_actions.restype = C.c_int32
     L.hs_sample_actions_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]       # (sim, hipStream_t, request)

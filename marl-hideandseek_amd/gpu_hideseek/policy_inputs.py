@@ -11,11 +11,24 @@ normaliser.
     out = sim.pack_policy_inputs(actor=rollout_actor[t], critic=rollout_critic[t], moments=True)
     tables = policy_inputs.views(rollout_actor[t])       # {"self": [R,45], "agents": [R,5,14], "boxes": ..., "ramps": ...}
     count, mean, var = policy_inputs.moments_to_mean_var(out["moments"])
+
+The normaliser the reference wraps around its policy (jax_policy.py:372-390, an exponential moving average with decay
+0.99999 over every column but prep_counter and self_type) lives on the device as an ObsNormaliser: the pack normalises
+with its table and collects the moments of the raw rows in the same launch, and update() folds them in with one kernel
+(hs_obs_norm_update), with no host synchronisation in between.
+
+    norm = policy_inputs.ObsNormaliser(gpu_id)
+    out = sim.pack_policy_inputs(actor=rollout_actor[t], critic=rollout_critic[t], moments=mom[t], normaliser=norm)
+    norm.update(sim, mom)                                # [T, 593], after the rollout
 """
 import ctypes as C
 
 ROW = 296            # HS_PACK_ROW
 MOMENTS = 593        # HS_PACK_MOMENTS: sum m x [296], sum m x x [296], sum m
+NORM_STATE = 593     # HS_NORM_STATE: m1 [296], m2 [296], N
+NORM_TABLE = 592     # HS_NORM_TABLE: mu [296], inv [296]
+NORM_MAX_MOMENTS = 4096      # HS_NORM_MAX_MOMENTS
+NORM_SKIP = ("prep_counter", "self_type")      # the columns an ObsNormaliser leaves alone (HS_NORM_SKIP_*)
 
 # name -> (first column, one past the last, shape of a row's slice); columns of the packed row in order
 LAYOUT = {
@@ -39,6 +52,12 @@ class HsPackRequest(C.Structure):
     """hs_pack_request (include/hideseek.h)."""
     _fields_ = [("actor", C.c_void_p), ("actor_dtype", C.c_int32), ("critic", C.c_void_p), ("critic_dtype", C.c_int32),
                 ("moments", C.c_void_p)]
+
+
+class HsObsNormRequest(C.Structure):
+    """hs_obs_norm_request (include/hideseek.h)."""
+    _fields_ = [("moments", C.c_void_p), ("num_moments", C.c_int32), ("decay", C.c_double), ("eps", C.c_double),
+                ("state", C.c_void_p), ("table", C.c_void_p)]
 
 
 def views(packed):
@@ -75,7 +94,8 @@ def _output(name, t, rows, dev, dtype):
         return torch.empty(shape, dtype=dt, device=dev)
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name} must be True, None or a torch tensor")
-    what = f"{name} must be a contiguous, 16-byte aligned {' / '.join(allowed)} tensor of shape {shape} on {dev}"
+    align = 8 if name == "moments" else 16       # a row mom[t] of a [T, 593] float64 buffer is 8-byte aligned
+    what = f"{name} must be a contiguous, {align}-byte aligned {' / '.join(allowed)} tensor of shape {shape} on {dev}"
     if tuple(t.shape) != shape:
         raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
     if str(t.dtype).replace("torch.", "") not in allowed:
@@ -84,8 +104,8 @@ def _output(name, t, rows, dev, dtype):
         raise ValueError(f"{what}: it is not contiguous")
     if t.device != dev:
         raise ValueError(f"{what}: it is on {t.device}")
-    if t.data_ptr() % 16:
-        raise ValueError(f"{what}: it starts {t.data_ptr() % 16} bytes past a 16-byte boundary")
+    if t.data_ptr() % align:
+        raise ValueError(f"{what}: it starts {t.data_ptr() % align} bytes past a {align}-byte boundary")
     return t
 
 
@@ -112,14 +132,44 @@ def stream_handle(stream):
     return int(getattr(stream, "cuda_stream", stream))
 
 
-def pack(sim, actor=None, critic=None, moments=None, dtype=None, stream=None):
-    """HideAndSeekSimulator.pack_policy_inputs."""
+def norm_table(normaliser, gpu_id):
+    """The f32 [592] table tensor of `normaliser` (an ObsNormaliser or the tensor itself), checked for GPU `gpu_id`."""
+    import torch
+    dev = torch.device("cuda", gpu_id)
+    t = normaliser.table if isinstance(normaliser, ObsNormaliser) else normaliser
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("normaliser must be None, an ObsNormaliser or a torch tensor")
+    what = f"normaliser must be (or own) a contiguous, 16-byte aligned float32 table of shape ({NORM_TABLE},) on {dev}"
+    if tuple(t.shape) != (NORM_TABLE,):
+        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: its dtype is {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: it is not contiguous")
+    if t.device != dev:
+        raise ValueError(f"{what}: it is on {t.device}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{what}: it starts {t.data_ptr() % 16} bytes past a 16-byte boundary")
+    return t
+
+
+def _launch(sim, req, table, stream):
+    """The pack entry point that fits (table, stream)."""
     from ._native import check
-    res, req = request(sim.num_worlds * sim.agents_per_world, sim.gpu_id, actor, critic, moments, dtype)
-    if stream is None:
-        check(sim._L.hs_pack_policy_inputs(sim._h, C.byref(req)))
+    L, h, st = sim._L, sim._h, None if stream is None else C.c_void_p(stream_handle(stream))
+    if table is None:
+        check(L.hs_pack_policy_inputs(h, C.byref(req)) if st is None else L.hs_pack_policy_inputs_async(h, st, C.byref(req)))
     else:
-        check(sim._L.hs_pack_policy_inputs_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+        tp = C.c_void_p(table.data_ptr())
+        check(L.hs_pack_policy_inputs_normalized(h, C.byref(req), tp) if st is None
+              else L.hs_pack_policy_inputs_normalized_async(h, st, C.byref(req), tp))
+
+
+def pack(sim, actor=None, critic=None, moments=None, dtype=None, stream=None, normaliser=None):
+    """HideAndSeekSimulator.pack_policy_inputs."""
+    res, req = request(sim.num_worlds * sim.agents_per_world, sim.gpu_id, actor, critic, moments, dtype)
+    table = None if normaliser is None else norm_table(normaliser, sim.gpu_id)
+    _launch(sim, req, table, stream)
     return res
 
 
@@ -132,23 +182,130 @@ def _per_shard(ssim, name, arg):
     return list(arg)
 
 
-def pack_sharded(ssim, actor=None, critic=None, moments=None, dtype=None, stream=None):
+def pack_sharded(ssim, actor=None, critic=None, moments=None, dtype=None, stream=None, normaliser=None):
     """ShardedSimulator.pack_policy_inputs: every shard packs its own rows on its own device.  Each of `actor`,
     `critic`, `moments` (and `stream`) is True / None for all shards or a list with one entry per shard; returns the list
     of the shards' results.  With stream=None every shard's pack is enqueued on a side stream of its device, ordered
-    after that device's current stream, before any is waited for."""
+    after that device's current stream, before any is waited for.  `normaliser` is None, a list with one ObsNormaliser
+    or table tensor per shard (each on its shard's device), or one of either for every shard, which then all have to be
+    on its device: a table is read by the kernel and is not copied between devices here.  With the shards on several
+    devices, keep one ObsNormaliser, update it with the shards' moments stacked on its device, and hand each other device
+    a copy of its table."""
     import torch
-    from ._native import check
     args = [_per_shard(ssim, k, v) for k, v in (("actor", actor), ("critic", critic), ("moments", moments))]
     streams = _per_shard(ssim, "stream", stream)
     reqs = [request(s.num_worlds * s.agents_per_world, s.gpu_id, a, c, m, dtype) for s, a, c, m in zip(ssim.shards, *args)]
+    norms = normaliser if isinstance(normaliser, (list, tuple)) else [normaliser] * len(ssim.shards)
+    if len(norms) != len(ssim.shards):
+        raise ValueError(f"normaliser: one entry per shard ({len(ssim.shards)}) expected")
+    tables = [None if n is None else norm_table(n, s.gpu_id) for s, n in zip(ssim.shards, norms)]
     waits = []
-    for s, (res, req), st in zip(ssim.shards, reqs, streams):
+    for s, (res, req), st, table in zip(ssim.shards, reqs, streams, tables):
         if st is None:
             st = torch.cuda.Stream(device=s.gpu_id)
             st.wait_stream(torch.cuda.current_stream(s.gpu_id))
             waits.append(st)
-        check(s._L.hs_pack_policy_inputs_async(s._h, C.c_void_p(stream_handle(st)), C.byref(req)))
+        _launch(s, req, table, st)
     for st in waits:
         st.synchronize()
     return [res for res, _ in reqs]
+
+
+def table_of_state(state, eps):
+    """The table [592] float32 (numpy) of a state [593] float64 (numpy), by the formula of hs_obs_norm_update."""
+    import numpy as np
+    m1, m2, N = state[:ROW], state[ROW:2 * ROW], state[2 * ROW]
+    mu, inv = np.zeros(ROW, np.float32), np.ones(ROW, np.float32)
+    if N > 0:
+        mean = m1 / N
+        v = m2 / N - mean * mean
+        v = np.where(v < 0, 0.0, v)
+        mu, inv = mean.astype(np.float32), (1.0 / np.sqrt(v + eps)).astype(np.float32)
+        for name in NORM_SKIP:
+            mu[LAYOUT[name][0]], inv[LAYOUT[name][0]] = 0.0, 1.0
+    return np.concatenate([mu, inv])
+
+
+def _decay_eps(decay, eps):
+    import math
+    decay, eps = float(decay), float(eps)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"decay must be in [0, 1), got {decay}")
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"eps must be finite and above 0, got {eps}")
+    return decay, eps
+
+
+class ObsNormaliser:
+    """The observation normaliser of the reference's policy (jax_policy.py:372-390) on GPU `gpu_id`: an exponential
+    moving average of the first and second moments of every column of the packed row, bias-corrected, kept in `state`
+    (float64 [593]: m1, m2, N) and turned into `table` (float32 [592]: mean, 1 / sqrt(var + eps); 0 and 1 for
+    prep_counter and self_type) by update().  Hand it to pack_policy_inputs(normaliser=...).  The arithmetic is stated
+    with hs_obs_norm_request in include/hideseek.h."""
+
+    def __init__(self, gpu_id, decay=0.99999, eps=1e-5):
+        import torch
+        self.gpu_id = int(gpu_id)
+        self.decay, self.eps = _decay_eps(decay, eps)
+        dev = torch.device("cuda", self.gpu_id)
+        self.state = torch.zeros(NORM_STATE, dtype=torch.float64, device=dev)
+        self.table = torch.empty(NORM_TABLE, dtype=torch.float32, device=dev)
+        self.reset()
+
+    def reset(self):
+        """A fresh normaliser: the state all zeros, the table the identity."""
+        self.state.zero_()
+        self.table[:ROW] = 0.0
+        self.table[ROW:] = 1.0
+
+    def update(self, sim, moments, stream=None):
+        """Fold the moments of one batch into the state and rewrite the table, in one kernel (hs_obs_norm_update).
+        `moments` is what pack_policy_inputs(moments=...) wrote: float64 [593], or [K, 593] for K shards or K steps of
+        a rollout (one batch), contiguous, on this normaliser's GPU, which is also `sim`'s.  stream=None blocks; a
+        torch.cuda.Stream or raw handle enqueues there without synchronising."""
+        import torch
+        from ._native import check
+        dev = self.state.device
+        what = f"moments must be a contiguous float64 tensor of shape ({MOMENTS},) or (K, {MOMENTS}), K <= {NORM_MAX_MOMENTS}, on {dev}"
+        if not isinstance(moments, torch.Tensor):
+            raise ValueError(f"{what}: got {type(moments).__name__}")
+        shape = tuple(moments.shape)
+        if not (shape == (MOMENTS,) or (len(shape) == 2 and shape[1] == MOMENTS and 1 <= shape[0] <= NORM_MAX_MOMENTS)):
+            raise ValueError(f"{what}: its shape is {shape}")
+        if moments.dtype != torch.float64:
+            raise ValueError(f"{what}: its dtype is {moments.dtype}")
+        if not moments.is_contiguous():
+            raise ValueError(f"{what}: it is not contiguous")
+        if moments.device != dev:
+            raise ValueError(f"{what}: it is on {moments.device}")
+        if sim.gpu_id != self.gpu_id:
+            raise ValueError(f"the simulator is on GPU {sim.gpu_id}, the normaliser on GPU {self.gpu_id}")
+        req = HsObsNormRequest(moments.data_ptr(), moments.numel() // MOMENTS, self.decay, self.eps, self.state.data_ptr(),
+                               self.table.data_ptr())
+        if stream is None:
+            check(sim._L.hs_obs_norm_update(sim._h, C.byref(req)))
+        else:
+            check(sim._L.hs_obs_norm_update_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+
+    def mean_var(self):
+        """(mean [296], biased variance [296], N) in float64 on the device, from the state, without synchronising: the
+        bias-corrected statistics of every column (the skipped ones included).  A fresh normaliser gives zeros."""
+        import torch
+        m1, m2, N = self.state[:ROW], self.state[ROW:2 * ROW], self.state[2 * ROW]
+        n = torch.where(N > 0, N, torch.ones_like(N))
+        mean = m1 / n
+        return mean, torch.clamp(m2 / n - mean * mean, min=0.0), N
+
+    def state_dict(self):
+        return {"state": self.state.detach().cpu().clone(), "decay": self.decay, "eps": self.eps}
+
+    def load_state_dict(self, d):
+        """Restore a state_dict(): the state, decay and eps; the table is computed again on the host by the formula of
+        hs_obs_norm_update."""
+        import torch
+        state = torch.as_tensor(d["state"])
+        if tuple(state.shape) != (NORM_STATE,) or state.dtype != torch.float64:
+            raise ValueError(f"state must be a float64 tensor of shape ({NORM_STATE},), got {state.dtype} {tuple(state.shape)}")
+        self.decay, self.eps = _decay_eps(d["decay"], d["eps"])
+        self.state.copy_(state)
+        self.table.copy_(torch.from_numpy(table_of_state(state.cpu().numpy(), self.eps)))

@@ -141,12 +141,13 @@ class ShardedSimulator:
         from . import spectate
         return spectate.render_sharded(self, cameras, width, height, depth, rgb, hit, out, exact)
 
-    def pack_policy_inputs(self, actor=None, critic=None, moments=None, *, dtype=None, stream=None):
+    def pack_policy_inputs(self, actor=None, critic=None, moments=None, *, dtype=None, stream=None, normaliser=None):
         """HideAndSeekSimulator.pack_policy_inputs per shard: a list of the shards' results, each on its own device.
         Every argument is True / None for all shards or a list with one entry per shard; every shard's pack is enqueued
-        before any is waited for."""
+        before any is waited for.  `normaliser`: a list with one ObsNormaliser or table per shard, each on its shard's
+        device, or one for all shards when they share its device (policy_inputs.pack_sharded)."""
         from . import policy_inputs
-        return policy_inputs.pack_sharded(self, actor, critic, moments, dtype, stream)
+        return policy_inputs.pack_sharded(self, actor, critic, moments, dtype, stream, normaliser)
 
     def sample_actions(self, logits, *, buckets=(5, 5, 5, 2, 2), mode="draw", seed=(0, 0), counter=0, action=None,
                        log_prob=None, entropy=None, head_log_prob=None, zero_inactive=False, stream=None):

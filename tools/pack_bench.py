@@ -4,7 +4,9 @@ eager ops on the exports, and next to a plain device-to-device copy of as many b
     python tools/pack_bench.py [--worlds 16000] [--calls 200] [--rounds 3] [--json out.json]
 
 At --worlds x (2+2) and x (3+3) agents, after 120 steps of the benchmark action stream: actor-bf16, critic-bf16,
-actor+critic-bf16 without and with moments, actor+critic-f32.  Each variant is timed with device events around --calls
+actor+critic-bf16 without and with moments, actor+critic-f32, and actor+critic-bf16 normalised (normaliser=table of a real
+update) without and with moments, whose eager composition is f32 rows -> (x - mu) * inv -> mask -> cast.  The time of
+hs_obs_norm_update is reported once per team size, for 1 and 40 moment vectors.  Each variant is timed with device events around --calls
 calls after warm-up; fused, eager and copy alternate inside each of --rounds rounds and the median window is reported
 with the spread (max - min) of the windows.  The fused and the eager rows are compared bit for bit once.  Algorithmic
 bytes = every input the variant needs read once + every output written once; bytes/s = that over the fused time.
@@ -54,6 +56,20 @@ def eager_rows(t, actor, dtype):
     return torch.cat(cols, 1).to(dtype)
 
 
+def eager_normalised(t, table, actor, critic, dtype):
+    """The normalised rows from eager ops: the f32 critic rows, (x - mu) * inv, the actor's masks, the cast."""
+    R = t["self_data"].shape[0]
+    y = (eager_rows(t, False, torch.float32) - table[:P.ROW]) * table[P.ROW:]
+    res = {}
+    if critic:
+        res["critic"] = y.to(dtype)
+    if actor:
+        ones = torch.ones(R, P.LAYOUT["agent_data"][0], device=y.device)
+        masks = [t[m].reshape(R, -1).repeat_interleave(P.LAYOUT[d][2][1], dim=1) for d, m in P.MASKS.items()]
+        res["actor"] = (y * torch.cat([ones] + masks, 1)).to(dtype)
+    return res
+
+
 def eager_moments(t):
     x = eager_rows(t, False, torch.float64)
     m = t["self_mask"].reshape(-1, 1).double()
@@ -83,28 +99,31 @@ def window(fn, calls):
     return a.elapsed_time(b) / calls      # ms per call
 
 
-def bench_variant(sim, t, name, actor, critic, moments, dtype, args):
+def bench_variant(sim, t, name, actor, critic, moments, dtype, args, table=None):
     R = t["self_data"].shape[0]
     dev = t["self_data"].device
     out = {k: torch.empty(R, P.ROW, dtype=dtype, device=dev) for k, on in (("actor", actor), ("critic", critic)) if on}
     if moments:
         out["moments"] = torch.empty(P.MOMENTS, dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream()
+    norm = {} if table is None else {"normaliser": table}      # (the keyword only where it is used)
 
     def fused():                          # enqueue only, like the eager ops: the events see device time
-        sim.pack_policy_inputs(out.get("actor"), out.get("critic"), out.get("moments"), stream=stream)
+        sim.pack_policy_inputs(out.get("actor"), out.get("critic"), out.get("moments"), stream=stream, **norm)
 
     def eager():
         res = {}
-        if actor:
+        if table is not None:
+            res = eager_normalised(t, table, actor, critic, dtype)
+        elif actor:
             res["actor"] = eager_rows(t, True, dtype)
-        if critic:
+        if critic and table is None:
             res["critic"] = eager_rows(t, False, dtype)
         if moments:
             res["moments"] = eager_moments(t)
         return res
 
-    nbytes = algorithmic_bytes(t, actor, critic, moments, dtype)
+    nbytes = algorithmic_bytes(t, actor, critic, moments, dtype) + (0 if table is None else table.numel() * 4)
     src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
     dst = torch.empty_like(src)
     variants = {"fused": fused, "eager": eager, "copy": lambda: dst.copy_(src)}      # the copy moves nbytes: half read, half written
@@ -135,6 +154,22 @@ def bench_variant(sim, t, name, actor, critic, moments, dtype, args):
     return res
 
 
+def bench_norm_update(sim, name, moments, args):
+    """hs_obs_norm_update over `moments` [K, 593], enqueued on the current stream: ms per call."""
+    norm = P.ObsNormaliser(sim.gpu_id)
+    stream = torch.cuda.current_stream()
+
+    def update():
+        norm.update(sim, moments, stream=stream)
+    for _ in range(5):
+        update()
+    ts = [window(update, args.calls) for _ in range(args.rounds)]
+    res = {"variant": name, "num_moments": int(moments.shape[0]),
+           "fused": {"ms": statistics.median(ts), "ms_windows": ts, "spread_ms": max(ts) - min(ts), "calls_per_window": args.calls}}
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worlds", type=int, default=16000)
@@ -153,6 +188,13 @@ def main():
         for c in cases:
             r = bench_variant(sim, t, f"{agents}+{agents}/{c[0]}", *c[1:], args)
             results.append(r)
+        mom = sim.pack_policy_inputs(moments=True)["moments"]
+        norm = P.ObsNormaliser(0, decay=0.9)
+        norm.update(sim, mom)
+        for c in (("actor_critic_bf16_normalised", True, True, False, bf16), ("actor_critic_bf16_normalised_moments", True, True, True, bf16)):
+            results.append(bench_variant(sim, t, f"{agents}+{agents}/{c[0]}", *c[1:], args, table=norm.table))
+        for k in (1, 40):
+            results.append(bench_norm_update(sim, f"{agents}+{agents}/norm_update_{k}", mom.repeat(k, 1), args))
         sim.close()
     meta = {"device": torch.cuda.get_device_name(0), "worlds": args.worlds, "calls_per_window": args.calls, "rounds": args.rounds}
     if args.json:
