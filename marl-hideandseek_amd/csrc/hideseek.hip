@@ -650,6 +650,8 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
         for (int k = 0; k < hs::kBalanceCols; ++k) s->bal_cols.base[k + 1] = s->bal_cols.base[k] + rows[k];
         s->col_slots = NP;
         s->col_arena_bytes = (size_t)s->bal_cols.base[hs::kBalanceCols] * NP * 4;
+        // (k_observe's staging copy addresses the arena by 32-bit byte offsets from its first column, S.bpos)
+        if (s->col_arena_bytes >> 32) return fail(HS_ERR_INVALID_ARG, "hs_create: num_worlds too large, the tiled columns would take 4 GiB or more");
         char *arena, *tmp;
         HS_ALLOC(arena, s->col_arena_bytes); HS_ALLOC(tmp, s->col_arena_bytes);
         s->col_arena = arena; s->bal_tmp = tmp;

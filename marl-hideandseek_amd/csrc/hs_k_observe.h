@@ -42,13 +42,17 @@ HSD RayId ray_id(int r, int visBase) {
     return {rr >> 4, 30 + (rr & 15)};
 }
 
-template <int NT>
-struct ObsShared {
-    static constexpr int kMaxRays = NT, kAgents = obs_max_agents(NT);
+// What stage_world copies from the tiled columns: the first part of ObsShared, the same for every NT.
+struct ObsStaged {
     WorldGeom g;
     float lin[kNumDSlots][3];
     float ang[kNumDSlots][3];
     int grab[kMaxAgents];
+};
+
+template <int NT>
+struct ObsShared : ObsStaged {
+    static constexpr int kMaxRays = NT, kAgents = obs_max_agents(NT);
     float rayD[kMaxRays][3];
     unsigned long long rayKey[kMaxRays];
     // (ray, hull) pairs that survive the bounding-sphere cull, ray << 5 | body slot: every wave of pass 1 fills its own
@@ -58,8 +62,8 @@ struct ObsShared {
     unsigned short rampPairs[kWaves][kWaveRampPairs];
     int nPairs[kWaves], nRampPairs[kWaves];
     unsigned present;                                      // bit b: body slot b exists
-    // per (agent, body slot), shared by the agent's 46 rays: origin - body position, |.|^2 - bounding radius^2, and
-    // the origin in the body's frame
+    // per (agent, OTHER body slot), shared by the agent's 46 rays: origin - body position, |.|^2 - bounding radius^2, and
+    // the origin in the body's frame.  An agent's own row is never written or used.
     alignas(16) float rel[kAgents][kNumDSlots][8];
     float fwd[kAgents][3], right[kAgents][3];              // the agents' forward / right axes
 };
@@ -69,26 +73,103 @@ HSD void store_posvel(float *o, V3 p, V3 e, V3 l, V3 a) {
     o[6] = l.x; o[7] = l.y; o[8] = l.z; o[9] = a.x; o[10] = a.y; o[11] = a.z;
 }
 
-// Cooperative load of one world's geometry from the SoA columns into LDS: stage_geom (hs_rays.h) fused with the loads of
-// the velocities and the grab state (the counts come with the slot header).
+// ---- staging: one world's poses, velocities, grab state and static geometry, tiled columns -> ObsStaged ----
+// The staged columns are pieces of one arena (hideseek.hip) and a column's rows of one octet are contiguous, so with the
+// columns laid end to end in a flat word index f the source of word f is
+//     arena + K[segment of f] + f * 32 bytes,        K uniform over the workgroup (scalar registers),
+// and the segment of f is known up to a few compile-time bounds per trip of the copy loop.  The destination inside
+// ObsStaged (a transposition for most columns) comes from a constant table read beside the data.  A lane's loads are
+// all issued before its first LDS store.
+struct StageSeg { int rows, inner, stride, dst; };         // source row c * inner + s -> word dst + s * stride + c of ObsStaged
+enum { kStMeta, kStPos, kStRot, kStLin, kStAng, kStWall, kStPlane, kStGrab, kStSegs };
+#define HS_ST_WORD(field) (int)(offsetof(ObsStaged, field) / 4)
+#define HS_ST_GWORD(field) (int)((offsetof(ObsStaged, g) + offsetof(WorldGeom, field)) / 4)
+constexpr StageSeg kStageSegs[kStSegs] = {
+    {kNumDSlots, kNumDSlots, 1, HS_ST_GWORD(meta)},         // (first: its lanes also give `present`, all in wave 0)
+    {3 * kNumDSlots, kNumDSlots, 3, HS_ST_GWORD(pos)},
+    {4 * kNumDSlots, kNumDSlots, 4, HS_ST_GWORD(rot)},
+    {3 * kNumDSlots, kNumDSlots, 3, HS_ST_WORD(lin)},
+    {3 * kNumDSlots, kNumDSlots, 3, HS_ST_WORD(ang)},
+    {4 * kMaxWalls, kMaxWalls, 4, HS_ST_GWORD(wall)},
+    {4 * kMaxPlanes, kMaxPlanes, 4, HS_ST_GWORD(plane)},
+    {kMaxAgents, kMaxAgents, 1, HS_ST_WORD(grab)},
+};
+constexpr int stage_seg_start(int k) { int f = 0; for (int j = 0; j < k; ++j) f += kStageSegs[j].rows; return f; }
+constexpr int stage_seg_of(int f) { int k = 0; while (k + 1 < kStSegs && stage_seg_start(k + 1) <= f) ++k; return k; }
+constexpr int kStageWords = stage_seg_start(kStSegs);
+constexpr int kStagedWords = (int)(sizeof(ObsStaged) / 4);
+struct StageTable { unsigned short dst[kStageWords]; };    // byte offset inside ObsStaged of flat word f
+constexpr StageTable make_stage_table() {
+    StageTable t = {};
+    int f = 0;
+    for (int k = 0; k < kStSegs; ++k)
+        for (int r = 0; r < kStageSegs[k].rows; ++r)
+            t.dst[f++] = (unsigned short)((kStageSegs[k].dst + (r % kStageSegs[k].inner) * kStageSegs[k].stride + r / kStageSegs[k].inner) * 4);
+    return t;
+}
+// every word of ObsStaged is written exactly once, but the two counts, which come with the slot header
+constexpr bool stage_table_covers() {
+    const StageTable t = make_stage_table();
+    int hits[kStagedWords] = {};
+    for (int f = 0; f < kStageWords; ++f) {
+        if (t.dst[f] % 4 != 0 || t.dst[f] / 4 >= kStagedWords) return false;
+        ++hits[t.dst[f] / 4];
+    }
+    for (int w = 0; w < kStagedWords; ++w)
+        if (hits[w] != (w == HS_ST_GWORD(numWalls) || w == HS_ST_GWORD(numPlanes) ? 0 : 1)) return false;
+    return true;
+}
+static_assert(stage_table_covers(), "the staging table must write every staged word of ObsStaged exactly once");
+static_assert(kStageWords == kNumDSlots + 3 * (3 * kNumDSlots) + 4 * kNumDSlots + 4 * kMaxWalls + 4 * kMaxPlanes + kMaxAgents,
+              "the staging table moves the words of the per-column loops it replaced");
+static_assert(kStagedWords == kStageWords + 2 && sizeof(ObsStaged) % 4 == 0, "ObsStaged holds the staged words and the two counts");
+// (a segment's source rows are 0 .. rows - 1 of its column)
+static_assert(kStageSegs[kStMeta].rows == decltype(SimState::bmeta)::kRows && kStageSegs[kStPos].rows == decltype(SimState::bpos)::kRows &&
+              kStageSegs[kStRot].rows == decltype(SimState::brot)::kRows && kStageSegs[kStLin].rows == decltype(SimState::blin)::kRows &&
+              kStageSegs[kStAng].rows == decltype(SimState::bang)::kRows && kStageSegs[kStWall].rows == decltype(SimState::walls)::kRows &&
+              kStageSegs[kStPlane].rows == decltype(SimState::planes)::kRows && kStageSegs[kStGrab].rows == decltype(SimState::grabOther)::kRows,
+              "every staged source row lies inside its column");
+#undef HS_ST_WORD
+#undef HS_ST_GWORD
+__device__ const StageTable kStageTable = make_stage_table();
+
+// Returns, in wave 0, the mask of the body slots that exist (meta != 0).
 template <int NT>
-HSD void stage_world(const SimState &S, int ps, ObsShared<NT> &sh, int tid) {
-    for (int i = tid; i < kNumDSlots; i += NT) sh.g.meta[i] = S.bmeta(i, ps);
-    for (int i = tid; i < kNumDSlots * 3; i += NT) {
-        int c = i / kNumDSlots, s = i % kNumDSlots;
-        sh.g.pos[s][c] = S.bpos(c * kNumDSlots + s, ps);
-        sh.lin[s][c] = S.blin(c * kNumDSlots + s, ps);
-        sh.ang[s][c] = S.bang(c * kNumDSlots + s, ps);
+HSD unsigned stage_world(const SimState &S, int ps, ObsShared<NT> &sh, int tid) {
+    typedef unsigned __attribute__((may_alias)) word_t;
+    // S.bpos is the arena's first column, and hs_create refuses an arena of 4 GiB or more: byte offsets fit 32 bits
+    const char *const arena = reinterpret_cast<const char *>(S.bpos.p);
+    const void *const cols[kStSegs] = {S.bmeta.p, S.bpos.p, S.brot.p, S.blin.p, S.bang.p, S.walls.p, S.planes.p, S.grabOther.p};
+    unsigned K[kStSegs];
+#pragma unroll
+    for (int k = 0; k < kStSegs; ++k)
+        K[k] = (unsigned)(reinterpret_cast<const char *>(cols[k]) - arena) +
+               (((unsigned)(ps >> 3) * kStageSegs[k].rows - stage_seg_start(k)) * kTile + (ps & 7)) * 4u;
+    constexpr int kTrips = (kStageWords + NT - 1) / NT;
+    unsigned v[kTrips], d[kTrips];
+#pragma unroll
+    for (int t = 0; t < kTrips; ++t) {
+        const int f = tid + t * NT;
+        // (the bounds of the segments that trip t crosses are compile-time constants: one select each)
+        const int lo = t * NT, hi = (t + 1) * NT < kStageWords ? (t + 1) * NT - 1 : kStageWords - 1;
+        unsigned k = K[stage_seg_of(lo)];
+#pragma unroll
+        for (int s = 1; s < kStSegs; ++s)
+            if (stage_seg_start(s) > lo && stage_seg_start(s) <= hi) k = f >= stage_seg_start(s) ? K[s] : k;
+        v[t] = 0; d[t] = 0;
+        if ((t + 1) * NT <= kStageWords || f < kStageWords) {
+            v[t] = *reinterpret_cast<const word_t *>(arena + (size_t)(k + (unsigned)f * (kTile * 4u)));
+            d[t] = kStageTable.dst[f];
+        }
     }
-    for (int i = tid; i < kNumDSlots * 4; i += NT) {
-        int c = i / kNumDSlots, s = i % kNumDSlots;
-        sh.g.rot[s][c] = S.brot(c * kNumDSlots + s, ps);
-    }
-    // (all 36 wall rows and 3 plane rows are fetched whatever the counts are: no load waits for another one)
-    for (int i = tid; i < 4 * kMaxWalls; i += NT) sh.g.wall[i % kMaxWalls][i / kMaxWalls] = S.walls(i, ps);
-    for (int i = tid; i < 4 * kMaxPlanes; i += NT) sh.g.plane[i % kMaxPlanes][i / kMaxPlanes] = S.planes(i, ps);
-    for (int i = tid; i < kMaxAgents; i += NT) sh.grab[i] = S.grabOther(i, ps);
+    static_assert(kStageSegs[kStMeta].rows <= 64 && stage_seg_start(kStMeta) == 0, "the metas are staged by wave 0 in its first trip");
+    const unsigned present = (unsigned)__ballot(tid < kNumDSlots && v[0] != 0);
+    char *const dst = reinterpret_cast<char *>(static_cast<ObsStaged *>(&sh));
+#pragma unroll
+    for (int t = 0; t < kTrips; ++t)
+        if ((t + 1) * NT <= kStageWords || tid + t * NT < kStageWords) *reinterpret_cast<word_t *>(dst + d[t]) = v[t];
     if (tid < NT / 64) { sh.nPairs[tid] = 0; sh.nRampPairs[tid] = 0; }
+    return present;
 }
 
 HSD unsigned long long ray_key(float t, int id) { return ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)id; }
@@ -120,10 +201,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
     const RayId myRay = ray_id(tid, visBase);
     float lidarS = 0.f, lidarC = 0.f;
     if (tid < visBase) { lidarS = S.lidarSinCos[myRay.k]; lidarC = S.lidarSinCos[30 + myRay.k]; }
-    stage_world<NT>(S, p, sh, tid);
+    const unsigned present = stage_world<NT>(S, p, sh, tid);
     const int w = hdr.x;
     if (w < 0) return;                                   // (empty slot of the last octet)
-    if (tid == 0) { sh.g.numWalls = hdr.y & 255; sh.g.numPlanes = (hdr.y >> 8) & 255; sh.present = 0; }
+    if (tid == 0) { sh.g.numWalls = hdr.y & 255; sh.g.numPlanes = (hdr.y >> 8) & 255; sh.present = present; }
     const int counts = hdr.z;
     const int teams = hdr.w;
     const int step = hdr.y >> 16;
@@ -131,11 +212,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
     const WorldGeom &g = sh.g;
     const int nAgents = cnt_agents(counts), nBoxes = cnt_boxes(counts), nRamps = cnt_ramps(counts);
     HS_OTICK(0)
-    for (int item = tid; item < nAgents * kNumDSlots; item += NT) {
-        const int i = item / kNumDSlots, b = item % kNumDSlots;
+    // items: (agent, other body).  An agent's own row is never read (the cull skips the agent's own hull, pass 2 reads
+    // the rows of listed pairs only), so it has no item: 4 agents fill exactly one wave.
+    static_assert(kNumDSlots - 1 == 16 && ObsShared<NT>::kAgents * 16 <= NT - 8, "item = agent * 16 + other body; the last 8 lanes have no item");
+    for (int item = tid; item < nAgents * 16; item += NT) {
+        const int i = item >> 4, ob = item & 15;
+        const int b = ob + (ob >= kAgentSlot0 + i ? 1 : 0);
         const int m = g.meta[b];
         if (m == 0) continue;
-        if (i == 0) atomicOr(&sh.present, 1u << b);
         const V3 mo = g.g_pos(kAgentSlot0 + i) - g.g_pos(b);
         const V3 ol = qrot(qinv(g.g_rot(b)), mo);
         float *e = sh.rel[i][b];                               // (the row of PixelView::set_hull, hs_k_render.h)

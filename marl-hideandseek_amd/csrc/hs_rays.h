@@ -30,7 +30,7 @@ struct WorldGeom {
 };
 
 // Cooperative load of world w, which lives in slot ps of the SoA columns, into LDS by nt threads (k_observe's
-// stage_world is the same fused with the velocity loads).
+// stage_world moves the same words, and the velocities, as one table-driven copy).
 HSD void stage_geom(const SimState &S, int ps, int w, WorldGeom &g, int tid, int nt) {
     for (int i = tid; i < kNumDSlots; i += nt) g.meta[i] = S.bmeta(i, ps);
     for (int i = tid; i < kNumDSlots * 3; i += nt) g.pos[i % kNumDSlots][i / kNumDSlots] = S.bpos(i, ps);
