@@ -463,6 +463,73 @@ typedef struct hs_ppo_request {
 int32_t hs_ppo_loss(hs_sim *sim, const hs_ppo_request *req);
 int32_t hs_ppo_loss_async(hs_sim *sim, void *hip_stream, const hs_ppo_request *req);
 
+/* The two-hot symlog critic head: the value leg of a learner whose critic emits a categorical distribution over B bins
+ * in symlog space, as the reference trains it (scripts/jax_train.py:164 dreamer_v3_critic, scripts/jax_policy.py:369
+ * DreamerV3Critic).  The reference's own arithmetic lives in madrona_learn, which is not part of its tree; this contract
+ * is the project's own, after Hafner et al. 2023 (DreamerV3, first version: the expectation is taken in symlog space and
+ * then decoded).  Over n samples (n is free, as for hs_ppo_loss) one kernel (csrc/hs_k_twohot.h) reads the B logits of a
+ * sample once and writes the decoded value and, with returns, the gradient of the cross-entropy against the two-hot
+ * target and the sums behind the value statistics.  Without returns the call is the rollout's decode.
+ * The arithmetic is the contract.  Narrow logits are widened to f32 exactly; everything is IEEE f32, unfused, in exactly
+ * this order; expf / logf / expm1f / log1pf are the accurate library functions.  B = bins, l_i the logits of a sample:
+ *   step = (hi - lo) / (float)(B - 1);       b_i = lo + (float)i * step
+ *   m = max_i l_i;   d_i = l_i - m;   e_i = expf(d_i)
+ *   S = sum_i e_i;   Y = sum_i (e_i * b_i)      both in this order: lane h of 8 adds its bins h, h + 8, h + 16, ... in
+ *                                               ascending order onto 0; the 8 partials p_h are combined as
+ *                                               ((p_0 + p_1) + (p_2 + p_3)) + ((p_4 + p_5) + (p_6 + p_7))
+ *   rS = 1.0f / S;   y = Y * rS;      v = copysignf(expm1f(fabsf(y)), y)                  the decoded value
+ * and with returns R:
+ *   z  = copysignf(log1pf(fabsf(R)), R);   zc = fminf(fmaxf(z, lo), hi)                   (R = +-inf lands on hi / lo)
+ *   u  = (zc - lo) / step;   k = min(max((int)floorf(u), 0), B - 2);   f = fminf(fmaxf(u - (float)k, 0), 1)
+ *   logS = logf(S);   lp_j = d_j - logS
+ *   ce = -((1.0f - f) * lp_k + f * lp_{k+1})
+ *   p_i = e_i * rS;   t_k = 1.0f - f;   t_{k+1} = f;   t_i = 0 elsewhere
+ *   active = mask == null || mask != 0;   cnt = the number of active samples (counted on the device before; the
+ *   normaliser of hs_ppo_loss, so the two calls' gradients add);   w = grad_scale / (float)cnt
+ *   g_i = w * (loss_coef * (p_i - t_i));      grad_logits_i = (active && g_i != 0) ? g_i : +0
+ *   value = (active && v != 0) ? v : +0
+ * These are selects: an inactive sample gets +0 in value and in every grad_logits_i whatever bytes it holds (a NaN
+ * there reaches no output) and enters no statistic; a zero of either sign is stored as +0.  An ACTIVE sample must hold
+ * finite logits and a return that is not NaN: nothing checks that on the device, and the sample's outputs and the
+ * statistics are unspecified otherwise.  The same bits come out on every call, at every position of the sample in the
+ * batch, and whichever path (16-byte or element accesses) its bytes take.  value is rounded to value_dtype and
+ * grad_logits to grad_dtype to nearest even; only columns 0 .. B-1 of a row of grad_stride elements are written.  With
+ * cnt == 0 every output is +0.
+ * stats [HS_TWOHOT_STATS] f64, sums over the active samples in f64 of the f32 per-sample values: [0] = sum ce,
+ * [1] = sum ((double)v - (double)R)^2, [2] = sum v, [3] = sum R, [4] = sum (double)R^2, [5] = cnt.  Summed without
+ * atomics in an order that depends on n alone.  The gradients are those of loss = grad_scale * loss_coef * stats[0] / cnt
+ * (loss_coef is the value_loss_coef of the reference's learner).
+ * The count and the partial sums go through a workspace of the handle: two calls on one handle must not overlap (a
+ * call of hs_ppo_loss may: the workspaces are separate).  value, grad_logits and stats may each be null, not all three;
+ * only what is requested is written.  Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing
+ * written, hs_last_error says which): a null request or null logits; every output null; grad_logits or stats without
+ * returns; an unknown dtype; bins outside [2, HS_TWOHOT_MAX_BINS]; a stride below bins; lo, hi, loss_coef or grad_scale
+ * not finite, or lo >= hi; n < 1 or n * stride >= 2^31; a pointer not aligned to its element size (stats: 8 bytes); an
+ * output range that overlaps an input range or another output; a call before hs_init or inside an open step.  It reads
+ * no export and writes no simulator state.  hs_twohot_value is ordered after the device's legacy default stream and
+ * blocking; hs_twohot_value_async enqueues on the caller's hipStream_t without synchronising. */
+enum { HS_TWOHOT_STATS = 6, HS_TWOHOT_MAX_BINS = 256 };
+typedef struct hs_twohot_request {
+    const void    *logits;        /* [n][logits_stride] of logits_dtype: the critic's logits over the bins */
+    const float   *returns;       /* [n] f32, or null = decode only (value alone may then be requested) */
+    const float   *mask;          /* [n] f32 (self_mask: 1.0 / 0.0), or null = all active */
+    int32_t n;                    /* samples, n >= 1 and n * stride < 2^31 */
+    int32_t logits_dtype;         /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t logits_stride;        /* elements, >= bins */
+    int32_t bins;                 /* B in [2, HS_TWOHOT_MAX_BINS]; 255 in the reference's configuration */
+    float lo, hi;                 /* the first and the last bin in symlog space, finite, lo < hi; -20, 20 */
+    float loss_coef, grad_scale;  /* finite */
+    int32_t value_dtype;          /* of value */
+    int32_t grad_dtype;           /* of grad_logits */
+    int32_t grad_stride;          /* elements, >= bins */
+    int32_t reserved;             /* ignored */
+    void   *value;                /* [n] of value_dtype, or null */
+    void   *grad_logits;          /* [n][grad_stride] of grad_dtype, or null */
+    double *stats;                /* [HS_TWOHOT_STATS] f64, or null */
+} hs_twohot_request;              /* 96 bytes */
+int32_t hs_twohot_value(hs_sim *sim, const hs_twohot_request *req);
+int32_t hs_twohot_value_async(hs_sim *sim, void *hip_stream, const hs_twohot_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

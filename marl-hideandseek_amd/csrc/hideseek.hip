@@ -25,6 +25,7 @@
 #include "hs_k_sample.h"
 #include "hs_k_gae.h"
 #include "hs_k_ppo.h"
+#include "hs_k_twohot.h"
 #include "hs_k_norm.h"
 #include "hs_solver.h"
 
@@ -82,6 +83,8 @@ struct hs_sim {
     double *gae_partials = nullptr;        // hs_compute_gae: the moments of each workgroup, [gae_grid][HS_GAE_MOMENTS]
     double *ppo_partials = nullptr;        // hs_ppo_loss: the statistics of each workgroup, [kPpoMaxGrid][HS_PPO_STATS]
     int32_t *ppo_counts = nullptr;         // hs_ppo_loss: the active samples each workgroup of k_ppo_count saw, [kPpoCountGrid]
+    double *twohot_partials = nullptr;     // hs_twohot_value: the statistics of each workgroup, [kTwMaxGrid][HS_TWOHOT_STATS]
+    int32_t *twohot_counts = nullptr;      // hs_twohot_value: its own counts of k_ppo_count, [kPpoCountGrid]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -583,6 +586,80 @@ int launch_pack_norm(hs_sim *s, hipStream_t strm, const hs_pack_request *r, cons
 }
 }  // namespace
 
+// ---- the two-hot symlog critic head (hs_k_twohot.h); after the launchers above, so that their kernels are instantiated in the same order as before ----
+namespace {
+static_assert(HS_TWOHOT_STATS == hs::kTwStats && HS_TWOHOT_MAX_BINS == hs::kTwMaxBins, "hs_twohot_request and k_twohot agree");
+static_assert(sizeof(hs_twohot_request) == 96 && offsetof(hs_twohot_request, n) == 24 && offsetof(hs_twohot_request, bins) == 36 &&
+              offsetof(hs_twohot_request, lo) == 40 && offsetof(hs_twohot_request, value_dtype) == 56 && offsetof(hs_twohot_request, value) == 72 &&
+              offsetof(hs_twohot_request, stats) == 88, "hs_twohot_request layout (gpu_hideseek/value_head.py mirrors it)");
+
+int check_twohot(hs_sim *s, const hs_twohot_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: null request");
+    if (!r->logits) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: null logits");
+    if (!r->value && !r->grad_logits && !r->stats) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: every output is null");
+    if (!r->returns && (r->grad_logits || r->stats)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: grad_logits or stats without returns");
+    if (!pack_dtype_ok(r->logits_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: logits dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->value && !pack_dtype_ok(r->value_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: value dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->grad_logits && !pack_dtype_ok(r->grad_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: grad dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (r->bins < 2 || r->bins > HS_TWOHOT_MAX_BINS) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: bins must be in [2, HS_TWOHOT_MAX_BINS]");
+    const int B = r->bins;
+    if (r->logits_stride < B) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: logits_stride is below bins");
+    if (r->grad_logits && r->grad_stride < B) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: grad_stride is below bins");
+    if (!std::isfinite(r->lo) || !std::isfinite(r->hi) || !(r->lo < r->hi)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: lo and hi must be finite and lo < hi");
+    if (!std::isfinite(r->loss_coef) || !std::isfinite(r->grad_scale)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: loss_coef and grad_scale must be finite");
+    if (r->n < 1 || (int64_t)r->n * r->logits_stride >= (int64_t)1 << 31 || (r->grad_logits && (int64_t)r->n * r->grad_stride >= (int64_t)1 << 31))
+        return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: n must be at least 1 and n * stride below 2^31");
+    const uintptr_t lsize = r->logits_dtype == HS_DTYPE_F32 ? 4u : 2u, gsize = r->grad_dtype == HS_DTYPE_F32 ? 4u : 2u, vsize = r->value_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if (((uintptr_t)r->returns | (uintptr_t)r->mask) & 3u) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: returns and mask must be 4-byte aligned");
+    if (((uintptr_t)r->logits & (lsize - 1)) || (r->grad_logits && ((uintptr_t)r->grad_logits & (gsize - 1))) || (r->value && ((uintptr_t)r->value & (vsize - 1))))
+        return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: logits, grad_logits and value must be aligned to their element size");
+    if ((uintptr_t)r->stats & 7u) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: stats must be 8-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange in[] = {range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + B) * lsize), range("returns", r->returns, n * 4),
+                           range("mask", r->mask, n * 4)};
+    const GaeRange out[] = {range("value", r->value, r->value ? n * vsize : 0),
+                            range("grad_logits", r->grad_logits, r->grad_logits ? ((n - 1) * (uintptr_t)r->grad_stride + B) * gsize : 0),
+                            range("stats", r->stats, HS_TWOHOT_STATS * sizeof(double))};
+    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
+        for (const GaeRange &x : in)
+            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_twohot_value: ") + out[i].name + " overlaps " + x.name);
+        for (size_t j = 0; j < i; ++j)
+            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_twohot_value: ") + out[i].name + " overlaps " + out[j].name);
+    }
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value inside an open step");
+    return HS_OK;
+}
+
+// With a mask the count of the active samples, then one k_twohot over the samples (the request has passed
+// check_twohot), then the fixed-order sum of the statistics.
+int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
+    hs::TwohotArgs a = {};
+    a.logits = r->logits; a.returns = r->returns; a.mask = r->mask; a.value = r->value; a.gradLogits = r->grad_logits;
+    a.partials = r->stats ? s->twohot_partials : nullptr; a.counts = s->twohot_counts;
+    a.n = r->n; a.stride = r->logits_stride; a.gradStride = r->grad_stride; a.B = r->bins; a.countParts = hs::ppo_count_grid(a.n);
+    a.lo = r->lo; a.hi = r->hi; a.lossCoef = r->loss_coef; a.gradScale = r->grad_scale;
+    const dim3 grid(hs::twohot_grid(a.n)), blk(hs::kTwThreads);
+    if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), dim3(hs::kPpoThreads), 0, strm, r->mask, a.n, s->twohot_counts);
+    auto with_logits = [&](auto tl) {
+        with_ppo_type(r->grad_logits, r->grad_dtype, [&](auto tg) {
+            with_ppo_type(r->value, r->value_dtype, [&](auto tv) {
+                hipLaunchKernelGGL((hs::k_twohot<decltype(tl), decltype(tg), decltype(tv)>), grid, blk, 0, strm, a);
+            });
+        });
+    };
+    if (r->logits_dtype == HS_DTYPE_F32) with_logits(float{});
+    else if (r->logits_dtype == HS_DTYPE_BF16) with_logits(hs::SampleBf16{});
+    else with_logits(hs::SampleF16{});
+    if (r->stats)
+        hipLaunchKernelGGL(hs::k_twohot_stats_sum<>, dim3(1), dim3(hs::kTwStats * hs::kTwSumSegs), 0, strm, (const double *)s->twohot_partials,
+                           hs::twohot_grid(a.n), r->stats);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -684,6 +761,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
     HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
     HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
+    HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1052,6 +1130,21 @@ int32_t hs_ppo_loss(hs_sim *s, const hs_ppo_request *req) {
     HS_TRY(check_ppo(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_ppo(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- the two-hot symlog critic head (hs_k_twohot.h; check_twohot / launch_twohot above) ----
+int32_t hs_twohot_value_async(hs_sim *s, void *hip_stream, const hs_twohot_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_twohot(s, req));
+    return launch_twohot(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_twohot_value(hs_sim *s, const hs_twohot_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_twohot(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_twohot(s, s->stream, req));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

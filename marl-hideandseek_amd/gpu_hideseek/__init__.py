@@ -214,6 +214,27 @@ class HideAndSeekSimulator:
                                  value_loss_coef=value_loss_coef, entropy_coef=entropy_coef, grad_scale=grad_scale,
                                  grad_logits=grad_logits, grad_value=grad_value, stats=stats, grad_dtype=grad_dtype)
 
+    def value_head(self, logits, returns=None, *, bins=255, lo=-20.0, hi=20.0, mask=None, value=True, grad_logits=None, stats=None,
+                   loss_coef=1.0, grad_scale=1.0, grad_dtype=None, value_dtype=None, stream=None):
+        """The two-hot symlog critic head in one kernel (gpu_hideseek.value_head; hs_twohot_value, whose header comment
+        states the arithmetic: IEEE f32 in a fixed order).  Over the n = logits.shape[0] samples: `logits`
+        [n, W >= bins] (float32, bfloat16 or float16, contiguous in the last dimension: pass logits.detach()) are the
+        critic's logits over `bins` bins from `lo` to `hi` in symlog space.  value = symexp(softmax(logits) . bins), the
+        decoded value.  With `returns` [n] float32 also grad_logits, the gradient of
+        grad_scale * loss_coef * (the mean over the active samples of the cross-entropy against the two-hot target of
+        symlog(returns)), and stats [6] float64 (value_head.stats_to_metrics).  `mask` [n] float32 or None marks the
+        active samples; an inactive one gets a value and gradients of exactly 0, and the count that divides is the one
+        ppo_loss divides by, so the two gradients add.  Each output is True (allocated: value in `value_dtype` and
+        grad_logits in `grad_dtype`, by default the logits' dtype), a preallocated tensor (for value a slot buf[t] of a
+        [T, rows] buffer will do) or None; value defaults to True, grad_logits and stats to True exactly when returns
+        are given.  Active samples must hold finite logits and returns that are not NaN.  stream=None blocks; a
+        torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {name: tensor} of what was
+        written, plus "coefficients" for value_head.attach."""
+        from . import value_head as _value_head
+        return _value_head.compute(self, logits, returns, stream, bins=bins, lo=lo, hi=hi, mask=mask, value=value,
+                                   grad_logits=grad_logits, stats=stats, loss_coef=loss_coef, grad_scale=grad_scale,
+                                   grad_dtype=grad_dtype, value_dtype=value_dtype)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

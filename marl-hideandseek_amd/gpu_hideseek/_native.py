@@ -110,6 +110,10 @@ def load():
     L.hs_ppo_loss.restype = C.c_int32
     L.hs_ppo_loss_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]             # (sim, hipStream_t, request)
     L.hs_ppo_loss_async.restype = C.c_int32
+    L.hs_twohot_value.argtypes = [C.c_void_p, C.c_void_p]                       # (sim, const hs_twohot_request *)
+    L.hs_twohot_value.restype = C.c_int32
+    L.hs_twohot_value_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]         # (sim, hipStream_t, request)
+    L.hs_twohot_value_async.restype = C.c_int32
     L.hs_trigger_reset.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.hs_trigger_reset.restype = C.c_int32
     L.hs_set_action.argtypes = [C.c_void_p] + [C.c_int32] * 6

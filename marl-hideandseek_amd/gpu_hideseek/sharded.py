@@ -182,6 +182,16 @@ class ShardedSimulator:
                                  value_loss_coef=value_loss_coef, entropy_coef=entropy_coef, grad_scale=grad_scale,
                                  grad_logits=grad_logits, grad_value=grad_value, stats=stats, grad_dtype=grad_dtype)
 
+    def value_head(self, logits, returns=None, *, bins=255, lo=-20.0, hi=20.0, mask=None, value=True, grad_logits=None, stats=None,
+                   loss_coef=1.0, grad_scale=1.0, grad_dtype=None, value_dtype=None, stream=None):
+        """HideAndSeekSimulator.value_head per shard: `logits` has one tensor per shard, on the shard's device; a list of
+        the shards' results.  `returns`, `mask`, every output and `stream` are True / None for all shards or a list with
+        one entry per shard (value_head.compute_sharded)."""
+        from . import value_head as _value_head
+        return _value_head.compute_sharded(self, logits, returns, stream, bins=bins, lo=lo, hi=hi, mask=mask, value=value,
+                                           grad_logits=grad_logits, stats=stats, loss_coef=loss_coef, grad_scale=grad_scale,
+                                           grad_dtype=grad_dtype, value_dtype=value_dtype)
+
     def device_status(self):
         out = {}
         for s in self.shards:
