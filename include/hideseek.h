@@ -530,6 +530,88 @@ typedef struct hs_twohot_request {
 int32_t hs_twohot_value(hs_sim *sim, const hs_twohot_request *req);
 int32_t hs_twohot_value_async(hs_sim *sim, void *hip_stream, const hs_twohot_request *req);
 
+/* The entity encoder: the first layer of the reference's SimpleNet (scripts/jax_policy.py:113-161, the network
+ * make_policy selects with use_simple=True) over rows of hs_pack_policy_inputs.  Every entity of the four tables
+ *   g = 0 self (K = 45 columns, 1 entity), 1 agents (K = 14, 5), 2 boxes (K = 17, 9), 3 ramps (K = 14, 2)
+ * (columns 0, 45, 115 and 268 of the row onwards, entity j of a table at its first column + j K) goes through the
+ * table's own Dense(E), a LayerNorm and a leaky ReLU; agents, boxes and ramps are max-pooled over their entities; the
+ * results are written side by side as features [n][4 E] in the order self | agents | boxes | ramps.  One kernel
+ * (csrc/hs_k_embed.h) reads a row once and writes its features; n is free, as for hs_ppo_loss.
+ * params is one array of HS_EMBED_PARAM_ROWS * E f32: for each table in the order above W_g [K_g][E] (in-features
+ * major), then b_g [E], gamma_g [E], beta_g [E]; the tables' blocks start at rows 0, 48, 65 and 85 of E floats.
+ * The arithmetic is the contract.  Narrow rows are widened to f32 exactly; everything is IEEE f32, unfused except
+ * where fmaf is written, in exactly this order.  For entity j of table g with inputs x_0 .. x_{K-1} and channel c < E:
+ *   z_c = b_g[c];   z_c = fmaf(x_k, W_g[k][c], z_c)   for k = 0, 1, ..., K - 1
+ *   sum_c(p): lane l < L = min(E, 64) starts from p_l and, at E = 128, adds p_{l+64}; then for m = 1, 2, 4, ..., L / 2
+ *             every lane replaces its value s_l by s_l + s_{l xor m} (a butterfly: every lane ends with the same bits)
+ *   mu = sum_c(z_c) / (float)E;   d_c = z_c - mu;   var = sum_c(d_c * d_c) / (float)E
+ *   rstd = 1.0f / sqrtf(var + eps)                                  (division and sqrtf correctly rounded)
+ *   zhat_c = d_c * rstd;   y_c = fmaf(zhat_c, gamma_g[c], beta_g[c])
+ *   a_c = y_c >= 0 ? y_c : slope * y_c
+ *   features[row][g E + c] = max_j a_c(j);   argmax[row][g - 1][c] = the LOWEST j that attains it (g >= 1)
+ * and for the self table features = a_c.  features is rounded to features_dtype to nearest even.  eps = 1e-6 and
+ * slope = 0.01 are flax's defaults; the reference's LayerNorm comes from madrona_learn, which is not part of its tree,
+ * so its constants are not pinned by it.
+ * Ties: an exact tie goes to the first entity, where JAX's gradient of max splits it evenly.  Apart from coincidences
+ * entities tie because their inputs are identical (the actor's masked-out entities are all-zero rows), and for
+ * identical inputs the gradient of every parameter is the same under either rule.
+ * hs_entity_encode_backward takes the same rows and parameters, the upstream grad_features [n][4 E] and the forward's
+ * argmax, recomputes z, mu, rstd, zhat and y as above (nothing but argmax is saved) and writes grad_params
+ * [HS_EMBED_PARAM_ROWS * E] f32 in the layout of params.  No gradient with respect to the rows is computed:
+ * observations are leaves and the normaliser is not trained by gradient.  Per entity j of table g:
+ *   dy_c = (g == 0 || argmax_c == j) ? grad_features_c * (y_c >= 0 ? 1.0f : slope) : 0
+ *   h_c = gamma_c * dy_c;   mh = sum_c(h_c) / (float)E;   mhz = sum_c(h_c * zhat_c) / (float)E
+ *   dz_c = rstd * ((h_c - mh) - zhat_c * mhz)
+ *   dW[k][c] = fmaf(x_k, dz_c, dW[k][c]);   db_c = db_c + dz_c;   dgamma_c = fmaf(dy_c, zhat_c, dgamma_c);
+ *   dbeta_c = dbeta_c + dy_c
+ * An entity that no channel selected adds nothing and may be skipped.  The sums over the rows run in an order that
+ * depends on n and E alone: with R = HS_EMBED_ROWS_PER_WAVE(E) * 4 rows per round and G = min(ceil(n / R),
+ * HS_EMBED_MAX_GRID_BWD) workgroups, workgroup b takes rounds b, b + G, ...; wave w of it the rows
+ * round * R + w * R / 4 + s (s < R / 4); a lane adds its rows' terms in round order onto +0 and the entities of a row in
+ * ascending j; at E = 32 the halves s = 0, 1 are added as (s0 + s1); the waves as ((w0 + w1) + w2) + w3; the workgroups'
+ * sums go to a workspace of the handle, where HS_EMBED_SUM_SEGS segments of ceil(G / segs) consecutive workgroups are
+ * each added in ascending order onto +0 and the segments then in ascending order.  No atomics: the same inputs give the
+ * same bits on every call, and a row's features do not depend on its position, on n or on the path (16-byte or element
+ * loads) its bytes take.  grad_features all +0 gives grad_params all +0.
+ * Rows, parameters and upstream gradients must be finite: nothing checks that on the device.
+ * Two backward calls on one handle must not overlap (the workspace); forward calls may.  Everything is validated
+ * before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request, null
+ * rows or params, every output null (backward: a null grad_features, argmax or grad_params); an unknown dtype;
+ * embed_dim not 32, 64 or 128; n < 1 or n * 296 or n * 4 E >= 2^31; eps or slope not finite, or eps <= 0; a pointer not
+ * aligned to its element size (params and grad_params: 4 bytes); an output range that overlaps an input range or
+ * another output; a call before hs_init or inside an open step.  The calls read no export and write no simulator
+ * state.  The blocking forms are ordered after the device's legacy default stream; the _async forms enqueue on the
+ * caller's hipStream_t without synchronising. */
+enum { HS_EMBED_PARAM_ROWS = 102, HS_EMBED_MAX_GRID_BWD = 512, HS_EMBED_SUM_SEGS = 8 };
+#define HS_EMBED_ROWS_PER_WAVE(E) ((E) == 32 ? 2 : 1)
+typedef struct hs_entity_encode_request {
+    const void    *rows;          /* [n][HS_PACK_ROW] of rows_dtype, contiguous */
+    const float   *params;        /* [HS_EMBED_PARAM_ROWS * embed_dim] f32 */
+    int32_t n;                    /* rows, n >= 1 */
+    int32_t rows_dtype;           /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t embed_dim;            /* E: 32, 64 (the reference's) or 128 */
+    int32_t features_dtype;       /* of features */
+    float eps, slope;             /* finite, eps > 0; 1e-6, 0.01 */
+    void    *features;            /* [n][4 E] of features_dtype, or null */
+    uint8_t *argmax;              /* [n][3][E]: agents, boxes, ramps; or null */
+} hs_entity_encode_request;       /* 56 bytes */
+typedef struct hs_entity_encode_backward_request {
+    const void    *rows;          /* as in the forward call */
+    const float   *params;
+    const void    *grad_features; /* [n][4 E] of grad_dtype */
+    const uint8_t *argmax;        /* [n][3][E], what the forward call wrote */
+    int32_t n;
+    int32_t rows_dtype;
+    int32_t embed_dim;
+    int32_t grad_dtype;           /* of grad_features: HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    float eps, slope;
+    float   *grad_params;         /* [HS_EMBED_PARAM_ROWS * embed_dim] f32 */
+} hs_entity_encode_backward_request;  /* 64 bytes */
+int32_t hs_entity_encode(hs_sim *sim, const hs_entity_encode_request *req);
+int32_t hs_entity_encode_async(hs_sim *sim, void *hip_stream, const hs_entity_encode_request *req);
+int32_t hs_entity_encode_backward(hs_sim *sim, const hs_entity_encode_backward_request *req);
+int32_t hs_entity_encode_backward_async(hs_sim *sim, void *hip_stream, const hs_entity_encode_backward_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

@@ -26,6 +26,7 @@
 #include "hs_k_gae.h"
 #include "hs_k_ppo.h"
 #include "hs_k_twohot.h"
+#include "hs_k_embed.h"
 #include "hs_k_norm.h"
 #include "hs_solver.h"
 
@@ -85,6 +86,7 @@ struct hs_sim {
     int32_t *ppo_counts = nullptr;         // hs_ppo_loss: the active samples each workgroup of k_ppo_count saw, [kPpoCountGrid]
     double *twohot_partials = nullptr;     // hs_twohot_value: the statistics of each workgroup, [kTwMaxGrid][HS_TWOHOT_STATS]
     int32_t *twohot_counts = nullptr;      // hs_twohot_value: its own counts of k_ppo_count, [kPpoCountGrid]
+    float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kEmbMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -660,6 +662,115 @@ int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
 }
 }  // namespace
 
+// ---- the entity encoder (hs_k_embed.h); after the launchers above, so that their kernels are instantiated in the same order as before ----
+namespace {
+static_assert(HS_EMBED_PARAM_ROWS == hs::kEmbParamRows && HS_EMBED_MAX_GRID_BWD == hs::kEmbMaxGridBwd && HS_EMBED_SUM_SEGS == hs::kEmbSumSegs &&
+              HS_EMBED_ROWS_PER_WAVE(32) == hs::EmbCfg<32>::kSub && HS_EMBED_ROWS_PER_WAVE(64) == hs::EmbCfg<64>::kSub &&
+              HS_EMBED_ROWS_PER_WAVE(128) == hs::EmbCfg<128>::kSub, "hs_entity_encode_request and k_embed agree");
+static_assert(sizeof(hs_entity_encode_request) == 56 && offsetof(hs_entity_encode_request, n) == 16 && offsetof(hs_entity_encode_request, embed_dim) == 24 &&
+              offsetof(hs_entity_encode_request, eps) == 32 && offsetof(hs_entity_encode_request, features) == 40 &&
+              offsetof(hs_entity_encode_request, argmax) == 48, "hs_entity_encode_request layout (gpu_hideseek/entity_encoder.py mirrors it)");
+static_assert(sizeof(hs_entity_encode_backward_request) == 64 && offsetof(hs_entity_encode_backward_request, grad_features) == 16 &&
+              offsetof(hs_entity_encode_backward_request, argmax) == 24 && offsetof(hs_entity_encode_backward_request, n) == 32 &&
+              offsetof(hs_entity_encode_backward_request, grad_dtype) == 44 && offsetof(hs_entity_encode_backward_request, eps) == 48 &&
+              offsetof(hs_entity_encode_backward_request, grad_params) == 56, "hs_entity_encode_backward_request layout (gpu_hideseek/entity_encoder.py mirrors it)");
+
+int embed_type(int32_t dtype) { return dtype == HS_DTYPE_F32 ? hs::kEmbF32 : dtype == HS_DTYPE_BF16 ? hs::kEmbBf16 : hs::kEmbF16; }
+
+// What the two calls share: `fn` is the entry point's name, `other` the dtype of features / grad_features.
+int check_embed_common(hs_sim *s, const char *fn, const void *rows, const float *params, int32_t n, int32_t rows_dtype, int32_t E, float eps, float slope) {
+    const std::string f = std::string(fn) + ": ";
+    if (!rows) return fail(HS_ERR_INVALID_ARG, f + "null rows");
+    if (!params) return fail(HS_ERR_INVALID_ARG, f + "null params");
+    if (!pack_dtype_ok(rows_dtype)) return fail(HS_ERR_INVALID_ARG, f + "rows dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (E != 32 && E != 64 && E != 128) return fail(HS_ERR_INVALID_ARG, f + "embed_dim must be 32, 64 or 128");
+    if (n < 1 || (int64_t)n * HS_PACK_ROW >= (int64_t)1 << 31 || (int64_t)n * 4 * E >= (int64_t)1 << 31)
+        return fail(HS_ERR_INVALID_ARG, f + "n must be at least 1 and n * 296 and n * 4 * embed_dim below 2^31");
+    if (!std::isfinite(eps) || !std::isfinite(slope) || !(eps > 0.f)) return fail(HS_ERR_INVALID_ARG, f + "eps and slope must be finite and eps > 0");
+    (void)s;
+    return HS_OK;
+}
+
+int check_embed_state(hs_sim *s, const char *fn) {
+    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, std::string(fn) + " before hs_init");
+    if (s->step_open) return fail(HS_ERR_INVALID_ARG, std::string(fn) + " inside an open step");
+    return HS_OK;
+}
+
+int check_embed(hs_sim *s, const hs_entity_encode_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: null request");
+    HS_TRY(check_embed_common(s, "hs_entity_encode", r->rows, r->params, r->n, r->rows_dtype, r->embed_dim, r->eps, r->slope));
+    if (!r->features && !r->argmax) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: every output is null");
+    if (r->features && !pack_dtype_ok(r->features_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: features dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    const uintptr_t rsize = r->rows_dtype == HS_DTYPE_F32 ? 4u : 2u, fsize = r->features_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if ((uintptr_t)r->params & 3u) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: params must be 4-byte aligned");
+    if (((uintptr_t)r->rows & (rsize - 1)) || (r->features && ((uintptr_t)r->features & (fsize - 1))))
+        return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: rows and features must be aligned to their element size");
+    const uintptr_t n = (uintptr_t)r->n, E = (uintptr_t)r->embed_dim;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange in[] = {range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_EMBED_PARAM_ROWS * E * 4)};
+    const GaeRange out[] = {range("features", r->features, r->features ? n * 4 * E * fsize : 0), range("argmax", r->argmax, r->argmax ? n * 3 * E : 0)};
+    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
+        for (const GaeRange &x : in)
+            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_entity_encode: ") + out[i].name + " overlaps " + x.name);
+        for (size_t j = 0; j < i; ++j)
+            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_entity_encode: ") + out[i].name + " overlaps " + out[j].name);
+    }
+    return check_embed_state(s, "hs_entity_encode");
+}
+
+int check_embed_bwd(hs_sim *s, const hs_entity_encode_backward_request *r) {
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null request");
+    HS_TRY(check_embed_common(s, "hs_entity_encode_backward", r->rows, r->params, r->n, r->rows_dtype, r->embed_dim, r->eps, r->slope));
+    if (!r->grad_features) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null grad_features");
+    if (!r->argmax) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null argmax");
+    if (!r->grad_params) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null grad_params");
+    if (!pack_dtype_ok(r->grad_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: grad dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    const uintptr_t rsize = r->rows_dtype == HS_DTYPE_F32 ? 4u : 2u, gsize = r->grad_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if (((uintptr_t)r->params | (uintptr_t)r->grad_params) & 3u) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: params and grad_params must be 4-byte aligned");
+    if (((uintptr_t)r->rows & (rsize - 1)) || ((uintptr_t)r->grad_features & (gsize - 1)))
+        return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: rows and grad_features must be aligned to their element size");
+    const uintptr_t n = (uintptr_t)r->n, E = (uintptr_t)r->embed_dim;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange out = range("grad_params", r->grad_params, HS_EMBED_PARAM_ROWS * E * 4);
+    const GaeRange in[] = {range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_EMBED_PARAM_ROWS * E * 4),
+                           range("grad_features", r->grad_features, n * 4 * E * gsize), range("argmax", r->argmax, n * 3 * E)};
+    for (const GaeRange &x : in)
+        if (gae_overlap(out, x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_entity_encode_backward: grad_params overlaps ") + x.name);
+    return check_embed_state(s, "hs_entity_encode_backward");
+}
+
+template <typename F> void with_embed_dim(int32_t E, F f) {
+    if (E == 32) f(std::integral_constant<int, 32>{});
+    else if (E == 64) f(std::integral_constant<int, 64>{});
+    else f(std::integral_constant<int, 128>{});
+}
+
+// One k_embed_fwd over the rows (the request has passed check_embed).
+int launch_embed(hs_sim *, hipStream_t strm, const hs_entity_encode_request *r) {
+    hs::EmbedArgs a = {};
+    a.rows = r->rows; a.params = r->params; a.features = r->features; a.argmax = r->argmax;
+    a.n = r->n; a.rowsType = embed_type(r->rows_dtype); a.featType = embed_type(r->features_dtype); a.eps = r->eps; a.slope = r->slope;
+    const dim3 grid(hs::emb_grid(a.n, r->embed_dim, hs::kEmbMaxGrid)), blk(hs::kEmbThreads);
+    with_embed_dim(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_fwd<decltype(e)::value>), grid, blk, 0, strm, a); });
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+// k_embed_bwd into the workspace's slices, then their fixed-order sum (the request has passed check_embed_bwd).
+int launch_embed_bwd(hs_sim *s, hipStream_t strm, const hs_entity_encode_backward_request *r) {
+    hs::EmbedBwdArgs a = {};
+    a.rows = r->rows; a.params = r->params; a.gradFeatures = r->grad_features; a.argmax = r->argmax; a.workspace = s->embed_partials;
+    a.n = r->n; a.rowsType = embed_type(r->rows_dtype); a.gradType = embed_type(r->grad_dtype); a.eps = r->eps; a.slope = r->slope;
+    const int nparts = hs::emb_grid(a.n, r->embed_dim, hs::kEmbMaxGridBwd), len = hs::kEmbParamRows * r->embed_dim;
+    with_embed_dim(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_bwd<decltype(e)::value>), dim3(nparts), dim3(hs::kEmbThreads), 0, strm, a); });
+    hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
+                       (const float *)s->embed_partials, nparts, len, r->grad_params);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -762,6 +873,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
     HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
+    HS_ALLOC(s->embed_partials, (size_t)hs::kEmbMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1145,6 +1257,34 @@ int32_t hs_twohot_value(hs_sim *s, const hs_twohot_request *req) {
     HS_TRY(check_twohot(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_twohot(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- the entity encoder (hs_k_embed.h; check_embed / launch_embed above) ----
+int32_t hs_entity_encode_async(hs_sim *s, void *hip_stream, const hs_entity_encode_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_embed(s, req));
+    return launch_embed(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_entity_encode(hs_sim *s, const hs_entity_encode_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_embed(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_embed(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+int32_t hs_entity_encode_backward_async(hs_sim *s, void *hip_stream, const hs_entity_encode_backward_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_embed_bwd(s, req));
+    return launch_embed_bwd(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_entity_encode_backward(hs_sim *s, const hs_entity_encode_backward_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_embed_bwd(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_embed_bwd(s, s->stream, req));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

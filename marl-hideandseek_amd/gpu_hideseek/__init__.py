@@ -235,6 +235,28 @@ class HideAndSeekSimulator:
                                    grad_logits=grad_logits, stats=stats, loss_coef=loss_coef, grad_scale=grad_scale,
                                    grad_dtype=grad_dtype, value_dtype=value_dtype)
 
+    def encode_entities(self, rows, params, *, embed_dim=64, eps=1e-6, slope=0.01, features=True, argmax=None, dtype=None, stream=None):
+        """The entity encoder in one kernel (gpu_hideseek.entity_encoder; hs_entity_encode, whose header comment states
+        the arithmetic: IEEE f32 in a fixed order).  `rows` [n, 296] (float32, bfloat16 or float16, contiguous) are rows of
+        pack_policy_inputs; `params` the flat float32 tensor of 102 * embed_dim elements (entity_encoder.param_layout).
+        Every entity of the four tables goes through its table's Dense(embed_dim), a LayerNorm (`eps`) and a leaky ReLU
+        (`slope`); agents, boxes and ramps are max-pooled.  features [n, 4 * embed_dim] in `dtype` (by default the rows')
+        and argmax [n, 3, embed_dim] uint8 (the first entity that attains the maximum: what the backward call needs) are
+        each True (allocated), a preallocated tensor (for features a slot buf[t] of a [T, rows, 4 E] buffer will do) or
+        None.  Rows and parameters must be finite.  stream=None blocks; a torch.cuda.Stream or raw handle enqueues there
+        without synchronising.  Returns {name: tensor} of what was written."""
+        from . import entity_encoder as _enc
+        return _enc.compute(self, rows, params, stream, embed_dim=embed_dim, eps=eps, slope=slope, features=features, argmax=argmax, dtype=dtype)
+
+    def encode_entities_backward(self, rows, params, grad_features, argmax, *, embed_dim=64, eps=1e-6, slope=0.01, grad_params=True, stream=None):
+        """The gradient of the encoder's parameters in one kernel plus a fixed-order sum (hs_entity_encode_backward): from
+        the rows and parameters of the forward call, the upstream `grad_features` [n, 4 * embed_dim] (float32, bfloat16 or
+        float16) and the forward's `argmax`.  grad_params (True or a float32 tensor of 102 * embed_dim elements) has the
+        layout of params.  No gradient with respect to the rows is computed.  The same inputs give the same bits on every
+        call.  Returns {"grad_params": tensor}."""
+        from . import entity_encoder as _enc
+        return _enc.compute_backward(self, rows, params, grad_features, argmax, stream, embed_dim=embed_dim, eps=eps, slope=slope, grad_params=grad_params)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

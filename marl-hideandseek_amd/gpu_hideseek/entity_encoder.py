@@ -1,0 +1,344 @@
+"""The entity encoder: the first layer of the reference's SimpleNet (scripts/jax_policy.py:113-161) over packed
+policy-input rows, forward and parameter gradient each by one kernel (hs_entity_encode, hs_entity_encode_backward,
+csrc/hs_k_embed.h).
+
+Every entity of the four tables of a row (policy_inputs.TABLES: self [45], agents [5, 14], boxes [9, 17], ramps [2, 14])
+goes through its table's Dense(E), a LayerNorm and a leaky ReLU; agents, boxes and ramps are max-pooled over their
+entities; the results are concatenated into [rows, 4 E].  include/hideseek.h states the arithmetic, IEEE f32 in a fixed
+order.  Actor and critic run it on their rows in every rollout step and every minibatch:
+
+    enc = entity_encoder.EntityEncoder(64).cuda()                    # one flat float32 Parameter of 102 * 64 elements
+    sim.pack_policy_inputs(actor=actor_rows[t], critic=critic_rows[t])
+    feats = enc(sim, actor_rows[t])                                  # [rows, 256], part of the autograd graph
+    loss = head(feats) ...; loss.backward(); optimiser.step()        # the backward kernel hands grad_params to autograd
+
+or without autograd, into a rollout buffer:
+
+    sim.encode_entities(actor_rows[t], enc.params.detach(), features=feat_buf[t])
+
+No gradient with respect to the rows is computed: observations are leaves and the normaliser is not trained by gradient.
+A tie of the max-pool goes to the first entity (JAX splits it evenly); entities tie in practice because their inputs are
+identical (the actor's masked-out entities are all-zero rows), and then every parameter's gradient is the same either
+way.  eager() is the same composition in plain torch, for readers, tools/embed_bench.py and the tests.
+"""
+import ctypes as C
+import math
+
+from .policy_inputs import _DTYPES, ROW, TABLES, _per_shard, stream_handle
+from .ppo_loss import _name, _overlap
+
+EMBED_DIMS = (32, 64, 128)
+PARAM_ROWS = 102          # HS_EMBED_PARAM_ROWS: the sum over the tables of K + 3
+MAX_GRID_BWD = 512        # HS_EMBED_MAX_GRID_BWD: workgroups (and workspace slices) of a backward call at the most
+SUM_SEGS = 8              # HS_EMBED_SUM_SEGS
+WAVES = 4                 # waves of a workgroup
+DEFAULT_EPS, DEFAULT_SLOPE = 1e-6, 0.01      # flax's LayerNorm epsilon and leaky_relu negative_slope
+POOLED = tuple(TABLES)[1:]                   # the max-pooled tables, in the order of argmax's second axis
+
+
+def rows_per_block(E):
+    """R: the rows a workgroup takes per round (HS_EMBED_ROWS_PER_WAVE(E) * 4)."""
+    return WAVES * (2 if E == 32 else 1)
+
+
+class HsEntityEncodeRequest(C.Structure):
+    """hs_entity_encode_request (include/hideseek.h)."""
+    _fields_ = [("rows", C.c_void_p), ("params", C.c_void_p), ("n", C.c_int32), ("rows_dtype", C.c_int32), ("embed_dim", C.c_int32),
+                ("features_dtype", C.c_int32), ("eps", C.c_float), ("slope", C.c_float), ("features", C.c_void_p), ("argmax", C.c_void_p)]
+
+
+class HsEntityEncodeBackwardRequest(C.Structure):
+    """hs_entity_encode_backward_request (include/hideseek.h)."""
+    _fields_ = [("rows", C.c_void_p), ("params", C.c_void_p), ("grad_features", C.c_void_p), ("argmax", C.c_void_p), ("n", C.c_int32),
+                ("rows_dtype", C.c_int32), ("embed_dim", C.c_int32), ("grad_dtype", C.c_int32), ("eps", C.c_float), ("slope", C.c_float),
+                ("grad_params", C.c_void_p)]
+
+
+# ---- the parameters: one description, from policy_inputs.TABLES ----
+def _embed_dim(E):
+    if isinstance(E, bool) or not isinstance(E, int) or E not in EMBED_DIMS:
+        raise ValueError(f"embed_dim must be one of {EMBED_DIMS}, got {E}")
+    return E
+
+
+def param_layout(E):
+    """{table: {"kernel": (first, one past the last, (K, E)), "bias": (.., (E,)), "scale": .., "shift": ..}}: the element
+    ranges of the flat parameter tensor of PARAM_ROWS * E float32, in order: for each table of policy_inputs.TABLES the
+    Dense kernel W [K, E] (in-features major), its bias, and the LayerNorm's scale (gamma) and shift (beta)."""
+    E = _embed_dim(E)
+    out, at = {}, 0
+    for name, (_, _, shape) in TABLES.items():
+        K = shape[-1]
+        out[name] = {}
+        for part, sh in (("kernel", (K, E)), ("bias", (E,)), ("scale", (E,)), ("shift", (E,))):
+            size = math.prod(sh)
+            out[name][part] = (at, at + size, sh)
+            at += size
+    assert at == PARAM_ROWS * E
+    return out
+
+
+def views(params, E):
+    """The named zero-copy views of a flat parameter (or gradient) tensor: {table: {part: tensor}} after param_layout."""
+    if params.dim() != 1 or params.numel() != PARAM_ROWS * _embed_dim(E):
+        raise ValueError(f"params must have shape ({PARAM_ROWS * E},), got {tuple(params.shape)}")
+    return {t: {p: params[lo:hi].view(sh) for p, (lo, hi, sh) in parts.items()} for t, parts in param_layout(E).items()}
+
+
+def init_params(E, generator=None):
+    """A fresh flat float32 parameter tensor (on the CPU) as SimpleNet.embed initialises it: kernels orthogonal with gain
+    sqrt(2), biases 0, LayerNorm scale 1 and shift 0."""
+    import torch
+    p = torch.zeros(PARAM_ROWS * _embed_dim(E), dtype=torch.float32)
+    for parts in views(p, E).values():
+        torch.nn.init.orthogonal_(parts["kernel"], gain=math.sqrt(2.0), generator=generator)
+        parts["scale"].fill_(1.0)
+    return p
+
+
+def eager(rows, params, E, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE):
+    """The plain-torch composition, in float32: [n, 4 E] features of rows [n, 296].  Differentiable in params."""
+    import torch
+    from .policy_inputs import views as tables
+    feats = []
+    for name, x in tables(rows.float()).items():
+        p = views(params, E)[name]
+        y = torch.nn.functional.layer_norm(x @ p["kernel"] + p["bias"], (E,), p["scale"], p["shift"], eps)
+        a = torch.nn.functional.leaky_relu(y, slope)
+        feats.append(a if name == "self" else a.amax(dim=-2))
+    return torch.cat(feats, dim=-1)
+
+
+# ---- the fused calls ----
+def _common(gpu_id, rows, params, embed_dim, eps, slope):
+    import torch
+    dev = torch.device("cuda", gpu_id)
+    E = _embed_dim(embed_dim)
+    coefs = dict(eps=float(eps), slope=float(slope))
+    for k, v in coefs.items():
+        if not math.isfinite(v) or not math.isfinite(C.c_float(v).value):
+            raise ValueError(f"{k} must be finite, got {v}")
+    if not C.c_float(coefs["eps"]).value > 0.0:
+        raise ValueError(f"eps must be above 0, got {eps}")
+    if not isinstance(rows, torch.Tensor):
+        raise ValueError("rows must be a torch tensor")
+    what = f"rows must be a contiguous {' / '.join(_DTYPES)} tensor of shape (n >= 1, {ROW}) on {dev}"
+    if rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] != ROW:
+        raise ValueError(f"{what}: its shape is {tuple(rows.shape)}")
+    if _name(rows.dtype) not in _DTYPES:
+        raise ValueError(f"{what}: its dtype is {rows.dtype}")
+    if not rows.is_contiguous():
+        raise ValueError(f"{what}: it is not contiguous")
+    n = int(rows.shape[0])
+    if n * max(ROW, 4 * E) >= 2 ** 31:
+        raise ValueError(f"{what}: n * {max(ROW, 4 * E)} must stay below 2^31")
+    _flat("params", params, E, dev)
+    return dev, E, n, coefs
+
+
+def _flat(name, t, E, dev):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    what = f"{name} must be a contiguous float32 tensor of shape ({PARAM_ROWS * E},) on {dev}"
+    if tuple(t.shape) != (PARAM_ROWS * E,):
+        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: its dtype is {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: it is not contiguous")
+
+
+def _given(name, t, shape, dtypes, dev):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be True, None or a torch tensor")
+    what = f"{name} must be a contiguous {' / '.join(dtypes)} tensor of shape {shape} on {dev}"
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
+    if _name(t.dtype) not in dtypes:
+        raise ValueError(f"{what}: its dtype is {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: it is not contiguous")
+
+
+def _disjoint(outputs, inputs, dev):
+    for k, t in outputs:
+        for k2, t2 in inputs:
+            if _overlap(t, t2):
+                raise ValueError(f"{k} overlaps {k2}")
+    for i, (k, t) in enumerate(outputs):
+        for k2, t2 in outputs[:i]:
+            if _overlap(t, t2):
+                raise ValueError(f"{k} overlaps {k2}")
+    for k, t in inputs + outputs:
+        if t.device != dev:
+            raise ValueError(f"{k} must be on {dev}: it is on {t.device}")
+
+
+def request(gpu_id, rows, params, embed_dim=64, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, features=True, argmax=None, dtype=None):
+    """Validate a forward call over the n = rows.shape[0] rows on GPU `gpu_id`, allocate the outputs given as True
+    (features in `dtype`, by default the dtype of the rows; argmax uint8 [n, 3, E]), and return ({name: tensor},
+    HsEntityEncodeRequest).  Raises ValueError before the library is involved."""
+    import torch
+    dev, E, n, coefs = _common(gpu_id, rows, params, embed_dim, eps, slope)
+    outputs = {k: t for k, t in (("features", features), ("argmax", argmax)) if t is not None and t is not False}
+    if not outputs:
+        raise ValueError("nothing to do: neither features nor argmax requested")
+    if dtype is not None and _name(dtype) not in _DTYPES:
+        raise ValueError(f"dtype must be one of {', '.join(_DTYPES)}, got {dtype}")
+    given = {k: t for k, t in outputs.items() if t is not True}
+    if "features" in given:
+        _given("features", given["features"], (n, 4 * E), tuple(_DTYPES), dev)
+    if "argmax" in given:
+        _given("argmax", given["argmax"], (n, 3, E), ("uint8",), dev)
+    _disjoint(list(given.items()), [("rows", rows), ("params", params)], dev)
+    res = dict(given)
+    if outputs.get("features") is True:
+        res["features"] = torch.empty((n, 4 * E), dtype=rows.dtype if dtype is None else dtype, device=dev)
+    if outputs.get("argmax") is True:
+        res["argmax"] = torch.empty((n, 3, E), dtype=torch.uint8, device=dev)
+    res = {k: res[k] for k in outputs}
+    req = HsEntityEncodeRequest(rows.data_ptr(), params.data_ptr(), n, _DTYPES[_name(rows.dtype)], E,
+                                _DTYPES[_name(res["features"].dtype)] if "features" in res else 0, coefs["eps"], coefs["slope"],
+                                res["features"].data_ptr() if "features" in res else None,
+                                res["argmax"].data_ptr() if "argmax" in res else None)
+    return res, req
+
+
+def request_backward(gpu_id, rows, params, grad_features, argmax, embed_dim=64, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, grad_params=True):
+    """Validate a backward call, allocate grad_params when it is True, and return ({"grad_params": tensor},
+    HsEntityEncodeBackwardRequest).  Raises ValueError before the library is involved."""
+    import torch
+    dev, E, n, coefs = _common(gpu_id, rows, params, embed_dim, eps, slope)
+    if not isinstance(grad_features, torch.Tensor) or not isinstance(argmax, torch.Tensor):
+        raise ValueError("grad_features and argmax must be torch tensors")
+    _given("grad_features", grad_features, (n, 4 * E), tuple(_DTYPES), dev)
+    _given("argmax", argmax, (n, 3, E), ("uint8",), dev)
+    inputs = [("rows", rows), ("params", params), ("grad_features", grad_features), ("argmax", argmax)]
+    if grad_params is True:
+        _disjoint([], inputs, dev)
+        grad_params = torch.empty(PARAM_ROWS * E, dtype=torch.float32, device=dev)
+    else:
+        _flat("grad_params", grad_params, E, dev)
+        _disjoint([("grad_params", grad_params)], inputs, dev)
+    req = HsEntityEncodeBackwardRequest(rows.data_ptr(), params.data_ptr(), grad_features.data_ptr(), argmax.data_ptr(), n,
+                                        _DTYPES[_name(rows.dtype)], E, _DTYPES[_name(grad_features.dtype)], coefs["eps"], coefs["slope"],
+                                        grad_params.data_ptr())
+    return {"grad_params": grad_params}, req
+
+
+def _run(sim, fn, req, stream):
+    from ._native import check
+    if stream is None:
+        check(getattr(sim._L, fn)(sim._h, C.byref(req)))
+    else:
+        check(getattr(sim._L, fn + "_async")(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+
+
+def compute(sim, rows, params, stream=None, **kw):
+    """HideAndSeekSimulator.encode_entities."""
+    res, req = request(sim.gpu_id, rows, params, **kw)
+    _run(sim, "hs_entity_encode", req, stream)
+    return res
+
+
+def compute_backward(sim, rows, params, grad_features, argmax, stream=None, **kw):
+    """HideAndSeekSimulator.encode_entities_backward."""
+    res, req = request_backward(sim.gpu_id, rows, params, grad_features, argmax, **kw)
+    _run(sim, "hs_entity_encode_backward", req, stream)
+    return res
+
+
+def _sharded(ssim, fn, make, stream):
+    import torch
+    streams = _per_shard(ssim, "stream", stream)
+    reqs = [make(i, s) for i, s in enumerate(ssim.shards)]
+    waits = []
+    for s, (res, req), st in zip(ssim.shards, reqs, streams):
+        if st is None:
+            st = torch.cuda.Stream(device=s.gpu_id)
+            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
+            waits.append(st)
+        _run(s, fn, req, st)
+    for st in waits:
+        st.synchronize()
+    return [res for res, _ in reqs]
+
+
+def _shard_params(ssim, params):
+    import torch
+    return [params] * len(ssim.shards) if isinstance(params, torch.Tensor) else _per_shard(ssim, "params", params)
+
+
+def _shard_list(ssim, name, arg):
+    import torch
+    if isinstance(arg, torch.Tensor) or arg is None or len(arg) != len(ssim.shards):
+        raise ValueError(f"{name}: one tensor per shard ({len(ssim.shards)}) expected")
+    return list(arg)
+
+
+def compute_sharded(ssim, rows, params, stream=None, features=True, argmax=None, **kw):
+    """ShardedSimulator.encode_entities: every shard encodes its own rows on its own device.  `rows` has one tensor per
+    shard; `params` is one tensor for every shard (which then all have to be on its device) or a list with one per
+    shard; features, argmax and `stream` are True / None for all shards or a list with one entry per shard; returns the
+    list of the shards' results.  With stream=None every shard's call is enqueued on a side stream of its device, ordered
+    after that device's current stream, before any is waited for."""
+    rows, ps = _shard_list(ssim, "rows", rows), _shard_params(ssim, params)
+    fs, am = _per_shard(ssim, "features", features), _per_shard(ssim, "argmax", argmax)
+    return _sharded(ssim, "hs_entity_encode", lambda i, s: request(s.gpu_id, rows[i], ps[i], features=fs[i], argmax=am[i], **kw), stream)
+
+
+def compute_backward_sharded(ssim, rows, params, grad_features, argmax, stream=None, grad_params=True, **kw):
+    """ShardedSimulator.encode_entities_backward: as compute_sharded; every shard's grad_params holds the sum over its own
+    rows (add them for shared parameters)."""
+    rows, ps = _shard_list(ssim, "rows", rows), _shard_params(ssim, params)
+    gf, am = _shard_list(ssim, "grad_features", grad_features), _shard_list(ssim, "argmax", argmax)
+    gp = _per_shard(ssim, "grad_params", grad_params)
+    return _sharded(ssim, "hs_entity_encode_backward",
+                    lambda i, s: request_backward(s.gpu_id, rows[i], ps[i], gf[i], am[i], grad_params=gp[i], **kw), stream)
+
+
+# ---- the autograd face ----
+def _function():
+    import torch
+
+    class _Encode(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, params, sim, rows, E, eps, slope, dtype):
+            out = compute(sim, rows, params.detach(), embed_dim=E, eps=eps, slope=slope, features=True, argmax=True, dtype=dtype)
+            ctx.save_for_backward(params, rows, out["argmax"])
+            ctx.call = (sim, E, eps, slope)
+            return out["features"]
+
+        @staticmethod
+        def backward(ctx, grad):
+            params, rows, argmax = ctx.saved_tensors
+            sim, E, eps, slope = ctx.call
+            g = compute_backward(sim, rows, params.detach(), grad.contiguous(), argmax, embed_dim=E, eps=eps, slope=slope)["grad_params"]
+            return g, None, None, None, None, None, None
+    return _Encode
+
+
+def _module_base():
+    import torch
+    return torch.nn.Module
+
+
+class EntityEncoder(_module_base()):
+    """The encoder as a torch module: one flat float32 Parameter `params` of PARAM_ROWS * embed_dim elements
+    (param_layout; named_views() gives the tables' kernels, biases, scales and shifts as views).  forward(sim, rows) runs
+    the forward kernel on `sim`'s device and returns features [n, 4 E] (in `dtype`, by default the rows' dtype) as part
+    of the autograd graph of `params`: its backward runs the backward kernel.  rows get no gradient."""
+
+    def __init__(self, embed_dim=64, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, generator=None):
+        import torch
+        super().__init__()
+        self.embed_dim, self.eps, self.slope = _embed_dim(embed_dim), float(eps), float(slope)
+        self.params = torch.nn.Parameter(init_params(embed_dim, generator))
+
+    def named_views(self):
+        return views(self.params, self.embed_dim)
+
+    def forward(self, sim, rows, dtype=None):
+        return _function().apply(self.params, sim, rows.detach(), self.embed_dim, self.eps, self.slope, dtype)

@@ -192,6 +192,19 @@ class ShardedSimulator:
                                            grad_logits=grad_logits, stats=stats, loss_coef=loss_coef, grad_scale=grad_scale,
                                            grad_dtype=grad_dtype, value_dtype=value_dtype)
 
+    def encode_entities(self, rows, params, *, embed_dim=64, eps=1e-6, slope=0.01, features=True, argmax=None, dtype=None, stream=None):
+        """HideAndSeekSimulator.encode_entities per shard: `rows` has one tensor per shard, on the shard's device; `params`
+        is one tensor for all shards or a list; a list of the shards' results (entity_encoder.compute_sharded)."""
+        from . import entity_encoder as _enc
+        return _enc.compute_sharded(self, rows, params, stream, features=features, argmax=argmax, embed_dim=embed_dim, eps=eps, slope=slope, dtype=dtype)
+
+    def encode_entities_backward(self, rows, params, grad_features, argmax, *, embed_dim=64, eps=1e-6, slope=0.01, grad_params=True, stream=None):
+        """HideAndSeekSimulator.encode_entities_backward per shard: every shard's grad_params is the sum over its own rows
+        (entity_encoder.compute_backward_sharded)."""
+        from . import entity_encoder as _enc
+        return _enc.compute_backward_sharded(self, rows, params, grad_features, argmax, stream, grad_params=grad_params, embed_dim=embed_dim,
+                                             eps=eps, slope=slope)
+
     def device_status(self):
         out = {}
         for s in self.shards:
