@@ -612,6 +612,100 @@ int32_t hs_entity_encode_async(hs_sim *sim, void *hip_stream, const hs_entity_en
 int32_t hs_entity_encode_backward(hs_sim *sim, const hs_entity_encode_backward_request *req);
 int32_t hs_entity_encode_backward_async(hs_sim *sim, void *hip_stream, const hs_entity_encode_backward_request *req);
 
+/* The recurrent core: what the reference's PolicyRNN (scripts/jax_policy.py, make_policy: an LSTM of 256 hidden channels
+ * and one layer, a LayerNorm on its output, clear_recurrent_state at episode ends) does after its two gate GEMMs.  The
+ * caller computes gates [n][4 H] = x W_in + h_prev W_rec with the BLAS library; one kernel (csrc/hs_k_lstm.h) then reads
+ * a row's 4 H gate values and H cell values once and writes y, h_next and c_next; n is free, as for hs_ppo_loss.
+ * madrona_learn's LSTM, LayerNorm and clear_recurrent_state are not part of the reference's tree: the gate order, the
+ * eps and the place of the clear below are the project's own and are not pinned by it.
+ * cell_params is one array of HS_LSTM_PARAM_ROWS * H f32: bias [4 H] | gamma [H] | beta [H].  The gate k of channel c
+ * is gates[r][k H + c] and bias[k H + c], in the order k = 0 i (input), 1 f (forget), 2 g (candidate), 3 o (output).
+ * The arithmetic is the contract.  Narrow gates are widened to f32 exactly; everything is IEEE f32, unfused except
+ * where fmaf is written, in exactly this order; expf and tanhf are the device library's accurate functions and are not
+ * pinned bit for bit.  For row r and channel c < H:
+ *   zi = gates_i + bias_i;   zf = gates_f + bias_f;   zg = gates_g + bias_g;   zo = gates_o + bias_o
+ *   sigma(x) = 1.0f / (1.0f + expf(-x))
+ *   i = sigma(zi);   f = sigma(zf);   g = tanhf(zg);   o = sigma(zo)
+ *   c' = fmaf(f, c_prev, i * g);   tc = tanhf(c');   h' = o * tc
+ *   sum_c(p): lane l < 64 adds p_l, p_{l+64}, ..., p_{l+H-64} in ascending order; then for m = 1, 2, 4, ..., 32 every
+ *             lane replaces its value s_l by s_l + s_{l xor m} (the butterfly of hs_entity_encode with L = 64: every
+ *             lane ends with the same bits)
+ *   mu = sum_c(h') / (float)H;   d = h' - mu;   var = sum_c(d * d) / (float)H
+ *   rstd = 1.0f / sqrtf(var + eps)                                  (division and sqrtf correctly rounded)
+ *   hhat = d * rstd;   y = fmaf(hhat, gamma, beta)
+ *   keep = clear == null || clear[r] == 0
+ *   y[r][c] = y;   h_next[r][c] = keep ? h' : +0;   c_next[r][c] = keep ? c' : +0           (selects, not products)
+ * clear [n] i32 is the done export of the step just taken (as hs_gae_request's done).  y is the LayerNorm of the
+ * UNCLEARED h': the reference's PolicyRNN.__call__ norms the LSTM's output, and the clear applies to the carried state
+ * alone.  gates is f32, bf16 or f16; c_prev and c_next are always f32; h_next has the dtype of gates (it feeds the next
+ * GEMM) and y its own y_dtype, both rounded to nearest even.  y, h_next and c_next may each be null, not all three; only
+ * what is requested is written.  A row's outputs do not depend on its position or on n.
+ * hs_lstm_cell_backward recomputes all of the above from gates, c_prev, cell_params and clear (nothing else is saved)
+ * and takes grad_y [n][H] of y_dtype, grad_h_next [n][H] of gates_dtype or null and grad_c_next [n][H] f32 or null; a
+ * null gradient counts as +0.  No gradient with respect to clear exists.
+ *   dy = grad_y;   hb = gamma * dy;   mh = sum_c(hb) / (float)H;   mhz = sum_c(hb * hhat) / (float)H
+ *   dh = rstd * ((hb - mh) - hhat * mhz) + (keep ? grad_h_next : 0)
+ *   dc = fmaf(dh * o, 1.0f - tc * tc, keep ? grad_c_next : 0)
+ *   dzo = (dh * tc) * (o * (1.0f - o));          dzi = (dc * g) * (i * (1.0f - i))
+ *   dzf = (dc * c_prev) * (f * (1.0f - f));      dzg = (dc * i) * (1.0f - g * g)
+ *   grad_gates[r][k H + c] = dz_k   (rounded to gates_dtype);     grad_c_prev[r][c] = dc * f
+ *   dbias_k[c] = dbias_k[c] + dz_k;   dgamma[c] = fmaf(dy, hhat, dgamma[c]);   dbeta[c] = dbeta[c] + dy
+ * grad_cell_params [HS_LSTM_PARAM_ROWS * H] f32 has the layout of cell_params.  Its sums over the rows run in an order
+ * that depends on n alone: with R = HS_LSTM_ROWS_PER_ROUND rows per round and G = min(ceil(n / R), HS_LSTM_MAX_GRID_BWD)
+ * workgroups, workgroup b takes rounds b, b + G, ...; wave w of it row round * R + w; a lane adds its rows' terms in
+ * round order onto +0; the waves add as ((w0 + w1) + w2) + w3; the workgroups' sums go to a workspace of the handle
+ * ([HS_LSTM_MAX_GRID_BWD][HS_LSTM_PARAM_ROWS * HS_LSTM_MAX_HIDDEN] f32), where HS_EMBED_SUM_SEGS segments of
+ * ceil(G / segs) consecutive workgroups are each added in ascending order onto +0 and the segments then in ascending
+ * order (the kernel that does so is hs_entity_encode_backward's).  Rows past n contribute nothing.  No atomics: the same
+ * inputs give the same bits on every call.  All-zero gradients give grad_cell_params all +0 (and grad_gates and
+ * grad_c_prev zeros of either sign).  grad_gates, grad_c_prev and grad_cell_params may each be null, not all three.
+ * Gates, cell values, parameters and gradients must be finite: nothing checks that on the device.
+ * Two backward calls on one handle must not overlap (the workspace); forward calls may.  Everything is validated
+ * before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request, null
+ * gates, c_prev or cell_params, every output null (backward: also a null grad_y); an unknown dtype; hidden not 64, 128,
+ * 256 or 512; n < 1 or n * 4 H >= 2^31; eps not finite or <= 0; a pointer not aligned to its element size (f32 and i32
+ * arrays: 4 bytes); an output range that overlaps an input range or another output; a call before hs_init or inside an
+ * open step.  The calls read no export and write no simulator state.  The blocking forms are ordered after the device's
+ * legacy default stream; the _async forms enqueue on the caller's hipStream_t without synchronising. */
+enum { HS_LSTM_PARAM_ROWS = 6, HS_LSTM_MAX_GRID_BWD = 512, HS_LSTM_MAX_HIDDEN = 512, HS_LSTM_ROWS_PER_ROUND = 4 };
+typedef struct hs_lstm_cell_request {
+    const void    *gates;         /* [n][4 hidden] of gates_dtype, contiguous: i | f | g | o */
+    const float   *c_prev;        /* [n][hidden] f32 */
+    const float   *cell_params;   /* [HS_LSTM_PARAM_ROWS * hidden] f32: bias [4 H] | gamma [H] | beta [H] */
+    const int32_t *clear;         /* [n] i32 (the done export: nonzero = the episode ended), or null = keep every row */
+    int32_t n;                    /* rows, n >= 1 and n * 4 * hidden < 2^31 */
+    int32_t hidden;               /* H: 64, 128, 256 (the reference's) or 512 */
+    int32_t gates_dtype;          /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16; of gates and h_next */
+    int32_t y_dtype;              /* of y */
+    float eps;                    /* finite, > 0; 1e-6 */
+    int32_t reserved;             /* ignored */
+    void    *y;                   /* [n][hidden] of y_dtype, or null */
+    void    *h_next;              /* [n][hidden] of gates_dtype, or null */
+    float   *c_next;              /* [n][hidden] f32, or null */
+} hs_lstm_cell_request;           /* 80 bytes */
+typedef struct hs_lstm_cell_backward_request {
+    const void    *gates;         /* as in the forward call */
+    const float   *c_prev;
+    const float   *cell_params;
+    const int32_t *clear;
+    const void    *grad_y;        /* [n][hidden] of y_dtype */
+    const void    *grad_h_next;   /* [n][hidden] of gates_dtype, or null = +0 */
+    const float   *grad_c_next;   /* [n][hidden] f32, or null = +0 */
+    int32_t n;
+    int32_t hidden;
+    int32_t gates_dtype;          /* of gates, grad_h_next and grad_gates */
+    int32_t y_dtype;              /* of grad_y */
+    float eps;
+    int32_t reserved;             /* ignored */
+    void    *grad_gates;          /* [n][4 hidden] of gates_dtype, or null */
+    float   *grad_c_prev;         /* [n][hidden] f32, or null */
+    float   *grad_cell_params;    /* [HS_LSTM_PARAM_ROWS * hidden] f32, or null */
+} hs_lstm_cell_backward_request;  /* 104 bytes */
+int32_t hs_lstm_cell(hs_sim *sim, const hs_lstm_cell_request *req);
+int32_t hs_lstm_cell_async(hs_sim *sim, void *hip_stream, const hs_lstm_cell_request *req);
+int32_t hs_lstm_cell_backward(hs_sim *sim, const hs_lstm_cell_backward_request *req);
+int32_t hs_lstm_cell_backward_async(hs_sim *sim, void *hip_stream, const hs_lstm_cell_backward_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

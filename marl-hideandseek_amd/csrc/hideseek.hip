@@ -29,6 +29,7 @@
 #include "hs_k_embed.h"
 #include "hs_k_norm.h"
 #include "hs_solver.h"
+#include "hs_k_lstm.h"
 
 namespace {
 
@@ -87,6 +88,7 @@ struct hs_sim {
     double *twohot_partials = nullptr;     // hs_twohot_value: the statistics of each workgroup, [kTwMaxGrid][HS_TWOHOT_STATS]
     int32_t *twohot_counts = nullptr;      // hs_twohot_value: its own counts of k_ppo_count, [kPpoCountGrid]
     float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kEmbMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
+    float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kLstmMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -771,6 +773,122 @@ int launch_embed_bwd(hs_sim *s, hipStream_t strm, const hs_entity_encode_backwar
 }
 }  // namespace
 
+// ---- the recurrent core (hs_k_lstm.h); after the launchers above, so that their kernels are instantiated in the same order as before ----
+namespace {
+static_assert(HS_LSTM_PARAM_ROWS == hs::kLstmParamRows && HS_LSTM_MAX_GRID_BWD == hs::kLstmMaxGridBwd && HS_LSTM_MAX_HIDDEN == hs::kLstmMaxH &&
+              HS_LSTM_ROWS_PER_ROUND == hs::kLstmWaves, "hs_lstm_cell_request and k_lstm agree");
+static_assert(sizeof(hs_lstm_cell_request) == 80 && offsetof(hs_lstm_cell_request, clear) == 24 && offsetof(hs_lstm_cell_request, n) == 32 &&
+              offsetof(hs_lstm_cell_request, y_dtype) == 44 && offsetof(hs_lstm_cell_request, eps) == 48 && offsetof(hs_lstm_cell_request, y) == 56 &&
+              offsetof(hs_lstm_cell_request, c_next) == 72, "hs_lstm_cell_request layout (gpu_hideseek/recurrent.py mirrors it)");
+static_assert(sizeof(hs_lstm_cell_backward_request) == 104 && offsetof(hs_lstm_cell_backward_request, grad_y) == 32 &&
+              offsetof(hs_lstm_cell_backward_request, grad_c_next) == 48 && offsetof(hs_lstm_cell_backward_request, n) == 56 &&
+              offsetof(hs_lstm_cell_backward_request, y_dtype) == 68 && offsetof(hs_lstm_cell_backward_request, eps) == 72 &&
+              offsetof(hs_lstm_cell_backward_request, grad_gates) == 80 && offsetof(hs_lstm_cell_backward_request, grad_cell_params) == 96,
+              "hs_lstm_cell_backward_request layout (gpu_hideseek/recurrent.py mirrors it)");
+
+// What the two calls share: `fn` is the entry point's name.
+int check_lstm_common(const char *fn, const void *gates, const float *c_prev, const float *cell_params, const int32_t *clear, int32_t n, int32_t H,
+                      int32_t gates_dtype, float eps) {
+    const std::string f = std::string(fn) + ": ";
+    if (!gates) return fail(HS_ERR_INVALID_ARG, f + "null gates");
+    if (!c_prev) return fail(HS_ERR_INVALID_ARG, f + "null c_prev");
+    if (!cell_params) return fail(HS_ERR_INVALID_ARG, f + "null cell_params");
+    if (!pack_dtype_ok(gates_dtype)) return fail(HS_ERR_INVALID_ARG, f + "gates dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    if (H != 64 && H != 128 && H != 256 && H != 512) return fail(HS_ERR_INVALID_ARG, f + "hidden must be 64, 128, 256 or 512");
+    if (n < 1 || (int64_t)n * 4 * H >= (int64_t)1 << 31) return fail(HS_ERR_INVALID_ARG, f + "n must be at least 1 and n * 4 * hidden below 2^31");
+    if (!std::isfinite(eps) || !(eps > 0.f)) return fail(HS_ERR_INVALID_ARG, f + "eps must be finite and above 0");
+    if (((uintptr_t)c_prev | (uintptr_t)cell_params | (uintptr_t)clear) & 3u)
+        return fail(HS_ERR_INVALID_ARG, f + "c_prev, cell_params and clear must be 4-byte aligned");
+    if ((uintptr_t)gates & (gates_dtype == HS_DTYPE_F32 ? 3u : 1u)) return fail(HS_ERR_INVALID_ARG, f + "gates must be aligned to its element size");
+    return HS_OK;
+}
+
+int check_lstm_ranges(hs_sim *s, const char *fn, const GaeRange *in, size_t nin, const GaeRange *out, size_t nout) {
+    for (size_t i = 0; i < nout; ++i) {
+        for (size_t k = 0; k < nin; ++k)
+            if (gae_overlap(out[i], in[k])) return fail(HS_ERR_INVALID_ARG, std::string(fn) + ": " + out[i].name + " overlaps " + in[k].name);
+        for (size_t j = 0; j < i; ++j)
+            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string(fn) + ": " + out[i].name + " overlaps " + out[j].name);
+    }
+    return check_embed_state(s, fn);
+}
+
+int check_lstm(hs_sim *s, const hs_lstm_cell_request *r) {
+    const char *fn = "hs_lstm_cell";
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: null request");
+    HS_TRY(check_lstm_common(fn, r->gates, r->c_prev, r->cell_params, r->clear, r->n, r->hidden, r->gates_dtype, r->eps));
+    if (!r->y && !r->h_next && !r->c_next) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: every output is null");
+    if (r->y && !pack_dtype_ok(r->y_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: y dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    const uintptr_t gsize = r->gates_dtype == HS_DTYPE_F32 ? 4u : 2u, ysize = r->y_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if ((r->y && ((uintptr_t)r->y & (ysize - 1))) || ((uintptr_t)r->h_next & (gsize - 1)))
+        return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: y and h_next must be aligned to their element size");
+    if ((uintptr_t)r->c_next & 3u) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: c_next must be 4-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n, H = (uintptr_t)r->hidden;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange in[] = {range("gates", r->gates, n * 4 * H * gsize), range("c_prev", r->c_prev, n * H * 4),
+                           range("cell_params", r->cell_params, HS_LSTM_PARAM_ROWS * H * 4), range("clear", r->clear, n * 4)};
+    const GaeRange out[] = {range("y", r->y, r->y ? n * H * ysize : 0), range("h_next", r->h_next, n * H * gsize), range("c_next", r->c_next, n * H * 4)};
+    return check_lstm_ranges(s, fn, in, 4, out, 3);
+}
+
+int check_lstm_bwd(hs_sim *s, const hs_lstm_cell_backward_request *r) {
+    const char *fn = "hs_lstm_cell_backward";
+    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: null request");
+    HS_TRY(check_lstm_common(fn, r->gates, r->c_prev, r->cell_params, r->clear, r->n, r->hidden, r->gates_dtype, r->eps));
+    if (!r->grad_y) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: null grad_y");
+    if (!r->grad_gates && !r->grad_c_prev && !r->grad_cell_params) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: every output is null");
+    if (!pack_dtype_ok(r->y_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: y dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    const uintptr_t gsize = r->gates_dtype == HS_DTYPE_F32 ? 4u : 2u, ysize = r->y_dtype == HS_DTYPE_F32 ? 4u : 2u;
+    if (((uintptr_t)r->grad_y & (ysize - 1)) || (((uintptr_t)r->grad_h_next | (uintptr_t)r->grad_gates) & (gsize - 1)))
+        return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: grad_y, grad_h_next and grad_gates must be aligned to their element size");
+    if (((uintptr_t)r->grad_c_next | (uintptr_t)r->grad_c_prev | (uintptr_t)r->grad_cell_params) & 3u)
+        return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: grad_c_next, grad_c_prev and grad_cell_params must be 4-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n, H = (uintptr_t)r->hidden;
+    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
+    const GaeRange in[] = {range("gates", r->gates, n * 4 * H * gsize), range("c_prev", r->c_prev, n * H * 4),
+                           range("cell_params", r->cell_params, HS_LSTM_PARAM_ROWS * H * 4), range("clear", r->clear, n * 4),
+                           range("grad_y", r->grad_y, n * H * ysize), range("grad_h_next", r->grad_h_next, n * H * gsize),
+                           range("grad_c_next", r->grad_c_next, n * H * 4)};
+    const GaeRange out[] = {range("grad_gates", r->grad_gates, n * 4 * H * gsize), range("grad_c_prev", r->grad_c_prev, n * H * 4),
+                            range("grad_cell_params", r->grad_cell_params, HS_LSTM_PARAM_ROWS * H * 4)};
+    return check_lstm_ranges(s, fn, in, 7, out, 3);
+}
+
+template <typename F> void with_lstm_hidden(int32_t H, F f) {
+    if (H == 64) f(std::integral_constant<int, 64>{});
+    else if (H == 128) f(std::integral_constant<int, 128>{});
+    else if (H == 256) f(std::integral_constant<int, 256>{});
+    else f(std::integral_constant<int, 512>{});
+}
+
+// One k_lstm_fwd over the rows (the request has passed check_lstm).
+int launch_lstm(hs_sim *, hipStream_t strm, const hs_lstm_cell_request *r) {
+    hs::LstmArgs a = {};
+    a.gates = r->gates; a.cPrev = r->c_prev; a.params = r->cell_params; a.clear = r->clear; a.y = r->y; a.hNext = r->h_next; a.cNext = r->c_next;
+    a.n = r->n; a.gatesType = embed_type(r->gates_dtype); a.yType = embed_type(r->y_dtype); a.eps = r->eps;
+    const dim3 grid(hs::lstm_grid(a.n, hs::kLstmMaxGrid)), blk(hs::kLstmThreads);
+    with_lstm_hidden(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_fwd<decltype(h)::value>), grid, blk, 0, strm, a); });
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+// k_lstm_bwd, its parameter sums into the workspace's slices, then their fixed-order sum (the request has passed check_lstm_bwd).
+int launch_lstm_bwd(hs_sim *s, hipStream_t strm, const hs_lstm_cell_backward_request *r) {
+    hs::LstmBwdArgs a = {};
+    a.gates = r->gates; a.cPrev = r->c_prev; a.params = r->cell_params; a.clear = r->clear;
+    a.gradY = r->grad_y; a.gradHNext = r->grad_h_next; a.gradCNext = r->grad_c_next;
+    a.gradGates = r->grad_gates; a.gradCPrev = r->grad_c_prev; a.workspace = r->grad_cell_params ? s->lstm_partials : nullptr;
+    a.n = r->n; a.gatesType = embed_type(r->gates_dtype); a.yType = embed_type(r->y_dtype); a.eps = r->eps;
+    const int nparts = hs::lstm_grid(a.n, hs::kLstmMaxGridBwd), len = hs::kLstmParamRows * r->hidden;
+    with_lstm_hidden(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_bwd<decltype(h)::value>), dim3(nparts), dim3(hs::kLstmThreads), 0, strm, a); });
+    if (r->grad_cell_params)
+        hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
+                           (const float *)s->lstm_partials, nparts, len, r->grad_cell_params);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -874,6 +992,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->embed_partials, (size_t)hs::kEmbMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
+    HS_ALLOC(s->lstm_partials, (size_t)hs::kLstmMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1285,6 +1404,34 @@ int32_t hs_entity_encode_backward(hs_sim *s, const hs_entity_encode_backward_req
     HS_TRY(check_embed_bwd(s, req));
     HS_TRY(order_after_default_stream(s));
     HS_TRY(launch_embed_bwd(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+
+// ---- the recurrent core (hs_k_lstm.h; check_lstm / launch_lstm above) ----
+int32_t hs_lstm_cell_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_lstm(s, req));
+    return launch_lstm(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_lstm_cell(hs_sim *s, const hs_lstm_cell_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_lstm(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_lstm(s, s->stream, req));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+int32_t hs_lstm_cell_backward_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_backward_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_lstm_bwd(s, req));
+    return launch_lstm_bwd(s, (hipStream_t)hip_stream, req);
+}
+int32_t hs_lstm_cell_backward(hs_sim *s, const hs_lstm_cell_backward_request *req) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check_lstm_bwd(s, req));
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch_lstm_bwd(s, s->stream, req));
     HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
 }

@@ -257,6 +257,31 @@ class HideAndSeekSimulator:
         from . import entity_encoder as _enc
         return _enc.compute_backward(self, rows, params, grad_features, argmax, stream, embed_dim=embed_dim, eps=eps, slope=slope, grad_params=grad_params)
 
+    def lstm_cell(self, gates, c_prev, cell_params, *, clear=None, hidden=None, eps=1e-6, y=True, h_next=True, c_next=True, y_dtype=None, stream=None):
+        """The recurrent core after its gate GEMMs in one kernel (gpu_hideseek.recurrent; hs_lstm_cell, whose header
+        comment states the arithmetic: IEEE f32 in a fixed order).  `gates` [n, 4 H] (float32, bfloat16 or float16,
+        contiguous; order i, f, g, o) is x W_in + h W_rec, `c_prev` [n, H] float32, `cell_params` the flat float32 tensor
+        bias [4 H] | gamma [H] | beta [H] (recurrent.param_layout), H one of 64, 128, 256, 512.  `clear` [n] int32 or None
+        is the done export of the step just taken: a nonzero row gets h_next and c_next of exactly 0, while y is the
+        LayerNorm (`eps`) of its uncleared output.  y [n, H] in `y_dtype` (by default the gates'), h_next in the gates'
+        dtype and c_next float32 are each True (allocated), a preallocated tensor (for y a slot buf[t] of a [T, rows, H]
+        buffer will do) or None.  stream=None blocks; a torch.cuda.Stream or raw handle enqueues there without
+        synchronising.  Returns {name: tensor} of what was written."""
+        from . import recurrent as _rec
+        return _rec.compute(self, gates, c_prev, cell_params, stream, clear=clear, hidden=hidden, eps=eps, y=y, h_next=h_next, c_next=c_next,
+                            y_dtype=y_dtype)
+
+    def lstm_cell_backward(self, gates, c_prev, cell_params, grad_y, *, clear=None, grad_h_next=None, grad_c_next=None, hidden=None, eps=1e-6,
+                           grad_gates=True, grad_c_prev=True, grad_cell_params=True, stream=None):
+        """The gradients of lstm_cell in one kernel plus a fixed-order sum (hs_lstm_cell_backward): recomputed from the
+        forward's gates, c_prev, cell_params and clear, with the upstream `grad_y` [n, H] (float32, bfloat16 or float16),
+        `grad_h_next` (the gates' dtype) and `grad_c_next` (float32), either of which may be None for zero.  grad_gates
+        [n, 4 H] in the gates' dtype, grad_c_prev [n, H] and grad_cell_params [6 H] float32 are each True, a tensor or
+        None.  The same inputs give the same bits on every call.  Returns {name: tensor} of what was written."""
+        from . import recurrent as _rec
+        return _rec.compute_backward(self, gates, c_prev, cell_params, grad_y, stream, clear=clear, grad_h_next=grad_h_next, grad_c_next=grad_c_next,
+                                     hidden=hidden, eps=eps, grad_gates=grad_gates, grad_c_prev=grad_c_prev, grad_cell_params=grad_cell_params)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -114,7 +114,7 @@ def load():
     L.hs_twohot_value.restype = C.c_int32
     L.hs_twohot_value_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]         # (sim, hipStream_t, request)
     L.hs_twohot_value_async.restype = C.c_int32
-    for fn in ("hs_entity_encode", "hs_entity_encode_backward"):
+    for fn in ("hs_entity_encode", "hs_entity_encode_backward", "hs_lstm_cell", "hs_lstm_cell_backward"):
         getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p]                          # (sim, const request *)
         getattr(L, fn).restype = C.c_int32
         getattr(L, fn + "_async").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]   # (sim, hipStream_t, request)

@@ -205,6 +205,23 @@ class ShardedSimulator:
         return _enc.compute_backward_sharded(self, rows, params, grad_features, argmax, stream, grad_params=grad_params, embed_dim=embed_dim,
                                              eps=eps, slope=slope)
 
+    def lstm_cell(self, gates, c_prev, cell_params, *, clear=None, hidden=None, eps=1e-6, y=True, h_next=True, c_next=True, y_dtype=None, stream=None):
+        """HideAndSeekSimulator.lstm_cell per shard: `gates`, `c_prev` (and `clear`) have one tensor per shard, on the
+        shard's device; `cell_params` is one tensor for all shards or a list; a list of the shards' results
+        (recurrent.compute_sharded)."""
+        from . import recurrent as _rec
+        return _rec.compute_sharded(self, gates, c_prev, cell_params, stream, clear=clear, y=y, h_next=h_next, c_next=c_next, hidden=hidden, eps=eps,
+                                    y_dtype=y_dtype)
+
+    def lstm_cell_backward(self, gates, c_prev, cell_params, grad_y, *, clear=None, grad_h_next=None, grad_c_next=None, hidden=None, eps=1e-6,
+                           grad_gates=True, grad_c_prev=True, grad_cell_params=True, stream=None):
+        """HideAndSeekSimulator.lstm_cell_backward per shard: every shard's grad_cell_params is the sum over its own rows
+        (recurrent.compute_backward_sharded)."""
+        from . import recurrent as _rec
+        return _rec.compute_backward_sharded(self, gates, c_prev, cell_params, grad_y, stream, clear=clear, grad_h_next=grad_h_next,
+                                             grad_c_next=grad_c_next, grad_gates=grad_gates, grad_c_prev=grad_c_prev,
+                                             grad_cell_params=grad_cell_params, hidden=hidden, eps=eps)
+
     def device_status(self):
         out = {}
         for s in self.shards:
