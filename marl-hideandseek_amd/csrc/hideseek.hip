@@ -254,36 +254,131 @@ int poll_status(hs_sim *s) {
 
 }  // namespace
 
+// ==== the learner calls ====
+// Each section below has the static_asserts that tie a request of hideseek.h to its kernel header, a check_* that refuses
+// a bad request with "<entry point>: <what>", and a launch_* that enqueues the kernels of an accepted one.  The order of
+// the sections and of the launches in them is the order in which the compiler instantiates the kernels, and it is kept:
+// the compiler numbers functions, and with them the branch labels of the device assembly, in order of emission, so a
+// kernel instantiated earlier or later than before would no longer compare equal to itself (tools/isa_diff.py, DESIGN.md
+// section 5).  Hence launch_* are ordinary functions, a new stage goes after the last one, and a kernel is launched from a
+// template only where that template is instantiated at its call (with_elem, by its deduced return type) or where the
+// kernel has always been launched from one (launch_pack_as, launch_pack_moments_sum<>, the with_* of an absent array).
+namespace {
+// ---- what the checks share ----
+size_t elem_size(int32_t dtype) { return dtype == HS_DTYPE_F32 ? 4u : 2u; }
+bool dtype_ok(int32_t d) { return d == HS_DTYPE_F32 || d == HS_DTYPE_BF16 || d == HS_DTYPE_F16; }
+// every pointer (null included) is a multiple of k, a power of two
+bool aligned(uintptr_t k, std::initializer_list<const void *> ps) {
+    uintptr_t bits = 0;
+    for (const void *p : ps) bits |= (uintptr_t)p;
+    return !(bits & (k - 1));
+}
+// n at least 1 and n * stride below 2^31 for every stride: the kernels index with int
+bool count_ok(int32_t n, std::initializer_list<int64_t> strides) {
+    for (int64_t st : strides)
+        if ((int64_t)n * st >= (int64_t)1 << 31) return false;
+    return n >= 1;
+}
+// The bytes an argument covers; a null argument covers none.
+struct ByteRange { const char *name; uintptr_t lo, hi; };
+ByteRange range(const char *name, const void *p, uintptr_t bytes) { return {name, (uintptr_t)p, p ? (uintptr_t)p + bytes : 0}; }
+bool overlap(const ByteRange &a, const ByteRange &b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
+
+// The entry point a check speaks for: its failures read "<fn>: <what>", and the string is built only then.
+struct Check {
+    const char *fn;
+    int bad(const std::string &what, int code = HS_ERR_INVALID_ARG) const { return fail(code, std::string(fn) + ": " + what); }
+    int dtype(int32_t d, const char *what) const {
+        return dtype_ok(d) ? HS_OK : bad(std::string(what) + " dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
+    }
+    // no output overlaps an input or an earlier output
+    int disjoint(std::initializer_list<ByteRange> in, std::initializer_list<ByteRange> out) const {
+        for (const ByteRange *o = out.begin(); o != out.end(); ++o) {
+            for (const ByteRange &x : in)
+                if (overlap(*o, x)) return bad(std::string(o->name) + " overlaps " + x.name);
+            for (const ByteRange *e = out.begin(); e != o; ++e)
+                if (overlap(*o, *e)) return bad(std::string(o->name) + " overlaps " + e->name);
+        }
+        return HS_OK;
+    }
+    // the learner calls read what a finished hs_init / step left
+    int handle_ready(const hs_sim *s) const {
+        if (!s->initialised) return fail(HS_ERR_INVALID_ARG, std::string(fn) + " before hs_init");
+        if (s->step_open) return fail(HS_ERR_INVALID_ARG, std::string(fn) + " inside an open step");
+        return HS_OK;
+    }
+    // the heads' bucket counts of a multi-discrete actor (sampler and PPO loss); *L is their sum
+    int buckets(const int32_t *k, int *L) const {
+        *L = 0;
+        for (int h = 0; h < HS_SAMPLE_HEADS; ++h) {
+            if (k[h] < 1 || k[h] > HS_SAMPLE_MAX_BUCKETS) return bad("a bucket count must be in [1, HS_SAMPLE_MAX_BUCKETS]");
+            *L += k[h];
+        }
+        return *L > HS_SAMPLE_MAX_LOGITS ? bad("more than HS_SAMPLE_MAX_LOGITS logits per row") : HS_OK;
+    }
+};
+// the bucket counts that passed Check::buckets as the kernels take them, a byte per head: the count and the first logit;
+// returns their sum
+int pack_buckets(const int32_t *k, uint64_t *bucketK, uint64_t *bucketOff) {
+    int off = 0;
+    for (int h = 0; h < HS_SAMPLE_HEADS; off += k[h++]) {
+        *bucketK |= (uint64_t)k[h] << (8 * h);
+        *bucketOff |= (uint64_t)off << (8 * h);
+    }
+    return off;
+}
+
+// ---- what the launches share ----
+// f(tag) with tag's type the element type of an array of type `dtype`.  The return type is deduced so that a call
+// instantiates f's body, and the kernels it launches, at that place in the file.
+template <typename F> auto with_elem(int32_t dtype, F f) {
+    if (dtype == HS_DTYPE_F32) f(float{});
+    else if (dtype == HS_DTYPE_BF16) f(hs::SampleBf16{});
+    else f(hs::SampleF16{});
+}
+// the same for an array that may be absent (null)
+template <typename F> void with_optional_elem(const void *p, int32_t dtype, F f) {
+    if (!p) f(hs::PpoAbsent{});
+    else with_elem(dtype, f);
+}
+// f(std::integral_constant<int, V>) for the V of Vs that `v` is.  A left fold: the compiler instantiates f for the Vs in
+// the order written (a right fold goes from the last to the first).
+template <int... Vs, typename F> void with_constant(int32_t v, F f) {
+    (void)(... || (v == Vs && (f(std::integral_constant<int, Vs>{}), true)));
+}
+// the element type of an array as the encoder's and the LSTM's kernels take it, a run-time code
+int elem_code(int32_t dtype) { return dtype == HS_DTYPE_F32 ? hs::kEmbF32 : dtype == HS_DTYPE_BF16 ? hs::kEmbBf16 : hs::kEmbF16; }
+}  // namespace
+
 // ---- policy inputs (hs_k_pack.h) ----
 namespace {
 template <typename TA, typename TC, bool MOM> void launch_pack_as(const hs::PackArgs &a, hipStream_t strm) {
     if constexpr (std::is_same<TA, hs::PackAbsent>::value && std::is_same<TC, hs::PackAbsent>::value && !MOM) return;
     else hipLaunchKernelGGL((hs::k_pack<TA, TC, MOM>), dim3(hs::pack_grid(a.rows)), dim3(hs::kPackThreads), 0, strm, a);
 }
-// f(tag) with the element type of output `p` of type `dtype` as tag's type
+// f(tag) with the element type of output `p` of type `dtype` as tag's type: k_pack has tags of its own
 template <typename F> void with_pack_type(const void *p, int32_t dtype, F f) {
     if (!p) f(hs::PackAbsent{});
     else if (dtype == HS_DTYPE_F32) f(float{});
     else if (dtype == HS_DTYPE_BF16) f(hs::PackBf16{});
     else f(hs::PackF16{});
 }
-bool pack_dtype_ok(int32_t d) { return d == HS_DTYPE_F32 || d == HS_DTYPE_BF16 || d == HS_DTYPE_F16; }
 
+// The one check that looks at the handle before the arguments.
 int check_pack(hs_sim *s, const hs_pack_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: null request");
-    if (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)
-        return fail(HS_ERR_UNSUPPORTED, "hs_pack_policy_inputs: HS_FLAG_EXT_SKIP_OBSERVATIONS leaves no observations to pack");
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs inside an open step");
-    if (!r->actor && !r->critic && !r->moments) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: every output is null");
-    if ((r->actor && !pack_dtype_ok(r->actor_dtype)) || (r->critic && !pack_dtype_ok(r->critic_dtype)))
-        return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: output dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (((uintptr_t)r->actor | (uintptr_t)r->critic) & 15u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: outputs must be 16-byte aligned");
-    if ((uintptr_t)r->moments & 7u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs: moments must be 8-byte aligned");
+    const Check c{"hs_pack_policy_inputs"};
+    if (!r) return c.bad("null request");
+    if (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) return c.bad("HS_FLAG_EXT_SKIP_OBSERVATIONS leaves no observations to pack", HS_ERR_UNSUPPORTED);
+    HS_TRY(c.handle_ready(s));
+    if (!r->actor && !r->critic && !r->moments) return c.bad("every output is null");
+    if (r->actor) HS_TRY(c.dtype(r->actor_dtype, "output"));
+    if (r->critic) HS_TRY(c.dtype(r->critic_dtype, "output"));
+    if (!aligned(16, {r->actor, r->critic})) return c.bad("outputs must be 16-byte aligned");
+    if (!aligned(8, {r->moments})) return c.bad("moments must be 8-byte aligned");
     return HS_OK;
 }
 // The fixed-order sum of the workgroups' moments, after a k_pack or k_pack_norm that wrote them.  A template, so that
-// k_pack_moments_sum is instantiated after the k_pack kernels of launch_pack, as it was when launch_pack launched it.
+// k_pack_moments_sum is instantiated after the k_pack kernels of launch_pack.
 template <int kSegs = hs::kPackSumSegs>
 int launch_pack_moments_sum(hs_sim *s, hipStream_t strm, const hs_pack_request *r, int rows) {
     constexpr int kCols = hs::kPackThreads / kSegs;
@@ -318,31 +413,22 @@ static_assert(HS_SAMPLE_HEADS == hs::kSampleHeads && HS_SAMPLE_MAX_BUCKETS == hs
               "hs_sample_request and k_sample agree");
 static_assert(kExports[HS_EXPORT_ACTION].tail[0] == HS_SAMPLE_HEADS && kExports[HS_EXPORT_ACTION].dtype == HS_DTYPE_I32, "k_sample writes the action export's rows");
 
-int sample_logits(const hs_sample_request *r) {
-    int L = 0;
-    for (int h = 0; h < HS_SAMPLE_HEADS; ++h) L += r->buckets[h];
-    return L;
-}
-
 int check_sample(hs_sim *s, const hs_sample_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: null request");
-    if (!r->logits) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: null logits");
-    if (!pack_dtype_ok(r->logits_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: logits dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->mode != HS_SAMPLE_DRAW && r->mode != HS_SAMPLE_GREEDY && r->mode != HS_SAMPLE_EVALUATE) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: unknown mode");
-    if (r->flags & ~(uint32_t)HS_SAMPLE_ZERO_INACTIVE) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: unknown flag");
-    for (int h = 0; h < HS_SAMPLE_HEADS; ++h)
-        if (r->buckets[h] < 1 || r->buckets[h] > HS_SAMPLE_MAX_BUCKETS) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: a bucket count must be in [1, HS_SAMPLE_MAX_BUCKETS]");
-    if (sample_logits(r) > HS_SAMPLE_MAX_LOGITS) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: more than HS_SAMPLE_MAX_LOGITS logits per row");
-    if (r->logits_stride < sample_logits(r)) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: logits_stride is below the sum of the buckets");
-    if ((uintptr_t)r->logits & (r->logits_dtype == HS_DTYPE_F32 ? 3u : 1u)) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: logits must be aligned to their element size");
-    if (((uintptr_t)r->action | (uintptr_t)r->log_prob | (uintptr_t)r->entropy | (uintptr_t)r->head_log_prob) & 3u)
-        return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: action, log_prob, entropy and head_log_prob must be 4-byte aligned");
-    if (r->mode == HS_SAMPLE_EVALUATE && !r->log_prob && !r->entropy && !r->head_log_prob)
-        return fail(HS_ERR_INVALID_ARG, "hs_sample_actions: HS_SAMPLE_EVALUATE with every output null");
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_sample_actions inside an open step");
+    const Check c{"hs_sample_actions"};
+    if (!r) return c.bad("null request");
+    if (!r->logits) return c.bad("null logits");
+    HS_TRY(c.dtype(r->logits_dtype, "logits"));
+    if (r->mode != HS_SAMPLE_DRAW && r->mode != HS_SAMPLE_GREEDY && r->mode != HS_SAMPLE_EVALUATE) return c.bad("unknown mode");
+    if (r->flags & ~(uint32_t)HS_SAMPLE_ZERO_INACTIVE) return c.bad("unknown flag");
+    int L;
+    HS_TRY(c.buckets(r->buckets, &L));
+    if (r->logits_stride < L) return c.bad("logits_stride is below the sum of the buckets");
+    if (!aligned(elem_size(r->logits_dtype), {r->logits})) return c.bad("logits must be aligned to their element size");
+    if (!aligned(4, {r->action, r->log_prob, r->entropy, r->head_log_prob})) return c.bad("action, log_prob, entropy and head_log_prob must be 4-byte aligned");
+    if (r->mode == HS_SAMPLE_EVALUATE && !r->log_prob && !r->entropy && !r->head_log_prob) return c.bad("HS_SAMPLE_EVALUATE with every output null");
+    HS_TRY(c.handle_ready(s));
     if ((r->flags & HS_SAMPLE_ZERO_INACTIVE) && (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS))
-        return fail(HS_ERR_UNSUPPORTED, "hs_sample_actions: HS_SAMPLE_ZERO_INACTIVE needs self_mask, which HS_FLAG_EXT_SKIP_OBSERVATIONS leaves unwritten");
+        return c.bad("HS_SAMPLE_ZERO_INACTIVE needs self_mask, which HS_FLAG_EXT_SKIP_OBSERVATIONS leaves unwritten", HS_ERR_UNSUPPORTED);
     return HS_OK;
 }
 // One k_sample over every agent row (the request has passed check_sample).
@@ -353,17 +439,12 @@ int launch_sample(hs_sim *s, hipStream_t strm, const hs_sample_request *r) {
     a.actionIn = a.action = r->action ? r->action : S.xAction;
     a.selfMask = (r->flags & HS_SAMPLE_ZERO_INACTIVE) ? S.xSelfMask : nullptr;
     a.logProb = r->log_prob; a.entropy = r->entropy; a.headLogProb = r->head_log_prob;
-    for (int h = 0, off = 0; h < HS_SAMPLE_HEADS; off += r->buckets[h++]) {
-        a.bucketK |= (uint64_t)r->buckets[h] << (8 * h);
-        a.bucketOff |= (uint64_t)off << (8 * h);
-    }
-    a.rows = S.N * s->A; a.stride = r->logits_stride; a.L = sample_logits(r); a.mode = r->mode;
+    a.L = pack_buckets(r->buckets, &a.bucketK, &a.bucketOff);
+    a.rows = S.N * s->A; a.stride = r->logits_stride; a.mode = r->mode;
     a.seed0 = r->seed[0]; a.seed1 = r->seed[1]; a.counter = r->counter;
     a.row0Global = (uint32_t)S.worldOffset * (uint32_t)s->A;
     const dim3 grid(hs::sample_grid(a.rows)), blk(hs::kSampleThreads);
-    if (r->logits_dtype == HS_DTYPE_F32) hipLaunchKernelGGL(hs::k_sample<float>, grid, blk, 0, strm, a);
-    else if (r->logits_dtype == HS_DTYPE_BF16) hipLaunchKernelGGL(hs::k_sample<hs::SampleBf16>, grid, blk, 0, strm, a);
-    else hipLaunchKernelGGL(hs::k_sample<hs::SampleF16>, grid, blk, 0, strm, a);
+    with_elem(r->logits_dtype, [&](auto t) { hipLaunchKernelGGL(hs::k_sample<decltype(t)>, grid, blk, 0, strm, a); });
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -378,49 +459,35 @@ static_assert(kExports[HS_EXPORT_REWARD].dtype == HS_DTYPE_F32 && kExports[HS_EX
               kExports[HS_EXPORT_REWARD].per_agent && kExports[HS_EXPORT_DONE].per_agent && kExports[HS_EXPORT_SELF_MASK].per_agent,
               "k_gae reads copies of the reward, done and self_mask exports");
 
-struct GaeRange { const char *name; uintptr_t lo, hi; };
-bool gae_overlap(const GaeRange &a, const GaeRange &b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
-
 int check_gae(hs_sim *s, const hs_gae_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null request");
-    if (!r->reward) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null reward");
-    if (!r->done) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null done");
-    if (!r->value) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null value");
-    if (!r->bootstrap) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: null bootstrap");
-    if (!r->advantage && !r->returns && !r->moments) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: every output is null");
-    if (!pack_dtype_ok(r->value_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: value dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->steps < 1 || r->steps > HS_GAE_MAX_STEPS) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: steps must be in [1, HS_GAE_MAX_STEPS]");
-    if (!(r->gamma >= 0.f && r->gamma <= 1.f)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: gamma must be finite and in [0, 1]");
-    if (!(r->lambda >= 0.f && r->lambda <= 1.f)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: lambda must be finite and in [0, 1]");
-    const uintptr_t vsize = r->value_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if (((uintptr_t)r->reward | (uintptr_t)r->done | (uintptr_t)r->mask | (uintptr_t)r->advantage | (uintptr_t)r->returns) & 3u)
-        return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: reward, done, mask, advantage and returns must be 4-byte aligned");
-    if (((uintptr_t)r->value | (uintptr_t)r->bootstrap) & (vsize - 1)) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: value and bootstrap must be aligned to their element size");
-    if ((uintptr_t)r->moments & 7u) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae: moments must be 8-byte aligned");
+    const Check c{"hs_compute_gae"};
+    if (!r) return c.bad("null request");
+    if (!r->reward) return c.bad("null reward");
+    if (!r->done) return c.bad("null done");
+    if (!r->value) return c.bad("null value");
+    if (!r->bootstrap) return c.bad("null bootstrap");
+    if (!r->advantage && !r->returns && !r->moments) return c.bad("every output is null");
+    HS_TRY(c.dtype(r->value_dtype, "value"));
+    if (r->steps < 1 || r->steps > HS_GAE_MAX_STEPS) return c.bad("steps must be in [1, HS_GAE_MAX_STEPS]");
+    if (!(r->gamma >= 0.f && r->gamma <= 1.f)) return c.bad("gamma must be finite and in [0, 1]");
+    if (!(r->lambda >= 0.f && r->lambda <= 1.f)) return c.bad("lambda must be finite and in [0, 1]");
+    const uintptr_t vsize = elem_size(r->value_dtype);
+    if (!aligned(4, {r->reward, r->done, r->mask, r->advantage, r->returns})) return c.bad("reward, done, mask, advantage and returns must be 4-byte aligned");
+    if (!aligned(vsize, {r->value, r->bootstrap})) return c.bad("value and bootstrap must be aligned to their element size");
+    if (!aligned(8, {r->moments})) return c.bad("moments must be 8-byte aligned");
     const uintptr_t rows = (uintptr_t)s->S.N * (uintptr_t)s->A, n = rows * (uintptr_t)r->steps;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange in[] = {range("reward", r->reward, n * 4), range("done", r->done, n * 4), range("value", r->value, n * vsize),
-                           range("bootstrap", r->bootstrap, rows * vsize), range("mask", r->mask, n * 4)};
-    const GaeRange out[] = {range("advantage", r->advantage, n * 4), range("returns", r->returns, n * 4),
-                            range("moments", r->moments, HS_GAE_MOMENTS * sizeof(double))};
-    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
-        for (const GaeRange &x : in)
-            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_compute_gae: ") + out[i].name + " overlaps " + x.name);
-        for (size_t j = 0; j < i; ++j)
-            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_compute_gae: ") + out[i].name + " overlaps " + out[j].name);
-    }
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_compute_gae inside an open step");
-    return HS_OK;
+    HS_TRY(c.disjoint({range("reward", r->reward, n * 4), range("done", r->done, n * 4), range("value", r->value, n * vsize),
+                       range("bootstrap", r->bootstrap, rows * vsize), range("mask", r->mask, n * 4)},
+                      {range("advantage", r->advantage, n * 4), range("returns", r->returns, n * 4),
+                       range("moments", r->moments, HS_GAE_MOMENTS * sizeof(double))}));
+    return c.handle_ready(s);
 }
 // One k_gae over every agent row (the request has passed check_gae), then the fixed-order sum of the moments.
 int launch_gae(hs_sim *s, hipStream_t strm, const hs_gae_request *r) {
     const hs::GaeArgs a = {r->reward, r->done, r->value, r->bootstrap, r->mask, r->advantage, r->returns,
                            r->moments ? s->gae_partials : nullptr, s->S.N * s->A, r->steps, r->gamma, r->lambda};
     const dim3 grid(hs::gae_grid(a.rows)), blk(hs::kGaeThreads);
-    if (r->value_dtype == HS_DTYPE_F32) hipLaunchKernelGGL(hs::k_gae<float>, grid, blk, 0, strm, a);
-    else if (r->value_dtype == HS_DTYPE_BF16) hipLaunchKernelGGL(hs::k_gae<hs::SampleBf16>, grid, blk, 0, strm, a);
-    else hipLaunchKernelGGL(hs::k_gae<hs::SampleF16>, grid, blk, 0, strm, a);
+    with_elem(r->value_dtype, [&](auto t) { hipLaunchKernelGGL(hs::k_gae<decltype(t)>, grid, blk, 0, strm, a); });
     if (r->moments)
         hipLaunchKernelGGL(hs::k_gae_moments_sum<>, dim3(1), dim3(hs::kGaeMoments * hs::kGaeSumSegs), 0, strm, (const double *)s->gae_partials,
                            hs::gae_grid(a.rows), r->moments);
@@ -437,64 +504,43 @@ static_assert(sizeof(hs_ppo_request) == 160 && offsetof(hs_ppo_request, n) == 72
               "hs_ppo_request layout (gpu_hideseek/ppo_loss.py mirrors it)");
 
 int check_ppo(hs_sim *s, const hs_ppo_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null request");
-    if (!r->logits) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null logits");
-    if (!r->action) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null action");
-    if (!r->old_log_prob) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null old_log_prob");
-    if (!r->advantage) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: null advantage");
-    if (!r->grad_logits && !r->grad_value && !r->stats) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: every output is null");
-    if (r->grad_value && !r->value) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: grad_value without value");
-    if (r->value && !r->returns) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: value without returns");
-    if (!r->value && (r->returns || r->old_value)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: returns or old_value without value");
-    if (!pack_dtype_ok(r->logits_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: logits dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->grad_logits && !pack_dtype_ok(r->grad_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: grad dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->value && !pack_dtype_ok(r->value_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: value dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    int L = 0;
-    for (int h = 0; h < HS_SAMPLE_HEADS; ++h) {
-        if (r->buckets[h] < 1 || r->buckets[h] > HS_SAMPLE_MAX_BUCKETS) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: a bucket count must be in [1, HS_SAMPLE_MAX_BUCKETS]");
-        L += r->buckets[h];
-    }
-    if (L > HS_SAMPLE_MAX_LOGITS) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: more than HS_SAMPLE_MAX_LOGITS logits per sample");
-    if (r->logits_stride < L) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: logits_stride is below the sum of the buckets");
-    if (r->grad_logits && r->grad_stride < L) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: grad_stride is below the sum of the buckets");
-    if (r->n < 1 || (int64_t)r->n * r->logits_stride >= (int64_t)1 << 31 || (r->grad_logits && (int64_t)r->n * r->grad_stride >= (int64_t)1 << 31))
-        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: n must be at least 1 and n * stride below 2^31");
-    if (!std::isfinite(r->clip_coef) || !(r->clip_coef > 0.f)) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: clip_coef must be finite and above 0");
+    const Check c{"hs_ppo_loss"};
+    if (!r) return c.bad("null request");
+    if (!r->logits) return c.bad("null logits");
+    if (!r->action) return c.bad("null action");
+    if (!r->old_log_prob) return c.bad("null old_log_prob");
+    if (!r->advantage) return c.bad("null advantage");
+    if (!r->grad_logits && !r->grad_value && !r->stats) return c.bad("every output is null");
+    if (r->grad_value && !r->value) return c.bad("grad_value without value");
+    if (r->value && !r->returns) return c.bad("value without returns");
+    if (!r->value && (r->returns || r->old_value)) return c.bad("returns or old_value without value");
+    HS_TRY(c.dtype(r->logits_dtype, "logits"));
+    if (r->grad_logits) HS_TRY(c.dtype(r->grad_dtype, "grad"));
+    if (r->value) HS_TRY(c.dtype(r->value_dtype, "value"));
+    int L;
+    HS_TRY(c.buckets(r->buckets, &L));
+    if (r->logits_stride < L) return c.bad("logits_stride is below the sum of the buckets");
+    if (r->grad_logits && r->grad_stride < L) return c.bad("grad_stride is below the sum of the buckets");
+    if (!count_ok(r->n, {r->logits_stride, r->grad_logits ? r->grad_stride : 0})) return c.bad("n must be at least 1 and n * stride below 2^31");
+    if (!std::isfinite(r->clip_coef) || !(r->clip_coef > 0.f)) return c.bad("clip_coef must be finite and above 0");
     if (!std::isfinite(r->value_loss_coef) || !std::isfinite(r->entropy_coef) || !std::isfinite(r->grad_scale))
-        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: value_loss_coef, entropy_coef and grad_scale must be finite");
-    const uintptr_t lsize = r->logits_dtype == HS_DTYPE_F32 ? 4u : 2u, gsize = r->grad_dtype == HS_DTYPE_F32 ? 4u : 2u, vsize = r->value_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if (((uintptr_t)r->action | (uintptr_t)r->old_log_prob | (uintptr_t)r->advantage | (uintptr_t)r->mask | (uintptr_t)r->returns | (uintptr_t)r->old_value) & 3u)
-        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: action, old_log_prob, advantage, mask, returns and old_value must be 4-byte aligned");
-    if (((uintptr_t)r->logits & (lsize - 1)) || (r->grad_logits && ((uintptr_t)r->grad_logits & (gsize - 1))) ||
-        (r->value && (((uintptr_t)r->value | (uintptr_t)r->grad_value) & (vsize - 1))))
-        return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: logits, grad_logits, value and grad_value must be aligned to their element size");
-    if (((uintptr_t)r->adv_moments | (uintptr_t)r->stats) & 7u) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss: adv_moments and stats must be 8-byte aligned");
+        return c.bad("value_loss_coef, entropy_coef and grad_scale must be finite");
+    const uintptr_t lsize = elem_size(r->logits_dtype), gsize = elem_size(r->grad_dtype), vsize = elem_size(r->value_dtype);
+    if (!aligned(4, {r->action, r->old_log_prob, r->advantage, r->mask, r->returns, r->old_value}))
+        return c.bad("action, old_log_prob, advantage, mask, returns and old_value must be 4-byte aligned");
+    if (!aligned(lsize, {r->logits}) || !aligned(gsize, {r->grad_logits}) || !aligned(vsize, {r->value, r->grad_value}))
+        return c.bad("logits, grad_logits, value and grad_value must be aligned to their element size");
+    if (!aligned(8, {r->adv_moments, r->stats})) return c.bad("adv_moments and stats must be 8-byte aligned");
     const uintptr_t n = (uintptr_t)r->n;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange in[] = {range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + L) * lsize), range("action", r->action, n * HS_SAMPLE_HEADS * 4),
-                           range("old_log_prob", r->old_log_prob, n * 4), range("advantage", r->advantage, n * 4),
-                           range("adv_moments", r->adv_moments, HS_GAE_MOMENTS * sizeof(double)), range("mask", r->mask, n * 4),
-                           range("value", r->value, n * vsize), range("returns", r->returns, n * 4), range("old_value", r->old_value, n * 4)};
-    const GaeRange out[] = {range("grad_logits", r->grad_logits, r->grad_logits ? ((n - 1) * (uintptr_t)r->grad_stride + L) * gsize : 0),
-                            range("grad_value", r->grad_value, n * vsize), range("stats", r->stats, HS_PPO_STATS * sizeof(double))};
-    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
-        for (const GaeRange &x : in)
-            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_ppo_loss: ") + out[i].name + " overlaps " + x.name);
-        for (size_t j = 0; j < i; ++j)
-            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_ppo_loss: ") + out[i].name + " overlaps " + out[j].name);
-    }
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_ppo_loss inside an open step");
-    return HS_OK;
+    HS_TRY(c.disjoint({range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + L) * lsize), range("action", r->action, n * HS_SAMPLE_HEADS * 4),
+                       range("old_log_prob", r->old_log_prob, n * 4), range("advantage", r->advantage, n * 4),
+                       range("adv_moments", r->adv_moments, HS_GAE_MOMENTS * sizeof(double)), range("mask", r->mask, n * 4),
+                       range("value", r->value, n * vsize), range("returns", r->returns, n * 4), range("old_value", r->old_value, n * 4)},
+                      {range("grad_logits", r->grad_logits, ((n - 1) * (uintptr_t)r->grad_stride + L) * gsize),
+                       range("grad_value", r->grad_value, n * vsize), range("stats", r->stats, HS_PPO_STATS * sizeof(double))}));
+    return c.handle_ready(s);
 }
 
-// f(tag) with the element type of array `p` of type `dtype` as tag's type
-template <typename F> void with_ppo_type(const void *p, int32_t dtype, F f) {
-    if (!p) f(hs::PpoAbsent{});
-    else if (dtype == HS_DTYPE_F32) f(float{});
-    else if (dtype == HS_DTYPE_BF16) f(hs::SampleBf16{});
-    else f(hs::SampleF16{});
-}
 // With a mask the count of the active samples, then one k_ppo over the samples (the request has passed check_ppo), then
 // the fixed-order sum of the statistics.
 int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
@@ -503,25 +549,18 @@ int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
     a.advMoments = r->adv_moments; a.mask = r->mask; a.value = r->value; a.returns = r->returns; a.oldValue = r->old_value;
     a.gradLogits = r->grad_logits; a.gradValue = r->grad_value; a.partials = r->stats ? s->ppo_partials : nullptr;
     a.counts = s->ppo_counts;
-    for (int h = 0, off = 0; h < HS_SAMPLE_HEADS; off += r->buckets[h++]) {
-        a.bucketK |= (uint64_t)r->buckets[h] << (8 * h);
-        a.bucketOff |= (uint64_t)off << (8 * h);
-        a.L = off + r->buckets[h];
-    }
+    a.L = pack_buckets(r->buckets, &a.bucketK, &a.bucketOff);
     a.n = r->n; a.stride = r->logits_stride; a.gradStride = r->grad_stride; a.countParts = hs::ppo_count_grid(a.n);
     a.clip = r->clip_coef; a.valueCoef = r->value_loss_coef; a.entropyCoef = r->entropy_coef; a.gradScale = r->grad_scale;
     const dim3 grid(hs::ppo_grid(a.n)), blk(hs::kPpoThreads);
     if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), blk, 0, strm, r->mask, a.n, s->ppo_counts);
-    auto with_logits = [&](auto tl) {
-        with_ppo_type(r->grad_logits, r->grad_dtype, [&](auto tg) {
-            with_ppo_type(r->value, r->value_dtype, [&](auto tv) {
+    with_elem(r->logits_dtype, [&](auto tl) {
+        with_optional_elem(r->grad_logits, r->grad_dtype, [&](auto tg) {
+            with_optional_elem(r->value, r->value_dtype, [&](auto tv) {
                 hipLaunchKernelGGL((hs::k_ppo<decltype(tl), decltype(tg), decltype(tv)>), grid, blk, 0, strm, a);
             });
         });
-    };
-    if (r->logits_dtype == HS_DTYPE_F32) with_logits(float{});
-    else if (r->logits_dtype == HS_DTYPE_BF16) with_logits(hs::SampleBf16{});
-    else with_logits(hs::SampleF16{});
+    });
     if (r->stats)
         hipLaunchKernelGGL(hs::k_ppo_stats_sum<>, dim3(1), dim3(hs::kPpoStats * hs::kPpoSumSegs), 0, strm, (const double *)s->ppo_partials,
                            hs::ppo_grid(a.n), r->stats);
@@ -530,7 +569,7 @@ int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
 }
 }  // namespace
 
-// ---- observation normaliser (hs_k_norm.h); after the other launchers, so that its kernels are instantiated last ----
+// ---- observation normaliser (hs_k_norm.h) ----
 namespace {
 static_assert(HS_NORM_STATE == hs::kNormState && HS_NORM_TABLE == hs::kNormTable && HS_NORM_MAX_MOMENTS == hs::kNormMaxMoments &&
               HS_NORM_STATE == HS_PACK_MOMENTS, "hs_obs_norm_request and k_norm_update agree");
@@ -541,26 +580,21 @@ static_assert(sizeof(hs_obs_norm_request) == 48 && offsetof(hs_obs_norm_request,
               "hs_obs_norm_request layout (gpu_hideseek/policy_inputs.py mirrors it)");
 
 int check_norm_update(hs_sim *s, const hs_obs_norm_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null request");
-    if (!r->moments) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null moments");
-    if (!r->state) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null state");
-    if (!r->table) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: null table");
-    if (r->num_moments < 1 || r->num_moments > HS_NORM_MAX_MOMENTS) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: num_moments must be in [1, HS_NORM_MAX_MOMENTS]");
-    if (!(r->decay >= 0.0 && r->decay < 1.0)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: decay must be in [0, 1)");
-    if (!std::isfinite(r->eps) || !(r->eps > 0.0)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: eps must be finite and above 0");
-    if (((uintptr_t)r->moments | (uintptr_t)r->state) & 7u) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: moments and state must be 8-byte aligned");
-    if ((uintptr_t)r->table & 15u) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: table must be 16-byte aligned");
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange moments = range("moments", r->moments, (uintptr_t)r->num_moments * HS_PACK_MOMENTS * sizeof(double));
-    const GaeRange state = range("state", r->state, HS_NORM_STATE * sizeof(double)), table = range("table", r->table, HS_NORM_TABLE * sizeof(float));
-    if (gae_overlap(state, moments)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: state overlaps moments");
-    if (gae_overlap(table, moments)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: table overlaps moments");
-    if (gae_overlap(table, state)) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update: table overlaps state");
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_obs_norm_update inside an open step");
-    return HS_OK;
+    const Check c{"hs_obs_norm_update"};
+    if (!r) return c.bad("null request");
+    if (!r->moments) return c.bad("null moments");
+    if (!r->state) return c.bad("null state");
+    if (!r->table) return c.bad("null table");
+    if (r->num_moments < 1 || r->num_moments > HS_NORM_MAX_MOMENTS) return c.bad("num_moments must be in [1, HS_NORM_MAX_MOMENTS]");
+    if (!(r->decay >= 0.0 && r->decay < 1.0)) return c.bad("decay must be in [0, 1)");
+    if (!std::isfinite(r->eps) || !(r->eps > 0.0)) return c.bad("eps must be finite and above 0");
+    if (!aligned(8, {r->moments, r->state})) return c.bad("moments and state must be 8-byte aligned");
+    if (!aligned(16, {r->table})) return c.bad("table must be 16-byte aligned");
+    HS_TRY(c.disjoint({range("moments", r->moments, (uintptr_t)r->num_moments * HS_PACK_MOMENTS * sizeof(double))},
+                      {range("state", r->state, HS_NORM_STATE * sizeof(double)), range("table", r->table, HS_NORM_TABLE * sizeof(float))}));
+    return c.handle_ready(s);
 }
-int launch_norm_update(hipStream_t strm, const hs_obs_norm_request *r) {
+int launch_norm_update(hs_sim *, hipStream_t strm, const hs_obs_norm_request *r) {
     const hs::NormArgs a = {r->moments, r->num_moments, r->decay, r->eps, r->state, r->table};
     hipLaunchKernelGGL(hs::k_norm_update<>, dim3(1), dim3(hs::kNormThreads), 0, strm, a);
     HS_HIP(hipGetLastError());
@@ -568,9 +602,10 @@ int launch_norm_update(hipStream_t strm, const hs_obs_norm_request *r) {
 }
 
 int check_pack_norm(hs_sim *s, const hs_pack_request *r, const float *table) {
+    const Check c{"hs_pack_policy_inputs_normalized"};
     HS_TRY(check_pack(s, r));
-    if (!table) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs_normalized: null table");
-    if ((uintptr_t)table & 15u) return fail(HS_ERR_INVALID_ARG, "hs_pack_policy_inputs_normalized: table must be 16-byte aligned");
+    if (!table) return c.bad("null table");
+    if (!aligned(16, {table})) return c.bad("table must be 16-byte aligned");
     return HS_OK;
 }
 // One k_pack_norm over every agent row (the request has passed check_pack_norm), then the fixed-order sum of the moments.
@@ -590,7 +625,7 @@ int launch_pack_norm(hs_sim *s, hipStream_t strm, const hs_pack_request *r, cons
 }
 }  // namespace
 
-// ---- the two-hot symlog critic head (hs_k_twohot.h); after the launchers above, so that their kernels are instantiated in the same order as before ----
+// ---- the two-hot symlog critic head (hs_k_twohot.h) ----
 namespace {
 static_assert(HS_TWOHOT_STATS == hs::kTwStats && HS_TWOHOT_MAX_BINS == hs::kTwMaxBins, "hs_twohot_request and k_twohot agree");
 static_assert(sizeof(hs_twohot_request) == 96 && offsetof(hs_twohot_request, n) == 24 && offsetof(hs_twohot_request, bins) == 36 &&
@@ -598,42 +633,32 @@ static_assert(sizeof(hs_twohot_request) == 96 && offsetof(hs_twohot_request, n) 
               offsetof(hs_twohot_request, stats) == 88, "hs_twohot_request layout (gpu_hideseek/value_head.py mirrors it)");
 
 int check_twohot(hs_sim *s, const hs_twohot_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: null request");
-    if (!r->logits) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: null logits");
-    if (!r->value && !r->grad_logits && !r->stats) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: every output is null");
-    if (!r->returns && (r->grad_logits || r->stats)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: grad_logits or stats without returns");
-    if (!pack_dtype_ok(r->logits_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: logits dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->value && !pack_dtype_ok(r->value_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: value dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->grad_logits && !pack_dtype_ok(r->grad_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: grad dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (r->bins < 2 || r->bins > HS_TWOHOT_MAX_BINS) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: bins must be in [2, HS_TWOHOT_MAX_BINS]");
+    const Check c{"hs_twohot_value"};
+    if (!r) return c.bad("null request");
+    if (!r->logits) return c.bad("null logits");
+    if (!r->value && !r->grad_logits && !r->stats) return c.bad("every output is null");
+    if (!r->returns && (r->grad_logits || r->stats)) return c.bad("grad_logits or stats without returns");
+    HS_TRY(c.dtype(r->logits_dtype, "logits"));
+    if (r->value) HS_TRY(c.dtype(r->value_dtype, "value"));
+    if (r->grad_logits) HS_TRY(c.dtype(r->grad_dtype, "grad"));
+    if (r->bins < 2 || r->bins > HS_TWOHOT_MAX_BINS) return c.bad("bins must be in [2, HS_TWOHOT_MAX_BINS]");
     const int B = r->bins;
-    if (r->logits_stride < B) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: logits_stride is below bins");
-    if (r->grad_logits && r->grad_stride < B) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: grad_stride is below bins");
-    if (!std::isfinite(r->lo) || !std::isfinite(r->hi) || !(r->lo < r->hi)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: lo and hi must be finite and lo < hi");
-    if (!std::isfinite(r->loss_coef) || !std::isfinite(r->grad_scale)) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: loss_coef and grad_scale must be finite");
-    if (r->n < 1 || (int64_t)r->n * r->logits_stride >= (int64_t)1 << 31 || (r->grad_logits && (int64_t)r->n * r->grad_stride >= (int64_t)1 << 31))
-        return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: n must be at least 1 and n * stride below 2^31");
-    const uintptr_t lsize = r->logits_dtype == HS_DTYPE_F32 ? 4u : 2u, gsize = r->grad_dtype == HS_DTYPE_F32 ? 4u : 2u, vsize = r->value_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if (((uintptr_t)r->returns | (uintptr_t)r->mask) & 3u) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: returns and mask must be 4-byte aligned");
-    if (((uintptr_t)r->logits & (lsize - 1)) || (r->grad_logits && ((uintptr_t)r->grad_logits & (gsize - 1))) || (r->value && ((uintptr_t)r->value & (vsize - 1))))
-        return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: logits, grad_logits and value must be aligned to their element size");
-    if ((uintptr_t)r->stats & 7u) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value: stats must be 8-byte aligned");
+    if (r->logits_stride < B) return c.bad("logits_stride is below bins");
+    if (r->grad_logits && r->grad_stride < B) return c.bad("grad_stride is below bins");
+    if (!std::isfinite(r->lo) || !std::isfinite(r->hi) || !(r->lo < r->hi)) return c.bad("lo and hi must be finite and lo < hi");
+    if (!std::isfinite(r->loss_coef) || !std::isfinite(r->grad_scale)) return c.bad("loss_coef and grad_scale must be finite");
+    if (!count_ok(r->n, {r->logits_stride, r->grad_logits ? r->grad_stride : 0})) return c.bad("n must be at least 1 and n * stride below 2^31");
+    const uintptr_t lsize = elem_size(r->logits_dtype), gsize = elem_size(r->grad_dtype), vsize = elem_size(r->value_dtype);
+    if (!aligned(4, {r->returns, r->mask})) return c.bad("returns and mask must be 4-byte aligned");
+    if (!aligned(lsize, {r->logits}) || !aligned(gsize, {r->grad_logits}) || !aligned(vsize, {r->value}))
+        return c.bad("logits, grad_logits and value must be aligned to their element size");
+    if (!aligned(8, {r->stats})) return c.bad("stats must be 8-byte aligned");
     const uintptr_t n = (uintptr_t)r->n;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange in[] = {range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + B) * lsize), range("returns", r->returns, n * 4),
-                           range("mask", r->mask, n * 4)};
-    const GaeRange out[] = {range("value", r->value, r->value ? n * vsize : 0),
-                            range("grad_logits", r->grad_logits, r->grad_logits ? ((n - 1) * (uintptr_t)r->grad_stride + B) * gsize : 0),
-                            range("stats", r->stats, HS_TWOHOT_STATS * sizeof(double))};
-    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
-        for (const GaeRange &x : in)
-            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_twohot_value: ") + out[i].name + " overlaps " + x.name);
-        for (size_t j = 0; j < i; ++j)
-            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_twohot_value: ") + out[i].name + " overlaps " + out[j].name);
-    }
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_twohot_value inside an open step");
-    return HS_OK;
+    HS_TRY(c.disjoint({range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + B) * lsize), range("returns", r->returns, n * 4),
+                       range("mask", r->mask, n * 4)},
+                      {range("value", r->value, n * vsize), range("grad_logits", r->grad_logits, ((n - 1) * (uintptr_t)r->grad_stride + B) * gsize),
+                       range("stats", r->stats, HS_TWOHOT_STATS * sizeof(double))}));
+    return c.handle_ready(s);
 }
 
 // With a mask the count of the active samples, then one k_twohot over the samples (the request has passed
@@ -646,16 +671,13 @@ int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
     a.lo = r->lo; a.hi = r->hi; a.lossCoef = r->loss_coef; a.gradScale = r->grad_scale;
     const dim3 grid(hs::twohot_grid(a.n)), blk(hs::kTwThreads);
     if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), dim3(hs::kPpoThreads), 0, strm, r->mask, a.n, s->twohot_counts);
-    auto with_logits = [&](auto tl) {
-        with_ppo_type(r->grad_logits, r->grad_dtype, [&](auto tg) {
-            with_ppo_type(r->value, r->value_dtype, [&](auto tv) {
+    with_elem(r->logits_dtype, [&](auto tl) {
+        with_optional_elem(r->grad_logits, r->grad_dtype, [&](auto tg) {
+            with_optional_elem(r->value, r->value_dtype, [&](auto tv) {
                 hipLaunchKernelGGL((hs::k_twohot<decltype(tl), decltype(tg), decltype(tv)>), grid, blk, 0, strm, a);
             });
         });
-    };
-    if (r->logits_dtype == HS_DTYPE_F32) with_logits(float{});
-    else if (r->logits_dtype == HS_DTYPE_BF16) with_logits(hs::SampleBf16{});
-    else with_logits(hs::SampleF16{});
+    });
     if (r->stats)
         hipLaunchKernelGGL(hs::k_twohot_stats_sum<>, dim3(1), dim3(hs::kTwStats * hs::kTwSumSegs), 0, strm, (const double *)s->twohot_partials,
                            hs::twohot_grid(a.n), r->stats);
@@ -664,7 +686,7 @@ int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
 }
 }  // namespace
 
-// ---- the entity encoder (hs_k_embed.h); after the launchers above, so that their kernels are instantiated in the same order as before ----
+// ---- the entity encoder (hs_k_embed.h) ----
 namespace {
 static_assert(HS_EMBED_PARAM_ROWS == hs::kEmbParamRows && HS_EMBED_MAX_GRID_BWD == hs::kEmbMaxGridBwd && HS_EMBED_SUM_SEGS == hs::kEmbSumSegs &&
               HS_EMBED_ROWS_PER_WAVE(32) == hs::EmbCfg<32>::kSub && HS_EMBED_ROWS_PER_WAVE(64) == hs::EmbCfg<64>::kSub &&
@@ -677,84 +699,57 @@ static_assert(sizeof(hs_entity_encode_backward_request) == 64 && offsetof(hs_ent
               offsetof(hs_entity_encode_backward_request, grad_dtype) == 44 && offsetof(hs_entity_encode_backward_request, eps) == 48 &&
               offsetof(hs_entity_encode_backward_request, grad_params) == 56, "hs_entity_encode_backward_request layout (gpu_hideseek/entity_encoder.py mirrors it)");
 
-int embed_type(int32_t dtype) { return dtype == HS_DTYPE_F32 ? hs::kEmbF32 : dtype == HS_DTYPE_BF16 ? hs::kEmbBf16 : hs::kEmbF16; }
-
-// What the two calls share: `fn` is the entry point's name, `other` the dtype of features / grad_features.
-int check_embed_common(hs_sim *s, const char *fn, const void *rows, const float *params, int32_t n, int32_t rows_dtype, int32_t E, float eps, float slope) {
-    const std::string f = std::string(fn) + ": ";
-    if (!rows) return fail(HS_ERR_INVALID_ARG, f + "null rows");
-    if (!params) return fail(HS_ERR_INVALID_ARG, f + "null params");
-    if (!pack_dtype_ok(rows_dtype)) return fail(HS_ERR_INVALID_ARG, f + "rows dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (E != 32 && E != 64 && E != 128) return fail(HS_ERR_INVALID_ARG, f + "embed_dim must be 32, 64 or 128");
-    if (n < 1 || (int64_t)n * HS_PACK_ROW >= (int64_t)1 << 31 || (int64_t)n * 4 * E >= (int64_t)1 << 31)
-        return fail(HS_ERR_INVALID_ARG, f + "n must be at least 1 and n * 296 and n * 4 * embed_dim below 2^31");
-    if (!std::isfinite(eps) || !std::isfinite(slope) || !(eps > 0.f)) return fail(HS_ERR_INVALID_ARG, f + "eps and slope must be finite and eps > 0");
-    (void)s;
-    return HS_OK;
-}
-
-int check_embed_state(hs_sim *s, const char *fn) {
-    if (!s->initialised) return fail(HS_ERR_INVALID_ARG, std::string(fn) + " before hs_init");
-    if (s->step_open) return fail(HS_ERR_INVALID_ARG, std::string(fn) + " inside an open step");
+// What the two calls share.
+int check_embed_common(const Check &c, const void *rows, const float *params, int32_t n, int32_t rows_dtype, int32_t E, float eps, float slope) {
+    if (!rows) return c.bad("null rows");
+    if (!params) return c.bad("null params");
+    HS_TRY(c.dtype(rows_dtype, "rows"));
+    if (E != 32 && E != 64 && E != 128) return c.bad("embed_dim must be 32, 64 or 128");
+    if (!count_ok(n, {HS_PACK_ROW, 4 * E})) return c.bad("n must be at least 1 and n * 296 and n * 4 * embed_dim below 2^31");
+    if (!std::isfinite(eps) || !std::isfinite(slope) || !(eps > 0.f)) return c.bad("eps and slope must be finite and eps > 0");
     return HS_OK;
 }
 
 int check_embed(hs_sim *s, const hs_entity_encode_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: null request");
-    HS_TRY(check_embed_common(s, "hs_entity_encode", r->rows, r->params, r->n, r->rows_dtype, r->embed_dim, r->eps, r->slope));
-    if (!r->features && !r->argmax) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: every output is null");
-    if (r->features && !pack_dtype_ok(r->features_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: features dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    const uintptr_t rsize = r->rows_dtype == HS_DTYPE_F32 ? 4u : 2u, fsize = r->features_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if ((uintptr_t)r->params & 3u) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: params must be 4-byte aligned");
-    if (((uintptr_t)r->rows & (rsize - 1)) || (r->features && ((uintptr_t)r->features & (fsize - 1))))
-        return fail(HS_ERR_INVALID_ARG, "hs_entity_encode: rows and features must be aligned to their element size");
+    const Check c{"hs_entity_encode"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_embed_common(c, r->rows, r->params, r->n, r->rows_dtype, r->embed_dim, r->eps, r->slope));
+    if (!r->features && !r->argmax) return c.bad("every output is null");
+    if (r->features) HS_TRY(c.dtype(r->features_dtype, "features"));
+    const uintptr_t rsize = elem_size(r->rows_dtype), fsize = elem_size(r->features_dtype);
+    if (!aligned(4, {r->params})) return c.bad("params must be 4-byte aligned");
+    if (!aligned(rsize, {r->rows}) || !aligned(fsize, {r->features})) return c.bad("rows and features must be aligned to their element size");
     const uintptr_t n = (uintptr_t)r->n, E = (uintptr_t)r->embed_dim;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange in[] = {range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_EMBED_PARAM_ROWS * E * 4)};
-    const GaeRange out[] = {range("features", r->features, r->features ? n * 4 * E * fsize : 0), range("argmax", r->argmax, r->argmax ? n * 3 * E : 0)};
-    for (size_t i = 0; i < sizeof(out) / sizeof(out[0]); ++i) {
-        for (const GaeRange &x : in)
-            if (gae_overlap(out[i], x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_entity_encode: ") + out[i].name + " overlaps " + x.name);
-        for (size_t j = 0; j < i; ++j)
-            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string("hs_entity_encode: ") + out[i].name + " overlaps " + out[j].name);
-    }
-    return check_embed_state(s, "hs_entity_encode");
+    HS_TRY(c.disjoint({range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_EMBED_PARAM_ROWS * E * 4)},
+                      {range("features", r->features, n * 4 * E * fsize), range("argmax", r->argmax, n * 3 * E)}));
+    return c.handle_ready(s);
 }
 
 int check_embed_bwd(hs_sim *s, const hs_entity_encode_backward_request *r) {
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null request");
-    HS_TRY(check_embed_common(s, "hs_entity_encode_backward", r->rows, r->params, r->n, r->rows_dtype, r->embed_dim, r->eps, r->slope));
-    if (!r->grad_features) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null grad_features");
-    if (!r->argmax) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null argmax");
-    if (!r->grad_params) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: null grad_params");
-    if (!pack_dtype_ok(r->grad_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: grad dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    const uintptr_t rsize = r->rows_dtype == HS_DTYPE_F32 ? 4u : 2u, gsize = r->grad_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if (((uintptr_t)r->params | (uintptr_t)r->grad_params) & 3u) return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: params and grad_params must be 4-byte aligned");
-    if (((uintptr_t)r->rows & (rsize - 1)) || ((uintptr_t)r->grad_features & (gsize - 1)))
-        return fail(HS_ERR_INVALID_ARG, "hs_entity_encode_backward: rows and grad_features must be aligned to their element size");
+    const Check c{"hs_entity_encode_backward"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_embed_common(c, r->rows, r->params, r->n, r->rows_dtype, r->embed_dim, r->eps, r->slope));
+    if (!r->grad_features) return c.bad("null grad_features");
+    if (!r->argmax) return c.bad("null argmax");
+    if (!r->grad_params) return c.bad("null grad_params");
+    HS_TRY(c.dtype(r->grad_dtype, "grad"));
+    const uintptr_t rsize = elem_size(r->rows_dtype), gsize = elem_size(r->grad_dtype);
+    if (!aligned(4, {r->params, r->grad_params})) return c.bad("params and grad_params must be 4-byte aligned");
+    if (!aligned(rsize, {r->rows}) || !aligned(gsize, {r->grad_features})) return c.bad("rows and grad_features must be aligned to their element size");
     const uintptr_t n = (uintptr_t)r->n, E = (uintptr_t)r->embed_dim;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange out = range("grad_params", r->grad_params, HS_EMBED_PARAM_ROWS * E * 4);
-    const GaeRange in[] = {range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_EMBED_PARAM_ROWS * E * 4),
-                           range("grad_features", r->grad_features, n * 4 * E * gsize), range("argmax", r->argmax, n * 3 * E)};
-    for (const GaeRange &x : in)
-        if (gae_overlap(out, x)) return fail(HS_ERR_INVALID_ARG, std::string("hs_entity_encode_backward: grad_params overlaps ") + x.name);
-    return check_embed_state(s, "hs_entity_encode_backward");
-}
-
-template <typename F> void with_embed_dim(int32_t E, F f) {
-    if (E == 32) f(std::integral_constant<int, 32>{});
-    else if (E == 64) f(std::integral_constant<int, 64>{});
-    else f(std::integral_constant<int, 128>{});
+    HS_TRY(c.disjoint({range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_EMBED_PARAM_ROWS * E * 4),
+                       range("grad_features", r->grad_features, n * 4 * E * gsize), range("argmax", r->argmax, n * 3 * E)},
+                      {range("grad_params", r->grad_params, HS_EMBED_PARAM_ROWS * E * 4)}));
+    return c.handle_ready(s);
 }
 
 // One k_embed_fwd over the rows (the request has passed check_embed).
 int launch_embed(hs_sim *, hipStream_t strm, const hs_entity_encode_request *r) {
     hs::EmbedArgs a = {};
     a.rows = r->rows; a.params = r->params; a.features = r->features; a.argmax = r->argmax;
-    a.n = r->n; a.rowsType = embed_type(r->rows_dtype); a.featType = embed_type(r->features_dtype); a.eps = r->eps; a.slope = r->slope;
+    a.n = r->n; a.rowsType = elem_code(r->rows_dtype); a.featType = elem_code(r->features_dtype); a.eps = r->eps; a.slope = r->slope;
     const dim3 grid(hs::emb_grid(a.n, r->embed_dim, hs::kEmbMaxGrid)), blk(hs::kEmbThreads);
-    with_embed_dim(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_fwd<decltype(e)::value>), grid, blk, 0, strm, a); });
+    with_constant<32, 64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_fwd<decltype(e)::value>), grid, blk, 0, strm, a); });
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -763,9 +758,9 @@ int launch_embed(hs_sim *, hipStream_t strm, const hs_entity_encode_request *r) 
 int launch_embed_bwd(hs_sim *s, hipStream_t strm, const hs_entity_encode_backward_request *r) {
     hs::EmbedBwdArgs a = {};
     a.rows = r->rows; a.params = r->params; a.gradFeatures = r->grad_features; a.argmax = r->argmax; a.workspace = s->embed_partials;
-    a.n = r->n; a.rowsType = embed_type(r->rows_dtype); a.gradType = embed_type(r->grad_dtype); a.eps = r->eps; a.slope = r->slope;
+    a.n = r->n; a.rowsType = elem_code(r->rows_dtype); a.gradType = elem_code(r->grad_dtype); a.eps = r->eps; a.slope = r->slope;
     const int nparts = hs::emb_grid(a.n, r->embed_dim, hs::kEmbMaxGridBwd), len = hs::kEmbParamRows * r->embed_dim;
-    with_embed_dim(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_bwd<decltype(e)::value>), dim3(nparts), dim3(hs::kEmbThreads), 0, strm, a); });
+    with_constant<32, 64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_bwd<decltype(e)::value>), dim3(nparts), dim3(hs::kEmbThreads), 0, strm, a); });
     hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
                        (const float *)s->embed_partials, nparts, len, r->grad_params);
     HS_HIP(hipGetLastError());
@@ -773,7 +768,7 @@ int launch_embed_bwd(hs_sim *s, hipStream_t strm, const hs_entity_encode_backwar
 }
 }  // namespace
 
-// ---- the recurrent core (hs_k_lstm.h); after the launchers above, so that their kernels are instantiated in the same order as before ----
+// ---- the recurrent core (hs_k_lstm.h) ----
 namespace {
 static_assert(HS_LSTM_PARAM_ROWS == hs::kLstmParamRows && HS_LSTM_MAX_GRID_BWD == hs::kLstmMaxGridBwd && HS_LSTM_MAX_HIDDEN == hs::kLstmMaxH &&
               HS_LSTM_ROWS_PER_ROUND == hs::kLstmWaves, "hs_lstm_cell_request and k_lstm agree");
@@ -786,88 +781,65 @@ static_assert(sizeof(hs_lstm_cell_backward_request) == 104 && offsetof(hs_lstm_c
               offsetof(hs_lstm_cell_backward_request, grad_gates) == 80 && offsetof(hs_lstm_cell_backward_request, grad_cell_params) == 96,
               "hs_lstm_cell_backward_request layout (gpu_hideseek/recurrent.py mirrors it)");
 
-// What the two calls share: `fn` is the entry point's name.
-int check_lstm_common(const char *fn, const void *gates, const float *c_prev, const float *cell_params, const int32_t *clear, int32_t n, int32_t H,
+// What the two calls share.
+int check_lstm_common(const Check &c, const void *gates, const float *c_prev, const float *cell_params, const int32_t *clear, int32_t n, int32_t H,
                       int32_t gates_dtype, float eps) {
-    const std::string f = std::string(fn) + ": ";
-    if (!gates) return fail(HS_ERR_INVALID_ARG, f + "null gates");
-    if (!c_prev) return fail(HS_ERR_INVALID_ARG, f + "null c_prev");
-    if (!cell_params) return fail(HS_ERR_INVALID_ARG, f + "null cell_params");
-    if (!pack_dtype_ok(gates_dtype)) return fail(HS_ERR_INVALID_ARG, f + "gates dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    if (H != 64 && H != 128 && H != 256 && H != 512) return fail(HS_ERR_INVALID_ARG, f + "hidden must be 64, 128, 256 or 512");
-    if (n < 1 || (int64_t)n * 4 * H >= (int64_t)1 << 31) return fail(HS_ERR_INVALID_ARG, f + "n must be at least 1 and n * 4 * hidden below 2^31");
-    if (!std::isfinite(eps) || !(eps > 0.f)) return fail(HS_ERR_INVALID_ARG, f + "eps must be finite and above 0");
-    if (((uintptr_t)c_prev | (uintptr_t)cell_params | (uintptr_t)clear) & 3u)
-        return fail(HS_ERR_INVALID_ARG, f + "c_prev, cell_params and clear must be 4-byte aligned");
-    if ((uintptr_t)gates & (gates_dtype == HS_DTYPE_F32 ? 3u : 1u)) return fail(HS_ERR_INVALID_ARG, f + "gates must be aligned to its element size");
+    if (!gates) return c.bad("null gates");
+    if (!c_prev) return c.bad("null c_prev");
+    if (!cell_params) return c.bad("null cell_params");
+    HS_TRY(c.dtype(gates_dtype, "gates"));
+    if (H != 64 && H != 128 && H != 256 && H != 512) return c.bad("hidden must be 64, 128, 256 or 512");
+    if (!count_ok(n, {4 * H})) return c.bad("n must be at least 1 and n * 4 * hidden below 2^31");
+    if (!std::isfinite(eps) || !(eps > 0.f)) return c.bad("eps must be finite and above 0");
+    if (!aligned(4, {c_prev, cell_params, clear})) return c.bad("c_prev, cell_params and clear must be 4-byte aligned");
+    if (!aligned(elem_size(gates_dtype), {gates})) return c.bad("gates must be aligned to its element size");
     return HS_OK;
 }
 
-int check_lstm_ranges(hs_sim *s, const char *fn, const GaeRange *in, size_t nin, const GaeRange *out, size_t nout) {
-    for (size_t i = 0; i < nout; ++i) {
-        for (size_t k = 0; k < nin; ++k)
-            if (gae_overlap(out[i], in[k])) return fail(HS_ERR_INVALID_ARG, std::string(fn) + ": " + out[i].name + " overlaps " + in[k].name);
-        for (size_t j = 0; j < i; ++j)
-            if (gae_overlap(out[i], out[j])) return fail(HS_ERR_INVALID_ARG, std::string(fn) + ": " + out[i].name + " overlaps " + out[j].name);
-    }
-    return check_embed_state(s, fn);
-}
-
 int check_lstm(hs_sim *s, const hs_lstm_cell_request *r) {
-    const char *fn = "hs_lstm_cell";
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: null request");
-    HS_TRY(check_lstm_common(fn, r->gates, r->c_prev, r->cell_params, r->clear, r->n, r->hidden, r->gates_dtype, r->eps));
-    if (!r->y && !r->h_next && !r->c_next) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: every output is null");
-    if (r->y && !pack_dtype_ok(r->y_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: y dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    const uintptr_t gsize = r->gates_dtype == HS_DTYPE_F32 ? 4u : 2u, ysize = r->y_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if ((r->y && ((uintptr_t)r->y & (ysize - 1))) || ((uintptr_t)r->h_next & (gsize - 1)))
-        return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: y and h_next must be aligned to their element size");
-    if ((uintptr_t)r->c_next & 3u) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell: c_next must be 4-byte aligned");
+    const Check c{"hs_lstm_cell"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_lstm_common(c, r->gates, r->c_prev, r->cell_params, r->clear, r->n, r->hidden, r->gates_dtype, r->eps));
+    if (!r->y && !r->h_next && !r->c_next) return c.bad("every output is null");
+    if (r->y) HS_TRY(c.dtype(r->y_dtype, "y"));
+    const uintptr_t gsize = elem_size(r->gates_dtype), ysize = elem_size(r->y_dtype);
+    if (!aligned(ysize, {r->y}) || !aligned(gsize, {r->h_next})) return c.bad("y and h_next must be aligned to their element size");
+    if (!aligned(4, {r->c_next})) return c.bad("c_next must be 4-byte aligned");
     const uintptr_t n = (uintptr_t)r->n, H = (uintptr_t)r->hidden;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange in[] = {range("gates", r->gates, n * 4 * H * gsize), range("c_prev", r->c_prev, n * H * 4),
-                           range("cell_params", r->cell_params, HS_LSTM_PARAM_ROWS * H * 4), range("clear", r->clear, n * 4)};
-    const GaeRange out[] = {range("y", r->y, r->y ? n * H * ysize : 0), range("h_next", r->h_next, n * H * gsize), range("c_next", r->c_next, n * H * 4)};
-    return check_lstm_ranges(s, fn, in, 4, out, 3);
+    HS_TRY(c.disjoint({range("gates", r->gates, n * 4 * H * gsize), range("c_prev", r->c_prev, n * H * 4),
+                       range("cell_params", r->cell_params, HS_LSTM_PARAM_ROWS * H * 4), range("clear", r->clear, n * 4)},
+                      {range("y", r->y, n * H * ysize), range("h_next", r->h_next, n * H * gsize), range("c_next", r->c_next, n * H * 4)}));
+    return c.handle_ready(s);
 }
 
 int check_lstm_bwd(hs_sim *s, const hs_lstm_cell_backward_request *r) {
-    const char *fn = "hs_lstm_cell_backward";
-    if (!r) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: null request");
-    HS_TRY(check_lstm_common(fn, r->gates, r->c_prev, r->cell_params, r->clear, r->n, r->hidden, r->gates_dtype, r->eps));
-    if (!r->grad_y) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: null grad_y");
-    if (!r->grad_gates && !r->grad_c_prev && !r->grad_cell_params) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: every output is null");
-    if (!pack_dtype_ok(r->y_dtype)) return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: y dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
-    const uintptr_t gsize = r->gates_dtype == HS_DTYPE_F32 ? 4u : 2u, ysize = r->y_dtype == HS_DTYPE_F32 ? 4u : 2u;
-    if (((uintptr_t)r->grad_y & (ysize - 1)) || (((uintptr_t)r->grad_h_next | (uintptr_t)r->grad_gates) & (gsize - 1)))
-        return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: grad_y, grad_h_next and grad_gates must be aligned to their element size");
-    if (((uintptr_t)r->grad_c_next | (uintptr_t)r->grad_c_prev | (uintptr_t)r->grad_cell_params) & 3u)
-        return fail(HS_ERR_INVALID_ARG, "hs_lstm_cell_backward: grad_c_next, grad_c_prev and grad_cell_params must be 4-byte aligned");
+    const Check c{"hs_lstm_cell_backward"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_lstm_common(c, r->gates, r->c_prev, r->cell_params, r->clear, r->n, r->hidden, r->gates_dtype, r->eps));
+    if (!r->grad_y) return c.bad("null grad_y");
+    if (!r->grad_gates && !r->grad_c_prev && !r->grad_cell_params) return c.bad("every output is null");
+    HS_TRY(c.dtype(r->y_dtype, "y"));
+    const uintptr_t gsize = elem_size(r->gates_dtype), ysize = elem_size(r->y_dtype);
+    if (!aligned(ysize, {r->grad_y}) || !aligned(gsize, {r->grad_h_next, r->grad_gates}))
+        return c.bad("grad_y, grad_h_next and grad_gates must be aligned to their element size");
+    if (!aligned(4, {r->grad_c_next, r->grad_c_prev, r->grad_cell_params})) return c.bad("grad_c_next, grad_c_prev and grad_cell_params must be 4-byte aligned");
     const uintptr_t n = (uintptr_t)r->n, H = (uintptr_t)r->hidden;
-    auto range = [](const char *name, const void *p, uintptr_t bytes) { return GaeRange{name, (uintptr_t)p, (uintptr_t)p + bytes}; };
-    const GaeRange in[] = {range("gates", r->gates, n * 4 * H * gsize), range("c_prev", r->c_prev, n * H * 4),
-                           range("cell_params", r->cell_params, HS_LSTM_PARAM_ROWS * H * 4), range("clear", r->clear, n * 4),
-                           range("grad_y", r->grad_y, n * H * ysize), range("grad_h_next", r->grad_h_next, n * H * gsize),
-                           range("grad_c_next", r->grad_c_next, n * H * 4)};
-    const GaeRange out[] = {range("grad_gates", r->grad_gates, n * 4 * H * gsize), range("grad_c_prev", r->grad_c_prev, n * H * 4),
-                            range("grad_cell_params", r->grad_cell_params, HS_LSTM_PARAM_ROWS * H * 4)};
-    return check_lstm_ranges(s, fn, in, 7, out, 3);
-}
-
-template <typename F> void with_lstm_hidden(int32_t H, F f) {
-    if (H == 64) f(std::integral_constant<int, 64>{});
-    else if (H == 128) f(std::integral_constant<int, 128>{});
-    else if (H == 256) f(std::integral_constant<int, 256>{});
-    else f(std::integral_constant<int, 512>{});
+    HS_TRY(c.disjoint({range("gates", r->gates, n * 4 * H * gsize), range("c_prev", r->c_prev, n * H * 4),
+                       range("cell_params", r->cell_params, HS_LSTM_PARAM_ROWS * H * 4), range("clear", r->clear, n * 4),
+                       range("grad_y", r->grad_y, n * H * ysize), range("grad_h_next", r->grad_h_next, n * H * gsize),
+                       range("grad_c_next", r->grad_c_next, n * H * 4)},
+                      {range("grad_gates", r->grad_gates, n * 4 * H * gsize), range("grad_c_prev", r->grad_c_prev, n * H * 4),
+                       range("grad_cell_params", r->grad_cell_params, HS_LSTM_PARAM_ROWS * H * 4)}));
+    return c.handle_ready(s);
 }
 
 // One k_lstm_fwd over the rows (the request has passed check_lstm).
 int launch_lstm(hs_sim *, hipStream_t strm, const hs_lstm_cell_request *r) {
     hs::LstmArgs a = {};
     a.gates = r->gates; a.cPrev = r->c_prev; a.params = r->cell_params; a.clear = r->clear; a.y = r->y; a.hNext = r->h_next; a.cNext = r->c_next;
-    a.n = r->n; a.gatesType = embed_type(r->gates_dtype); a.yType = embed_type(r->y_dtype); a.eps = r->eps;
+    a.n = r->n; a.gatesType = elem_code(r->gates_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps;
     const dim3 grid(hs::lstm_grid(a.n, hs::kLstmMaxGrid)), blk(hs::kLstmThreads);
-    with_lstm_hidden(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_fwd<decltype(h)::value>), grid, blk, 0, strm, a); });
+    with_constant<64, 128, 256, 512>(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_fwd<decltype(h)::value>), grid, blk, 0, strm, a); });
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -878,9 +850,9 @@ int launch_lstm_bwd(hs_sim *s, hipStream_t strm, const hs_lstm_cell_backward_req
     a.gates = r->gates; a.cPrev = r->c_prev; a.params = r->cell_params; a.clear = r->clear;
     a.gradY = r->grad_y; a.gradHNext = r->grad_h_next; a.gradCNext = r->grad_c_next;
     a.gradGates = r->grad_gates; a.gradCPrev = r->grad_c_prev; a.workspace = r->grad_cell_params ? s->lstm_partials : nullptr;
-    a.n = r->n; a.gatesType = embed_type(r->gates_dtype); a.yType = embed_type(r->y_dtype); a.eps = r->eps;
+    a.n = r->n; a.gatesType = elem_code(r->gates_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps;
     const int nparts = hs::lstm_grid(a.n, hs::kLstmMaxGridBwd), len = hs::kLstmParamRows * r->hidden;
-    with_lstm_hidden(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_bwd<decltype(h)::value>), dim3(nparts), dim3(hs::kLstmThreads), 0, strm, a); });
+    with_constant<64, 128, 256, 512>(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_bwd<decltype(h)::value>), dim3(nparts), dim3(hs::kLstmThreads), 0, strm, a); });
     if (r->grad_cell_params)
         hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
                            (const float *)s->lstm_partials, nparts, len, r->grad_cell_params);
@@ -905,6 +877,36 @@ int load_slots(hs_sim *s, std::vector<int32_t> &slot) {
     slot.resize(s->S.N);
     HS_HIP(hipMemcpy(slot.data(), s->S.slotOfWorld, slot.size() * 4, hipMemcpyDeviceToHost));
     return HS_OK;
+}
+}  // namespace
+
+namespace {
+// The handle's own stream starts after everything already queued on the device's legacy default stream: that is
+// where torch (and scripts/benchmark.py:82-84) writes `action` / `reset` between steps.
+int order_after_default_stream(hs_sim *s) {
+    HS_HIP(hipEventRecord(s->evIn, nullptr));
+    HS_HIP(hipStreamWaitEvent(s->stream, s->evIn, 0));
+    return HS_OK;
+}
+// A blocking call: `launch(s, stream, args...)` on the handle's own stream, after the default stream's work, and waited for.
+template <typename... A> int run_blocking(hs_sim *s, int (*launch)(hs_sim *, hipStream_t, A...), std::common_type_t<A>... args) {
+    HS_TRY(order_after_default_stream(s));
+    HS_TRY(launch(s, s->stream, args...));
+    HS_HIP(hipStreamSynchronize(s->stream));
+    return HS_OK;
+}
+// The two forms of a learner entry point: `check(s, args...)`, then `launch` blocking as above, or on the caller's stream.
+template <typename... A>
+int call_blocking(hs_sim *s, int (*check)(hs_sim *, A...), int (*launch)(hs_sim *, hipStream_t, A...), std::common_type_t<A>... args) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check(s, args...));
+    return run_blocking(s, launch, args...);
+}
+template <typename... A>
+int call_async(hs_sim *s, void *hip_stream, int (*check)(hs_sim *, A...), int (*launch)(hs_sim *, hipStream_t, A...), std::common_type_t<A>... args) {
+    HS_ENTER(s, "null sim");
+    HS_TRY(check(s, args...));
+    return launch(s, (hipStream_t)hip_stream, args...);
 }
 }  // namespace
 
@@ -1033,26 +1035,9 @@ void hs_destroy(hs_sim *s) {
 
 int32_t hs_agents_per_world(const hs_sim *s) { return s ? s->A : 0; }
 
-namespace {
-// The handle's own stream starts after everything already queued on the device's legacy default stream: that is
-// where torch (and scripts/benchmark.py:82-84) writes `action` / `reset` between steps.
-int order_after_default_stream(hs_sim *s) {
-    HS_HIP(hipEventRecord(s->evIn, nullptr));
-    HS_HIP(hipStreamWaitEvent(s->stream, s->evIn, 0));
-    return HS_OK;
-}
-// A blocking call: `launch(s, stream)` on the handle's own stream, after the default stream's work, and waited for.
-int run_blocking(hs_sim *s, int (*launch)(hs_sim *, hipStream_t)) {
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch(s, s->stream));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-}  // namespace
-
 int32_t hs_init(hs_sim *s) {
     HS_ENTER(s, "null sim");
-    HS_TRY(run_blocking(s, [](hs_sim *s, hipStream_t strm) { return launch_step(s, strm, true); }));
+    HS_TRY(run_blocking(s, +[](hs_sim *s, hipStream_t strm) { return launch_step(s, strm, true); }));
     s->initialised = true;
     return HS_OK;
 }
@@ -1117,7 +1102,7 @@ int32_t hs_render(hs_sim *s) {
     if (!s->initialised) return fail(HS_ERR_INVALID_ARG, "hs_render before hs_init");
     if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_render inside an open step");
     HS_TRY(ensure_render_buffers(s));
-    return run_blocking(s, [](hs_sim *s, hipStream_t strm) -> int {
+    return run_blocking(s, +[](hs_sim *s, hipStream_t strm) -> int {
         launch_render(s, strm);
         HS_HIP(hipGetLastError());
         return HS_OK;
@@ -1305,163 +1290,32 @@ int32_t hs_jax_load_checkpoints(hs_sim *s, void *hip_stream, void **buffers) {
     return copy_out_observations(s, strm, &buffers);
 }
 
-// ---- policy inputs (hs_k_pack.h; check_pack / launch_pack above) ----
-int32_t hs_pack_policy_inputs_async(hs_sim *s, void *hip_stream, const hs_pack_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_pack(s, req));
-    return launch_pack(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_pack_policy_inputs(hs_sim *s, const hs_pack_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_pack(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_pack(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- action sampling (hs_k_sample.h; check_sample / launch_sample above) ----
-int32_t hs_sample_actions_async(hs_sim *s, void *hip_stream, const hs_sample_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_sample(s, req));
-    return launch_sample(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_sample_actions(hs_sim *s, const hs_sample_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_sample(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_sample(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- advantages and value targets (hs_k_gae.h; check_gae / launch_gae above) ----
-int32_t hs_compute_gae_async(hs_sim *s, void *hip_stream, const hs_gae_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_gae(s, req));
-    return launch_gae(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_compute_gae(hs_sim *s, const hs_gae_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_gae(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_gae(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- the PPO loss and its gradients (hs_k_ppo.h; check_ppo / launch_ppo above) ----
-int32_t hs_ppo_loss_async(hs_sim *s, void *hip_stream, const hs_ppo_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_ppo(s, req));
-    return launch_ppo(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_ppo_loss(hs_sim *s, const hs_ppo_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_ppo(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_ppo(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- the two-hot symlog critic head (hs_k_twohot.h; check_twohot / launch_twohot above) ----
-int32_t hs_twohot_value_async(hs_sim *s, void *hip_stream, const hs_twohot_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_twohot(s, req));
-    return launch_twohot(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_twohot_value(hs_sim *s, const hs_twohot_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_twohot(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_twohot(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- the entity encoder (hs_k_embed.h; check_embed / launch_embed above) ----
-int32_t hs_entity_encode_async(hs_sim *s, void *hip_stream, const hs_entity_encode_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_embed(s, req));
-    return launch_embed(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_entity_encode(hs_sim *s, const hs_entity_encode_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_embed(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_embed(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-int32_t hs_entity_encode_backward_async(hs_sim *s, void *hip_stream, const hs_entity_encode_backward_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_embed_bwd(s, req));
-    return launch_embed_bwd(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_entity_encode_backward(hs_sim *s, const hs_entity_encode_backward_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_embed_bwd(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_embed_bwd(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- the recurrent core (hs_k_lstm.h; check_lstm / launch_lstm above) ----
-int32_t hs_lstm_cell_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_lstm(s, req));
-    return launch_lstm(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_lstm_cell(hs_sim *s, const hs_lstm_cell_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_lstm(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_lstm(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-int32_t hs_lstm_cell_backward_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_backward_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_lstm_bwd(s, req));
-    return launch_lstm_bwd(s, (hipStream_t)hip_stream, req);
-}
-int32_t hs_lstm_cell_backward(hs_sim *s, const hs_lstm_cell_backward_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_lstm_bwd(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_lstm_bwd(s, s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
-}
-
-// ---- observation normaliser (hs_k_norm.h; check_norm_update / launch_pack_norm above) ----
-int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_norm_update(s, req));
-    return launch_norm_update((hipStream_t)hip_stream, req);
-}
-int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_norm_update(s, req));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_norm_update(s->stream, req));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
+// ---- the learner calls (check_* / launch_* above) ----
+int32_t hs_pack_policy_inputs(hs_sim *s, const hs_pack_request *req) { return call_blocking(s, check_pack, launch_pack, req); }
+int32_t hs_pack_policy_inputs_async(hs_sim *s, void *hip_stream, const hs_pack_request *req) { return call_async(s, hip_stream, check_pack, launch_pack, req); }
+int32_t hs_sample_actions(hs_sim *s, const hs_sample_request *req) { return call_blocking(s, check_sample, launch_sample, req); }
+int32_t hs_sample_actions_async(hs_sim *s, void *hip_stream, const hs_sample_request *req) { return call_async(s, hip_stream, check_sample, launch_sample, req); }
+int32_t hs_compute_gae(hs_sim *s, const hs_gae_request *req) { return call_blocking(s, check_gae, launch_gae, req); }
+int32_t hs_compute_gae_async(hs_sim *s, void *hip_stream, const hs_gae_request *req) { return call_async(s, hip_stream, check_gae, launch_gae, req); }
+int32_t hs_ppo_loss(hs_sim *s, const hs_ppo_request *req) { return call_blocking(s, check_ppo, launch_ppo, req); }
+int32_t hs_ppo_loss_async(hs_sim *s, void *hip_stream, const hs_ppo_request *req) { return call_async(s, hip_stream, check_ppo, launch_ppo, req); }
+int32_t hs_twohot_value(hs_sim *s, const hs_twohot_request *req) { return call_blocking(s, check_twohot, launch_twohot, req); }
+int32_t hs_twohot_value_async(hs_sim *s, void *hip_stream, const hs_twohot_request *req) { return call_async(s, hip_stream, check_twohot, launch_twohot, req); }
+int32_t hs_entity_encode(hs_sim *s, const hs_entity_encode_request *req) { return call_blocking(s, check_embed, launch_embed, req); }
+int32_t hs_entity_encode_async(hs_sim *s, void *hip_stream, const hs_entity_encode_request *req) { return call_async(s, hip_stream, check_embed, launch_embed, req); }
+int32_t hs_entity_encode_backward(hs_sim *s, const hs_entity_encode_backward_request *req) { return call_blocking(s, check_embed_bwd, launch_embed_bwd, req); }
+int32_t hs_entity_encode_backward_async(hs_sim *s, void *hip_stream, const hs_entity_encode_backward_request *req) { return call_async(s, hip_stream, check_embed_bwd, launch_embed_bwd, req); }
+int32_t hs_lstm_cell(hs_sim *s, const hs_lstm_cell_request *req) { return call_blocking(s, check_lstm, launch_lstm, req); }
+int32_t hs_lstm_cell_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_request *req) { return call_async(s, hip_stream, check_lstm, launch_lstm, req); }
+int32_t hs_lstm_cell_backward(hs_sim *s, const hs_lstm_cell_backward_request *req) { return call_blocking(s, check_lstm_bwd, launch_lstm_bwd, req); }
+int32_t hs_lstm_cell_backward_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_backward_request *req) { return call_async(s, hip_stream, check_lstm_bwd, launch_lstm_bwd, req); }
+int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
+int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
+int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {
+    return call_blocking(s, check_pack_norm, launch_pack_norm, req, table);
 }
 int32_t hs_pack_policy_inputs_normalized_async(hs_sim *s, void *hip_stream, const hs_pack_request *req, const float *table) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_pack_norm(s, req, table));
-    return launch_pack_norm(s, (hipStream_t)hip_stream, req, table);
-}
-int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {
-    HS_ENTER(s, "null sim");
-    HS_TRY(check_pack_norm(s, req, table));
-    HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_pack_norm(s, s->stream, req, table));
-    HS_HIP(hipStreamSynchronize(s->stream));
-    return HS_OK;
+    return call_async(s, hip_stream, check_pack_norm, launch_pack_norm, req, table);
 }
 
 // ---- XLA custom-call targets (the original, status-less GPU custom-call ABI) ----

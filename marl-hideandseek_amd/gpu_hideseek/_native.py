@@ -86,38 +86,14 @@ def load():
     L.hs_render_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     L.hs_render_cameras.restype = C.c_int32
-    L.hs_pack_policy_inputs.argtypes = [C.c_void_p, C.c_void_p]                 # (sim, const hs_pack_request *)
-    L.hs_pack_policy_inputs.restype = C.c_int32
-    L.hs_pack_policy_inputs_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]   # (sim, hipStream_t, request)
-    L.hs_pack_policy_inputs_async.restype = C.c_int32
-    L.hs_pack_policy_inputs_normalized.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]      # (sim, request, const float *table)
-    L.hs_pack_policy_inputs_normalized.restype = C.c_int32
-    L.hs_pack_policy_inputs_normalized_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]    # (sim, hipStream_t, request, table)
-    L.hs_pack_policy_inputs_normalized_async.restype = C.c_int32
-    L.hs_obs_norm_update.argtypes = [C.c_void_p, C.c_void_p]                    # (sim, const hs_obs_norm_request *)
-    L.hs_obs_norm_update.restype = C.c_int32
-    L.hs_obs_norm_update_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]      # (sim, hipStream_t, request)
-    L.hs_obs_norm_update_async.restype = C.c_int32
-    L.hs_sample_actions.argtypes = [C.c_void_p, C.c_void_p]                     # (sim, const hs_sample_request *)
-    L.hs_sample_actions.restype = C.c_int32
-    L.hs_sample_actions_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]       # (sim, hipStream_t, request)
-    L.hs_sample_actions_async.restype = C.c_int32
-    L.hs_compute_gae.argtypes = [C.c_void_p, C.c_void_p]                        # (sim, const hs_gae_request *)
-    L.hs_compute_gae.restype = C.c_int32
-    L.hs_compute_gae_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]          # (sim, hipStream_t, request)
-    L.hs_compute_gae_async.restype = C.c_int32
-    L.hs_ppo_loss.argtypes = [C.c_void_p, C.c_void_p]                           # (sim, const hs_ppo_request *)
-    L.hs_ppo_loss.restype = C.c_int32
-    L.hs_ppo_loss_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]             # (sim, hipStream_t, request)
-    L.hs_ppo_loss_async.restype = C.c_int32
-    L.hs_twohot_value.argtypes = [C.c_void_p, C.c_void_p]                       # (sim, const hs_twohot_request *)
-    L.hs_twohot_value.restype = C.c_int32
-    L.hs_twohot_value_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]         # (sim, hipStream_t, request)
-    L.hs_twohot_value_async.restype = C.c_int32
-    for fn in ("hs_entity_encode", "hs_entity_encode_backward", "hs_lstm_cell", "hs_lstm_cell_backward"):
-        getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p]                          # (sim, const request *)
+    # the request entry points: fn(sim, const request *) and fn_async(sim, hipStream_t, const request *); the _normalized
+    # pack takes `const float *table` after the request
+    for fn, extra in (("hs_pack_policy_inputs", []), ("hs_pack_policy_inputs_normalized", [C.c_void_p]), ("hs_obs_norm_update", []),
+                      ("hs_sample_actions", []), ("hs_compute_gae", []), ("hs_ppo_loss", []), ("hs_twohot_value", []),
+                      ("hs_entity_encode", []), ("hs_entity_encode_backward", []), ("hs_lstm_cell", []), ("hs_lstm_cell_backward", [])):
+        getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p] + extra
         getattr(L, fn).restype = C.c_int32
-        getattr(L, fn + "_async").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]   # (sim, hipStream_t, request)
+        getattr(L, fn + "_async").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + extra
         getattr(L, fn + "_async").restype = C.c_int32
     L.hs_trigger_reset.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.hs_trigger_reset.restype = C.c_int32

@@ -13,7 +13,7 @@ dealt to shards.
 """
 import ctypes as C
 
-from .policy_inputs import _DTYPES, _per_shard, stream_handle
+from ._request import _DTYPES, _name, _per_shard, _run, _sharded
 
 HEADS = 5             # HS_SAMPLE_HEADS
 MAX_BUCKETS = 16      # HS_SAMPLE_MAX_BUCKETS
@@ -33,10 +33,6 @@ class HsSampleRequest(C.Structure):
                 ("buckets", C.c_int32 * HEADS), ("mode", C.c_int32), ("flags", C.c_uint32), ("seed", C.c_uint32 * 2),
                 ("counter", C.c_uint32), ("action", C.c_void_p), ("log_prob", C.c_void_p), ("entropy", C.c_void_p),
                 ("head_log_prob", C.c_void_p)]
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
 
 
 def _output(name, t, rows, dev):
@@ -115,12 +111,8 @@ def _result(sim, res):
 
 def sample(sim, logits, stream=None, **kw):
     """HideAndSeekSimulator.sample_actions."""
-    from ._native import check
     res, req = request(sim.num_worlds * sim.agents_per_world, sim.gpu_id, logits, **kw)
-    if stream is None:
-        check(sim._L.hs_sample_actions(sim._h, C.byref(req)))
-    else:
-        check(sim._L.hs_sample_actions_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+    _run(sim, "hs_sample_actions", req, stream)
     return _result(sim, res)
 
 
@@ -130,22 +122,11 @@ def sample_sharded(ssim, logits, stream=None, action=None, log_prob=None, entrop
     per shard; returns the list of the shards' results.  With stream=None every shard's call is enqueued on a side stream
     of its device, ordered after that device's current stream, before any is waited for."""
     import torch
-    from ._native import check
     n = len(ssim.shards)
     if isinstance(logits, torch.Tensor) or len(logits) != n:
         raise ValueError(f"logits: one tensor per shard ({n}) expected")
-    outs = [_per_shard(ssim, k, v) for k, v in (("action", action), ("log_prob", log_prob), ("entropy", entropy),
-                                                 ("head_log_prob", head_log_prob))]
-    streams = _per_shard(ssim, "stream", stream)
-    reqs = [request(s.num_worlds * s.agents_per_world, s.gpu_id, lg, action=a, log_prob=lp, entropy=e, head_log_prob=hl, **kw)
-            for s, lg, a, lp, e, hl in zip(ssim.shards, logits, *outs)]
-    waits = []
-    for s, (res, req), st in zip(ssim.shards, reqs, streams):
-        if st is None:
-            st = torch.cuda.Stream(device=s.gpu_id)
-            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
-            waits.append(st)
-        check(s._L.hs_sample_actions_async(s._h, C.c_void_p(stream_handle(st)), C.byref(req)))
-    for st in waits:
-        st.synchronize()
-    return [_result(s, res) for s, (res, _) in zip(ssim.shards, reqs)]
+    outs = {k: _per_shard(ssim, k, v) for k, v in (("action", action), ("log_prob", log_prob), ("entropy", entropy),
+                                                   ("head_log_prob", head_log_prob))}
+    res = _sharded(ssim, "hs_sample_actions", lambda i, s: request(s.num_worlds * s.agents_per_world, s.gpu_id, logits[i],
+                                                                    **{k: v[i] for k, v in outs.items()}, **kw), stream)
+    return [_result(s, r) for s, r in zip(ssim.shards, res)]

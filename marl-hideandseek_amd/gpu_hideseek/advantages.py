@@ -14,7 +14,7 @@ is the same bit for bit on every call, and for every way of dealing the worlds t
 import ctypes as C
 import math
 
-from .policy_inputs import _DTYPES, _per_shard, stream_handle
+from ._request import _DTYPES, _name, _per_shard, _run, _sharded
 
 MAX_STEPS = 4096      # HS_GAE_MAX_STEPS
 MOMENTS = 5           # HS_GAE_MOMENTS: sum adv, sum adv^2, sum ret, sum ret^2, count of active (t, row) pairs
@@ -27,10 +27,6 @@ class HsGaeRequest(C.Structure):
     _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("value", C.c_void_p), ("bootstrap", C.c_void_p),
                 ("mask", C.c_void_p), ("value_dtype", C.c_int32), ("steps", C.c_int32), ("gamma", C.c_float),
                 ("lambda", C.c_float), ("advantage", C.c_void_p), ("returns", C.c_void_p), ("moments", C.c_void_p)]
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
 
 
 def moments_to_mean_std(moments):
@@ -146,12 +142,8 @@ def request(num_worlds, agents, gpu_id, rewards, dones, values, bootstrap, gamma
 
 def compute(sim, rewards, dones, values, bootstrap, stream=None, **kw):
     """HideAndSeekSimulator.compute_advantages."""
-    from ._native import check
     res, req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, rewards, dones, values, bootstrap, **kw)
-    if stream is None:
-        check(sim._L.hs_compute_gae(sim._h, C.byref(req)))
-    else:
-        check(sim._L.hs_compute_gae_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+    _run(sim, "hs_compute_gae", req, stream)
     return res
 
 
@@ -162,22 +154,11 @@ def compute_sharded(ssim, rewards, dones, values, bootstrap, stream=None, mask=N
     or a list with one entry per shard; returns the list of the shards' results.  With stream=None every shard's call is
     enqueued on a side stream of its device, ordered after that device's current stream, before any is waited for."""
     import torch
-    from ._native import check
     n = len(ssim.shards)
     for name, arg in (("rewards", rewards), ("dones", dones), ("values", values), ("bootstrap", bootstrap)):
         if isinstance(arg, torch.Tensor) or len(arg) != n:
             raise ValueError(f"{name}: one tensor per shard ({n}) expected")
-    opt = [_per_shard(ssim, k, v) for k, v in (("mask", mask), ("advantages", advantages), ("returns", returns), ("moments", moments))]
-    streams = _per_shard(ssim, "stream", stream)
-    reqs = [request(s.num_worlds, s.agents_per_world, s.gpu_id, r, d, v, b, mask=m, advantages=a, returns=rt, moments=mo, **kw)
-            for s, r, d, v, b, m, a, rt, mo in zip(ssim.shards, rewards, dones, values, bootstrap, *opt)]
-    waits = []
-    for s, (res, req), st in zip(ssim.shards, reqs, streams):
-        if st is None:
-            st = torch.cuda.Stream(device=s.gpu_id)
-            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
-            waits.append(st)
-        check(s._L.hs_compute_gae_async(s._h, C.c_void_p(stream_handle(st)), C.byref(req)))
-    for st in waits:
-        st.synchronize()
-    return [res for res, _ in reqs]
+    opt = {k: _per_shard(ssim, k, v) for k, v in (("mask", mask), ("advantages", advantages), ("returns", returns), ("moments", moments))}
+    return _sharded(ssim, "hs_compute_gae",
+                    lambda i, s: request(s.num_worlds, s.agents_per_world, s.gpu_id, rewards[i], dones[i], values[i], bootstrap[i],
+                                         **{k: v[i] for k, v in opt.items()}, **kw), stream)

@@ -24,8 +24,8 @@ way.  eager() is the same composition in plain torch, for readers, tools/embed_b
 import ctypes as C
 import math
 
-from .policy_inputs import _DTYPES, ROW, TABLES, _per_shard, stream_handle
-from .ppo_loss import _name, _overlap
+from ._request import _DTYPES, _disjoint, _given, _name, _per_shard, _run, _shard_list, _shard_params, _sharded
+from .policy_inputs import ROW, TABLES
 
 EMBED_DIMS = (32, 64, 128)
 PARAM_ROWS = 102          # HS_EMBED_PARAM_ROWS: the sum over the tables of K + 3
@@ -149,33 +149,6 @@ def _flat(name, t, E, dev):
         raise ValueError(f"{what}: it is not contiguous")
 
 
-def _given(name, t, shape, dtypes, dev):
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be True, None or a torch tensor")
-    what = f"{name} must be a contiguous {' / '.join(dtypes)} tensor of shape {shape} on {dev}"
-    if tuple(t.shape) != shape:
-        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
-    if _name(t.dtype) not in dtypes:
-        raise ValueError(f"{what}: its dtype is {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
-
-
-def _disjoint(outputs, inputs, dev):
-    for k, t in outputs:
-        for k2, t2 in inputs:
-            if _overlap(t, t2):
-                raise ValueError(f"{k} overlaps {k2}")
-    for i, (k, t) in enumerate(outputs):
-        for k2, t2 in outputs[:i]:
-            if _overlap(t, t2):
-                raise ValueError(f"{k} overlaps {k2}")
-    for k, t in inputs + outputs:
-        if t.device != dev:
-            raise ValueError(f"{k} must be on {dev}: it is on {t.device}")
-
-
 def request(gpu_id, rows, params, embed_dim=64, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, features=True, argmax=None, dtype=None):
     """Validate a forward call over the n = rows.shape[0] rows on GPU `gpu_id`, allocate the outputs given as True
     (features in `dtype`, by default the dtype of the rows; argmax uint8 [n, 3, E]), and return ({name: tensor},
@@ -228,14 +201,6 @@ def request_backward(gpu_id, rows, params, grad_features, argmax, embed_dim=64, 
     return {"grad_params": grad_params}, req
 
 
-def _run(sim, fn, req, stream):
-    from ._native import check
-    if stream is None:
-        check(getattr(sim._L, fn)(sim._h, C.byref(req)))
-    else:
-        check(getattr(sim._L, fn + "_async")(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
-
-
 def compute(sim, rows, params, stream=None, **kw):
     """HideAndSeekSimulator.encode_entities."""
     res, req = request(sim.gpu_id, rows, params, **kw)
@@ -248,34 +213,6 @@ def compute_backward(sim, rows, params, grad_features, argmax, stream=None, **kw
     res, req = request_backward(sim.gpu_id, rows, params, grad_features, argmax, **kw)
     _run(sim, "hs_entity_encode_backward", req, stream)
     return res
-
-
-def _sharded(ssim, fn, make, stream):
-    import torch
-    streams = _per_shard(ssim, "stream", stream)
-    reqs = [make(i, s) for i, s in enumerate(ssim.shards)]
-    waits = []
-    for s, (res, req), st in zip(ssim.shards, reqs, streams):
-        if st is None:
-            st = torch.cuda.Stream(device=s.gpu_id)
-            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
-            waits.append(st)
-        _run(s, fn, req, st)
-    for st in waits:
-        st.synchronize()
-    return [res for res, _ in reqs]
-
-
-def _shard_params(ssim, params):
-    import torch
-    return [params] * len(ssim.shards) if isinstance(params, torch.Tensor) else _per_shard(ssim, "params", params)
-
-
-def _shard_list(ssim, name, arg):
-    import torch
-    if isinstance(arg, torch.Tensor) or arg is None or len(arg) != len(ssim.shards):
-        raise ValueError(f"{name}: one tensor per shard ({len(ssim.shards)}) expected")
-    return list(arg)
 
 
 def compute_sharded(ssim, rows, params, stream=None, features=True, argmax=None, **kw):

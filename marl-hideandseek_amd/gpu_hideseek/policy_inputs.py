@@ -23,6 +23,8 @@ with its table and collects the moments of the raw rows in the same launch, and 
 """
 import ctypes as C
 
+from ._request import _DTYPES, _per_shard, _run, _sharded, stream_handle      # noqa: F401 (stream_handle: part of this module's face)
+
 ROW = 296            # HS_PACK_ROW
 MOMENTS = 593        # HS_PACK_MOMENTS: sum m x [296], sum m x x [296], sum m
 NORM_STATE = 593     # HS_NORM_STATE: m1 [296], m2 [296], N
@@ -44,9 +46,6 @@ LAYOUT = {
 MASKS = {"agent_data": "visible_agents_mask", "box_data": "visible_boxes_mask", "ramp_data": "visible_ramps_mask"}
 # the policy's four tables as column ranges of the row (extract_self_obs, then agents / boxes / ramps)
 TABLES = {"self": (0, 45, (45,)), "agents": LAYOUT["agent_data"], "boxes": LAYOUT["box_data"], "ramps": LAYOUT["ramp_data"]}
-
-_DTYPES = {"float32": 1, "bfloat16": 3, "float16": 4}      # HS_DTYPE_F32 / _BF16 / _F16
-
 
 class HsPackRequest(C.Structure):
     """hs_pack_request (include/hideseek.h)."""
@@ -127,11 +126,6 @@ def request(rows, gpu_id, actor=None, critic=None, moments=None, dtype=None):
     return res, HsPackRequest(ptr("actor"), code("actor"), ptr("critic"), code("critic"), ptr("moments"))
 
 
-def stream_handle(stream):
-    """The raw hipStream_t of a torch.cuda.Stream (or the integer itself)."""
-    return int(getattr(stream, "cuda_stream", stream))
-
-
 def norm_table(normaliser, gpu_id):
     """The f32 [592] table tensor of `normaliser` (an ObsNormaliser or the tensor itself), checked for GPU `gpu_id`."""
     import torch
@@ -155,14 +149,10 @@ def norm_table(normaliser, gpu_id):
 
 def _launch(sim, req, table, stream):
     """The pack entry point that fits (table, stream)."""
-    from ._native import check
-    L, h, st = sim._L, sim._h, None if stream is None else C.c_void_p(stream_handle(stream))
     if table is None:
-        check(L.hs_pack_policy_inputs(h, C.byref(req)) if st is None else L.hs_pack_policy_inputs_async(h, st, C.byref(req)))
+        _run(sim, "hs_pack_policy_inputs", req, stream)
     else:
-        tp = C.c_void_p(table.data_ptr())
-        check(L.hs_pack_policy_inputs_normalized(h, C.byref(req), tp) if st is None
-              else L.hs_pack_policy_inputs_normalized_async(h, st, C.byref(req), tp))
+        _run(sim, "hs_pack_policy_inputs_normalized", req, stream, C.c_void_p(table.data_ptr()))
 
 
 def pack(sim, actor=None, critic=None, moments=None, dtype=None, stream=None, normaliser=None):
@@ -171,15 +161,6 @@ def pack(sim, actor=None, critic=None, moments=None, dtype=None, stream=None, no
     table = None if normaliser is None else norm_table(normaliser, sim.gpu_id)
     _launch(sim, req, table, stream)
     return res
-
-
-def _per_shard(ssim, name, arg):
-    n = len(ssim.shards)
-    if arg is None or arg is True or arg is False:
-        return [arg] * n
-    if len(arg) != n:
-        raise ValueError(f"{name}: one entry per shard ({n}) expected")
-    return list(arg)
 
 
 def pack_sharded(ssim, actor=None, critic=None, moments=None, dtype=None, stream=None, normaliser=None):
@@ -191,24 +172,15 @@ def pack_sharded(ssim, actor=None, critic=None, moments=None, dtype=None, stream
     on its device: a table is read by the kernel and is not copied between devices here.  With the shards on several
     devices, keep one ObsNormaliser, update it with the shards' moments stacked on its device, and hand each other device
     a copy of its table."""
-    import torch
-    args = [_per_shard(ssim, k, v) for k, v in (("actor", actor), ("critic", critic), ("moments", moments))]
-    streams = _per_shard(ssim, "stream", stream)
-    reqs = [request(s.num_worlds * s.agents_per_world, s.gpu_id, a, c, m, dtype) for s, a, c, m in zip(ssim.shards, *args)]
+    a, c, m = (_per_shard(ssim, k, v) for k, v in (("actor", actor), ("critic", critic), ("moments", moments)))
     norms = normaliser if isinstance(normaliser, (list, tuple)) else [normaliser] * len(ssim.shards)
     if len(norms) != len(ssim.shards):
         raise ValueError(f"normaliser: one entry per shard ({len(ssim.shards)}) expected")
-    tables = [None if n is None else norm_table(n, s.gpu_id) for s, n in zip(ssim.shards, norms)]
-    waits = []
-    for s, (res, req), st, table in zip(ssim.shards, reqs, streams, tables):
-        if st is None:
-            st = torch.cuda.Stream(device=s.gpu_id)
-            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
-            waits.append(st)
-        _launch(s, req, table, st)
-    for st in waits:
-        st.synchronize()
-    return [res for res, _ in reqs]
+
+    def make(i, s):        # the "request" of a shard is its (request, table)
+        res, req = request(s.num_worlds * s.agents_per_world, s.gpu_id, a[i], c[i], m[i], dtype)
+        return res, (req, None if norms[i] is None else norm_table(norms[i], s.gpu_id))
+    return _sharded(ssim, lambda s, rt, st: _launch(s, *rt, st), make, stream)
 
 
 def table_of_state(state, eps):
@@ -264,7 +236,6 @@ class ObsNormaliser:
         a rollout (one batch), contiguous, on this normaliser's GPU, which is also `sim`'s.  stream=None blocks; a
         torch.cuda.Stream or raw handle enqueues there without synchronising."""
         import torch
-        from ._native import check
         dev = self.state.device
         what = f"moments must be a contiguous float64 tensor of shape ({MOMENTS},) or (K, {MOMENTS}), K <= {NORM_MAX_MOMENTS}, on {dev}"
         if not isinstance(moments, torch.Tensor):
@@ -282,10 +253,7 @@ class ObsNormaliser:
             raise ValueError(f"the simulator is on GPU {sim.gpu_id}, the normaliser on GPU {self.gpu_id}")
         req = HsObsNormRequest(moments.data_ptr(), moments.numel() // MOMENTS, self.decay, self.eps, self.state.data_ptr(),
                                self.table.data_ptr())
-        if stream is None:
-            check(sim._L.hs_obs_norm_update(sim._h, C.byref(req)))
-        else:
-            check(sim._L.hs_obs_norm_update_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+        _run(sim, "hs_obs_norm_update", req, stream)
 
     def mean_var(self):
         """(mean [296], biased variance [296], N) in float64 on the device, from the state, without synchronising: the

@@ -22,7 +22,7 @@ import math
 
 from .action_sampling import DEFAULT_BUCKETS, HEADS, MAX_BUCKETS, MAX_LOGITS
 from .advantages import MOMENTS
-from .policy_inputs import _DTYPES, _per_shard, stream_handle
+from ._request import _DTYPES, _disjoint, _name, _per_shard, _rows, _run, _sharded, _vector
 
 STATS = 7             # HS_PPO_STATS: sum pg, sum vl, sum ent, sum kl, policy-clipped, value-clipped, count
 ROWS_PER_BLOCK = 32   # kPpoRows: samples a workgroup takes at a time
@@ -41,50 +41,6 @@ class HsPpoRequest(C.Structure):
                 ("buckets", C.c_int32 * HEADS), ("clip_coef", C.c_float), ("value_loss_coef", C.c_float),
                 ("entropy_coef", C.c_float), ("grad_scale", C.c_float), ("grad_logits", C.c_void_p),
                 ("grad_value", C.c_void_p), ("stats", C.c_void_p)]
-
-
-def _name(dtype):
-    return str(dtype).replace("torch.", "")
-
-
-def _rows(name, t, n, L, dev, what):
-    """Check a [n, W >= L] tensor that is contiguous in its last dimension (logits, grad_logits)."""
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor")
-    what = f"{name} must be a {' / '.join(_DTYPES)} tensor of shape ({what}, W >= {L}), contiguous in its last dimension, on {dev}"
-    if t.dim() != 2 or t.shape[0] < 1 or (n is not None and t.shape[0] != n) or t.shape[1] < L:
-        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
-    if _name(t.dtype) not in _DTYPES:
-        raise ValueError(f"{what}: its dtype is {t.dtype}")
-    stride = max(int(t.stride(0)), L) if t.shape[0] > 1 else max(int(t.shape[1]), L)
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < L) or t.shape[0] * stride >= 2 ** 31:
-        raise ValueError(f"{what}: its stride is {tuple(t.stride())} (n * stride must stay below 2^31)")
-    return stride
-
-
-def _vector(name, t, n, dev, dtypes, tail=()):
-    """Check a contiguous per-sample tensor [n] + tail (or [n, 1] when tail is empty)."""
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor")
-    shape = (n,) + tail
-    what = f"{name} must be a contiguous {' / '.join(dtypes)} tensor of shape {shape} on {dev}"
-    if tuple(t.shape) != shape and not (not tail and tuple(t.shape) == (n, 1)):
-        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
-    if _name(t.dtype) not in dtypes:
-        raise ValueError(f"{what}: its dtype is {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
-
-
-def _overlap(a, b):
-    """Whether the storage ranges of two tensors intersect."""
-    def span(t):
-        last = sum((s - 1) * st for s, st in zip(t.shape, t.stride()))
-        return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
-    (a0, a1), (b0, b1) = span(a), span(b)
-    return a0 < b1 and b0 < a1
 
 
 def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUCKETS, adv_moments=None, mask=None,
@@ -155,19 +111,7 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
         _vector("stats", given["stats"], STATS, dev, ("float64",))
         if tuple(given["stats"].shape) != (STATS,):
             raise ValueError(f"stats must have shape ({STATS},): its shape is {tuple(given['stats'].shape)}")
-    for k, t in given.items():
-        for k2, t2 in inputs:
-            if _overlap(t, t2):
-                raise ValueError(f"{k} overlaps {k2}")
-    names = list(given)
-    for i, k in enumerate(names):
-        for k2 in names[:i]:
-            if _overlap(given[k], given[k2]):
-                raise ValueError(f"{k} overlaps {k2}")
-    # shapes, dtypes and strides first, so that every one of them is reported whatever device the tensors are on
-    for k, t in inputs + list(given.items()):
-        if t.device != dev:
-            raise ValueError(f"{k} must be on {dev}: it is on {t.device}")
+    _disjoint(list(given.items()), inputs, dev)
 
     res = dict(given)
     if outputs.get("grad_logits") is True:        # as wide as the logits tensor, so that logits.backward() takes it
@@ -194,12 +138,8 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
 
 def compute(sim, logits, action, old_log_prob, advantage, stream=None, **kw):
     """HideAndSeekSimulator.ppo_loss."""
-    from ._native import check
     res, req = request(sim.gpu_id, logits, action, old_log_prob, advantage, **kw)
-    if stream is None:
-        check(sim._L.hs_ppo_loss(sim._h, C.byref(req)))
-    else:
-        check(sim._L.hs_ppo_loss_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+    _run(sim, "hs_ppo_loss", req, stream)
     return res
 
 
@@ -214,25 +154,13 @@ def compute_sharded(ssim, logits, action, old_log_prob, advantage, stream=None, 
     current stream, before any is waited for.  Every shard divides by its own count of active samples: weigh the shards'
     gradients with grad_scale when their counts differ."""
     import torch
-    from ._native import check
     n = len(ssim.shards)
     for name, arg in (("logits", logits), ("action", action), ("old_log_prob", old_log_prob), ("advantage", advantage)):
         if isinstance(arg, torch.Tensor) or len(arg) != n:
             raise ValueError(f"{name}: one tensor per shard ({n}) expected")
     per = {k: _per_shard(ssim, k, kw.pop(k)) for k in _PER_SHARD if k in kw}
-    streams = _per_shard(ssim, "stream", stream)
-    reqs = [request(s.gpu_id, lg, a, lp, adv, **{k: v[i] for k, v in per.items()}, **kw)
-            for i, (s, lg, a, lp, adv) in enumerate(zip(ssim.shards, logits, action, old_log_prob, advantage))]
-    waits = []
-    for s, (res, req), st in zip(ssim.shards, reqs, streams):
-        if st is None:
-            st = torch.cuda.Stream(device=s.gpu_id)
-            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
-            waits.append(st)
-        check(s._L.hs_ppo_loss_async(s._h, C.c_void_p(stream_handle(st)), C.byref(req)))
-    for st in waits:
-        st.synchronize()
-    return [res for res, _ in reqs]
+    return _sharded(ssim, "hs_ppo_loss", lambda i, s: request(s.gpu_id, logits[i], action[i], old_log_prob[i], advantage[i],
+                                                              **{k: v[i] for k, v in per.items()}, **kw), stream)
 
 
 def stats_to_metrics(stats, entropy_coef=DEFAULT_ENTROPY_COEF, value_loss_coef=DEFAULT_VALUE_LOSS_COEF, grad_scale=1.0):

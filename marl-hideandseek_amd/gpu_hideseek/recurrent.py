@@ -22,9 +22,7 @@ same composition in plain torch, for readers, tools/lstm_bench.py and the tests.
 import ctypes as C
 import math
 
-from .entity_encoder import _disjoint, _given, _run, _shard_list, _shard_params, _sharded
-from .policy_inputs import _DTYPES, _per_shard
-from .ppo_loss import _name
+from ._request import _DTYPES, _disjoint, _given, _name, _per_shard, _run, _shard_list, _shard_params, _sharded
 
 HIDDEN = (64, 128, 256, 512)
 PARAM_ROWS = 6            # HS_LSTM_PARAM_ROWS: bias i, f, g, o | gamma | beta, rows of H floats

@@ -23,8 +23,7 @@ symlog(), symexp() and twohot() are the eager composition in plain torch, for re
 import ctypes as C
 import math
 
-from .policy_inputs import _DTYPES, _per_shard, stream_handle
-from .ppo_loss import _name, _overlap, _rows, _vector
+from ._request import _DTYPES, _disjoint, _name, _per_shard, _rows, _run, _sharded, _vector
 
 STATS = 6             # HS_TWOHOT_STATS: sum ce, sum (v - R)^2, sum v, sum R, sum R^2, count
 MAX_BINS = 256        # HS_TWOHOT_MAX_BINS
@@ -146,18 +145,7 @@ def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=D
         _vector("stats", given["stats"], STATS, dev, ("float64",))
         if tuple(given["stats"].shape) != (STATS,):
             raise ValueError(f"stats must have shape ({STATS},): its shape is {tuple(given['stats'].shape)}")
-    for k, t in given.items():
-        for k2, t2 in inputs:
-            if _overlap(t, t2):
-                raise ValueError(f"{k} overlaps {k2}")
-    names = list(given)
-    for i, k in enumerate(names):
-        for k2 in names[:i]:
-            if _overlap(given[k], given[k2]):
-                raise ValueError(f"{k} overlaps {k2}")
-    for k, t in inputs + list(given.items()):
-        if t.device != dev:
-            raise ValueError(f"{k} must be on {dev}: it is on {t.device}")
+    _disjoint(list(given.items()), inputs, dev)
 
     res = dict(given)
     if outputs.get("value") is True:
@@ -182,12 +170,8 @@ def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=D
 
 def compute(sim, logits, returns=None, stream=None, **kw):
     """HideAndSeekSimulator.value_head."""
-    from ._native import check
     res, req = request(sim.gpu_id, logits, returns, **kw)
-    if stream is None:
-        check(sim._L.hs_twohot_value(sim._h, C.byref(req)))
-    else:
-        check(sim._L.hs_twohot_value_async(sim._h, C.c_void_p(stream_handle(stream)), C.byref(req)))
+    _run(sim, "hs_twohot_value", req, stream)
     return res
 
 
@@ -201,24 +185,12 @@ def compute_sharded(ssim, logits, returns=None, stream=None, **kw):
     device, ordered after that device's current stream, before any is waited for.  Every shard divides by its own count of
     active samples."""
     import torch
-    from ._native import check
     n = len(ssim.shards)
     if isinstance(logits, torch.Tensor) or len(logits) != n:
         raise ValueError(f"logits: one tensor per shard ({n}) expected")
     rets = _per_shard(ssim, "returns", returns)
     per = {k: _per_shard(ssim, k, kw.pop(k)) for k in _PER_SHARD if k in kw}
-    streams = _per_shard(ssim, "stream", stream)
-    reqs = [request(s.gpu_id, lg, rets[i], **{k: v[i] for k, v in per.items()}, **kw) for i, (s, lg) in enumerate(zip(ssim.shards, logits))]
-    waits = []
-    for s, (res, req), st in zip(ssim.shards, reqs, streams):
-        if st is None:
-            st = torch.cuda.Stream(device=s.gpu_id)
-            st.wait_stream(torch.cuda.current_stream(s.gpu_id))
-            waits.append(st)
-        check(s._L.hs_twohot_value_async(s._h, C.c_void_p(stream_handle(st)), C.byref(req)))
-    for st in waits:
-        st.synchronize()
-    return [res for res, _ in reqs]
+    return _sharded(ssim, "hs_twohot_value", lambda i, s: request(s.gpu_id, logits[i], rets[i], **{k: v[i] for k, v in per.items()}, **kw), stream)
 
 
 def stats_to_metrics(stats):
