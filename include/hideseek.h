@@ -706,6 +706,81 @@ int32_t hs_lstm_cell_async(hs_sim *sim, void *hip_stream, const hs_lstm_cell_req
 int32_t hs_lstm_cell_backward(hs_sim *sim, const hs_lstm_cell_backward_request *req);
 int32_t hs_lstm_cell_backward_async(hs_sim *sim, void *hip_stream, const hs_lstm_cell_backward_request *req);
 
+/* A dense layer after its GEMM: what one layer of the reference's MLP(num_channels=256, num_layers=3) at the end of
+ * SimpleNet (scripts/jax_policy.py:163-167) does to the GEMM's result, Dense -> LayerNorm -> leaky ReLU, the order
+ * SimpleNet.embed shows.  The caller computes z [n][C] = x W with the BLAS library, WITHOUT the bias; one kernel
+ * (csrc/hs_k_dense.h) then reads a row's C values once and writes y; n is free, as for hs_lstm_cell.  madrona_learn's MLP
+ * and LayerNorm are not part of the reference's tree: eps = 1e-6 and slope = 0.01 are flax's defaults and
+ * hs_entity_encode's, and are not pinned by it.
+ * params is one array of HS_DENSE_PARAM_ROWS * C f32: bias [C] | gamma [C] | beta [C].
+ * The arithmetic is the contract.  A narrow z is widened to f32 exactly; everything is IEEE f32, unfused except where
+ * fmaf is written, in exactly this order.  For row r and channel c < C:
+ *   a_c = z_c + bias_c
+ *   sum_c(p): with V = C / 64, lane l < 64 holds the ADJACENT channels V l, ..., V l + V - 1 and adds p_{V l}, p_{V l + 1},
+ *             ..., p_{V l + V - 1} in ascending order; then for m = 1, 2, 4, ..., 32 every lane replaces its value s_l by
+ *             s_l + s_{l xor m} (a butterfly: every lane ends with the same bits).  This order is this call's own: it is
+ *             not hs_lstm_cell's, whose lane l holds the channels l, l + 64, ...
+ *   mu = sum_c(a_c) / (float)C;   d_c = a_c - mu;   var = sum_c(d_c * d_c) / (float)C
+ *   rstd = 1.0f / sqrtf(var + eps)                                  (division and sqrtf correctly rounded)
+ *   h_c = d_c * rstd;   u_c = fmaf(gamma_c, h_c, beta_c)
+ *   y[r][c] = u_c > 0 ? u_c : slope * u_c                           (rounded to y_dtype to nearest even)
+ * The LayerNorm is hs_entity_encode's and hs_lstm_cell's expression.  u_c == 0 takes the slope branch here and in the
+ * backward (torch's convention).  A row's y does not depend on its position or on n.
+ * hs_dense_norm_act_backward recomputes all of the above from z and params (nothing else is saved) and takes grad_y
+ * [n][C] of y_dtype:
+ *   g_c = grad_y[r][c];   du_c = u_c > 0 ? g_c : slope * g_c
+ *   dh_c = du_c * gamma_c;   m1 = sum_c(dh_c) / (float)C;   m2 = sum_c(dh_c * h_c) / (float)C
+ *   da_c = rstd * ((dh_c - m1) - h_c * m2);   grad_z[r][c] = da_c   (rounded to z_dtype)
+ *   dbias_c = dbias_c + da_c;   dgamma_c = fmaf(du_c, h_c, dgamma_c);   dbeta_c = dbeta_c + du_c
+ * grad_params [HS_DENSE_PARAM_ROWS * C] f32 has the layout of params.  Its sums over the rows run in an order that
+ * depends on n alone: with R = HS_DENSE_ROWS_PER_ROUND rows per round and G = min(ceil(n / R), HS_DENSE_MAX_GRID_BWD)
+ * workgroups, workgroup b takes rounds b, b + G, ...; wave w of it row round * R + w; a lane adds its rows' terms in
+ * round order onto +0; the waves add as ((w0 + w1) + w2) + w3; the workgroups' sums go to a workspace of the handle
+ * ([HS_DENSE_MAX_GRID_BWD][HS_DENSE_PARAM_ROWS * HS_DENSE_MAX_CHANNELS] f32, this call's own), where HS_EMBED_SUM_SEGS
+ * segments of ceil(G / segs) consecutive workgroups are each added in ascending order onto +0 and the segments then in
+ * ascending order (the kernel that does so is hs_entity_encode_backward's).  Rows past n contribute nothing.  No
+ * atomics: the same inputs give the same bits on every call.  An all-zero grad_y gives grad_params all +0 (and grad_z
+ * zeros of either sign).  grad_z and grad_params may each be null, not both; only what is requested is written.
+ * z, parameters and gradients must be finite: nothing checks that on the device.
+ * A lane reads and writes its V adjacent elements of a row as one piece of up to 16 bytes, so z, y, grad_y and grad_z
+ * must be 16-byte aligned: any contiguous [n][C] array that starts at a row boundary of a 16-byte aligned allocation
+ * is.  There is no by-element path for other pointers: they are refused.
+ * Two backward calls on one handle must not overlap (the workspace); forward calls may.  Everything is validated
+ * before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request, null z,
+ * params or y (backward: null grad_y, or grad_z and grad_params both null); an unknown dtype; channels not 64, 128, 256
+ * or 512; n < 1 or n * C >= 2^31; eps not finite or <= 0; slope not finite or outside [0, 1]; z, y, grad_y or grad_z
+ * not 16-byte aligned, params or grad_params not 4-byte aligned; an output range that overlaps an input range or
+ * another output; a call before hs_init or inside an open step.  The calls read no export and write no simulator
+ * state.  The blocking forms are ordered after the device's legacy default stream; the _async forms enqueue on the
+ * caller's hipStream_t without synchronising. */
+enum { HS_DENSE_PARAM_ROWS = 3, HS_DENSE_MAX_GRID_BWD = 512, HS_DENSE_MAX_CHANNELS = 512, HS_DENSE_ROWS_PER_ROUND = 4 };
+typedef struct hs_dense_norm_act_request {
+    const void    *z;             /* [n][channels] of z_dtype, contiguous, 16-byte aligned: x W without the bias */
+    const float   *params;        /* [HS_DENSE_PARAM_ROWS * channels] f32: bias [C] | gamma [C] | beta [C] */
+    int32_t n;                    /* rows, n >= 1 and n * channels < 2^31 */
+    int32_t channels;             /* C: 64, 128, 256 (the reference's) or 512 */
+    int32_t z_dtype;              /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t y_dtype;              /* of y */
+    float eps, slope;             /* finite, eps > 0, 0 <= slope <= 1; 1e-6, 0.01 */
+    void    *y;                   /* [n][channels] of y_dtype, 16-byte aligned */
+} hs_dense_norm_act_request;      /* 48 bytes */
+typedef struct hs_dense_norm_act_backward_request {
+    const void    *z;             /* as in the forward call */
+    const float   *params;
+    const void    *grad_y;        /* [n][channels] of y_dtype, 16-byte aligned */
+    int32_t n;
+    int32_t channels;
+    int32_t z_dtype;              /* of z and grad_z */
+    int32_t y_dtype;              /* of grad_y */
+    float eps, slope;
+    void    *grad_z;              /* [n][channels] of z_dtype, 16-byte aligned, or null */
+    float   *grad_params;         /* [HS_DENSE_PARAM_ROWS * channels] f32, or null */
+} hs_dense_norm_act_backward_request;  /* 64 bytes */
+int32_t hs_dense_norm_act(hs_sim *sim, const hs_dense_norm_act_request *req);
+int32_t hs_dense_norm_act_async(hs_sim *sim, void *hip_stream, const hs_dense_norm_act_request *req);
+int32_t hs_dense_norm_act_backward(hs_sim *sim, const hs_dense_norm_act_backward_request *req);
+int32_t hs_dense_norm_act_backward_async(hs_sim *sim, void *hip_stream, const hs_dense_norm_act_backward_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

@@ -30,6 +30,7 @@
 #include "hs_k_norm.h"
 #include "hs_solver.h"
 #include "hs_k_lstm.h"
+#include "hs_k_dense.h"
 
 namespace {
 
@@ -89,6 +90,7 @@ struct hs_sim {
     int32_t *twohot_counts = nullptr;      // hs_twohot_value: its own counts of k_ppo_count, [kPpoCountGrid]
     float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kEmbMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
     float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kLstmMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
+    float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kDenseMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -861,6 +863,89 @@ int launch_lstm_bwd(hs_sim *s, hipStream_t strm, const hs_lstm_cell_backward_req
 }
 }  // namespace
 
+// ---- a dense layer after its GEMM (hs_k_dense.h) ----
+namespace {
+static_assert(HS_DENSE_PARAM_ROWS == hs::kDenseParamRows && HS_DENSE_MAX_GRID_BWD == hs::kDenseMaxGridBwd && HS_DENSE_MAX_CHANNELS == hs::kDenseMaxC &&
+              HS_DENSE_ROWS_PER_ROUND == hs::kDenseWaves, "hs_dense_norm_act_request and k_dense agree");
+static_assert(sizeof(hs_dense_norm_act_request) == 48 && offsetof(hs_dense_norm_act_request, params) == 8 && offsetof(hs_dense_norm_act_request, n) == 16 &&
+              offsetof(hs_dense_norm_act_request, y_dtype) == 28 && offsetof(hs_dense_norm_act_request, eps) == 32 &&
+              offsetof(hs_dense_norm_act_request, slope) == 36 && offsetof(hs_dense_norm_act_request, y) == 40,
+              "hs_dense_norm_act_request layout (gpu_hideseek/mlp.py mirrors it)");
+static_assert(sizeof(hs_dense_norm_act_backward_request) == 64 && offsetof(hs_dense_norm_act_backward_request, grad_y) == 16 &&
+              offsetof(hs_dense_norm_act_backward_request, n) == 24 && offsetof(hs_dense_norm_act_backward_request, y_dtype) == 36 &&
+              offsetof(hs_dense_norm_act_backward_request, eps) == 40 && offsetof(hs_dense_norm_act_backward_request, slope) == 44 &&
+              offsetof(hs_dense_norm_act_backward_request, grad_z) == 48 && offsetof(hs_dense_norm_act_backward_request, grad_params) == 56,
+              "hs_dense_norm_act_backward_request layout (gpu_hideseek/mlp.py mirrors it)");
+
+// What the two calls share.
+int check_dense_common(const Check &c, const void *z, const float *params, int32_t n, int32_t C, int32_t z_dtype, float eps, float slope) {
+    if (!z) return c.bad("null z");
+    if (!params) return c.bad("null params");
+    HS_TRY(c.dtype(z_dtype, "z"));
+    if (C != 64 && C != 128 && C != 256 && C != 512) return c.bad("channels must be 64, 128, 256 or 512");
+    if (!count_ok(n, {C})) return c.bad("n must be at least 1 and n * channels below 2^31");
+    if (!std::isfinite(eps) || !(eps > 0.f)) return c.bad("eps must be finite and above 0");
+    if (!std::isfinite(slope) || !(slope >= 0.f && slope <= 1.f)) return c.bad("slope must be finite and in [0, 1]");
+    if (!aligned(4, {params})) return c.bad("params must be 4-byte aligned");
+    if (!aligned(16, {z})) return c.bad("z must be 16-byte aligned");
+    return HS_OK;
+}
+
+int check_dense(hs_sim *s, const hs_dense_norm_act_request *r) {
+    const Check c{"hs_dense_norm_act"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_dense_common(c, r->z, r->params, r->n, r->channels, r->z_dtype, r->eps, r->slope));
+    if (!r->y) return c.bad("every output is null");
+    HS_TRY(c.dtype(r->y_dtype, "y"));
+    if (!aligned(16, {r->y})) return c.bad("y must be 16-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n, C = (uintptr_t)r->channels;
+    HS_TRY(c.disjoint({range("z", r->z, n * C * elem_size(r->z_dtype)), range("params", r->params, HS_DENSE_PARAM_ROWS * C * 4)},
+                      {range("y", r->y, n * C * elem_size(r->y_dtype))}));
+    return c.handle_ready(s);
+}
+
+int check_dense_bwd(hs_sim *s, const hs_dense_norm_act_backward_request *r) {
+    const Check c{"hs_dense_norm_act_backward"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_dense_common(c, r->z, r->params, r->n, r->channels, r->z_dtype, r->eps, r->slope));
+    if (!r->grad_y) return c.bad("null grad_y");
+    if (!r->grad_z && !r->grad_params) return c.bad("every output is null");
+    HS_TRY(c.dtype(r->y_dtype, "y"));
+    if (!aligned(16, {r->grad_y, r->grad_z})) return c.bad("grad_y and grad_z must be 16-byte aligned");
+    if (!aligned(4, {r->grad_params})) return c.bad("grad_params must be 4-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n, C = (uintptr_t)r->channels, zsize = elem_size(r->z_dtype);
+    HS_TRY(c.disjoint({range("z", r->z, n * C * zsize), range("params", r->params, HS_DENSE_PARAM_ROWS * C * 4),
+                       range("grad_y", r->grad_y, n * C * elem_size(r->y_dtype))},
+                      {range("grad_z", r->grad_z, n * C * zsize), range("grad_params", r->grad_params, HS_DENSE_PARAM_ROWS * C * 4)}));
+    return c.handle_ready(s);
+}
+
+// One k_dense_fwd over the rows (the request has passed check_dense).
+int launch_dense(hs_sim *, hipStream_t strm, const hs_dense_norm_act_request *r) {
+    hs::DenseArgs a = {};
+    a.z = r->z; a.params = r->params; a.y = r->y;
+    a.n = r->n; a.zType = elem_code(r->z_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps; a.slope = r->slope;
+    const dim3 grid(hs::dense_grid(a.n, hs::kDenseMaxGrid)), blk(hs::kDenseThreads);
+    with_constant<64, 128, 256, 512>(r->channels, [&](auto ch) { hipLaunchKernelGGL((hs::k_dense_fwd<decltype(ch)::value>), grid, blk, 0, strm, a); });
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+// k_dense_bwd, its parameter sums into the workspace's slices, then their fixed-order sum (the request has passed check_dense_bwd).
+int launch_dense_bwd(hs_sim *s, hipStream_t strm, const hs_dense_norm_act_backward_request *r) {
+    hs::DenseBwdArgs a = {};
+    a.z = r->z; a.params = r->params; a.gradY = r->grad_y; a.gradZ = r->grad_z; a.workspace = r->grad_params ? s->dense_partials : nullptr;
+    a.n = r->n; a.zType = elem_code(r->z_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps; a.slope = r->slope;
+    const int nparts = hs::dense_grid(a.n, hs::kDenseMaxGridBwd), len = hs::kDenseParamRows * r->channels;
+    with_constant<64, 128, 256, 512>(r->channels, [&](auto ch) { hipLaunchKernelGGL((hs::k_dense_bwd<decltype(ch)::value>), dim3(nparts), dim3(hs::kDenseThreads), 0, strm, a); });
+    if (r->grad_params)
+        hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
+                           (const float *)s->dense_partials, nparts, len, r->grad_params);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -995,6 +1080,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->embed_partials, (size_t)hs::kEmbMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
     HS_ALLOC(s->lstm_partials, (size_t)hs::kLstmMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
+    HS_ALLOC(s->dense_partials, (size_t)hs::kDenseMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1309,6 +1395,10 @@ int32_t hs_lstm_cell(hs_sim *s, const hs_lstm_cell_request *req) { return call_b
 int32_t hs_lstm_cell_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_request *req) { return call_async(s, hip_stream, check_lstm, launch_lstm, req); }
 int32_t hs_lstm_cell_backward(hs_sim *s, const hs_lstm_cell_backward_request *req) { return call_blocking(s, check_lstm_bwd, launch_lstm_bwd, req); }
 int32_t hs_lstm_cell_backward_async(hs_sim *s, void *hip_stream, const hs_lstm_cell_backward_request *req) { return call_async(s, hip_stream, check_lstm_bwd, launch_lstm_bwd, req); }
+int32_t hs_dense_norm_act(hs_sim *s, const hs_dense_norm_act_request *req) { return call_blocking(s, check_dense, launch_dense, req); }
+int32_t hs_dense_norm_act_async(hs_sim *s, void *hip_stream, const hs_dense_norm_act_request *req) { return call_async(s, hip_stream, check_dense, launch_dense, req); }
+int32_t hs_dense_norm_act_backward(hs_sim *s, const hs_dense_norm_act_backward_request *req) { return call_blocking(s, check_dense_bwd, launch_dense_bwd, req); }
+int32_t hs_dense_norm_act_backward_async(hs_sim *s, void *hip_stream, const hs_dense_norm_act_backward_request *req) { return call_async(s, hip_stream, check_dense_bwd, launch_dense_bwd, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

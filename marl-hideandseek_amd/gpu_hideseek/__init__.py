@@ -282,6 +282,25 @@ class HideAndSeekSimulator:
         return _rec.compute_backward(self, gates, c_prev, cell_params, grad_y, stream, clear=clear, grad_h_next=grad_h_next, grad_c_next=grad_c_next,
                                      hidden=hidden, eps=eps, grad_gates=grad_gates, grad_c_prev=grad_c_prev, grad_cell_params=grad_cell_params)
 
+    def dense_norm_act(self, z, params, *, channels=None, eps=1e-6, slope=0.01, y=True, y_dtype=None, stream=None):
+        """A dense layer after its GEMM in one kernel (gpu_hideseek.mlp; hs_dense_norm_act, whose header comment states
+        the arithmetic: IEEE f32 in a fixed order).  `z` [n, C] (float32, bfloat16 or float16, contiguous, 16-byte
+        aligned) is x W without the bias, `params` the flat float32 tensor bias [C] | gamma [C] | beta [C]
+        (mlp.param_layout), C one of 64, 128, 256, 512.  y [n, C] = leaky_relu(LayerNorm(z + bias), `slope`) in `y_dtype`
+        (by default z's) is True (allocated) or a preallocated tensor.  stream=None blocks; a torch.cuda.Stream or raw
+        handle enqueues there without synchronising.  Returns {"y": tensor}."""
+        from . import mlp as _mlp
+        return _mlp.compute(self, z, params, stream, channels=channels, eps=eps, slope=slope, y=y, y_dtype=y_dtype)
+
+    def dense_norm_act_backward(self, z, params, grad_y, *, channels=None, eps=1e-6, slope=0.01, grad_z=True, grad_params=True, stream=None):
+        """The gradients of dense_norm_act in one kernel plus a fixed-order sum (hs_dense_norm_act_backward): recomputed
+        from the forward's z and params, with the upstream `grad_y` [n, C] (float32, bfloat16 or float16).  grad_z [n, C]
+        in z's dtype and grad_params [3 C] float32 are each True, a tensor or None.  The same inputs give the same bits
+        on every call.  Returns {name: tensor} of what was written."""
+        from . import mlp as _mlp
+        return _mlp.compute_backward(self, z, params, grad_y, stream, channels=channels, eps=eps, slope=slope, grad_z=grad_z,
+                                     grad_params=grad_params)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -97,11 +97,12 @@ def init_params(E, generator=None):
 
 
 def eager(rows, params, E, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE):
-    """The plain-torch composition, in float32: [n, 4 E] features of rows [n, 296].  Differentiable in params."""
+    """The plain-torch composition in the dtype of params (float32, or float64 for a reference): [n, 4 E] features of
+    rows [n, 296].  Differentiable in params."""
     import torch
     from .policy_inputs import views as tables
     feats = []
-    for name, x in tables(rows.float()).items():
+    for name, x in tables(rows.to(params.dtype)).items():
         p = views(params, E)[name]
         y = torch.nn.functional.layer_norm(x @ p["kernel"] + p["bias"], (E,), p["scale"], p["shift"], eps)
         a = torch.nn.functional.leaky_relu(y, slope)

@@ -1,0 +1,141 @@
+"""The reference's make_policy (scripts/jax_policy.py) as torch modules, assembled from the project's own: an actor
+backbone and a separate critic backbone (BackboneSeparate), each the entity encoder (SimpleNet's first layer), the MLP of
+three layers of 256 channels and the recurrent core (an LSTM of 256 hidden channels and its LayerNorm), and the two heads
+on top: the multi-discrete actor's 5 + 5 + 5 + 2 + 2 logits and the two-hot critic's 255 bins.
+
+    net = policy.make_policy(torch.bfloat16).cuda()
+    state = net.init_state(rows, "cuda")
+    for t in range(T):                                                   # the rollout
+        sim.step()
+        sim.pack_policy_inputs(actor=actor[t], critic=critic[t])
+        done = sim.done_tensor().to_torch().reshape(rows)
+        with torch.no_grad():
+            logits, critic_logits, state = net(sim, actor[t], critic[t], state, clear=done)
+    logits, critic_logits, _ = net.sequence(sim, actor, critic, state0, clears)      # a BPTT chunk, [T, rows, ...]
+
+Composition only: this file contains no kernel call of its own.  Every piece runs its fused kernels on `sim`'s device
+(entity_encoder, mlp, recurrent); with fused=False every piece runs its eager() in plain torch on the same parameters
+(then `sim` is not used and may be None), for the tests and tools/mlp_bench.py.
+
+In a chunk the encoder and the MLP do not depend on time: sequence() runs them once over the T * n flattened rows and
+only the LSTM step by step.
+"""
+from . import entity_encoder, mlp, recurrent
+
+BUCKETS = (5, 5, 5, 2, 2)     # the reference's action heads: move amount, move angle, rotate, grab, lock
+BINS = 255                    # the two-hot critic's bins (value_head)
+
+
+def _module_base():
+    import torch
+    return torch.nn.Module
+
+
+class Backbone(_module_base()):
+    """EntityEncoder(embed) -> MLP(4 * embed, channels, layers) -> LSTMCore(channels, hidden) over k_pack's rows.  The
+    compute dtype is the one the state's h carries: the encoder writes its features in it, and the GEMMs run in it."""
+
+    def __init__(self, embed=64, channels=256, layers=3, hidden=256, fused=True, generator=None):
+        super().__init__()
+        self.fused = bool(fused)
+        self.encoder = entity_encoder.EntityEncoder(embed, generator=generator)
+        self.mlp = mlp.MLP(4 * embed, channels, layers, fused=fused, generator=generator)
+        self.core = recurrent.LSTMCore(channels, hidden, generator=generator)
+
+    def set_fused(self, fused):
+        """Switch every piece between its kernels and its eager() on the same parameters."""
+        self.fused = self.mlp.fused = bool(fused)
+        return self
+
+    def init_state(self, n, device, dtype=None):
+        """(h [n, hidden] zeros in `dtype` (float32 by default), c [n, hidden] float32 zeros)."""
+        return self.core.init_state(n, device, dtype)
+
+    def features(self, sim, rows, dtype):
+        """The encoder and the MLP over rows [n, W]: [n, channels] in `dtype`.  They carry no state."""
+        if self.fused:
+            feats = self.encoder(sim, rows, dtype)
+        else:
+            feats = entity_encoder.eager(rows, self.encoder.params, self.encoder.embed_dim, self.encoder.eps, self.encoder.slope).to(dtype)
+        return self.mlp(sim, feats)
+
+    def forward(self, sim, rows, state, clear=None):
+        """One step: rows [n, W], state (h, c), clear [n] int32 or None -> (y [n, hidden], the new state)."""
+        x = self.features(sim, rows, state[0].dtype)
+        if self.fused:
+            return self.core(sim, x, state, clear)
+        ys, state = self._eager_steps(x.unsqueeze(0), state, None if clear is None else clear.reshape(1, -1))
+        return ys[0], state
+
+    def sequence(self, sim, rows, state, clears=None):
+        """A chunk: rows [T, n, W], clears [T, n] int32 or None -> (ys [T, n, hidden], the final state).  The encoder and
+        the MLP run once over the T * n flattened rows, the LSTM over the T steps."""
+        T, n = rows.shape[0], rows.shape[1]
+        xs = self.features(sim, rows.reshape(T * n, rows.shape[2]), state[0].dtype).reshape(T, n, -1)
+        if self.fused:
+            return self.core.sequence(sim, xs, state, clears)
+        return self._eager_steps(xs, state, clears)
+
+    def _eager_steps(self, xs, state, clears):
+        h, c = state
+        ys, (h2, c2) = recurrent.eager_sequence(xs, self.core.w_in, self.core.w_rec, self.core.cell_params, (h, c), clears, self.core.eps)
+        return ys.to(h.dtype), (h2.to(h.dtype), c2)
+
+
+class ActorCritic(_module_base()):
+    """An actor Backbone and a separate critic Backbone (the reference's BackboneSeparate) and the two heads:
+    actor_head Linear(hidden, sum(buckets)), orthogonal with gain 0.01 and a zero bias, and critic_head
+    Linear(hidden, bins), zero-initialised as DreamerV3's two-hot head is, so that a fresh critic predicts 0.  Both
+    initialisers are the project's choices: madrona_learn's heads are not part of the reference's tree and pin neither.
+    The heads run in the dtype of the backbones' output.  state = (actor_state, critic_state), each (h, c)."""
+
+    def __init__(self, buckets=BUCKETS, bins=BINS, dtype=None, generator=None, **backbone_kw):
+        import torch
+        super().__init__()
+        self.buckets, self.bins = tuple(int(b) for b in buckets), int(bins)
+        self.dtype = torch.float32 if dtype is None else dtype
+        self.actor = Backbone(generator=generator, **backbone_kw)
+        self.critic = Backbone(generator=generator, **backbone_kw)
+        hidden = self.actor.core.hidden
+        self.actor_head = torch.nn.Linear(hidden, sum(self.buckets))
+        self.critic_head = torch.nn.Linear(hidden, self.bins)
+        with torch.no_grad():
+            torch.nn.init.orthogonal_(self.actor_head.weight, gain=0.01, generator=generator)
+            self.actor_head.bias.zero_()
+            self.critic_head.weight.zero_()
+            self.critic_head.bias.zero_()
+
+    def set_fused(self, fused):
+        """Switch both backbones between their kernels and their eager() on the same parameters."""
+        self.actor.set_fused(fused)
+        self.critic.set_fused(fused)
+        return self
+
+    def init_state(self, n, device, dtype=None):
+        """((h, c) of the actor, (h, c) of the critic): zeros, h in `dtype` (by default the policy's compute dtype)."""
+        dtype = self.dtype if dtype is None else dtype
+        return self.actor.init_state(n, device, dtype), self.critic.init_state(n, device, dtype)
+
+    def _heads(self, ya, yc):
+        import torch
+        lin = torch.nn.functional.linear
+        return (lin(ya, self.actor_head.weight.to(ya.dtype), self.actor_head.bias.to(ya.dtype)),
+                lin(yc, self.critic_head.weight.to(yc.dtype), self.critic_head.bias.to(yc.dtype)))
+
+    def forward(self, sim, actor_rows, critic_rows, state, clear=None):
+        """One step -> (logits [n, sum(buckets)], critic_logits [n, bins], the new state)."""
+        ya, sa = self.actor(sim, actor_rows, state[0], clear)
+        yc, sc = self.critic(sim, critic_rows, state[1], clear)
+        return (*self._heads(ya, yc), (sa, sc))
+
+    def sequence(self, sim, actor_rows, critic_rows, state, clears=None):
+        """A chunk [T, n, W] -> (logits [T, n, sum(buckets)], critic_logits [T, n, bins], the final state)."""
+        ya, sa = self.actor.sequence(sim, actor_rows, state[0], clears)
+        yc, sc = self.critic.sequence(sim, critic_rows, state[1], clears)
+        return (*self._heads(ya, yc), (sa, sc))
+
+
+def make_policy(dtype=None, fused=True, generator=None):
+    """An ActorCritic of the reference's sizes: embed 64, three layers of 256 channels, 256 hidden channels, heads of
+    5 + 5 + 5 + 2 + 2 logits and 255 bins.  `dtype` (float32 by default) is the compute dtype the state's h carries."""
+    return ActorCritic(BUCKETS, BINS, dtype=dtype, generator=generator, embed=64, channels=256, layers=3, hidden=256, fused=fused)

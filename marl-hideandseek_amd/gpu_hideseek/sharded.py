@@ -222,6 +222,19 @@ class ShardedSimulator:
                                              grad_c_next=grad_c_next, grad_gates=grad_gates, grad_c_prev=grad_c_prev,
                                              grad_cell_params=grad_cell_params, hidden=hidden, eps=eps)
 
+    def dense_norm_act(self, z, params, *, channels=None, eps=1e-6, slope=0.01, y=True, y_dtype=None, stream=None):
+        """HideAndSeekSimulator.dense_norm_act per shard: `z` has one tensor per shard, on the shard's device; `params` is
+        one tensor for all shards or a list; a list of the shards' results (mlp.compute_sharded)."""
+        from . import mlp as _mlp
+        return _mlp.compute_sharded(self, z, params, stream, y=y, channels=channels, eps=eps, slope=slope, y_dtype=y_dtype)
+
+    def dense_norm_act_backward(self, z, params, grad_y, *, channels=None, eps=1e-6, slope=0.01, grad_z=True, grad_params=True, stream=None):
+        """HideAndSeekSimulator.dense_norm_act_backward per shard: every shard's grad_params is the sum over its own rows
+        (mlp.compute_backward_sharded)."""
+        from . import mlp as _mlp
+        return _mlp.compute_backward_sharded(self, z, params, grad_y, stream, grad_z=grad_z, grad_params=grad_params, channels=channels,
+                                             eps=eps, slope=slope)
+
     def device_status(self):
         out = {}
         for s in self.shards:
