@@ -26,6 +26,7 @@
 #include "hs_k_gae.h"
 #include "hs_k_ppo.h"
 #include "hs_k_twohot.h"
+#include "hs_rows.h"
 #include "hs_k_embed.h"
 #include "hs_k_norm.h"
 #include "hs_solver.h"
@@ -88,9 +89,9 @@ struct hs_sim {
     int32_t *ppo_counts = nullptr;         // hs_ppo_loss: the active samples each workgroup of k_ppo_count saw, [kPpoCountGrid]
     double *twohot_partials = nullptr;     // hs_twohot_value: the statistics of each workgroup, [kTwMaxGrid][HS_TWOHOT_STATS]
     int32_t *twohot_counts = nullptr;      // hs_twohot_value: its own counts of k_ppo_count, [kPpoCountGrid]
-    float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kEmbMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
-    float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kLstmMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
-    float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kDenseMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
+    float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
+    float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
+    float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -265,6 +266,8 @@ int poll_status(hs_sim *s) {
 // section 5).  Hence launch_* are ordinary functions, a new stage goes after the last one, and a kernel is launched from a
 // template only where that template is instantiated at its call (with_elem, by its deduced return type) or where the
 // kernel has always been launched from one (launch_pack_as, launch_pack_moments_sum<>, the with_* of an absent array).
+// What the row-wise kernels (k_embed, k_lstm, k_dense) share, and the one fixed-order sum kernel of every stage, is in
+// hs_rows.h.
 namespace {
 // ---- what the checks share ----
 size_t elem_size(int32_t dtype) { return dtype == HS_DTYPE_F32 ? 4u : 2u; }
@@ -348,8 +351,13 @@ template <typename F> void with_optional_elem(const void *p, int32_t dtype, F f)
 template <int... Vs, typename F> void with_constant(int32_t v, F f) {
     (void)(... || (v == Vs && (f(std::integral_constant<int, Vs>{}), true)));
 }
-// the element type of an array as the encoder's and the LSTM's kernels take it, a run-time code
-int elem_code(int32_t dtype) { return dtype == HS_DTYPE_F32 ? hs::kEmbF32 : dtype == HS_DTYPE_BF16 ? hs::kEmbBf16 : hs::kEmbF16; }
+// the element type of an array as the row-wise kernels take it, a run-time code
+int elem_code(int32_t dtype) { return dtype == HS_DTYPE_F32 ? hs::kElemF32 : dtype == HS_DTYPE_BF16 ? hs::kElemBf16 : hs::kElemF16; }
+// The fixed-order sum of a stage's `nparts` workspace slices of `len` values into `out`.  The return type is deduced, as
+// with_elem's, so that a call instantiates k_partials_sum at that place in the file.
+template <typename T, int kCols, int kSegs> auto launch_partials_sum(hipStream_t strm, const T *partials, int nparts, int len, T *out) {
+    hipLaunchKernelGGL((hs::k_partials_sum<T, kCols, kSegs>), dim3((len + kCols - 1) / kCols), dim3(kCols * kSegs), 0, strm, partials, nparts, len, out);
+}
 }  // namespace
 
 // ---- policy inputs (hs_k_pack.h) ----
@@ -380,13 +388,10 @@ int check_pack(hs_sim *s, const hs_pack_request *r) {
     return HS_OK;
 }
 // The fixed-order sum of the workgroups' moments, after a k_pack or k_pack_norm that wrote them.  A template, so that
-// k_pack_moments_sum is instantiated after the k_pack kernels of launch_pack.
+// its k_partials_sum is instantiated after the k_pack kernels of launch_pack.
 template <int kSegs = hs::kPackSumSegs>
 int launch_pack_moments_sum(hs_sim *s, hipStream_t strm, const hs_pack_request *r, int rows) {
-    constexpr int kCols = hs::kPackThreads / kSegs;
-    if (r->moments)
-        hipLaunchKernelGGL(hs::k_pack_moments_sum<kSegs>, dim3((hs::kPackMoments + kCols - 1) / kCols), dim3(hs::kPackThreads), 0, strm,
-                           (const double *)s->pack_partials, hs::pack_grid(rows), r->moments);
+    if (r->moments) launch_partials_sum<double, hs::kPackThreads / kSegs, kSegs>(strm, s->pack_partials, hs::pack_grid(rows), hs::kPackMoments, r->moments);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -490,9 +495,7 @@ int launch_gae(hs_sim *s, hipStream_t strm, const hs_gae_request *r) {
                            r->moments ? s->gae_partials : nullptr, s->S.N * s->A, r->steps, r->gamma, r->lambda};
     const dim3 grid(hs::gae_grid(a.rows)), blk(hs::kGaeThreads);
     with_elem(r->value_dtype, [&](auto t) { hipLaunchKernelGGL(hs::k_gae<decltype(t)>, grid, blk, 0, strm, a); });
-    if (r->moments)
-        hipLaunchKernelGGL(hs::k_gae_moments_sum<>, dim3(1), dim3(hs::kGaeMoments * hs::kGaeSumSegs), 0, strm, (const double *)s->gae_partials,
-                           hs::gae_grid(a.rows), r->moments);
+    if (r->moments) launch_partials_sum<double, hs::kGaeMoments, hs::kGaeSumSegs>(strm, s->gae_partials, hs::gae_grid(a.rows), hs::kGaeMoments, r->moments);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -563,9 +566,7 @@ int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
             });
         });
     });
-    if (r->stats)
-        hipLaunchKernelGGL(hs::k_ppo_stats_sum<>, dim3(1), dim3(hs::kPpoStats * hs::kPpoSumSegs), 0, strm, (const double *)s->ppo_partials,
-                           hs::ppo_grid(a.n), r->stats);
+    if (r->stats) launch_partials_sum<double, hs::kPpoStats, hs::kPpoSumSegs>(strm, s->ppo_partials, hs::ppo_grid(a.n), hs::kPpoStats, r->stats);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -680,9 +681,7 @@ int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
             });
         });
     });
-    if (r->stats)
-        hipLaunchKernelGGL(hs::k_twohot_stats_sum<>, dim3(1), dim3(hs::kTwStats * hs::kTwSumSegs), 0, strm, (const double *)s->twohot_partials,
-                           hs::twohot_grid(a.n), r->stats);
+    if (r->stats) launch_partials_sum<double, hs::kTwStats, hs::kTwSumSegs>(strm, s->twohot_partials, hs::twohot_grid(a.n), hs::kTwStats, r->stats);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -690,7 +689,7 @@ int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
 
 // ---- the entity encoder (hs_k_embed.h) ----
 namespace {
-static_assert(HS_EMBED_PARAM_ROWS == hs::kEmbParamRows && HS_EMBED_MAX_GRID_BWD == hs::kEmbMaxGridBwd && HS_EMBED_SUM_SEGS == hs::kEmbSumSegs &&
+static_assert(HS_EMBED_PARAM_ROWS == hs::kEmbParamRows && HS_EMBED_MAX_GRID_BWD == hs::kRowsMaxGridBwd && HS_EMBED_SUM_SEGS == hs::kRowsSumSegs &&
               HS_EMBED_ROWS_PER_WAVE(32) == hs::EmbCfg<32>::kSub && HS_EMBED_ROWS_PER_WAVE(64) == hs::EmbCfg<64>::kSub &&
               HS_EMBED_ROWS_PER_WAVE(128) == hs::EmbCfg<128>::kSub, "hs_entity_encode_request and k_embed agree");
 static_assert(sizeof(hs_entity_encode_request) == 56 && offsetof(hs_entity_encode_request, n) == 16 && offsetof(hs_entity_encode_request, embed_dim) == 24 &&
@@ -750,7 +749,7 @@ int launch_embed(hs_sim *, hipStream_t strm, const hs_entity_encode_request *r) 
     hs::EmbedArgs a = {};
     a.rows = r->rows; a.params = r->params; a.features = r->features; a.argmax = r->argmax;
     a.n = r->n; a.rowsType = elem_code(r->rows_dtype); a.featType = elem_code(r->features_dtype); a.eps = r->eps; a.slope = r->slope;
-    const dim3 grid(hs::emb_grid(a.n, r->embed_dim, hs::kEmbMaxGrid)), blk(hs::kEmbThreads);
+    const dim3 grid(hs::rows_grid(a.n, hs::emb_rows(r->embed_dim), hs::kRowsMaxGrid)), blk(hs::kRowsThreads);
     with_constant<32, 64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_fwd<decltype(e)::value>), grid, blk, 0, strm, a); });
     HS_HIP(hipGetLastError());
     return HS_OK;
@@ -761,10 +760,9 @@ int launch_embed_bwd(hs_sim *s, hipStream_t strm, const hs_entity_encode_backwar
     hs::EmbedBwdArgs a = {};
     a.rows = r->rows; a.params = r->params; a.gradFeatures = r->grad_features; a.argmax = r->argmax; a.workspace = s->embed_partials;
     a.n = r->n; a.rowsType = elem_code(r->rows_dtype); a.gradType = elem_code(r->grad_dtype); a.eps = r->eps; a.slope = r->slope;
-    const int nparts = hs::emb_grid(a.n, r->embed_dim, hs::kEmbMaxGridBwd), len = hs::kEmbParamRows * r->embed_dim;
-    with_constant<32, 64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_bwd<decltype(e)::value>), dim3(nparts), dim3(hs::kEmbThreads), 0, strm, a); });
-    hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
-                       (const float *)s->embed_partials, nparts, len, r->grad_params);
+    const int nparts = hs::rows_grid(a.n, hs::emb_rows(r->embed_dim), hs::kRowsMaxGridBwd), len = hs::kEmbParamRows * r->embed_dim;
+    with_constant<32, 64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_embed_bwd<decltype(e)::value>), dim3(nparts), dim3(hs::kRowsThreads), 0, strm, a); });
+    launch_partials_sum<float, hs::kRowsSumCols, hs::kRowsSumSegs>(strm, s->embed_partials, nparts, len, r->grad_params);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -772,8 +770,8 @@ int launch_embed_bwd(hs_sim *s, hipStream_t strm, const hs_entity_encode_backwar
 
 // ---- the recurrent core (hs_k_lstm.h) ----
 namespace {
-static_assert(HS_LSTM_PARAM_ROWS == hs::kLstmParamRows && HS_LSTM_MAX_GRID_BWD == hs::kLstmMaxGridBwd && HS_LSTM_MAX_HIDDEN == hs::kLstmMaxH &&
-              HS_LSTM_ROWS_PER_ROUND == hs::kLstmWaves, "hs_lstm_cell_request and k_lstm agree");
+static_assert(HS_LSTM_PARAM_ROWS == hs::kLstmParamRows && HS_LSTM_MAX_GRID_BWD == hs::kRowsMaxGridBwd && HS_LSTM_MAX_HIDDEN == hs::kLstmMaxH &&
+              HS_LSTM_ROWS_PER_ROUND == hs::kRowsWaves, "hs_lstm_cell_request and k_lstm agree");
 static_assert(sizeof(hs_lstm_cell_request) == 80 && offsetof(hs_lstm_cell_request, clear) == 24 && offsetof(hs_lstm_cell_request, n) == 32 &&
               offsetof(hs_lstm_cell_request, y_dtype) == 44 && offsetof(hs_lstm_cell_request, eps) == 48 && offsetof(hs_lstm_cell_request, y) == 56 &&
               offsetof(hs_lstm_cell_request, c_next) == 72, "hs_lstm_cell_request layout (gpu_hideseek/recurrent.py mirrors it)");
@@ -840,7 +838,7 @@ int launch_lstm(hs_sim *, hipStream_t strm, const hs_lstm_cell_request *r) {
     hs::LstmArgs a = {};
     a.gates = r->gates; a.cPrev = r->c_prev; a.params = r->cell_params; a.clear = r->clear; a.y = r->y; a.hNext = r->h_next; a.cNext = r->c_next;
     a.n = r->n; a.gatesType = elem_code(r->gates_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps;
-    const dim3 grid(hs::lstm_grid(a.n, hs::kLstmMaxGrid)), blk(hs::kLstmThreads);
+    const dim3 grid(hs::rows_grid(a.n, hs::kRowsWaves, hs::kRowsMaxGrid)), blk(hs::kRowsThreads);
     with_constant<64, 128, 256, 512>(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_fwd<decltype(h)::value>), grid, blk, 0, strm, a); });
     HS_HIP(hipGetLastError());
     return HS_OK;
@@ -853,11 +851,9 @@ int launch_lstm_bwd(hs_sim *s, hipStream_t strm, const hs_lstm_cell_backward_req
     a.gradY = r->grad_y; a.gradHNext = r->grad_h_next; a.gradCNext = r->grad_c_next;
     a.gradGates = r->grad_gates; a.gradCPrev = r->grad_c_prev; a.workspace = r->grad_cell_params ? s->lstm_partials : nullptr;
     a.n = r->n; a.gatesType = elem_code(r->gates_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps;
-    const int nparts = hs::lstm_grid(a.n, hs::kLstmMaxGridBwd), len = hs::kLstmParamRows * r->hidden;
-    with_constant<64, 128, 256, 512>(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_bwd<decltype(h)::value>), dim3(nparts), dim3(hs::kLstmThreads), 0, strm, a); });
-    if (r->grad_cell_params)
-        hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
-                           (const float *)s->lstm_partials, nparts, len, r->grad_cell_params);
+    const int nparts = hs::rows_grid(a.n, hs::kRowsWaves, hs::kRowsMaxGridBwd), len = hs::kLstmParamRows * r->hidden;
+    with_constant<64, 128, 256, 512>(r->hidden, [&](auto h) { hipLaunchKernelGGL((hs::k_lstm_bwd<decltype(h)::value>), dim3(nparts), dim3(hs::kRowsThreads), 0, strm, a); });
+    if (r->grad_cell_params) launch_partials_sum<float, hs::kRowsSumCols, hs::kRowsSumSegs>(strm, s->lstm_partials, nparts, len, r->grad_cell_params);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -865,8 +861,8 @@ int launch_lstm_bwd(hs_sim *s, hipStream_t strm, const hs_lstm_cell_backward_req
 
 // ---- a dense layer after its GEMM (hs_k_dense.h) ----
 namespace {
-static_assert(HS_DENSE_PARAM_ROWS == hs::kDenseParamRows && HS_DENSE_MAX_GRID_BWD == hs::kDenseMaxGridBwd && HS_DENSE_MAX_CHANNELS == hs::kDenseMaxC &&
-              HS_DENSE_ROWS_PER_ROUND == hs::kDenseWaves, "hs_dense_norm_act_request and k_dense agree");
+static_assert(HS_DENSE_PARAM_ROWS == hs::kDenseParamRows && HS_DENSE_MAX_GRID_BWD == hs::kRowsMaxGridBwd && HS_DENSE_MAX_CHANNELS == hs::kDenseMaxC &&
+              HS_DENSE_ROWS_PER_ROUND == hs::kRowsWaves, "hs_dense_norm_act_request and k_dense agree");
 static_assert(sizeof(hs_dense_norm_act_request) == 48 && offsetof(hs_dense_norm_act_request, params) == 8 && offsetof(hs_dense_norm_act_request, n) == 16 &&
               offsetof(hs_dense_norm_act_request, y_dtype) == 28 && offsetof(hs_dense_norm_act_request, eps) == 32 &&
               offsetof(hs_dense_norm_act_request, slope) == 36 && offsetof(hs_dense_norm_act_request, y) == 40,
@@ -925,7 +921,7 @@ int launch_dense(hs_sim *, hipStream_t strm, const hs_dense_norm_act_request *r)
     hs::DenseArgs a = {};
     a.z = r->z; a.params = r->params; a.y = r->y;
     a.n = r->n; a.zType = elem_code(r->z_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps; a.slope = r->slope;
-    const dim3 grid(hs::dense_grid(a.n, hs::kDenseMaxGrid)), blk(hs::kDenseThreads);
+    const dim3 grid(hs::rows_grid(a.n, hs::kRowsWaves, hs::kRowsMaxGrid)), blk(hs::kRowsThreads);
     with_constant<64, 128, 256, 512>(r->channels, [&](auto ch) { hipLaunchKernelGGL((hs::k_dense_fwd<decltype(ch)::value>), grid, blk, 0, strm, a); });
     HS_HIP(hipGetLastError());
     return HS_OK;
@@ -936,11 +932,9 @@ int launch_dense_bwd(hs_sim *s, hipStream_t strm, const hs_dense_norm_act_backwa
     hs::DenseBwdArgs a = {};
     a.z = r->z; a.params = r->params; a.gradY = r->grad_y; a.gradZ = r->grad_z; a.workspace = r->grad_params ? s->dense_partials : nullptr;
     a.n = r->n; a.zType = elem_code(r->z_dtype); a.yType = elem_code(r->y_dtype); a.eps = r->eps; a.slope = r->slope;
-    const int nparts = hs::dense_grid(a.n, hs::kDenseMaxGridBwd), len = hs::kDenseParamRows * r->channels;
-    with_constant<64, 128, 256, 512>(r->channels, [&](auto ch) { hipLaunchKernelGGL((hs::k_dense_bwd<decltype(ch)::value>), dim3(nparts), dim3(hs::kDenseThreads), 0, strm, a); });
-    if (r->grad_params)
-        hipLaunchKernelGGL(hs::k_embed_grad_sum<>, dim3((len + hs::kEmbSumCols - 1) / hs::kEmbSumCols), dim3(hs::kEmbSumCols * hs::kEmbSumSegs), 0, strm,
-                           (const float *)s->dense_partials, nparts, len, r->grad_params);
+    const int nparts = hs::rows_grid(a.n, hs::kRowsWaves, hs::kRowsMaxGridBwd), len = hs::kDenseParamRows * r->channels;
+    with_constant<64, 128, 256, 512>(r->channels, [&](auto ch) { hipLaunchKernelGGL((hs::k_dense_bwd<decltype(ch)::value>), dim3(nparts), dim3(hs::kRowsThreads), 0, strm, a); });
+    if (r->grad_params) launch_partials_sum<float, hs::kRowsSumCols, hs::kRowsSumSegs>(strm, s->dense_partials, nparts, len, r->grad_params);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }
@@ -1078,9 +1072,9 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
     HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
-    HS_ALLOC(s->embed_partials, (size_t)hs::kEmbMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
-    HS_ALLOC(s->lstm_partials, (size_t)hs::kLstmMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
-    HS_ALLOC(s->dense_partials, (size_t)hs::kDenseMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
+    HS_ALLOC(s->embed_partials, (size_t)hs::kRowsMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
+    HS_ALLOC(s->lstm_partials, (size_t)hs::kRowsMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
+    HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {

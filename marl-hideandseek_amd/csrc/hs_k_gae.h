@@ -10,7 +10,7 @@
 //                adv   = ended ? delta : delta + gl * carry;   ret = adv + v;   carry = adv
 // Moments (optional), over the active (t, row) pairs, in f64: sum adv, sum adv^2, sum ret, sum ret^2, count.  Every lane
 // adds its own terms from t = T-1 down, the workgroup's lanes are added in lane order, the workgroups' partials are added
-// by k_gae_moments_sum in a fixed order: no atomics, and an order that depends on (rows, T) alone.
+// by k_partials_sum (hs_rows.h) in its fixed order: no atomics, and an order that depends on (rows, T) alone.
 //
 // The recurrence is serial in t and independent across rows: one lane per row, so that a wave's access to time slice t
 // of an array is one contiguous 256-byte range (128 for bf16 / f16 values).  The chain is two to three dependent f32
@@ -27,7 +27,7 @@ namespace hs {
 constexpr int kGaeMaxSteps = 4096, kGaeMoments = 5;
 constexpr int kGaeThreads = 64;           // one wave per workgroup: 96 000 rows are 1 500 workgroups over 256 CUs
 constexpr int kGaeBlock = 8;              // time steps a lane holds in registers per block; two blocks alternate
-constexpr int kGaeSumSegs = 32;           // k_gae_moments_sum: segments of the partials summed side by side
+constexpr int kGaeSumSegs = 32;           // k_partials_sum: segments of the partials summed side by side
 
 struct GaeArgs {
     const float *reward;
@@ -132,25 +132,6 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(GaeArgs a) {
             for (int k = 1; k < kGaeThreads; ++k) s += red[tid][k];
             a.partials[(size_t)blockIdx.x * kGaeMoments + tid] = s;
         }
-    }
-}
-
-// out[c] = sum of partials[0 .. nparts)[c], always in the same order: kSegs lanes per moment each add a contiguous
-// run of workgroups in order, then the first of them adds the runs in order (the pattern of k_pack_moments_sum).
-template <int kSegs = kGaeSumSegs>
-__global__ __launch_bounds__(kGaeMoments * kSegs) void k_gae_moments_sum(const double *__restrict__ partials, int nparts, double *__restrict__ out) {
-    __shared__ double seg[kSegs][kGaeMoments];
-    const int c = threadIdx.x % kGaeMoments, sg = threadIdx.x / kGaeMoments;
-    const int per = (nparts + kSegs - 1) / kSegs;
-    const int b0 = sg * per, b1 = b0 + per < nparts ? b0 + per : nparts;
-    double s = 0.0;
-    for (int b = b0; b < b1; ++b) s += partials[(size_t)b * kGaeMoments + c];
-    seg[sg][c] = s;
-    __syncthreads();
-    if (sg == 0) {
-        double t = seg[0][c];
-        for (int k = 1; k < kSegs; ++k) t += seg[k][c];
-        out[c] = t;
     }
 }
 

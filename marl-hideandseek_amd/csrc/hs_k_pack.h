@@ -15,7 +15,7 @@
 // (an IEEE f32 multiplication, not a select).  Narrowing to bf16 / f16 rounds the f32 value to nearest even.
 // Moments (optional): with m = self_mask of the row and x the f32 critic value, sum m x, sum m x x per column and sum m,
 // in f64: each workgroup keeps its sums in registers over the row blocks it owns and stores them to its row of
-// a workspace; k_pack_moments_sum adds the rows in a fixed order.  No atomics, so the result is the same on every run.
+// a workspace; k_partials_sum (hs_rows.h) adds the rows in its fixed order.  No atomics, so the result is the same on every run.
 //
 // It is a gather / convert / scatter kernel bound by HBM.  A workgroup takes kPackRows consecutive agent rows at a time
 // (grid-stride over row blocks).  Every input table is ONE contiguous byte range over those rows, starting on a
@@ -46,7 +46,7 @@ static_assert(kPackRow % 8 == 0, "a 16-byte piece of a bf16 / f16 row must not c
 constexpr int kPackThreads = 256;
 constexpr int kPackRows = 32;             // agent rows per block: 37 KB of image, four workgroups per CU
 constexpr int kPackMaxGrid = 1024;        // workgroups (and rows of the moments workspace): 256 CUs x 4
-constexpr int kPackSumSegs = 16;          // k_pack_moments_sum: segments of the workspace rows summed side by side
+constexpr int kPackSumSegs = 16;          // k_partials_sum: segments of the workspace rows summed side by side
 
 struct PackAbsent {};                     // element type of an output that was not requested
 typedef __bf16 PackBf16;
@@ -235,27 +235,6 @@ HSD void pack_blocks(const PackArgs a, const float *__restrict__ table) {
 template <typename TA, typename TC, bool MOM>
 __global__ __launch_bounds__(kPackThreads) void k_pack(PackArgs a) {
     pack_blocks<TA, TC, MOM, false>(a, nullptr);
-}
-
-// out[c] = sum of partials[0 .. nparts)[c], always in the same order: kPackSumSegs lanes per column each add a
-// contiguous run of rows in row order, then the first of them adds the runs in order.
-template <int kSegs = kPackSumSegs>
-__global__ __launch_bounds__(kPackThreads) void k_pack_moments_sum(const double *__restrict__ partials, int nparts, double *__restrict__ out) {
-    constexpr int kCols = kPackThreads / kSegs;
-    __shared__ double seg[kSegs][kCols];
-    const int cl = threadIdx.x % kCols, sg = threadIdx.x / kCols, c = blockIdx.x * kCols + cl;
-    const int per = (nparts + kSegs - 1) / kSegs;
-    const int b0 = sg * per, b1 = b0 + per < nparts ? b0 + per : nparts;
-    double s = 0.0;
-    if (c < kPackMoments)
-        for (int b = b0; b < b1; ++b) s += partials[(size_t)b * kPackMoments + c];
-    seg[sg][cl] = s;
-    __syncthreads();
-    if (sg == 0 && c < kPackMoments) {
-        double t = seg[0][cl];
-        for (int k = 1; k < kSegs; ++k) t += seg[k][cl];
-        out[c] = t;
-    }
 }
 
 }  // namespace hs

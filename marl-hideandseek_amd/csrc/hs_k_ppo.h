@@ -18,8 +18,8 @@
 //           in the image with their gradients; e_i is recomputed by the same expf of the same argument.  The lane of
 //           head 0 also makes the value term and adds the sample's terms to its f64 statistics.
 //   store   lane q stores element q of the block's gradients, rounded to grad_dtype, and lane r the r-th grad_value.
-// The statistics of a workgroup's samples are added in lane order and left in partials[blockIdx.x]; k_ppo_stats_sum adds
-// the workgroups in a fixed order (the pattern of k_gae_moments_sum).  No atomics, no scratch, no register array indexed
+// The statistics of a workgroup's samples are added in lane order and left in partials[blockIdx.x]; k_partials_sum
+// (hs_rows.h) adds the workgroups in its fixed order.  No atomics, no scratch, no register array indexed
 // dynamically; nothing in a sample's results depends on the grid or on the block it falls into.
 //
 // The number of active samples, which every gradient is divided by, is counted before: k_ppo_count leaves one integer
@@ -37,7 +37,7 @@ constexpr int kPpoLanesPerRow = kSampleLanesPerRow;                     // five 
 constexpr int kPpoRows = kPpoThreads / kPpoLanesPerRow;                 // 32 samples per block
 constexpr int kPpoMaxGrid = 2048;                                       // 256 CUs x the 8 workgroups of 4 waves a CU holds
 constexpr int kPpoCountGrid = kPpoThreads;                              // k_ppo_count: one partial per lane of k_ppo
-constexpr int kPpoSumSegs = 32;                                         // k_ppo_stats_sum: segments summed side by side
+constexpr int kPpoSumSegs = 32;                                         // k_partials_sum: segments summed side by side
 constexpr int kPpoRowArrays = 6;                                        // old_log_prob, advantage, mask, value, returns, old_value
 static_assert(kPpoRows * kSampleHeads <= kPpoThreads && kPpoRowArrays * kPpoRows <= kPpoThreads, "a lane per staged element");
 static_assert(kPpoRows == 32, "the lanes of a per-sample array are half a wave");
@@ -242,25 +242,6 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo(PpoArgs a) {
             for (int k = 1; k < kPpoRows; ++k) s += im.stat[tid][k];
             a.partials[(size_t)blockIdx.x * kPpoStats + tid] = s;
         }
-    }
-}
-
-// out[c] = sum of partials[0 .. nparts)[c], always in the same order: kSegs lanes per statistic each add a contiguous
-// run of workgroups in order, then the first of them adds the runs in order (k_gae_moments_sum's pattern).
-template <int kSegs = kPpoSumSegs>
-__global__ __launch_bounds__(kPpoStats * kSegs) void k_ppo_stats_sum(const double *__restrict__ partials, int nparts, double *__restrict__ out) {
-    __shared__ double seg[kSegs][kPpoStats];
-    const int c = threadIdx.x % kPpoStats, sg = threadIdx.x / kPpoStats;
-    const int per = (nparts + kSegs - 1) / kSegs;
-    const int b0 = sg * per, b1 = b0 + per < nparts ? b0 + per : nparts;
-    double s = 0.0;
-    for (int b = b0; b < b1; ++b) s += partials[(size_t)b * kPpoStats + c];
-    seg[sg][c] = s;
-    __syncthreads();
-    if (sg == 0) {
-        double t = seg[0][c];
-        for (int k = 1; k < kSegs; ++k) t += seg[k][c];
-        out[c] = t;
     }
 }
 

@@ -19,7 +19,7 @@
 //   store   lane i stores the i-th 16 bytes of the block's gradients where grad_stride == B and the base is aligned,
 //           else by element; lane r stores the r-th value.
 // The statistics of a workgroup's samples are added in lane order and left in partials[blockIdx.x];
-// k_twohot_stats_sum adds the workgroups in a fixed order (k_ppo_stats_sum's pattern).  No atomics, no scratch; nothing
+// k_partials_sum (hs_rows.h) adds the workgroups in its fixed order.  No atomics, no scratch; nothing
 // in a sample's results depends on the grid, on the block it falls into or on the path its bytes took.
 //
 // The number of active samples comes from k_ppo_count (hs_k_ppo.h) into a counts buffer of this call's own.
@@ -224,24 +224,6 @@ __global__ __launch_bounds__(kTwThreads) void k_twohot(TwohotArgs a) {
             for (int k = 1; k < kTwRows; ++k) s += im.stat[tid][k];
             a.partials[(size_t)blockIdx.x * kTwStats + tid] = s;
         }
-    }
-}
-
-// out[c] = sum of partials[0 .. nparts)[c], always in the same order (k_ppo_stats_sum's pattern).
-template <int kSegs = kTwSumSegs>
-__global__ __launch_bounds__(kTwStats * kSegs) void k_twohot_stats_sum(const double *__restrict__ partials, int nparts, double *__restrict__ out) {
-    __shared__ double seg[kSegs][kTwStats];
-    const int c = threadIdx.x % kTwStats, sg = threadIdx.x / kTwStats;
-    const int per = (nparts + kSegs - 1) / kSegs;
-    const int b0 = sg * per, b1 = b0 + per < nparts ? b0 + per : nparts;
-    double s = 0.0;
-    for (int b = b0; b < b1; ++b) s += partials[(size_t)b * kTwStats + c];
-    seg[sg][c] = s;
-    __syncthreads();
-    if (sg == 0) {
-        double t = seg[0][c];
-        for (int k = 1; k < kSegs; ++k) t += seg[k][c];
-        out[c] = t;
     }
 }
 

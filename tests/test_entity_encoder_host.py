@@ -549,9 +549,11 @@ def test_header_states_the_requests(hideseek_lib):
     lib = C.CDLL(hideseek_lib)
     for fn in ("hs_entity_encode", "hs_entity_encode_async", "hs_entity_encode_backward", "hs_entity_encode_backward_async"):
         assert hasattr(lib, fn)
-    kernel = open(os.path.join(root, "marl-hideandseek_amd", "csrc", "hs_k_embed.h")).read()
-    assert int(re.search(r"kEmbMaxGridBwd = (\d+);", kernel).group(1)) == MAX_GRID_BWD
-    assert int(re.search(r"kEmbSumSegs = (\d+);", kernel).group(1)) == SUM_SEGS
+    csrc = os.path.join(root, "marl-hideandseek_amd", "csrc")
+    kernel, shared, host = (open(os.path.join(csrc, f)).read() for f in ("hs_k_embed.h", "hs_rows.h", "hideseek.hip"))
+    assert '#include "hs_rows.h"' in kernel and "HS_EMBED_MAX_GRID_BWD == hs::kRowsMaxGridBwd && HS_EMBED_SUM_SEGS == hs::kRowsSumSegs" in host
+    assert int(re.search(r"kRowsMaxGridBwd = (\d+);", shared).group(1)) == MAX_GRID_BWD
+    assert int(re.search(r"kRowsSumSegs = (\d+),", shared).group(1)) == SUM_SEGS
     assert int(re.search(r"kEmbParamRows = (\d+);", kernel).group(1)) == PARAM_ROWS
-    assert "kEmbWaves = kEmbThreads / 64" in kernel and int(re.search(r"kEmbThreads = (\d+)", kernel).group(1)) == 64 * WAVES == 64 * N.WAVES
+    assert "kRowsWaves = kRowsThreads / 64" in shared and int(re.search(r"kRowsThreads = (\d+)", shared).group(1)) == 64 * WAVES == 64 * N.WAVES
     assert (N.DEFAULT_EPS, N.DEFAULT_SLOPE) == (EPS, SLOPE)

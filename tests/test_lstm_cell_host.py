@@ -521,7 +521,10 @@ def test_header_states_the_requests(hideseek_lib):
     lib = C.CDLL(hideseek_lib)
     for fn in ("hs_lstm_cell", "hs_lstm_cell_async", "hs_lstm_cell_backward", "hs_lstm_cell_backward_async"):
         assert hasattr(lib, fn)
-    kernel = open(os.path.join(root, "marl-hideandseek_amd", "csrc", "hs_k_lstm.h")).read()
+    csrc = os.path.join(root, "marl-hideandseek_amd", "csrc")
+    kernel, shared, host = (open(os.path.join(csrc, f)).read() for f in ("hs_k_lstm.h", "hs_rows.h", "hideseek.hip"))
     assert int(re.search(r"kLstmParamRows = (\d+);", kernel).group(1)) == PARAM_ROWS and int(re.search(r"kLstmMaxH = (\d+);", kernel).group(1)) == max(HIDDEN)
-    assert "kLstmMaxGridBwd = kEmbMaxGridBwd" in kernel and "kLstmMaxGrid = kEmbMaxGrid;" in kernel
-    assert "kLstmWaves = kLstmThreads / 64" in kernel and int(re.search(r"kLstmThreads = (\d+)", kernel).group(1)) == 64 * WAVES
+    # the grid caps, the workgroup and the segments are the ones every row-wise kernel shares (hs_rows.h)
+    assert '#include "hs_rows.h"' in kernel and "HS_LSTM_MAX_GRID_BWD == hs::kRowsMaxGridBwd" in host and "HS_LSTM_ROWS_PER_ROUND == hs::kRowsWaves" in host
+    assert int(re.search(r"kRowsMaxGridBwd = (\d+);", shared).group(1)) == MAX_GRID_BWD and int(re.search(r"kRowsSumSegs = (\d+),", shared).group(1)) == SUM_SEGS
+    assert "kRowsWaves = kRowsThreads / 64" in shared and int(re.search(r"kRowsThreads = (\d+)", shared).group(1)) == 64 * WAVES

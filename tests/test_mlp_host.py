@@ -514,10 +514,13 @@ def test_header_states_the_requests(hideseek_lib):
         assert hasattr(lib, fn)
     # the stated defaults: eps and slope in the header's text
     assert "eps = 1e-6 and slope = 0.01" in src
-    kernel = open(os.path.join(root, "marl-hideandseek_amd", "csrc", "hs_k_dense.h")).read()
+    csrc = os.path.join(root, "marl-hideandseek_amd", "csrc")
+    kernel, shared, host = (open(os.path.join(csrc, f)).read() for f in ("hs_k_dense.h", "hs_rows.h", "hideseek.hip"))
     assert int(re.search(r"kDenseParamRows = (\d+);", kernel).group(1)) == PARAM_ROWS and int(re.search(r"kDenseMaxC = (\d+);", kernel).group(1)) == max(CHANNELS)
-    assert "kDenseMaxGridBwd = kEmbMaxGridBwd" in kernel and "kDenseMaxGrid = kEmbMaxGrid;" in kernel
-    assert "kDenseWaves = kDenseThreads / 64" in kernel and int(re.search(r"kDenseThreads = (\d+)", kernel).group(1)) == 64 * WAVES
+    # the grid caps, the workgroup and the segments are the ones every row-wise kernel shares (hs_rows.h)
+    assert '#include "hs_rows.h"' in kernel and "HS_DENSE_MAX_GRID_BWD == hs::kRowsMaxGridBwd" in host and "HS_DENSE_ROWS_PER_ROUND == hs::kRowsWaves" in host
+    assert int(re.search(r"kRowsMaxGridBwd = (\d+);", shared).group(1)) == MAX_GRID_BWD and int(re.search(r"kRowsSumSegs = (\d+),", shared).group(1)) == SUM_SEGS
+    assert "kRowsWaves = kRowsThreads / 64" in shared and int(re.search(r"kRowsThreads = (\d+)", shared).group(1)) == 64 * WAVES
 
 
 # ---- the policy modules on the CPU, with eager pieces ----

@@ -8,11 +8,13 @@ import sys
 
 
 def kernels(path):
+    lines = open(path).readlines()
+    funcs = set(re.findall(r"^\s*\.type\s+(\w+),@function", "".join(lines), re.M))     # not the data objects
     out, name = {}, None
-    for l in open(path):
+    for l in lines:
         l = re.sub(r"\s*(;|//).*", "", l).strip()
         m = re.match(r"((?:_Z|k_)\w+):$", l)      # mangled names, and the extern "C" kernels of hideseek.hip
-        if m:
+        if m and m.group(1) in funcs:
             name = m.group(1)
             out[name] = []
         elif l.startswith(".Lfunc_end"):
