@@ -837,7 +837,9 @@ int32_t hs_train_interface(const hs_iface_entry **entries);
  *     are identical to an unbounded solver.  Sticky totals since hs_create; a performance signal, not an error.
  *   dropped_dd_pairs / dropped_static_pairs: candidate pairs discarded.  Always 0 (nothing can overflow the spill
  *     lists); kept so that callers can assert it (bench.py, tools/train_config_bench.py do).
- *   graphs_in_use: always 0 (HIP-graph replay was removed); the field keeps the layout. */
+ *   graphs_in_use: always 0 (HIP-graph replay was removed); the field keeps the layout.
+ *   split_steps: blocking steps (hs_step) that ran as two chains, late and early octets, since hs_create; late_octets:
+ *     the octets of their late groups, summed over those steps (hs_set_late_threshold). */
 typedef struct hs_device_status {
     int64_t dropped_dd_pairs;
     int64_t dropped_static_pairs;
@@ -845,8 +847,18 @@ typedef struct hs_device_status {
     int32_t reserved;
     int64_t spilled_dd_pairs;
     int64_t spilled_static_pairs;
+    int64_t split_steps;
+    int64_t late_octets;
 } hs_device_status;
 int32_t hs_get_device_status(hs_sim *sim, hs_device_status *out);
+
+/* The one tunable of the split schedule of the blocking hs_step: the octets (8 worlds, one physics
+ * wave) whose mean time over the last two steps exceeded `factor` x the mean over all octets form the late group of the
+ * next step, the others the early group; the two groups run as independent k_physics -> k_observe chains on two
+ * streams.  A parameter of that one schedule, not a switch: 0 makes every octet late, a huge value (values above 1e6
+ * are taken as 1e6) nobody, and one launch of each pair then finds no octet to serve.  Results do not depend on it.
+ * The default is fixed by measurement.  Takes effect from the groups the next step forms, i.e. one step later. */
+int32_t hs_set_late_threshold(hs_sim *sim, float factor);
 
 /* maxAgentsPerWorld (src/mgr.cpp:684). */
 int32_t hs_agents_per_world(const hs_sim *sim);

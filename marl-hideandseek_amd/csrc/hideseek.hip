@@ -57,6 +57,9 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
         HS_HIP(hipSetDevice(s->cfg.gpu_id));                                                  \
     } while (0)
 
+// hs_set_late_threshold: the default (fixed by measurement) and the largest factor kept ("nobody is late")
+constexpr float kDefaultLateFactor = 1.00f, kMaxLateFactor = 1.0e6f;
+
 }  // namespace
 
 struct hs_sim {
@@ -80,6 +83,9 @@ struct hs_sim {
     hipStream_t stream = nullptr;          // this handle's own stream: hs_init / hs_step / checkpoints run here
     hipEvent_t evIn = nullptr;             // orders `stream` after the device's legacy default stream (torch's writes to `action`)
     bool step_open = false;                // hs_step_begin without its hs_step_end
+    bool split_fits = false;               // the octets leave physics wave slots free (hs_create): two launches place their waves at once
+    bool split_open = false;               // the open step runs split: its early chain is on `stream` (launch_step)
+    int64_t split_steps = 0;               // steps run split since hs_create (hs_get_device_status)
     std::atomic<int32_t> async_error{0};   // a failed XLA custom call on this handle (hs_xla_*: the ABI has no status channel; XLA's thread)
     hs::SpectateCam *cams = nullptr;       // hs_render_cameras: the device copy of the cameras, grown on demand
     int cam_cap = 0;
@@ -184,9 +190,11 @@ void launch_render(hs_sim *s, hipStream_t strm) {
                        (unsigned *)s->exports[HS_EXPORT_RGB].ptr, (int)d.dims[2], (int)d.dims[1]);
 }
 
-void launch_observe(hs_sim *s, hipStream_t strm) {
+// (serve / step_idx: the group of octets the launch observes and the ring position of the step's groups, hs_state.h)
+void launch_observe(hs_sim *s, hipStream_t strm, int serve = hs::kGroupAll, int step_idx = 0) {
     hs::SimState S = s->S;
     if (S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) return;
+    S.stepIdx = hs::step_idx_arg(step_idx, serve);
     struct RenderAfter {        // HS_FLAG_EXT_RENDER: the agent views are part of every step's observations
         hs_sim *s; hipStream_t strm;
         ~RenderAfter() { if ((s->S.flags & hs::FLAG_EXT_RENDER) && s->exports[HS_EXPORT_DEPTH].ptr) launch_render(s, strm); }
@@ -201,6 +209,8 @@ void launch_observe(hs_sim *s, hipStream_t strm) {
 
 // Deal the worlds to the octets by contact load (hs_k_balance.h), every kBalancePeriod steps: histogram, scan, deal, one copy
 // of the column arena, one move kernel over all columns, commit (six launches and a copy; it was 26 launches and 11 copies).
+int order_after_default_stream(hs_sim *s);
+
 int balance_worlds(hs_sim *s, hipStream_t strm) {
     const hs::SimState &S = s->S;
     const int nfull = S.N / hs::kTile * hs::kTile;
@@ -218,24 +228,50 @@ int balance_worlds(hs_sim *s, hipStream_t strm) {
     return HS_OK;
 }
 
+void launch_physics(hs_sim *s, hipStream_t strm, const hs::SimState &S) {
+    const int noct = (S.N + hs::kTile - 1) / hs::kTile;
+    // rounds of 64 lanes over the octet's bodies: 16 body slots per world with up to 5 agents, 17 with 6
+    if (s->A > hs::kMaxAgents - 1) hipLaunchKernelGGL(hs::k_physics<3>, dim3(noct), dim3(hs::kPhysThreads), 0, strm, S);
+    else hipLaunchKernelGGL(hs::k_physics<2>, dim3(noct), dim3(hs::kPhysThreads), 0, strm, S);
+}
+
 // One step = k_physics (movement + actionSystem, 4 XPBD substeps, rewards / dones / episode results, reset: one
 // kernel, a wave per octet of 8 worlds, hs_k_physics.h) and k_observe.  Manager::init = k_reset then k_observe.
-int launch_step(hs_sim *s, hipStream_t strm, bool first) {
+//
+// `split` (the blocking hs_step only, whose caller waits for the whole device anyway): the step runs as two independent
+// chains, k_physics -> k_observe of the late octets on `strm` and k_physics -> k_observe of the early octets on the
+// handle's own stream, ordered after what `strm` (the legacy default stream) held before the step.  Worlds never
+// interact and every export is indexed by world id, so the chains share nothing but the commuting tick sum; the early
+// group's k_observe fills the SIMDs its physics waves have left while the slowest physics waves finish.  The
+// dependencies are kernel boundaries only.  The caller waits for both streams (hs_step_end).  The steps that keep the
+// one-chain schedule: the one with the periodic deal, profiled steps (ev[0..3] bracket whole kernels), observations
+// skipped or followed by k_render.
+int launch_step(hs_sim *s, hipStream_t strm, bool first, bool split = false) {
     if (!first && ++s->steps_since_balance >= hs::kBalancePeriod) {
         s->steps_since_balance = 0;
+        split = false;
         int rc = balance_worlds(s, strm);
         if (rc != HS_OK) return rc;
     }
     const bool prof = s->profiling;
     hs::SimState S = s->S;
-    const int N = S.N, noct = (N + hs::kTile - 1) / hs::kTile;
-    S.stepIdx = s->step_idx; if (!first) s->step_idx = (s->step_idx + 1) % 3;
-    if (prof) HS_HIP(hipEventRecord(s->ev[0], strm));
-    if (!first) {
-        // rounds of 64 lanes over the octet's bodies: 16 body slots per world with up to 5 agents, 17 with 6
-        if (s->A > hs::kMaxAgents - 1) hipLaunchKernelGGL(hs::k_physics<3>, dim3(noct), dim3(hs::kPhysThreads), 0, strm, S);
-        else hipLaunchKernelGGL(hs::k_physics<2>, dim3(noct), dim3(hs::kPhysThreads), 0, strm, S);
+    const int N = S.N;
+    const int sidx = s->step_idx;
+    S.stepIdx = hs::step_idx_arg(sidx, hs::kGroupAll); if (!first) s->step_idx = (s->step_idx + 1) % 3;
+    if (split && s->split_fits && !first && !prof && !(S.flags & (hs::FLAG_EXT_SKIP_OBSERVATIONS | hs::FLAG_EXT_RENDER))) {
+        HS_TRY(order_after_default_stream(s));       // (before the late chain is queued on the default stream)
+        S.stepIdx = hs::step_idx_arg(sidx, hs::kGroupLate);
+        launch_physics(s, strm, S);
+        launch_observe(s, strm, hs::kGroupLate, sidx);
+        S.stepIdx = hs::step_idx_arg(sidx, hs::kGroupEarly);
+        launch_physics(s, s->stream, S);
+        launch_observe(s, s->stream, hs::kGroupEarly, sidx);
+        s->split_open = true; ++s->split_steps;
+        HS_HIP(hipGetLastError());
+        return HS_OK;
     }
+    if (prof) HS_HIP(hipEventRecord(s->ev[0], strm));
+    if (!first) launch_physics(s, strm, S);
     if (prof) HS_HIP(hipEventRecord(s->ev[1], strm));
     // in a step the reset is the tail of k_physics; only Manager::init launches it on its own
     if (first) hipLaunchKernelGGL(hs::k_reset, dim3((N + 31) / 32), dim3(32), 0, strm, S);     // half-filled waves: the generator diverges per world
@@ -1065,7 +1101,17 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(S.slotOfWorld, N); HS_ALLOC(S.worldOfSlot, NP); HS_ALLOC(S.loadAcc, N); HS_ALLOC(S.wallHist, N);
     HS_ALLOC(S.slotHdr, NP, 0xFF);                                                          // world id -1: empty slot
     HS_ALLOC(S.lidarSinCos, 60);
-    HS_ALLOC(S.octTicks, NP / hs::kTile); HS_ALLOC(S.tickSum, 3);
+    HS_ALLOC(S.octTicks, NP / hs::kTile); HS_ALLOC(S.tickSum, hs::sched_alloc_sums((int)(NP / hs::kTile)));   // + the split schedule's words
+    S.stepIdx = hs::step_idx_arg(0, hs::kGroupAll);
+    {
+        // k_physics holds two waves on each of a CU's four SIMDs.  Two launches place all their waves at once only while
+        // some slots stay free: measured at 2 000 octets for 2 048 slots (every wave starts within 12 us) and at 2 048 for
+        // 2 048 (a second round of waves, 25 % slower than one chain).  Above 63/64 of the slots a step keeps the one chain.
+        int cus = 0;
+        HS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->gpu_id));
+        const int64_t slots = (int64_t)cus * 4 * 2;
+        s->split_fits = (int64_t)(NP / hs::kTile) * 64 <= slots * 63;
+    }
     HS_ALLOC(s->bal_hist, hs::kBalanceBins); HS_ALLOC(s->bal_cursor, hs::kBalanceBins); HS_ALLOC(s->bal_new_slot, N);
     HS_ALLOC(S.status, 4);
     if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
@@ -1079,6 +1125,14 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
         std::vector<int32_t> ones(N, 1), neg(AG * NP, -1), ident(NP);
+        // the first step's groups (ring position 0): every octet early
+        const int32_t noct = (int32_t)(NP / hs::kTile);
+        std::vector<int32_t> octs(noct);
+        for (int32_t i = 0; i < noct; ++i) octs[i] = i;
+        if (hipMemcpy(hs::oct_list(S, 0, hs::kGroupEarly, noct), octs.data(), (size_t)noct * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(hs::group_count(S, 0, hs::kGroupEarly), &noct, 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(hs::sched_words(S) + hs::kSchedFactor, &kDefaultLateFactor, 4, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(HS_ERR_HIP, "initial upload failed");
         for (size_t i = 0; i < NP; ++i) ident[i] = i < N ? (int32_t)i : -1;      // slot == world until k_balance deals them
         if (hipMemcpy(S.slotOfWorld, ident.data(), N * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(S.worldOfSlot, ident.data(), NP * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1132,7 +1186,7 @@ int step_begin(hs_sim *s, bool own_stream) {
     if (s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_step_begin: the previous step was not ended");
     s->step_stream = own_stream ? s->stream : nullptr;
     if (own_stream) HS_TRY(order_after_default_stream(s));
-    HS_TRY(launch_step(s, s->step_stream, false));
+    HS_TRY(launch_step(s, s->step_stream, false, !own_stream));
     s->step_open = true;
     return HS_OK;
 }
@@ -1144,6 +1198,10 @@ int32_t hs_step_end(hs_sim *s) {
     HS_ENTER(s, "null sim");
     if (!s->step_open) return fail(HS_ERR_INVALID_ARG, "hs_step_end without hs_step_begin");
     s->step_open = false;
+    if (s->split_open) {                   // the early chain; the late one is on step_stream
+        s->split_open = false;
+        HS_HIP(hipStreamSynchronize(s->stream));
+    }
     HS_HIP(hipStreamSynchronize(s->step_stream));
     if (s->profiling) {
         HS_HIP(hipEventElapsedTime(&s->last_ms[0], s->ev[0], s->ev[1]));
@@ -1579,12 +1637,24 @@ int32_t hs_get_device_status(hs_sim *s, hs_device_status *out) {
     HS_HIP(hipDeviceSynchronize());
     int st[4];
     HS_HIP(hipMemcpy(st, s->S.status, sizeof(st), hipMemcpyDeviceToHost));
+    out->split_steps = s->split_steps;
+    out->late_octets = (uint32_t)st[2];
     out->spilled_dd_pairs = st[0];
     out->spilled_static_pairs = st[1];
     out->dropped_dd_pairs = 0;             // nothing can overflow the spill lists (hs_k_physics.h: sized for every pair)
     out->dropped_static_pairs = 0;
     out->graphs_in_use = 0;                // (HIP-graph replay was removed)
     out->reserved = 0;
+    return HS_OK;
+}
+
+int32_t hs_set_late_threshold(hs_sim *s, float factor) {
+    if (!s) return fail(HS_ERR_INVALID_ARG, "null sim");
+    if (!(factor >= 0.f)) return fail(HS_ERR_INVALID_ARG, "hs_set_late_threshold: the factor must be >= 0");
+    HS_HIP(hipSetDevice(s->cfg.gpu_id));
+    const float f = factor < kMaxLateFactor ? factor : kMaxLateFactor;
+    HS_HIP(hipDeviceSynchronize());
+    HS_HIP(hipMemcpy(hs::sched_words(s->S) + hs::kSchedFactor, &f, 4, hipMemcpyHostToDevice));
     return HS_OK;
 }
 

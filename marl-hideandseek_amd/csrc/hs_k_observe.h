@@ -189,8 +189,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
 #endif
     // blocks b, b + 8, ..., b + 56 (same XCD under round-robin placement) take the 8 worlds of one octet
     const int blk = blockIdx.x;
-    const int oct = ((blk >> 6) << 3) + (blk & 7);
-    if (oct >= (S.N + kTile - 1) / kTile) return;        // (the grid covers whole groups of 8 octets)
+    int oct = ((blk >> 6) << 3) + (blk & 7);
+    const int noct = (S.N + kTile - 1) / kTile;
+    if (oct >= noct) return;                             // (the grid covers whole groups of 8 octets)
+    // the split schedule (hs_state.h): a launch that serves one group takes its octets from the group's list
+    if (step_serve(S) != kGroupAll) {
+        if (oct >= *group_count(S, step_ring(S), step_serve(S))) return;
+        oct = oct_list(S, step_ring(S), step_serve(S), noct)[oct];
+    }
     const int p = oct * kTile + ((blk >> 3) & 7);       // slot in the tiled columns
     // the world that lives there and its scalars (exports are indexed by world id): one load, issued beside the
     // column loads

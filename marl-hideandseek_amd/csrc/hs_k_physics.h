@@ -1442,24 +1442,46 @@ HSD void substep_rest(const SimState &S, OctRes &R, BodyReg (&br)[ROUNDS], int n
 // 6 agents (17 slots x 8 worlds = 136 bodies at most).
 template <int ROUNDS>
 HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
-    const int L = hs_lane(), o = blockIdx.x;            // o: this wave's octet
+    const int L = hs_lane();
+    const int noct = gridDim.x;
+    const int sidx = step_ring(S), prevIdx = sidx == 0 ? 2 : sidx - 1, nextIdx = sidx == 2 ? 0 : sidx + 1;
+    // the split schedule (hs_state.h): a launch that serves one group takes its octets from the group's list and leaves
+    // the others to its twin.  A step has exactly one launch that is not the early one: its first wave clears what the
+    // next steps accumulate into.
+    const int serve = step_serve(S);
+    if (serve != kGroupEarly && blockIdx.x == 0 && L == 0) {
+        S.tickSum[nextIdx] = 0ull;
+        atomicExch(group_count(S, prevIdx, kGroupEarly), 0); atomicExch(group_count(S, prevIdx, kGroupLate), 0);
+    }
+    int o = blockIdx.x;                                 // o: this wave's octet
+    if (serve != kGroupAll) {
+        if (o >= *group_count(S, sidx, serve)) return;
+        o = oct_list(S, sidx, serve, noct)[o];
+    }
     S.wbeg = o * kTile;                               // first slot of the octet in the tiled columns
     const int p0 = S.wbeg;
     const int NS = kAgentSlot0 + S.A;                 // body slots in use
-    const int noct = gridDim.x;
     // The launch ends with its slowest wave: the physics waves that were slow in the previous step (the same worlds:
     // contact piles persist) go first on their SIMD, the partner of a slow wave has slack.
     // Measured: k_physics 0.387 -> 0.380 ms; boosting a wave while it is inside a chain of manifolds or an extra round
     // of convex tests instead gave 0.382.
     const long long tStart = wall_clock64();
+    // Next step's group of this octet (appended to its list at the tail): late when the mean of this step's and the previous step's
+    // ticks exceeds lateFactor x the previous launch mean, i.e. ticks + prevTicks > lateAbove.  A wave's time alternates
+    // from step to step (the priorities below see to that), the mean of two steps follows its work.  Two scalars.
+    int prevTicks, lateAbove;
     {
-        const int sidx = S.stepIdx, prevIdx = sidx == 0 ? 2 : sidx - 1, nextIdx = sidx == 2 ? 0 : sidx + 1;
-        if (o == 0 && L == 0) S.tickSum[nextIdx] = 0ull;
-        const float mean = (float)S.tickSum[prevIdx] / (float)noct, mine = (float)S.octTicks[o];
+        prevTicks = S.octTicks[o];
+        const float mean = (float)S.tickSum[prevIdx] / (float)noct, mine = (float)prevTicks;
         const bool known = mean > 0.f;
+        lateAbove = __builtin_amdgcn_readfirstlane(known ? (int)fminf(2.f * __int_as_float(sched_words(S)[kSchedFactor]) * mean, 2.0e9f) : 0x7fffffff);
+        // (a late octet is on the critical path of the step by prediction: never below priority 1 beside the observation
+        // waves of the early group, which run at priority 0)
+        const bool late = serve == kGroupLate;
+        if (late && L == 0) atomicAdd(&S.status[2], 1);
         if (known && mine > 1.10f * mean) __builtin_amdgcn_s_setprio(3);
         else if (known && mine > 0.98f * mean) __builtin_amdgcn_s_setprio(2);
-        else if (known && mine > 0.88f * mean) __builtin_amdgcn_s_setprio(1);
+        else if ((known && mine > 0.88f * mean) || (known && late)) __builtin_amdgcn_s_setprio(1);
         else if (known) __builtin_amdgcn_s_setprio(0);
         else __builtin_amdgcn_s_setprio(2);
     }
@@ -1562,7 +1584,9 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
     if (L == 0) {
         const int dt = (int)(wall_clock64() - tStart);
         S.octTicks[o] = dt;
-        atomicAdd(&S.tickSum[S.stepIdx], (unsigned long long)dt);
+        atomicAdd(&S.tickSum[sidx], (unsigned long long)dt);
+        const int group = dt + prevTicks > lateAbove ? kGroupLate : kGroupEarly;
+        oct_list(S, nextIdx, group, noct)[atomicAdd(group_count(S, nextIdx, group), 1)] = o;
     }
 #ifdef HS_PHASE_TIMING
     if (L == 0) for (int i = 0; i < 10; ++i) S.phaseTicks[(size_t)o * 10 + i] += acc[i];

@@ -48,8 +48,8 @@ struct SimState {
     // How long each physics wave took in the previous step (100 MHz ticks) and the sums over all waves of the last
     // three steps: a wave that was slower than the average raises its issue priority (hs_k_physics.h).
     int *octTicks;         // [octets]
-    unsigned long long *tickSum;   // [3], indexed by stepIdx
-    int stepIdx;           // launch counter mod 3
+    unsigned long long *tickSum;   // [3], indexed by the ring position; the split schedule's words follow (sched_words below)
+    int stepIdx;           // launch counter mod 3 (the ring position) | the group the launch serves (step_idx_arg below)
     float *lidarSinCos;    // [60] hs_sincosf of the 30 lidar angles (sim.cpp:727-738), filled by k_lidar_table at hs_create
 
     // --- movable bodies: 17 slots (9 boxes, 2 ramps, 6 agents)
@@ -95,6 +95,26 @@ struct SimState {
     long long *phaseTicks; // [physics waves][10] accumulated per-phase ticks, then k_observe's sections from
                            // phase_ticks_obs_base() on (HS_PHASE_TIMING builds only)
 };
+
+// --- The split schedule of a blocking step (hideseek.hip launch_step): the octets predicted to be among the slowest ("late",
+// group 1) and the others ("early", group 0) run as two independent k_physics -> k_observe chains.  Each group is a compact
+// list of octets, indexed by workgroup: the lane of k_physics that writes octTicks[o] also appends the octet to the list of
+// its group for the NEXT step, in the buffers of the next ring position (a k_observe of this step may still be reading this
+// step's).  The host never reads a count: both launches of a pair cover every octet and a workgroup beyond its group's
+// count returns.  SimState itself is as it was (it is a kernel argument of every kernel): the group a launch serves rides
+// in stepIdx above the ring position, and the schedule's words follow tickSum's three sums in the same allocation:
+//   word kSchedFactor: lateFactor (float) — late: mean ticks of the octet's last two steps > lateFactor x the launch mean
+//   group_count(): [3][2] counters, a cache line each; the position a step appends to was cleared two steps before
+//   oct_list():    [3][2][octets]
+constexpr int kGroupAll = -1, kGroupEarly = 0, kGroupLate = 1;
+constexpr int kSchedBase = 32, kSchedFactor = 0, kCountStride = 32, kSchedCounts = 32, kSchedLists = kSchedCounts + 6 * kCountStride;
+__host__ __device__ inline int step_idx_arg(int ring, int serve) { return ring | (serve + 1) << 2; }
+__host__ __device__ inline int step_ring(const SimState &S) { return S.stepIdx & 3; }
+__host__ __device__ inline int step_serve(const SimState &S) { return (S.stepIdx >> 2) - 1; }
+__host__ __device__ inline int *sched_words(const SimState &S) { return reinterpret_cast<int *>(S.tickSum) + kSchedBase; }
+__host__ __device__ inline size_t sched_alloc_sums(int noct) { return ((size_t)kSchedBase + kSchedLists + (size_t)6 * noct + 1) / 2; }   // in tickSum's elements
+__host__ __device__ inline int *group_count(const SimState &S, int idx, int group) { return sched_words(S) + kSchedCounts + (idx * 2 + group) * kCountStride; }
+__host__ __device__ inline int *oct_list(const SimState &S, int idx, int group, int noct) { return sched_words(S) + kSchedLists + (size_t)(idx * 2 + group) * noct; }
 
 // phaseTicks: the physics waves' part, one wave per octet
 __host__ __device__ inline size_t phase_ticks_obs_base(int N) { return (size_t)10 * ((N + kTile - 1) / kTile); }

@@ -449,14 +449,23 @@ class HideAndSeekSimulator:
 
     def device_status(self):
         """hs_get_device_status: sticky device-side counters — candidate pairs that took the spill path of the physics
-        kernel (beyond its LDS capacities; results unaffected), dropped pairs (always 0); graphs_in_use is always False."""
+        kernel (beyond its LDS capacities; results unaffected), dropped pairs (always 0); graphs_in_use is always False;
+        split_steps: blocking steps that ran as two chains of late and early octets, late_octets: the octets of their late
+        groups summed over those steps (set_late_threshold)."""
         st = _native.HsDeviceStatus()
         _check(self._L.hs_get_device_status(self._h, C.byref(st)))
         return {"dropped_dd_pairs": int(st.dropped_dd_pairs), "dropped_static_pairs": int(st.dropped_static_pairs),
                 "dropped_candidate_pairs": int(st.dropped_dd_pairs + st.dropped_static_pairs),
                 "spilled_dd_pairs": int(st.spilled_dd_pairs), "spilled_static_pairs": int(st.spilled_static_pairs),
                 "spilled_candidate_pairs": int(st.spilled_dd_pairs + st.spilled_static_pairs),
-                "graphs_in_use": bool(st.graphs_in_use)}
+                "graphs_in_use": bool(st.graphs_in_use),
+                "split_steps": int(st.split_steps), "late_octets": int(st.late_octets)}
+
+    def set_late_threshold(self, factor):
+        """hs_set_late_threshold: the one tunable of the split schedule of the blocking step().  An octet (8 worlds, one
+        physics wave) whose mean time over the last two steps exceeded `factor` x the mean over all octets is in the late
+        group of the next step.  0: every octet is late; float("inf"): none is.  Results do not depend on it."""
+        _check(self._L.hs_set_late_threshold(self._h, float(factor)))
 
     def warning(self):
         """The library's last message for this thread."""

@@ -28,7 +28,8 @@ class HsIfaceEntry(C.Structure):
 class HsDeviceStatus(C.Structure):
     _fields_ = [("dropped_dd_pairs", C.c_int64), ("dropped_static_pairs", C.c_int64),
                 ("graphs_in_use", C.c_int32), ("reserved", C.c_int32),
-                ("spilled_dd_pairs", C.c_int64), ("spilled_static_pairs", C.c_int64)]
+                ("spilled_dd_pairs", C.c_int64), ("spilled_static_pairs", C.c_int64),
+                ("split_steps", C.c_int64), ("late_octets", C.c_int64)]
 
 
 class HsCamera(C.Structure):
@@ -110,6 +111,8 @@ def load():
     L.hs_debug_dump_bodies.restype = C.c_int32
     L.hs_debug_dump_walls.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.hs_debug_dump_walls.restype = C.c_int32
+    L.hs_set_late_threshold.argtypes = [C.c_void_p, C.c_float]
+    L.hs_set_late_threshold.restype = C.c_int32
     L.hs_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     L.hs_set_profiling.restype = C.c_int32
     L.hs_last_step_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float * 3)]
