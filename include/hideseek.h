@@ -781,6 +781,73 @@ int32_t hs_dense_norm_act_async(hs_sim *sim, void *hip_stream, const hs_dense_no
 int32_t hs_dense_norm_act_backward(hs_sim *sim, const hs_dense_norm_act_backward_request *req);
 int32_t hs_dense_norm_act_backward_async(hs_sim *sim, void *hip_stream, const hs_dense_norm_act_backward_request *req);
 
+/* The optimiser: the clip by the global gradient norm and the Adam step that end every update of the reference's learner
+ * (scripts/jax_train.py: lr = 1e-4, max_grad_norm = 5), over ONE flat f32 buffer each of parameters, gradients and the
+ * two moments, n elements each (gpu_hideseek.optim.flatten lays a module's parameters out in such a buffer).  Two
+ * kernels (csrc/hs_k_adam.h): one leaves partial sums of squares, the other adds them and updates.  madrona_learn's
+ * optimiser is not part of the reference's tree: the rule is optax's clip_by_global_norm followed by Adam (AdamW with
+ * weight_decay > 0), this project's statement of it, and not pinned by the reference.
+ * The arithmetic is the contract.
+ * The norm.  The buffer is cut into quads of 4 adjacent floats, quad q = elements 4 q .. 4 q + 3, Q = ceil(n / 4) quads,
+ * the last one short when n is no multiple of 4.  With G = min(ceil(Q / 256), HS_ADAM_MAX_GRID) workgroups of 256 lanes,
+ * quad q = (trip * G + b) * 256 + lane belongs to lane `lane` of workgroup b in its trip `trip`.  In f64:
+ *   a lane adds (double)g * (double)g (exact) of its elements onto +0, its quads in trip order and a quad's elements in
+ *   index order;  a workgroup's partial is ((lane_0 + lane_1) + lane_2) + ... + lane_255;
+ *   sum = ((partial_0 + partial_1) + ...) + partial_{G-1}     (every workgroup of the update adds them itself: same bits)
+ *   gnorm = grad_scale * sqrt(sum);   skipped = gnorm is not finite        (sqrt and the divisions correctly rounded)
+ *   clip = skipped ? 0 : (max_grad_norm > 0 && gnorm > max_grad_norm) ? max_grad_norm / gnorm : 1      (optax's form)
+ *   s = (float)(grad_scale * clip)                                       rounded once
+ * (grad_scale and max_grad_norm are f64 in the request; a norm that is finite in the gradients' own scale can still
+ * overflow through grad_scale, and is then skipped).  No atomics: the same inputs give the same bits on every call.
+ * The state, f64 [HS_ADAM_STATE] on the device, = {beta1^t, beta2^t, t, the number of skipped steps}; a fresh one is
+ * {1, 1, 0, 0}.  A step that is not skipped multiplies the products by (double)beta1 and (double)beta2, adds 1 to t, and
+ *   bc1 = (float)(1 - beta1^t);   bc2 = (float)(1 - beta2^t)             with the new products: no pow
+ * Then per element, in IEEE f32, unfused, in exactly this order, with omb1 = (float)(1 - (double)beta1) and
+ * omb2 = (float)(1 - (double)beta2) rounded once on the host:
+ *   g = g_raw * s
+ *   m = beta1 * m + omb1 * g
+ *   v = beta2 * v + omb2 * (g * g)
+ *   u = (m / bc1) / (sqrtf(v / bc2) + eps)                               (division and sqrtf correctly rounded)
+ *   p = p - lr * (u + weight_decay * p)          weight_decay == 0:  p = p - lr * u  (the term is left out, not added as 0)
+ * An element's result does not depend on its position or on n, given s, bc1 and bc2.  An element with p = g = m = v = +0
+ * stays +0 in p, m and v and adds nothing to the norm: padding between parameters is inert.
+ * A skipped step (a NaN or an infinity among the gradients, or a norm that overflows) leaves params, m, v, beta1^t, beta2^t
+ * and t exactly as they were; only state[3] grows by 1.  With zero_grad != 0 every element of grads is overwritten with
+ * +0, on a skipped step too; with zero_grad == 0 grads is not written.
+ * stats, f64 [HS_ADAM_STATS] or null, receives {gnorm, clip, skipped ? 1 : 0, t after the call}.
+ * The partial sums and a snapshot of the state go through a workspace of the handle: the first kernel copies the state
+ * there and the second reads only that copy and writes only the caller's state, so no workgroup can read a state
+ * another has already advanced, whatever order they run in.  Two calls on one handle must not overlap.
+ * A lane reads and writes a quad as one piece of 16 bytes, so params, grads, m and v must be 16-byte aligned; any n >= 1
+ * is accepted, the short quad goes by element and nothing past n is read or written.  Everything is validated before
+ * anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null request, null params,
+ * grads, m, v or state; n < 1 or n >= 2^31; params, grads, m or v not 16-byte aligned, state or stats not 8-byte aligned;
+ * lr, eps, weight_decay, grad_scale or max_grad_norm not finite; eps <= 0, lr < 0, weight_decay < 0 or grad_scale <= 0; a
+ * beta outside [0, 1); two of the arrays overlapping; a call before hs_init or inside an open step.  The call reads no
+ * export and writes no simulator state.  hs_adam_step is ordered after the device's legacy default stream and blocking;
+ * hs_adam_step_async enqueues on the caller's hipStream_t without synchronising.
+ * Not part of this call: parameters spread over several devices and the reduction of gradients between shards, and a
+ * bf16 / f16 shadow copy of the weights (the modules cast their weights inside the autograd graph). */
+enum { HS_ADAM_MAX_GRID = 256, HS_ADAM_STATE = 4, HS_ADAM_STATS = 4 };
+typedef struct hs_adam_request {
+    float   *params;              /* [n] f32, 16-byte aligned: updated in place */
+    float   *grads;               /* [n] f32, 16-byte aligned: read; overwritten with +0 when zero_grad != 0 */
+    float   *m;                   /* [n] f32, 16-byte aligned: the first moment, updated in place */
+    float   *v;                   /* [n] f32, 16-byte aligned: the second moment, updated in place */
+    int64_t n;                    /* elements, 1 <= n < 2^31 */
+    float lr;                     /* finite, >= 0; 1e-4 */
+    float beta1, beta2;           /* in [0, 1); 0.9, 0.999 */
+    float eps;                    /* finite, > 0; 1e-8 */
+    float weight_decay;           /* finite, >= 0; 0 = plain Adam */
+    double max_grad_norm;         /* finite; <= 0 = no clipping; 5 */
+    double grad_scale;            /* finite, > 0: the gradients are g_raw * grad_scale (1 / loss scale); 1 */
+    int32_t zero_grad;            /* != 0: grads is +0 after the call */
+    double *state;                /* [HS_ADAM_STATE] f64 on the device: beta1^t, beta2^t, t, skipped steps */
+    double *stats;                /* [HS_ADAM_STATS] f64 on the device, or null */
+} hs_adam_request;                /* 104 bytes */
+int32_t hs_adam_step(hs_sim *sim, const hs_adam_request *req);
+int32_t hs_adam_step_async(hs_sim *sim, void *hip_stream, const hs_adam_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

@@ -32,6 +32,7 @@
 #include "hs_solver.h"
 #include "hs_k_lstm.h"
 #include "hs_k_dense.h"
+#include "hs_k_adam.h"
 
 namespace {
 
@@ -98,6 +99,7 @@ struct hs_sim {
     float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
     float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
     float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
+    double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -976,6 +978,56 @@ int launch_dense_bwd(hs_sim *s, hipStream_t strm, const hs_dense_norm_act_backwa
 }
 }  // namespace
 
+// ---- the optimiser (hs_k_adam.h) ----
+namespace {
+static_assert(HS_ADAM_MAX_GRID == hs::kAdamMaxGrid && HS_ADAM_STATE == hs::kAdamState && HS_ADAM_STATS == hs::kAdamStats, "hs_adam_request and k_adam agree");
+static_assert(sizeof(hs_adam_request) == 104 && offsetof(hs_adam_request, grads) == 8 && offsetof(hs_adam_request, v) == 24 && offsetof(hs_adam_request, n) == 32 &&
+              offsetof(hs_adam_request, lr) == 40 && offsetof(hs_adam_request, weight_decay) == 56 && offsetof(hs_adam_request, max_grad_norm) == 64 &&
+              offsetof(hs_adam_request, grad_scale) == 72 && offsetof(hs_adam_request, zero_grad) == 80 && offsetof(hs_adam_request, state) == 88 &&
+              offsetof(hs_adam_request, stats) == 96,
+              "hs_adam_request layout (gpu_hideseek/optim.py mirrors it)");
+
+int check_adam(hs_sim *s, const hs_adam_request *r) {
+    const Check c{"hs_adam_step"};
+    if (!r) return c.bad("null request");
+    if (!r->params) return c.bad("null params");
+    if (!r->grads) return c.bad("null grads");
+    if (!r->m) return c.bad("null m");
+    if (!r->v) return c.bad("null v");
+    if (!r->state) return c.bad("null state");
+    if (r->n < 1 || r->n >= (int64_t)1 << 31) return c.bad("n must be at least 1 and below 2^31");
+    if (!aligned(16, {r->params, r->grads, r->m, r->v})) return c.bad("params, grads, m and v must be 16-byte aligned");
+    if (!aligned(8, {r->state, r->stats})) return c.bad("state and stats must be 8-byte aligned");
+    if (!std::isfinite(r->lr) || !std::isfinite(r->eps) || !std::isfinite(r->weight_decay) || !std::isfinite(r->grad_scale) || !std::isfinite(r->max_grad_norm))
+        return c.bad("lr, eps, weight_decay, grad_scale and max_grad_norm must be finite");
+    if (!(r->eps > 0.f)) return c.bad("eps must be above 0");
+    if (r->lr < 0.f) return c.bad("lr must be at least 0");
+    if (r->weight_decay < 0.f) return c.bad("weight_decay must be at least 0");
+    if (!(r->grad_scale > 0.0)) return c.bad("grad_scale must be above 0");
+    if (!(r->beta1 >= 0.f && r->beta1 < 1.f) || !(r->beta2 >= 0.f && r->beta2 < 1.f)) return c.bad("beta1 and beta2 must be in [0, 1)");
+    const uintptr_t bytes = (uintptr_t)r->n * 4;
+    HS_TRY(c.disjoint({}, {range("params", r->params, bytes), range("grads", r->grads, bytes), range("m", r->m, bytes), range("v", r->v, bytes),
+                           range("state", r->state, HS_ADAM_STATE * sizeof(double)), range("stats", r->stats, HS_ADAM_STATS * sizeof(double))}));
+    return c.handle_ready(s);
+}
+
+// k_adam_norm, its partial sums of squares and the snapshot of the state into the workspace, then one k_adam_step over the
+// elements (the request has passed check_adam).
+int launch_adam(hs_sim *s, hipStream_t strm, const hs_adam_request *r) {
+    hs::AdamArgs a = {};
+    a.p = r->params; a.g = r->grads; a.m = r->m; a.v = r->v; a.ws = s->adam_workspace; a.state = r->state; a.stats = r->stats;
+    a.n = (int)r->n; a.nparts = hs::adam_grid(a.n, hs::kAdamMaxGrid); a.zeroGrad = r->zero_grad != 0;
+    a.lr = r->lr; a.b1 = r->beta1; a.b2 = r->beta2; a.eps = r->eps; a.wd = r->weight_decay;
+    a.omb1 = (float)(1.0 - (double)r->beta1); a.omb2 = (float)(1.0 - (double)r->beta2);
+    a.gradScale = r->grad_scale; a.maxNorm = r->max_grad_norm;
+    const dim3 blk(hs::kAdamThreads);
+    hipLaunchKernelGGL(hs::k_adam_norm<>, dim3(a.nparts), blk, 0, strm, (const float *)r->grads, a.n, (const double *)r->state, s->adam_workspace);
+    hipLaunchKernelGGL(hs::k_adam_step<>, dim3(hs::adam_grid(a.n, hs::kAdamStepMaxGrid)), blk, 0, strm, a);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1121,6 +1173,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->embed_partials, (size_t)hs::kRowsMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
     HS_ALLOC(s->lstm_partials, (size_t)hs::kRowsMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
     HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
+    HS_ALLOC(s->adam_workspace, hs::kAdamWorkspace);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1451,6 +1504,8 @@ int32_t hs_dense_norm_act(hs_sim *s, const hs_dense_norm_act_request *req) { ret
 int32_t hs_dense_norm_act_async(hs_sim *s, void *hip_stream, const hs_dense_norm_act_request *req) { return call_async(s, hip_stream, check_dense, launch_dense, req); }
 int32_t hs_dense_norm_act_backward(hs_sim *s, const hs_dense_norm_act_backward_request *req) { return call_blocking(s, check_dense_bwd, launch_dense_bwd, req); }
 int32_t hs_dense_norm_act_backward_async(hs_sim *s, void *hip_stream, const hs_dense_norm_act_backward_request *req) { return call_async(s, hip_stream, check_dense_bwd, launch_dense_bwd, req); }
+int32_t hs_adam_step(hs_sim *s, const hs_adam_request *req) { return call_blocking(s, check_adam, launch_adam, req); }
+int32_t hs_adam_step_async(hs_sim *s, void *hip_stream, const hs_adam_request *req) { return call_async(s, hip_stream, check_adam, launch_adam, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

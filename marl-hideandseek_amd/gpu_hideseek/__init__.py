@@ -301,6 +301,21 @@ class HideAndSeekSimulator:
         return _mlp.compute_backward(self, z, params, grad_y, stream, channels=channels, eps=eps, slope=slope, grad_z=grad_z,
                                      grad_params=grad_params)
 
+    def adam_step(self, params, grads, m, v, state, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=5.0, grad_scale=1.0,
+                  zero_grad=True, stats=True, stream=None):
+        """The clip by the global gradient norm and one Adam step over flat buffers in two kernels (gpu_hideseek.optim;
+        hs_adam_step, whose header comment states the arithmetic: the norm in float64 and the update in IEEE f32, both in a
+        fixed order).  `params`, `grads`, `m` and `v` are float32 [n], contiguous, 16-byte aligned and disjoint, updated in
+        place; `state` is float64 [4] = beta1^t, beta2^t, t, skipped steps (optim.fresh_state()).  The gradients are taken as
+        grads * grad_scale and scaled by max_grad_norm / norm when their norm exceeds max_grad_norm (<= 0 or None: no
+        clip); a step whose norm is not finite changes nothing but the skip count.  With zero_grad the gradients are +0
+        afterwards.  stats [4] float64 = norm, clip factor, skipped, t is True (allocated), a tensor or None.  stream=None
+        blocks; a torch.cuda.Stream or raw handle enqueues there without synchronising.  The same inputs give the same
+        bits on every call.  Returns {"stats": tensor} or {}.  optim.Adam is the torch optimiser built on this call."""
+        from . import optim as _optim
+        return _optim.compute(self, params, grads, m, v, state, stream, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                              max_grad_norm=max_grad_norm, grad_scale=grad_scale, zero_grad=zero_grad, stats=stats)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))
