@@ -848,6 +848,54 @@ typedef struct hs_adam_request {
 int32_t hs_adam_step(hs_sim *sim, const hs_adam_request *req);
 int32_t hs_adam_step_async(hs_sim *sim, void *hip_stream, const hs_adam_request *req);
 
+/* The minibatch gather: cutting shuffled sequences out of a rollout for one minibatch of the update, every field of the
+ * rollout in one kernel (csrc/hs_k_gather.h).  The reference trains on back-propagation-through-time chunks
+ * (scripts/jax_train.py: steps_per_update = 40, num_bptt_chunks = 8, num_mini_batches = 2); madrona_learn's own gather is
+ * not part of the reference's tree, so the layout below is the project's.
+ * A rollout of K = chunks chunks of L = chunk_steps steps over n = rows agent rows has K n sequences; sequence id
+ * s = k n + r is chunk k of row r.  index [m] i32 on the device holds the ids of a minibatch (a slice of a permutation
+ * drawn on the device: nothing here needs the host to know them).  Up to HS_GATHER_MAX_FIELDS fields per call, each
+ * {src, dst, row_bytes, per_chunk}:
+ *   per_chunk == 0 (a per-step field):   src [K L][n][row_bytes],  dst [L][m][row_bytes]
+ *       dst[t][j] = src[k_j L + t][r_j]        for t < L, j < m, with s_j = index[j], k_j = s_j / n, r_j = s_j % n
+ *   per_chunk != 0 (a per-chunk field):  src [K][n][row_bytes],    dst [m][row_bytes]
+ *       dst[j] = src[k_j][r_j]                 (the LSTM states at the chunks' starts)
+ * A pure copy: the bytes of a row arrive unchanged whatever type they hold.  row_bytes is a multiple of 4 and src and dst
+ * are 4-byte aligned; a field whose row_bytes is a multiple of 16 and whose src and dst are both 16-byte aligned moves as
+ * 16-byte accesses (rows of 592, 512 and 1024 bytes), any other as dwords (rows of 4 and 20 bytes).  Byte offsets are
+ * 64-bit: a source may be larger than 2^31 bytes.
+ * The kernel never reads outside a source: an id outside [0, K n) leaves zeros in its destination rows of every field,
+ * and bad [1] i32, when given, receives the number of such ids among the m (it is zeroed by the call first).  Repeated
+ * ids are allowed.  No output may overlap an input or another output.
+ * Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a
+ * null request or index; m, chunks, chunk_steps or rows below 1; chunks * rows or (num_fields + 1) * m at or above 2^31;
+ * num_fields outside [1, HS_GATHER_MAX_FIELDS]; a field with a null src or dst, a row_bytes below 4, above
+ * HS_GATHER_MAX_ROW_BYTES or no multiple of 4, or a pointer not 4-byte aligned; index or bad not 4-byte aligned; a dst or
+ * bad that overlaps a src, index or another output; a call before hs_init or inside an open step.  The sizes of the
+ * sources cannot be checked here: the caller vouches that each holds the rows stated above.  The call reads no export and
+ * writes no simulator state.  hs_gather_sequences is ordered after the device's legacy default stream and blocking;
+ * hs_gather_sequences_async enqueues on the caller's hipStream_t without synchronising. */
+enum { HS_GATHER_MAX_FIELDS = 16, HS_GATHER_MAX_ROW_BYTES = 1048576 };
+typedef struct hs_gather_field {
+    const void *src;              /* [K L][n][row_bytes] or, per chunk, [K][n][row_bytes]; 4-byte aligned */
+    void *dst;                    /* [L][m][row_bytes] or, per chunk, [m][row_bytes]; 4-byte aligned */
+    int32_t row_bytes;            /* a multiple of 4, 4 .. HS_GATHER_MAX_ROW_BYTES */
+    int32_t per_chunk;            /* 0: a row per step; != 0: a row per chunk */
+} hs_gather_field;                /* 24 bytes */
+typedef struct hs_gather_request {
+    const int32_t *index;         /* [m] i32 on the device: sequence ids k * rows + r */
+    int32_t m;                    /* sequences of the minibatch, >= 1 */
+    int32_t chunks;               /* K >= 1 */
+    int32_t chunk_steps;          /* L >= 1 */
+    int32_t rows;                 /* n >= 1; chunks * rows < 2^31 */
+    int32_t num_fields;           /* 1 .. HS_GATHER_MAX_FIELDS */
+    int32_t reserved;
+    int32_t *bad;                 /* [1] i32 on the device or null: the number of ids outside [0, chunks * rows) */
+    hs_gather_field fields[HS_GATHER_MAX_FIELDS];
+} hs_gather_request;              /* 424 bytes */
+int32_t hs_gather_sequences(hs_sim *sim, const hs_gather_request *req);
+int32_t hs_gather_sequences_async(hs_sim *sim, void *hip_stream, const hs_gather_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

@@ -32,6 +32,7 @@
 #include "hs_solver.h"
 #include "hs_k_lstm.h"
 #include "hs_k_dense.h"
+#include "hs_k_gather.h"                  // ahead of hs_k_adam.h: its one kernel is a template, emitted where launch_gather (the last stage) names it
 #include "hs_k_adam.h"
 
 namespace {
@@ -1028,6 +1029,77 @@ int launch_adam(hs_sim *s, hipStream_t strm, const hs_adam_request *r) {
 }
 }  // namespace
 
+// ---- the minibatch gather (hs_k_gather.h) ----
+namespace {
+static_assert(HS_GATHER_MAX_FIELDS == hs::kGatherMaxFields, "hs_gather_request and k_gather agree");
+static_assert(sizeof(hs_gather_field) == 24 && offsetof(hs_gather_field, dst) == 8 && offsetof(hs_gather_field, row_bytes) == 16 &&
+              offsetof(hs_gather_field, per_chunk) == 20, "hs_gather_field layout (gpu_hideseek/rollout.py mirrors it)");
+static_assert(sizeof(hs_gather_request) == 424 && offsetof(hs_gather_request, m) == 8 && offsetof(hs_gather_request, chunks) == 12 &&
+              offsetof(hs_gather_request, chunk_steps) == 16 && offsetof(hs_gather_request, rows) == 20 && offsetof(hs_gather_request, num_fields) == 24 &&
+              offsetof(hs_gather_request, bad) == 32 && offsetof(hs_gather_request, fields) == 40,
+              "hs_gather_request layout (gpu_hideseek/rollout.py mirrors it)");
+
+// the bytes field i of an accepted request reads and writes
+ByteRange gather_src(const hs_gather_request *r, int i) {
+    const hs_gather_field &f = r->fields[i];
+    return range("src", f.src, (uintptr_t)r->chunks * (f.per_chunk ? 1u : (uintptr_t)r->chunk_steps) * (uintptr_t)r->rows * (uintptr_t)f.row_bytes);
+}
+ByteRange gather_dst(const hs_gather_request *r, int i) {
+    const hs_gather_field &f = r->fields[i];
+    return range("dst", f.dst, (f.per_chunk ? 1u : (uintptr_t)r->chunk_steps) * (uintptr_t)r->m * (uintptr_t)f.row_bytes);
+}
+
+int check_gather(hs_sim *s, const hs_gather_request *r) {
+    const Check c{"hs_gather_sequences"};
+    if (!r) return c.bad("null request");
+    if (!r->index) return c.bad("null index");
+    if (r->m < 1 || r->chunks < 1 || r->chunk_steps < 1 || r->rows < 1) return c.bad("m, chunks, chunk_steps and rows must be at least 1");
+    if ((int64_t)r->chunks * r->rows >= (int64_t)1 << 31) return c.bad("chunks * rows must stay below 2^31");
+    if (r->num_fields < 1 || r->num_fields > HS_GATHER_MAX_FIELDS) return c.bad("num_fields must be in [1, HS_GATHER_MAX_FIELDS]");
+    if ((int64_t)(r->num_fields + 1) * r->m >= (int64_t)1 << 31) return c.bad("(num_fields + 1) * m must stay below 2^31");
+    if (!aligned(4, {r->index, r->bad})) return c.bad("index and bad must be 4-byte aligned");
+    for (int i = 0; i < r->num_fields; ++i) {
+        const hs_gather_field &f = r->fields[i];
+        const std::string which = "field " + std::to_string(i);
+        if (!f.src || !f.dst) return c.bad(which + ": null src or dst");
+        if (f.row_bytes < 4 || f.row_bytes > HS_GATHER_MAX_ROW_BYTES || f.row_bytes % 4) return c.bad(which + ": row_bytes must be a multiple of 4 in [4, HS_GATHER_MAX_ROW_BYTES]");
+        if (!aligned(4, {f.src, f.dst})) return c.bad(which + ": src and dst must be 4-byte aligned");
+    }
+    // no output (a dst, bad) overlaps an input (a src, index) or an earlier output
+    const ByteRange index = range("index", r->index, (uintptr_t)r->m * 4), bad = range("bad", r->bad, 4);
+    for (int i = 0; i <= r->num_fields; ++i) {
+        const ByteRange o = i < r->num_fields ? gather_dst(r, i) : bad;
+        const std::string which = i < r->num_fields ? "field " + std::to_string(i) + ": dst" : std::string("bad");
+        if (overlap(o, index)) return c.bad(which + " overlaps index");
+        for (int k = 0; k < r->num_fields; ++k)
+            if (overlap(o, gather_src(r, k))) return c.bad(which + " overlaps the src of field " + std::to_string(k));
+        for (int k = 0; k < i; ++k)
+            if (overlap(o, gather_dst(r, k))) return c.bad(which + " overlaps the dst of field " + std::to_string(k));
+    }
+    return c.handle_ready(s);
+}
+
+// bad zeroed, then one k_gather over every field (the request has passed check_gather): the fields that move as 16-byte
+// pieces first, in the request's order, then the others.
+int launch_gather(hs_sim *, hipStream_t strm, const hs_gather_request *r) {
+    hs::GatherArgs a = {};
+    const auto wide = [](const hs_gather_field &f) { return f.row_bytes % hs::kGatherVec == 0 && aligned(hs::kGatherVec, {f.src, f.dst}); };
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int i = 0; i < r->num_fields; ++i)
+            if (wide(r->fields[i]) == (pass == 0))
+                a.f[a.nFields++] = {(const char *)r->fields[i].src, (char *)r->fields[i].dst, r->fields[i].row_bytes, r->fields[i].per_chunk != 0};
+        if (pass == 0) a.nWide = a.nFields;
+    }
+    a.index = r->index; a.bad = r->bad; a.m = r->m; a.L = r->chunk_steps; a.n = r->rows; a.total = r->chunks * r->rows;
+    a.units = (uint32_t)(a.nWide + (a.nFields > a.nWide ? 1 : 0)) * (uint32_t)r->m;
+    if (r->bad) HS_HIP(hipMemsetAsync(r->bad, 0, sizeof(int32_t), strm));
+    const uint32_t blocks = (a.units + hs::kGatherWaves - 1) / hs::kGatherWaves;
+    hipLaunchKernelGGL(hs::k_gather<>, dim3(blocks < (uint32_t)hs::kGatherMaxGrid ? blocks : hs::kGatherMaxGrid), dim3(hs::kGatherThreads), 0, strm, a);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1506,6 +1578,8 @@ int32_t hs_dense_norm_act_backward(hs_sim *s, const hs_dense_norm_act_backward_r
 int32_t hs_dense_norm_act_backward_async(hs_sim *s, void *hip_stream, const hs_dense_norm_act_backward_request *req) { return call_async(s, hip_stream, check_dense_bwd, launch_dense_bwd, req); }
 int32_t hs_adam_step(hs_sim *s, const hs_adam_request *req) { return call_blocking(s, check_adam, launch_adam, req); }
 int32_t hs_adam_step_async(hs_sim *s, void *hip_stream, const hs_adam_request *req) { return call_async(s, hip_stream, check_adam, launch_adam, req); }
+int32_t hs_gather_sequences(hs_sim *s, const hs_gather_request *req) { return call_blocking(s, check_gather, launch_gather, req); }
+int32_t hs_gather_sequences_async(hs_sim *s, void *hip_stream, const hs_gather_request *req) { return call_async(s, hip_stream, check_gather, launch_gather, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

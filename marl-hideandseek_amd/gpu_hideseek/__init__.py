@@ -316,6 +316,20 @@ class HideAndSeekSimulator:
         return _optim.compute(self, params, grads, m, v, state, stream, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                               max_grad_norm=max_grad_norm, grad_scale=grad_scale, zero_grad=zero_grad, stats=stats)
 
+    def gather_sequences(self, index, fields, *, chunks, chunk_steps, rows, bad=None, stream=None):
+        """Cut the m sequences `index` (int32 [m] on the device; id = chunk * rows + row) out of a rollout of `chunks` x
+        `chunk_steps` steps over `rows` rows, every field in one kernel (gpu_hideseek.rollout; hs_gather_sequences, whose
+        header comment states the contract).  `fields` is a list of up to 16 (src, dst, per_chunk): a per-step src
+        [chunks * chunk_steps, rows, ...] goes to dst [chunk_steps, m, ...] as dst[t, j] = src[k_j * chunk_steps + t, r_j],
+        a per-chunk src [chunks, rows, ...] to dst [m, ...] as dst[j] = src[k_j, r_j]; dst None allocates it.  A pure copy
+        of rows of a multiple of 4 bytes, bit-identical to torch indexing for every dtype; 16-byte accesses where a row is
+        a multiple of 16 bytes and both bases are 16-byte aligned.  An id outside [0, chunks * rows) leaves zero rows and
+        is counted in `bad` (True or an int32 [1] tensor); nothing is read out of range.  stream=None blocks; a
+        torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {"fields": [dst, ...]} and "bad"
+        when asked for.  rollout.Rollout.minibatch is the buffer built on this call."""
+        from . import rollout as _rollout
+        return _rollout.compute(self, index, fields, chunks, chunk_steps, rows, bad=bad, stream=stream)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -109,10 +109,31 @@ def _shard_params(ssim, params):
 
 
 # ---- the calls ----
+_enqueue = [0]              # depth of on_current_stream() contexts
+
+
+class on_current_stream:
+    """Inside this context a call given stream=None is enqueued on torch's current stream of the handle's device without
+    waiting, where it would otherwise block: the module faces (EntityEncoder, MLP, LSTMCore and their backward) pass no
+    stream, and the update loop (gpu_hideseek.trainer) runs them here so that nothing in it waits for the device."""
+
+    def __enter__(self):
+        _enqueue[0] += 1
+        return self
+
+    def __exit__(self, *exc):
+        _enqueue[0] -= 1
+        return False
+
+
 def _run(sim, fn, req, stream, *extra):
     """Entry point `fn` of `sim`'s handle with request `req` (and what follows it in the signature): blocking with
-    stream=None, else `fn`_async on the torch.cuda.Stream or raw handle, without synchronising."""
+    stream=None (outside on_current_stream()), else `fn`_async on the torch.cuda.Stream or raw handle, without
+    synchronising."""
     from ._native import check
+    if stream is None and _enqueue[0]:
+        import torch
+        stream = torch.cuda.current_stream(sim.gpu_id)
     if stream is None:
         check(getattr(sim._L, fn)(sim._h, C.byref(req), *extra))
     else:

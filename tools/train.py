@@ -1,0 +1,151 @@
+"""Train the policy on the simulator: the update loop of gpu_hideseek.trainer behind the arguments of the reference's
+scripts/jax_train.py that make sense here, on one GPU.
+
+    python tools/train.py --num-worlds 16000 --num-updates 100 --bf16 [--ckpt-dir ckpts --run-name run0 [--restore 50]]
+    python tools/train.py --num-worlds 16000 --num-updates 10 --bf16 --phases [--out profiles/train_phases.txt]
+
+The simulator runs with the reference's flags, RandomFlipTeams | UseFixedWorld | ZeroAgentVelocity.  Every 10 updates it
+prints `Update: N` and `  FPS: ...` as the reference does: world steps per second, num_worlds * steps_per_update * updates
+/ wall time since the last print (an agent-row rate is that times the agents per world).  With --ckpt-dir and --run-name
+the trainer's state_dict goes to <ckpt-dir>/<run-name>/<update> at the end and every --ckpt-frequency updates, and
+--restore N loads <ckpt-dir>/<run-name>/N first; the simulator's own state is not part of it.
+--phases puts device events around the phases of every update (trainer.PHASES: simulator steps, pack, rollout forward, GAE
+with the bootstrap, gather, update forward + backward, Adam), waits for the device once per update, and prints each
+phase's time per update and share, over the updates after the first (which warms up); what the phases leave out (copies
+of exports into slots, the permutation, Python between the calls) is the row "other".
+Not here: PBT, Elo evaluation, tensorboard / wandb, several GPUs.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
+import torch  # noqa: E402
+import gpu_hideseek  # noqa: E402
+from gpu_hideseek import trainer  # noqa: E402
+
+PRINT_EVERY = 10
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--gpu-id", type=int, default=0)
+    ap.add_argument("--ckpt-dir", type=str)
+    ap.add_argument("--run-name", type=str)
+    ap.add_argument("--restore", type=int)
+    ap.add_argument("--ckpt-frequency", type=int, default=500)
+    ap.add_argument("--num-worlds", type=int, required=True)
+    ap.add_argument("--num-updates", type=int, required=True)
+    ap.add_argument("--steps-per-update", type=int, default=40)
+    ap.add_argument("--num-bptt-chunks", type=int, default=8)
+    ap.add_argument("--num-minibatches", type=int, default=2)
+    ap.add_argument("--num-epochs", type=int, default=4)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--gamma", type=float, default=0.998)
+    ap.add_argument("--entropy-loss-coef", type=float, default=0.01)
+    ap.add_argument("--value-loss-coef", type=float, default=1.0)
+    ap.add_argument("--fp16", action="store_true")
+    ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--num-hiders", type=int, default=3)
+    ap.add_argument("--num-seekers", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--eager", action="store_true", help="the policy's eager pieces and the gather by torch indexing (Trainer(fused=False))")
+    ap.add_argument("--phases", action="store_true")
+    ap.add_argument("--out", type=str, help="with --phases: write the table here too")
+    args = ap.parse_args(argv)
+    if args.fp16 and args.bf16:
+        ap.error("--fp16 and --bf16 exclude each other")
+    if (args.ckpt_dir is None) != (args.run_name is None):
+        ap.error("--ckpt-dir and --run-name go together")
+    if args.restore is not None and args.ckpt_dir is None:
+        ap.error("--restore needs --ckpt-dir and --run-name")
+    return args
+
+
+def config(args):
+    dtype = torch.float16 if args.fp16 else torch.bfloat16 if args.bf16 else torch.float32
+    return trainer.TrainConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
+                               num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
+                               value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed)
+
+
+def phase_table(totals, wall_ms, updates, args, fps):
+    """The lines of the --phases table: per phase the milliseconds per update and the share of the wall time."""
+    lines = ["%d worlds x (%d + %d) agents, %s, T = %d, K = %d, %d minibatches x %d epochs; %d updates after 1 warm-up update" % (
+        args.num_worlds, args.num_hiders, args.num_seekers, "float16" if args.fp16 else "bfloat16" if args.bf16 else "float32", args.steps_per_update,
+        args.num_bptt_chunks, args.num_minibatches, args.num_epochs, updates),
+        "FPS (world steps per second, as the reference prints it): %.0f;  agent rows per second: %.0f" % (fps, fps * (args.num_hiders + args.num_seekers)),
+        "%-26s %14s %8s" % ("phase", "ms per update", "share")]
+    rest = wall_ms
+    for k in trainer.PHASES:
+        lines.append("%-26s %14.2f %7.1f%%" % (k, totals[k] / updates, 100 * totals[k] / wall_ms))
+        rest -= totals[k]
+    lines.append("%-26s %14.2f %7.1f%%" % ("other", rest / updates, 100 * rest / wall_ms))
+    lines.append("%-26s %14.2f %7.1f%%" % ("wall", wall_ms / updates, 100.0))
+    return lines
+
+
+def main(argv=None):
+    args = parse(argv)
+    F = gpu_hideseek.SimFlags
+    sim = gpu_hideseek.HideAndSeekSimulator(
+        exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
+        sim_flags=F.RandomFlipTeams | F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders,
+        max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=1)
+    sim.init()
+    tr = trainer.Trainer(sim, config(args), fused=not args.eager)
+    run_dir = None if args.ckpt_dir is None else os.path.join(args.ckpt_dir, args.run_name)
+    if args.restore is not None:
+        tr.load_state_dict(torch.load(os.path.join(run_dir, str(args.restore)), map_location=tr.device, weights_only=False))
+    if args.phases:
+        tr.phases = trainer.PhaseTimer()
+
+    def save():
+        if run_dir is not None:
+            os.makedirs(run_dir, exist_ok=True)
+            torch.save(tr.state_dict(), os.path.join(run_dir, str(tr.update_index)))
+
+    totals, wall_ms, timed = {k: 0.0 for k in trainer.PHASES}, 0.0, 0
+    last_time, last_update, metrics = 0.0, tr.update_index, {}
+    for i in range(args.num_updates):
+        if (tr.update_index - last_update) % PRINT_EVERY == 0 or i == 0:
+            now = time.time()
+            print(f"Update: {tr.update_index}")
+            if last_time != 0:
+                print("  FPS:", args.num_worlds * args.steps_per_update * (tr.update_index - last_update) / (now - last_time))
+                print("  " + json.dumps({k: v for k, v in metrics.items() if not isinstance(v, list)}))
+            last_time, last_update = now, tr.update_index
+        t0 = time.perf_counter()
+        metrics = tr.update_iter()
+        if args.phases:
+            spans = tr.phases.totals()
+            print("  update %d: %.1f ms" % (tr.update_index, 1e3 * (time.perf_counter() - t0)), flush=True)
+            if i > 0:                                                  # the first update warms up
+                wall_ms += 1e3 * (time.perf_counter() - t0)
+                timed += 1
+                for k in totals:
+                    totals[k] += spans[k]
+        if args.ckpt_frequency > 0 and tr.update_index % args.ckpt_frequency == 0:
+            save()
+    print(f"Update: {tr.update_index}")
+    print("  " + json.dumps({k: v for k, v in metrics.items() if not isinstance(v, list)}))
+    save()
+    if args.phases and timed:
+        fps = args.num_worlds * args.steps_per_update * timed / (wall_ms * 1e-3)
+        lines = phase_table(totals, wall_ms, timed, args, fps)
+        print("\n".join(lines))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps({"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "updates": timed, "wall_ms_per_update": wall_ms / timed,
+                                    "fps_world_steps": fps, "phases_ms_per_update": {k: v / timed for k, v in totals.items()},
+                                    "last_metrics": {k: v for k, v in metrics.items() if not isinstance(v, list)}}) + "\n\n")
+                f.write("\n".join(lines) + "\n")
+    sim.close()
+
+
+if __name__ == "__main__":
+    main()
