@@ -13,7 +13,7 @@ dealt to shards.
 """
 import ctypes as C
 
-from ._request import _DTYPES, _name, _per_shard, _run, _sharded
+from ._request import _DTYPES, _name, _run, _shard_calls
 
 HEADS = 5             # HS_SAMPLE_HEADS
 MAX_BUCKETS = 16      # HS_SAMPLE_MAX_BUCKETS
@@ -117,16 +117,8 @@ def sample(sim, logits, stream=None, **kw):
 
 
 def sample_sharded(ssim, logits, stream=None, action=None, log_prob=None, entropy=None, head_log_prob=None, **kw):
-    """ShardedSimulator.sample_actions: every shard samples its own rows on its own device from its own logits tensor.
-    `logits` has one tensor per shard; each output (and `stream`) is True / None for all shards or a list with one entry
-    per shard; returns the list of the shards' results.  With stream=None every shard's call is enqueued on a side stream
-    of its device, ordered after that device's current stream, before any is waited for."""
-    import torch
-    n = len(ssim.shards)
-    if isinstance(logits, torch.Tensor) or len(logits) != n:
-        raise ValueError(f"logits: one tensor per shard ({n}) expected")
-    outs = {k: _per_shard(ssim, k, v) for k, v in (("action", action), ("log_prob", log_prob), ("entropy", entropy),
-                                                   ("head_log_prob", head_log_prob))}
-    res = _sharded(ssim, "hs_sample_actions", lambda i, s: request(s.num_worlds * s.agents_per_world, s.gpu_id, logits[i],
-                                                                    **{k: v[i] for k, v in outs.items()}, **kw), stream)
+    """ShardedSimulator.sample_actions: every shard samples its own rows on its own device from its own logits tensor."""
+    res = _shard_calls(ssim, "hs_sample_actions", request, stream, dict(logits=logits),
+                       per_shard=dict(action=action, log_prob=log_prob, entropy=entropy, head_log_prob=head_log_prob), kw=kw,
+                       lead=lambda s: (s.num_worlds * s.agents_per_world, s.gpu_id))
     return [_result(s, r) for s, r in zip(ssim.shards, res)]

@@ -22,9 +22,10 @@ identical (the actor's masked-out entities are all-zero rows), and then every pa
 way.  eager() is the same composition in plain torch, for readers, tools/embed_bench.py and the tests.
 """
 import ctypes as C
+import functools
 import math
 
-from ._request import _DTYPES, _disjoint, _given, _name, _per_shard, _run, _shard_list, _shard_params, _sharded
+from ._request import _DTYPES, _above_zero, _dtype_arg, _finite, _module_base, _name, _one_of, _outputs, _run, _shard_calls, _tensor, _wanted
 from .policy_inputs import ROW, TABLES
 
 EMBED_DIMS = (32, 64, 128)
@@ -56,9 +57,7 @@ class HsEntityEncodeBackwardRequest(C.Structure):
 
 # ---- the parameters: one description, from policy_inputs.TABLES ----
 def _embed_dim(E):
-    if isinstance(E, bool) or not isinstance(E, int) or E not in EMBED_DIMS:
-        raise ValueError(f"embed_dim must be one of {EMBED_DIMS}, got {E}")
-    return E
+    return _one_of("embed_dim", E, EMBED_DIMS)
 
 
 def param_layout(E):
@@ -115,39 +114,11 @@ def _common(gpu_id, rows, params, embed_dim, eps, slope):
     import torch
     dev = torch.device("cuda", gpu_id)
     E = _embed_dim(embed_dim)
-    coefs = dict(eps=float(eps), slope=float(slope))
-    for k, v in coefs.items():
-        if not math.isfinite(v) or not math.isfinite(C.c_float(v).value):
-            raise ValueError(f"{k} must be finite, got {v}")
-    if not C.c_float(coefs["eps"]).value > 0.0:
-        raise ValueError(f"eps must be above 0, got {eps}")
-    if not isinstance(rows, torch.Tensor):
-        raise ValueError("rows must be a torch tensor")
-    what = f"rows must be a contiguous {' / '.join(_DTYPES)} tensor of shape (n >= 1, {ROW}) on {dev}"
-    if rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] != ROW:
-        raise ValueError(f"{what}: its shape is {tuple(rows.shape)}")
-    if _name(rows.dtype) not in _DTYPES:
-        raise ValueError(f"{what}: its dtype is {rows.dtype}")
-    if not rows.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
-    n = int(rows.shape[0])
-    if n * max(ROW, 4 * E) >= 2 ** 31:
-        raise ValueError(f"{what}: n * {max(ROW, 4 * E)} must stay below 2^31")
-    _flat("params", params, E, dev)
-    return dev, E, n, coefs
-
-
-def _flat(name, t, E, dev):
-    import torch
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch tensor")
-    what = f"{name} must be a contiguous float32 tensor of shape ({PARAM_ROWS * E},) on {dev}"
-    if tuple(t.shape) != (PARAM_ROWS * E,):
-        raise ValueError(f"{what}: its shape is {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{what}: its dtype is {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
+    eps, slope = _finite("eps", eps), _finite("slope", slope)
+    _above_zero("eps", eps)
+    _tensor("rows", rows, ("n >= 1", ROW), _DTYPES, dev, bound=max(ROW, 4 * E))
+    _tensor("params", params, (PARAM_ROWS * E,), ("float32",), dev)
+    return dev, E, int(rows.shape[0]), eps, slope
 
 
 def request(gpu_id, rows, params, embed_dim=64, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, features=True, argmax=None, dtype=None):
@@ -155,28 +126,13 @@ def request(gpu_id, rows, params, embed_dim=64, eps=DEFAULT_EPS, slope=DEFAULT_S
     (features in `dtype`, by default the dtype of the rows; argmax uint8 [n, 3, E]), and return ({name: tensor},
     HsEntityEncodeRequest).  Raises ValueError before the library is involved."""
     import torch
-    dev, E, n, coefs = _common(gpu_id, rows, params, embed_dim, eps, slope)
-    outputs = {k: t for k, t in (("features", features), ("argmax", argmax)) if t is not None and t is not False}
-    if not outputs:
-        raise ValueError("nothing to do: neither features nor argmax requested")
-    if dtype is not None and _name(dtype) not in _DTYPES:
-        raise ValueError(f"dtype must be one of {', '.join(_DTYPES)}, got {dtype}")
-    given = {k: t for k, t in outputs.items() if t is not True}
-    if "features" in given:
-        _given("features", given["features"], (n, 4 * E), tuple(_DTYPES), dev)
-    if "argmax" in given:
-        _given("argmax", given["argmax"], (n, 3, E), ("uint8",), dev)
-    _disjoint(list(given.items()), [("rows", rows), ("params", params)], dev)
-    res = dict(given)
-    if outputs.get("features") is True:
-        res["features"] = torch.empty((n, 4 * E), dtype=rows.dtype if dtype is None else dtype, device=dev)
-    if outputs.get("argmax") is True:
-        res["argmax"] = torch.empty((n, 3, E), dtype=torch.uint8, device=dev)
-    res = {k: res[k] for k in outputs}
+    dev, E, n, eps, slope = _common(gpu_id, rows, params, embed_dim, eps, slope)
+    outputs = _wanted((("features", features), ("argmax", argmax)), "neither features nor argmax requested")
+    _dtype_arg("dtype", dtype)
+    specs = {"features": ((n, 4 * E), rows.dtype if dtype is None else dtype, _DTYPES), "argmax": ((n, 3, E), torch.uint8)}
+    res, ptr = _outputs(outputs, specs, [("rows", rows), ("params", params)], dev)
     req = HsEntityEncodeRequest(rows.data_ptr(), params.data_ptr(), n, _DTYPES[_name(rows.dtype)], E,
-                                _DTYPES[_name(res["features"].dtype)] if "features" in res else 0, coefs["eps"], coefs["slope"],
-                                res["features"].data_ptr() if "features" in res else None,
-                                res["argmax"].data_ptr() if "argmax" in res else None)
+                                _DTYPES[_name(res["features"].dtype)] if "features" in res else 0, eps, slope, ptr("features"), ptr("argmax"))
     return res, req
 
 
@@ -184,22 +140,17 @@ def request_backward(gpu_id, rows, params, grad_features, argmax, embed_dim=64, 
     """Validate a backward call, allocate grad_params when it is True, and return ({"grad_params": tensor},
     HsEntityEncodeBackwardRequest).  Raises ValueError before the library is involved."""
     import torch
-    dev, E, n, coefs = _common(gpu_id, rows, params, embed_dim, eps, slope)
+    dev, E, n, eps, slope = _common(gpu_id, rows, params, embed_dim, eps, slope)
     if not isinstance(grad_features, torch.Tensor) or not isinstance(argmax, torch.Tensor):
         raise ValueError("grad_features and argmax must be torch tensors")
-    _given("grad_features", grad_features, (n, 4 * E), tuple(_DTYPES), dev)
-    _given("argmax", argmax, (n, 3, E), ("uint8",), dev)
+    _tensor("grad_features", grad_features, (n, 4 * E), _DTYPES, dev)
+    _tensor("argmax", argmax, (n, 3, E), ("uint8",), dev)
     inputs = [("rows", rows), ("params", params), ("grad_features", grad_features), ("argmax", argmax)]
-    if grad_params is True:
-        _disjoint([], inputs, dev)
-        grad_params = torch.empty(PARAM_ROWS * E, dtype=torch.float32, device=dev)
-    else:
-        _flat("grad_params", grad_params, E, dev)
-        _disjoint([("grad_params", grad_params)], inputs, dev)
+    flat = ((PARAM_ROWS * E,), torch.float32, lambda k, t: _tensor(k, t, (PARAM_ROWS * E,), ("float32",), dev))      # the one output: not optional
+    res, ptr = _outputs({"grad_params": grad_params}, {"grad_params": flat}, inputs, dev)
     req = HsEntityEncodeBackwardRequest(rows.data_ptr(), params.data_ptr(), grad_features.data_ptr(), argmax.data_ptr(), n,
-                                        _DTYPES[_name(rows.dtype)], E, _DTYPES[_name(grad_features.dtype)], coefs["eps"], coefs["slope"],
-                                        grad_params.data_ptr())
-    return {"grad_params": grad_params}, req
+                                        _DTYPES[_name(rows.dtype)], E, _DTYPES[_name(grad_features.dtype)], eps, slope, ptr("grad_params"))
+    return res, req
 
 
 def compute(sim, rows, params, stream=None, **kw):
@@ -217,27 +168,19 @@ def compute_backward(sim, rows, params, grad_features, argmax, stream=None, **kw
 
 
 def compute_sharded(ssim, rows, params, stream=None, features=True, argmax=None, **kw):
-    """ShardedSimulator.encode_entities: every shard encodes its own rows on its own device.  `rows` has one tensor per
-    shard; `params` is one tensor for every shard (which then all have to be on its device) or a list with one per
-    shard; features, argmax and `stream` are True / None for all shards or a list with one entry per shard; returns the
-    list of the shards' results.  With stream=None every shard's call is enqueued on a side stream of its device, ordered
-    after that device's current stream, before any is waited for."""
-    rows, ps = _shard_list(ssim, "rows", rows), _shard_params(ssim, params)
-    fs, am = _per_shard(ssim, "features", features), _per_shard(ssim, "argmax", argmax)
-    return _sharded(ssim, "hs_entity_encode", lambda i, s: request(s.gpu_id, rows[i], ps[i], features=fs[i], argmax=am[i], **kw), stream)
+    """ShardedSimulator.encode_entities: every shard encodes its own rows on its own device."""
+    return _shard_calls(ssim, "hs_entity_encode", request, stream, dict(rows=rows), dict(params=params), dict(features=features, argmax=argmax), kw)
 
 
 def compute_backward_sharded(ssim, rows, params, grad_features, argmax, stream=None, grad_params=True, **kw):
     """ShardedSimulator.encode_entities_backward: as compute_sharded; every shard's grad_params holds the sum over its own
     rows (add them for shared parameters)."""
-    rows, ps = _shard_list(ssim, "rows", rows), _shard_params(ssim, params)
-    gf, am = _shard_list(ssim, "grad_features", grad_features), _shard_list(ssim, "argmax", argmax)
-    gp = _per_shard(ssim, "grad_params", grad_params)
-    return _sharded(ssim, "hs_entity_encode_backward",
-                    lambda i, s: request_backward(s.gpu_id, rows[i], ps[i], gf[i], am[i], grad_params=gp[i], **kw), stream)
+    return _shard_calls(ssim, "hs_entity_encode_backward", request_backward, stream, dict(rows=rows, grad_features=grad_features, argmax=argmax),
+                        dict(params=params), dict(grad_params=grad_params), kw)
 
 
 # ---- the autograd face ----
+@functools.lru_cache(maxsize=None)
 def _function():
     import torch
 
@@ -256,11 +199,6 @@ def _function():
             g = compute_backward(sim, rows, params.detach(), grad.contiguous(), argmax, embed_dim=E, eps=eps, slope=slope)["grad_params"]
             return g, None, None, None, None, None, None
     return _Encode
-
-
-def _module_base():
-    import torch
-    return torch.nn.Module
 
 
 class EntityEncoder(_module_base()):

@@ -17,9 +17,10 @@ The kernel reads and writes a lane's adjacent channels as one piece of up to 16 
 be 16-byte aligned: any contiguous [n, C] view that starts at a row boundary of a torch allocation is.
 """
 import ctypes as C
+import functools
 import math
 
-from ._request import _DTYPES, _disjoint, _given, _name, _per_shard, _run, _shard_list, _shard_params, _sharded
+from ._request import _DTYPES, _OUTPUT, _above_zero, _dtype_arg, _module_base, _name, _one_of, _outputs, _run, _shard_calls, _tensor, _wanted
 
 CHANNELS = (64, 128, 256, 512)
 PARAM_ROWS = 3            # HS_DENSE_PARAM_ROWS: bias | gamma | beta, rows of C floats
@@ -46,9 +47,7 @@ class HsDenseNormActBackwardRequest(C.Structure):
 
 # ---- the parameters ----
 def _channels(Cn):
-    if isinstance(Cn, bool) or not isinstance(Cn, int) or Cn not in CHANNELS:
-        raise ValueError(f"channels must be one of {CHANNELS}, got {Cn}")
-    return Cn
+    return _one_of("channels", Cn, CHANNELS)
 
 
 def param_layout(Cn):
@@ -84,13 +83,6 @@ def eager(z, params, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE):
 
 
 # ---- the fused calls ----
-def _rows(name, t, shape, dtypes, dev):
-    """_given, plus the alignment the kernel's accesses need."""
-    _given(name, t, shape, dtypes, dev)
-    if t.data_ptr() % ALIGN:
-        raise ValueError(f"{name} must be {ALIGN}-byte aligned (a contiguous view that starts at a row boundary is): its address is {t.data_ptr():#x}")
-
-
 def _common(gpu_id, z, params, channels, eps, slope):
     import torch
     dev = torch.device("cuda", gpu_id)
@@ -101,49 +93,29 @@ def _common(gpu_id, z, params, channels, eps, slope):
             raise ValueError(f"z must be a tensor of shape (n >= 1, channels): its shape is {tuple(z.shape)}")
         channels = int(z.shape[1])
     Cn = _channels(channels)
-    e, sl = float(eps), float(slope)
-    if not math.isfinite(e) or not math.isfinite(C.c_float(e).value):
-        raise ValueError(f"eps must be finite, got {eps}")
-    if not C.c_float(e).value > 0.0:
-        raise ValueError(f"eps must be above 0, got {eps}")
+    e, sl = _above_zero("eps", eps), float(slope)
     if not math.isfinite(sl) or not 0.0 <= C.c_float(sl).value <= 1.0:
         raise ValueError(f"slope must be finite and in [0, 1], got {slope}")
-    what = f"z must be a contiguous {' / '.join(_DTYPES)} tensor of shape (n >= 1, {Cn}) on {dev}"
-    if z.dim() != 2 or z.shape[0] < 1 or z.shape[1] != Cn:
-        raise ValueError(f"{what}: its shape is {tuple(z.shape)}")
-    if _name(z.dtype) not in _DTYPES:
-        raise ValueError(f"{what}: its dtype is {z.dtype}")
-    if not z.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
-    n = int(z.shape[0])
-    if n * Cn >= 2 ** 31:
-        raise ValueError(f"{what}: n * {Cn} must stay below 2^31")
-    if z.data_ptr() % ALIGN:
-        raise ValueError(f"z must be {ALIGN}-byte aligned (a contiguous view that starts at a row boundary is): its address is {z.data_ptr():#x}")
-    if not isinstance(params, torch.Tensor):
-        raise ValueError("params must be a torch tensor")
-    _given("params", params, (PARAM_ROWS * Cn,), ("float32",), dev)
-    return dev, Cn, n, e, sl, [("z", z), ("params", params)]
+    _tensor("z", z, ("n >= 1", Cn), _DTYPES, dev, bound=Cn, align=ALIGN)
+    _tensor("params", params, (PARAM_ROWS * Cn,), ("float32",), dev)
+    return dev, Cn, int(z.shape[0]), e, sl, [("z", z), ("params", params)]
+
+
+def _aligned_rows(n, Cn, dtypes, dev):
+    """The checker of a [n, C] output: the plain one, plus the alignment the kernel's accesses need."""
+    return lambda k, t: _tensor(k, t, (n, Cn), dtypes, dev, _OUTPUT, align=ALIGN)
 
 
 def request(gpu_id, z, params, channels=None, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, y=True, y_dtype=None):
     """Validate a forward call over the n = z.shape[0] rows on GPU `gpu_id` (channels defaults to z's width), allocate y
     when given as True (in `y_dtype`, by default the dtype of z), and return ({"y": tensor}, HsDenseNormActRequest).
     Raises ValueError before the library is involved."""
-    import torch
     dev, Cn, n, eps, slope, inputs = _common(gpu_id, z, params, channels, eps, slope)
-    if y is None or y is False:
-        raise ValueError("nothing to do: y not requested")
-    if y_dtype is not None and _name(y_dtype) not in _DTYPES:
-        raise ValueError(f"y_dtype must be one of {', '.join(_DTYPES)}, got {y_dtype}")
-    if y is not True:
-        _rows("y", y, (n, Cn), tuple(_DTYPES), dev)
-        _disjoint([("y", y)], inputs, dev)
-    else:
-        _disjoint([], inputs, dev)
-        y = torch.empty((n, Cn), dtype=z.dtype if y_dtype is None else y_dtype, device=dev)
-    req = HsDenseNormActRequest(z.data_ptr(), params.data_ptr(), n, Cn, _DTYPES[_name(z.dtype)], _DTYPES[_name(y.dtype)], eps, slope, y.data_ptr())
-    return {"y": y}, req
+    outputs = _wanted((("y", y),), "y not requested")
+    _dtype_arg("y_dtype", y_dtype)
+    res, ptr = _outputs(outputs, {"y": ((n, Cn), z.dtype if y_dtype is None else y_dtype, _aligned_rows(n, Cn, _DTYPES, dev))}, inputs, dev)
+    req = HsDenseNormActRequest(z.data_ptr(), params.data_ptr(), n, Cn, _DTYPES[_name(z.dtype)], _DTYPES[_name(res["y"].dtype)], eps, slope, ptr("y"))
+    return res, req
 
 
 def request_backward(gpu_id, z, params, grad_y, channels=None, eps=DEFAULT_EPS, slope=DEFAULT_SLOPE, grad_z=True, grad_params=True):
@@ -152,20 +124,12 @@ def request_backward(gpu_id, z, params, grad_y, channels=None, eps=DEFAULT_EPS, 
     forward's y).  Raises ValueError before the library is involved."""
     import torch
     dev, Cn, n, eps, slope, inputs = _common(gpu_id, z, params, channels, eps, slope)
-    if not isinstance(grad_y, torch.Tensor):
-        raise ValueError("grad_y must be a torch tensor")
-    _rows("grad_y", grad_y, (n, Cn), tuple(_DTYPES), dev)
+    _tensor("grad_y", grad_y, (n, Cn), _DTYPES, dev, align=ALIGN)
     inputs.append(("grad_y", grad_y))
-    outputs = {k: t for k, t in (("grad_z", grad_z), ("grad_params", grad_params)) if t is not None and t is not False}
-    if not outputs:
-        raise ValueError("nothing to do: neither grad_z nor grad_params requested")
-    shapes = {"grad_z": ((n, Cn), z.dtype), "grad_params": ((PARAM_ROWS * Cn,), torch.float32)}
-    given = {k: t for k, t in outputs.items() if t is not True}
-    for k, t in given.items():
-        (_rows if k == "grad_z" else _given)(k, t, shapes[k][0], (_name(shapes[k][1]),), dev)
-    _disjoint(list(given.items()), inputs, dev)
-    res = {k: (torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) if t is True else t) for k, t in outputs.items()}
-    ptr = lambda k: res[k].data_ptr() if k in res else None                    # noqa: E731
+    outputs = _wanted((("grad_z", grad_z), ("grad_params", grad_params)), "neither grad_z nor grad_params requested")
+    specs = {"grad_z": ((n, Cn), z.dtype, _aligned_rows(n, Cn, (_name(z.dtype),), dev)),
+             "grad_params": ((PARAM_ROWS * Cn,), torch.float32)}
+    res, ptr = _outputs(outputs, specs, inputs, dev)
     req = HsDenseNormActBackwardRequest(z.data_ptr(), params.data_ptr(), grad_y.data_ptr(), n, Cn, _DTYPES[_name(z.dtype)],
                                         _DTYPES[_name(grad_y.dtype)], eps, slope, ptr("grad_z"), ptr("grad_params"))
     return res, req
@@ -186,21 +150,15 @@ def compute_backward(sim, z, params, grad_y, stream=None, **kw):
 
 
 def compute_sharded(ssim, z, params, stream=None, y=True, **kw):
-    """ShardedSimulator.dense_norm_act: every shard works its own rows on its own device.  z has one tensor per shard;
-    params is one tensor for every shard (which then all have to be on its device) or a list; y and `stream` are True /
-    None for all shards or a list with one entry per shard; returns the list of the shards' results
-    (recurrent.compute_sharded's conventions)."""
-    zs, ps, ys = _shard_list(ssim, "z", z), _shard_params(ssim, params), _per_shard(ssim, "y", y)
-    return _sharded(ssim, "hs_dense_norm_act", lambda i, s: request(s.gpu_id, zs[i], ps[i], y=ys[i], **kw), stream)
+    """ShardedSimulator.dense_norm_act: every shard works its own rows on its own device."""
+    return _shard_calls(ssim, "hs_dense_norm_act", request, stream, dict(z=z), dict(params=params), dict(y=y), kw)
 
 
 def compute_backward_sharded(ssim, z, params, grad_y, stream=None, grad_z=True, grad_params=True, **kw):
     """ShardedSimulator.dense_norm_act_backward: as compute_sharded; every shard's grad_params holds the sum over its own
     rows (add them for shared parameters)."""
-    zs, ps, gy = _shard_list(ssim, "z", z), _shard_params(ssim, params), _shard_list(ssim, "grad_y", grad_y)
-    gz, gp = _per_shard(ssim, "grad_z", grad_z), _per_shard(ssim, "grad_params", grad_params)
-    return _sharded(ssim, "hs_dense_norm_act_backward",
-                    lambda i, s: request_backward(s.gpu_id, zs[i], ps[i], gy[i], grad_z=gz[i], grad_params=gp[i], **kw), stream)
+    return _shard_calls(ssim, "hs_dense_norm_act_backward", request_backward, stream, dict(z=z, grad_y=grad_y), dict(params=params),
+                        dict(grad_z=grad_z, grad_params=grad_params), kw)
 
 
 # ---- the autograd face ----
@@ -210,6 +168,7 @@ def _aligned(t):
     return t.clone() if t.data_ptr() % ALIGN else t
 
 
+@functools.lru_cache(maxsize=None)
 def _function():
     import torch
 
@@ -230,11 +189,6 @@ def _function():
                                    grad_z=ctx.needs_input_grad[0] or None, grad_params=ctx.needs_input_grad[1] or None)
             return res.get("grad_z"), res.get("grad_params"), None, None, None
     return _DenseNormAct
-
-
-def _module_base():
-    import torch
-    return torch.nn.Module
 
 
 class DenseNormAct(_module_base()):

@@ -30,7 +30,7 @@ autograd graph).
 import ctypes as C
 import math
 
-from ._request import _disjoint, _given, _run
+from ._request import _OUTPUT, _above_zero, _disjoint, _finite, _run, _tensor
 
 ALIGN = 16                # bytes: params, grads, m and v
 PAD = 64                  # elements: every parameter of a flat buffer starts at a multiple of it
@@ -60,10 +60,7 @@ def _f32(name, x):
     """x as the float32 the request carries; finite before and after the rounding."""
     if isinstance(x, bool) or not isinstance(x, (int, float)):
         raise ValueError(f"{name} must be a number, got {x!r}")
-    x = float(x)
-    if not math.isfinite(x) or not math.isfinite(C.c_float(x).value):
-        raise ValueError(f"{name} must be finite, got {x}")
-    return C.c_float(x).value
+    return C.c_float(_finite(name, x)).value
 
 
 def _f64(name, x):
@@ -75,8 +72,7 @@ def _f64(name, x):
 def _hyper(lr, betas, eps, weight_decay, max_grad_norm, grad_scale):
     lr, eps, wd = _f32("lr", lr), _f32("eps", eps), _f32("weight_decay", weight_decay)
     gs, mgn = _f64("grad_scale", grad_scale), _f64("max_grad_norm", 0.0 if max_grad_norm is None else max_grad_norm)
-    if not eps > 0.0:
-        raise ValueError(f"eps must be above 0, got {eps}")
+    _above_zero("eps", eps)
     if lr < 0.0:
         raise ValueError(f"lr must be at least 0, got {lr}")
     if wd < 0.0:
@@ -111,18 +107,12 @@ def request(gpu_id, params, grads, m, v, state, lr=DEFAULTS["lr"], betas=DEFAULT
     n = int(params.shape[0])
     arrays = [("params", params), ("grads", grads), ("m", m), ("v", v)]
     for name, t in arrays:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor")
-        _given(name, t, (n,), ("float32",), dev)
-        if t.data_ptr() % ALIGN:
-            raise ValueError(f"{name} must be {ALIGN}-byte aligned: its address is {t.data_ptr():#x}")
-    if not isinstance(state, torch.Tensor):
-        raise ValueError("state must be a torch tensor")
-    _given("state", state, (STATE,), ("float64",), dev)
+        _tensor(name, t, (n,), ("float32",), dev, align=ALIGN)
+    _tensor("state", state, (STATE,), ("float64",), dev)
     arrays.append(("state", state))
     if stats is not None and stats is not False:
         if stats is not True:
-            _given("stats", stats, (STATS,), ("float64",), dev)
+            _tensor("stats", stats, (STATS,), ("float64",), dev, _OUTPUT)
             arrays.append(("stats", stats))
     else:
         stats = None

@@ -21,14 +21,10 @@ In a chunk the encoder and the MLP do not depend on time: sequence() runs them o
 only the LSTM step by step.
 """
 from . import entity_encoder, mlp, recurrent
+from ._request import _module_base
 
 BUCKETS = (5, 5, 5, 2, 2)     # the reference's action heads: move amount, move angle, rotate, grab, lock
 BINS = 255                    # the two-hot critic's bins (value_head)
-
-
-def _module_base():
-    import torch
-    return torch.nn.Module
 
 
 class Backbone(_module_base()):

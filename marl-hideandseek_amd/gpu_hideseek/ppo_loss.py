@@ -18,11 +18,10 @@ or, for a learner that wants a loss tensor to call backward on:
     loss = ppo_loss.attach(logits, value, out)                    # a scalar; loss.backward() hands the gradients on
 """
 import ctypes as C
-import math
 
 from .action_sampling import DEFAULT_BUCKETS, HEADS, MAX_BUCKETS, MAX_LOGITS
 from .advantages import MOMENTS
-from ._request import _DTYPES, _disjoint, _name, _per_shard, _rows, _run, _sharded, _vector
+from ._request import _DTYPES, _OUTPUT, _above_zero, _dtype_arg, _finite, _name, _outputs, _rows, _run, _shard_calls, _stride, _tensor, _vector, _wanted
 
 STATS = 7             # HS_PPO_STATS: sum pg, sum vl, sum ent, sum kl, policy-clipped, value-clipped, count
 ROWS_PER_BLOCK = 32   # kPpoRows: samples a workgroup takes at a time
@@ -58,19 +57,12 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
     L = sum(buckets)
     if L > MAX_LOGITS:
         raise ValueError(f"buckets sum to {L} logits per sample, more than {MAX_LOGITS}")
-    coefs = dict(clip_coef=float(clip_coef), value_loss_coef=float(value_loss_coef), entropy_coef=float(entropy_coef),
-                 grad_scale=float(grad_scale))
-    for k, v in coefs.items():
-        if not math.isfinite(v) or not math.isfinite(C.c_float(v).value):
-            raise ValueError(f"{k} must be finite, got {v}")
-    if not coefs["clip_coef"] > 0.0 or not C.c_float(coefs["clip_coef"]).value > 0.0:
-        raise ValueError(f"clip_coef must be above 0, got {clip_coef}")
+    coefs = {k: _finite(k, v) for k, v in (("clip_coef", clip_coef), ("value_loss_coef", value_loss_coef), ("entropy_coef", entropy_coef),
+                                           ("grad_scale", grad_scale))}
+    _above_zero("clip_coef", clip_coef)
     if grad_value is None:
         grad_value = value is not None
-    outputs = {k: t for k, t in (("grad_logits", grad_logits), ("grad_value", grad_value), ("stats", stats))
-               if t is not None and t is not False}
-    if not outputs:
-        raise ValueError("nothing to do: none of grad_logits, grad_value and stats requested")
+    outputs = _wanted((("grad_logits", grad_logits), ("grad_value", grad_value), ("stats", stats)), "none of grad_logits, grad_value and stats requested")
     if "grad_value" in outputs and value is None:
         raise ValueError("grad_value needs value")
     if value is not None and returns is None:
@@ -80,49 +72,32 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
 
     stride = _rows("logits", logits, None, L, dev, "n")
     n = int(logits.shape[0])
-    _vector("action", action, n, dev, ("int32",), (HEADS,))
+    _tensor("action", action, (n, HEADS), ("int32",), dev)
     _vector("old_log_prob", old_log_prob, n, dev, ("float32",))
     _vector("advantage", advantage, n, dev, ("float32",))
     if adv_moments is not None:
-        _vector("adv_moments", adv_moments, MOMENTS, dev, ("float64",))
-        if tuple(adv_moments.shape) != (MOMENTS,):
-            raise ValueError(f"adv_moments must have shape ({MOMENTS},): its shape is {tuple(adv_moments.shape)}")
+        _tensor("adv_moments", adv_moments, (MOMENTS,), ("float64",), dev)
     if mask is not None:
         _vector("mask", mask, n, dev, ("float32",))
     if value is not None:
-        _vector("value", value, n, dev, tuple(_DTYPES))
+        _vector("value", value, n, dev, _DTYPES)
         _vector("returns", returns, n, dev, ("float32",))
         if old_value is not None:
             _vector("old_value", old_value, n, dev, ("float32",))
     inputs = [(k, t) for k, t in (("logits", logits), ("action", action), ("old_log_prob", old_log_prob), ("advantage", advantage),
                                   ("adv_moments", adv_moments), ("mask", mask), ("value", value), ("returns", returns),
                                   ("old_value", old_value)) if t is not None]
-    given = {k: t for k, t in outputs.items() if t is not True}
-    gstride = L
-    if "grad_logits" in given:
-        gstride = _rows("grad_logits", given["grad_logits"], n, L, dev, n)
-    elif "grad_logits" in outputs:
-        gdt = logits.dtype if grad_dtype is None else grad_dtype
-        if _name(gdt) not in _DTYPES:
-            raise ValueError(f"grad_dtype must be one of {', '.join(_DTYPES)}, got {gdt}")
-    if "grad_value" in given:
-        _vector("grad_value", given["grad_value"], n, dev, (_name(value.dtype),))
-    if "stats" in given:
-        _vector("stats", given["stats"], STATS, dev, ("float64",))
-        if tuple(given["stats"].shape) != (STATS,):
-            raise ValueError(f"stats must have shape ({STATS},): its shape is {tuple(given['stats'].shape)}")
-    _disjoint(list(given.items()), inputs, dev)
-
-    res = dict(given)
-    if outputs.get("grad_logits") is True:        # as wide as the logits tensor, so that logits.backward() takes it
-        W = int(logits.shape[1])
-        res["grad_logits"] = (torch.zeros if W > L else torch.empty)((n, W), dtype=gdt, device=dev)
-        gstride = max(W, L)
-    if outputs.get("grad_value") is True:
-        res["grad_value"] = torch.empty(tuple(value.shape), dtype=value.dtype, device=dev)
-    if outputs.get("stats") is True:
-        res["stats"] = torch.empty(STATS, dtype=torch.float64, device=dev)
-    res = {k: res[k] for k in outputs}
+    gdt = logits.dtype if grad_dtype is None else grad_dtype
+    if outputs.get("grad_logits") is True:
+        _dtype_arg("grad_dtype", gdt)
+    W = int(logits.shape[1])
+    # grad_logits is as wide as the logits tensor, so that logits.backward() takes it: zeros where it is wider than L
+    specs = {"grad_logits": ((n, W), gdt, lambda k, t: _rows(k, t, n, L, dev, n), W > L), "stats": ((STATS,), torch.float64)}
+    if value is not None:
+        specs["grad_value"] = (tuple(value.shape), value.dtype, lambda k, t: _vector(k, t, n, dev, (_name(value.dtype),), _OUTPUT))
+    res, out = _outputs(outputs, specs, inputs, dev)
+    g = outputs.get("grad_logits")
+    gstride = L if g is None else max(W, L) if g is True else _stride(g, L)
 
     def ptr(t):
         return t.data_ptr() if t is not None else None
@@ -131,7 +106,7 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
                        _DTYPES[_name(res["grad_logits"].dtype)] if "grad_logits" in res else 0, gstride,
                        _DTYPES[_name(value.dtype)] if value is not None else 0, (C.c_int32 * HEADS)(*buckets),
                        coefs["clip_coef"], coefs["value_loss_coef"], coefs["entropy_coef"], coefs["grad_scale"],
-                       ptr(res.get("grad_logits")), ptr(res.get("grad_value")), ptr(res.get("stats")))
+                       out("grad_logits"), out("grad_value"), out("stats"))
     res["coefficients"] = {k: C.c_float(v).value for k, v in coefs.items()}       # as the kernel saw them (f32)
     return res, req
 
@@ -147,20 +122,10 @@ _PER_SHARD = ("adv_moments", "mask", "value", "returns", "old_value", "grad_logi
 
 
 def compute_sharded(ssim, logits, action, old_log_prob, advantage, stream=None, **kw):
-    """ShardedSimulator.ppo_loss: every shard computes its own minibatch on its own device.  `logits`, `action`,
-    `old_log_prob` and `advantage` have one tensor per shard; adv_moments, mask, value, returns, old_value, each output
-    and `stream` are True / None for all shards or a list with one entry per shard; returns the list of the shards'
-    results.  With stream=None every shard's call is enqueued on a side stream of its device, ordered after that device's
-    current stream, before any is waited for.  Every shard divides by its own count of active samples: weigh the shards'
-    gradients with grad_scale when their counts differ."""
-    import torch
-    n = len(ssim.shards)
-    for name, arg in (("logits", logits), ("action", action), ("old_log_prob", old_log_prob), ("advantage", advantage)):
-        if isinstance(arg, torch.Tensor) or len(arg) != n:
-            raise ValueError(f"{name}: one tensor per shard ({n}) expected")
-    per = {k: _per_shard(ssim, k, kw.pop(k)) for k in _PER_SHARD if k in kw}
-    return _sharded(ssim, "hs_ppo_loss", lambda i, s: request(s.gpu_id, logits[i], action[i], old_log_prob[i], advantage[i],
-                                                              **{k: v[i] for k, v in per.items()}, **kw), stream)
+    """ShardedSimulator.ppo_loss: every shard computes its own minibatch on its own device.  Every shard divides by its
+    own count of active samples: weigh the shards' gradients with grad_scale when their counts differ."""
+    return _shard_calls(ssim, "hs_ppo_loss", request, stream, dict(logits=logits, action=action, old_log_prob=old_log_prob, advantage=advantage),
+                        per_shard={k: kw.pop(k) for k in _PER_SHARD if k in kw}, kw=kw)
 
 
 def stats_to_metrics(stats, entropy_coef=DEFAULT_ENTROPY_COEF, value_loss_coef=DEFAULT_VALUE_LOSS_COEF, grad_scale=1.0):

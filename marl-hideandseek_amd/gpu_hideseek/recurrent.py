@@ -20,9 +20,9 @@ or without autograd: sim.lstm_cell(gates, c_prev, core.cell_params.detach(), cle
 same composition in plain torch, for readers, tools/lstm_bench.py and the tests.
 """
 import ctypes as C
-import math
+import functools
 
-from ._request import _DTYPES, _disjoint, _given, _name, _per_shard, _run, _shard_list, _shard_params, _sharded
+from ._request import _DTYPES, _above_zero, _dtype_arg, _module_base, _name, _one_of, _outputs, _run, _shard_calls, _tensor, _vector, _wanted
 
 HIDDEN = (64, 128, 256, 512)
 PARAM_ROWS = 6            # HS_LSTM_PARAM_ROWS: bias i, f, g, o | gamma | beta, rows of H floats
@@ -50,9 +50,7 @@ class HsLstmCellBackwardRequest(C.Structure):
 
 # ---- the parameters ----
 def _hidden(H):
-    if isinstance(H, bool) or not isinstance(H, int) or H not in HIDDEN:
-        raise ValueError(f"hidden must be one of {HIDDEN}, got {H}")
-    return H
+    return _one_of("hidden", H, HIDDEN)
 
 
 def param_layout(H):
@@ -115,46 +113,16 @@ def _common(gpu_id, gates, c_prev, cell_params, clear, hidden, eps):
     if hidden is None and isinstance(c_prev, torch.Tensor) and c_prev.dim() == 2:
         hidden = int(c_prev.shape[1])
     H = _hidden(hidden)
-    e = float(eps)
-    if not math.isfinite(e) or not math.isfinite(C.c_float(e).value):
-        raise ValueError(f"eps must be finite, got {eps}")
-    if not C.c_float(e).value > 0.0:
-        raise ValueError(f"eps must be above 0, got {eps}")
-    if not isinstance(gates, torch.Tensor):
-        raise ValueError("gates must be a torch tensor")
-    what = f"gates must be a contiguous {' / '.join(_DTYPES)} tensor of shape (n >= 1, {4 * H}) on {dev}"
-    if gates.dim() != 2 or gates.shape[0] < 1 or gates.shape[1] != 4 * H:
-        raise ValueError(f"{what}: its shape is {tuple(gates.shape)}")
-    if _name(gates.dtype) not in _DTYPES:
-        raise ValueError(f"{what}: its dtype is {gates.dtype}")
-    if not gates.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
+    e = _above_zero("eps", eps)
+    _tensor("gates", gates, ("n >= 1", 4 * H), _DTYPES, dev, bound=4 * H)
     n = int(gates.shape[0])
-    if n * 4 * H >= 2 ** 31:
-        raise ValueError(f"{what}: n * {4 * H} must stay below 2^31")
-    if not isinstance(c_prev, torch.Tensor):
-        raise ValueError("c_prev must be a torch tensor")
-    _given("c_prev", c_prev, (n, H), ("float32",), dev)
-    if not isinstance(cell_params, torch.Tensor):
-        raise ValueError("cell_params must be a torch tensor")
-    _given("cell_params", cell_params, (PARAM_ROWS * H,), ("float32",), dev)
+    _tensor("c_prev", c_prev, (n, H), ("float32",), dev)
+    _tensor("cell_params", cell_params, (PARAM_ROWS * H,), ("float32",), dev)
     inputs = [("gates", gates), ("c_prev", c_prev), ("cell_params", cell_params)]
     if clear is not None:
-        if not isinstance(clear, torch.Tensor):
-            raise ValueError("clear must be None or a torch tensor")
-        what = f"clear must be a contiguous int32 tensor of shape ({n},) or ({n}, 1) on {dev}"
-        if tuple(clear.shape) not in ((n,), (n, 1)):
-            raise ValueError(f"{what}: its shape is {tuple(clear.shape)}")
-        if clear.dtype != torch.int32:
-            raise ValueError(f"{what}: its dtype is {clear.dtype}")
-        if not clear.is_contiguous():
-            raise ValueError(f"{what}: it is not contiguous")
+        _vector("clear", clear, n, dev, ("int32",), "None or a torch tensor")
         inputs.append(("clear", clear))
     return dev, H, n, e, inputs
-
-
-def _wanted(pairs):
-    return {k: t for k, t in pairs if t is not None and t is not False}
 
 
 def request(gpu_id, gates, c_prev, cell_params, clear=None, hidden=None, eps=DEFAULT_EPS, y=True, h_next=True, c_next=True, y_dtype=None):
@@ -163,25 +131,14 @@ def request(gpu_id, gates, c_prev, cell_params, clear=None, hidden=None, eps=DEF
     c_next float32), and return ({name: tensor}, HsLstmCellRequest).  Raises ValueError before the library is involved."""
     import torch
     dev, H, n, eps, inputs = _common(gpu_id, gates, c_prev, cell_params, clear, hidden, eps)
-    outputs = _wanted((("y", y), ("h_next", h_next), ("c_next", c_next)))
-    if not outputs:
-        raise ValueError("nothing to do: none of y, h_next and c_next requested")
-    if y_dtype is not None and _name(y_dtype) not in _DTYPES:
-        raise ValueError(f"y_dtype must be one of {', '.join(_DTYPES)}, got {y_dtype}")
-    gname = _name(gates.dtype)
-    given = {k: t for k, t in outputs.items() if t is not True}
-    for k, dts in (("y", tuple(_DTYPES)), ("h_next", (gname,)), ("c_next", ("float32",))):
-        if k in given:
-            _given(k, given[k], (n, H), dts, dev)
-    _disjoint(list(given.items()), inputs, dev)
-    res = dict(given)
-    for k, dt in (("y", gates.dtype if y_dtype is None else y_dtype), ("h_next", gates.dtype), ("c_next", torch.float32)):
-        if outputs.get(k) is True:
-            res[k] = torch.empty((n, H), dtype=dt, device=dev)
-    res = {k: res[k] for k in outputs}
-    ptr = lambda k: res[k].data_ptr() if k in res else None                    # noqa: E731
+    outputs = _wanted((("y", y), ("h_next", h_next), ("c_next", c_next)), "none of y, h_next and c_next requested")
+    _dtype_arg("y_dtype", y_dtype)
+    specs = {"y": ((n, H), gates.dtype if y_dtype is None else y_dtype, _DTYPES), "h_next": ((n, H), gates.dtype),
+             "c_next": ((n, H), torch.float32)}
+    res, ptr = _outputs(outputs, specs, inputs, dev)
     req = HsLstmCellRequest(gates.data_ptr(), c_prev.data_ptr(), cell_params.data_ptr(), None if clear is None else clear.data_ptr(), n, H,
-                            _DTYPES[gname], _DTYPES[_name(res["y"].dtype)] if "y" in res else 0, eps, 0, ptr("y"), ptr("h_next"), ptr("c_next"))
+                            _DTYPES[_name(gates.dtype)], _DTYPES[_name(res["y"].dtype)] if "y" in res else 0, eps, 0, ptr("y"), ptr("h_next"),
+                            ptr("c_next"))
     return res, req
 
 
@@ -194,26 +151,17 @@ def request_backward(gpu_id, gates, c_prev, cell_params, grad_y, clear=None, gra
     import torch
     dev, H, n, eps, inputs = _common(gpu_id, gates, c_prev, cell_params, clear, hidden, eps)
     gname = _name(gates.dtype)
-    if not isinstance(grad_y, torch.Tensor):
-        raise ValueError("grad_y must be a torch tensor")
-    _given("grad_y", grad_y, (n, H), tuple(_DTYPES), dev)
+    _tensor("grad_y", grad_y, (n, H), _DTYPES, dev)
     inputs.append(("grad_y", grad_y))
     for k, t, dts in (("grad_h_next", grad_h_next, (gname,)), ("grad_c_next", grad_c_next, ("float32",))):
         if t is not None:
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{k} must be None or a torch tensor")
-            _given(k, t, (n, H), dts, dev)
+            _tensor(k, t, (n, H), dts, dev, "None or a torch tensor")
             inputs.append((k, t))
-    outputs = _wanted((("grad_gates", grad_gates), ("grad_c_prev", grad_c_prev), ("grad_cell_params", grad_cell_params)))
-    if not outputs:
-        raise ValueError("nothing to do: none of grad_gates, grad_c_prev and grad_cell_params requested")
-    shapes = {"grad_gates": ((n, 4 * H), gates.dtype), "grad_c_prev": ((n, H), torch.float32), "grad_cell_params": ((PARAM_ROWS * H,), torch.float32)}
-    given = {k: t for k, t in outputs.items() if t is not True}
-    for k, t in given.items():
-        _given(k, t, shapes[k][0], (_name(shapes[k][1]),), dev)
-    _disjoint(list(given.items()), inputs, dev)
-    res = {k: (torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) if t is True else t) for k, t in outputs.items()}
-    ptr = lambda k: res[k].data_ptr() if k in res else None                    # noqa: E731
+    outputs = _wanted((("grad_gates", grad_gates), ("grad_c_prev", grad_c_prev), ("grad_cell_params", grad_cell_params)),
+                      "none of grad_gates, grad_c_prev and grad_cell_params requested")
+    specs = {"grad_gates": ((n, 4 * H), gates.dtype), "grad_c_prev": ((n, H), torch.float32),
+             "grad_cell_params": ((PARAM_ROWS * H,), torch.float32)}
+    res, ptr = _outputs(outputs, specs, inputs, dev)
     opt = lambda t: None if t is None else t.data_ptr()                        # noqa: E731
     req = HsLstmCellBackwardRequest(gates.data_ptr(), c_prev.data_ptr(), cell_params.data_ptr(), opt(clear), grad_y.data_ptr(), opt(grad_h_next),
                                     opt(grad_c_next), n, H, _DTYPES[gname], _DTYPES[_name(grad_y.dtype)], eps, 0, ptr("grad_gates"),
@@ -235,34 +183,23 @@ def compute_backward(sim, gates, c_prev, cell_params, grad_y, stream=None, **kw)
     return res
 
 
-def _opt_list(ssim, name, arg):
-    return [None] * len(ssim.shards) if arg is None else _shard_list(ssim, name, arg)
-
-
 def compute_sharded(ssim, gates, c_prev, cell_params, stream=None, clear=None, y=True, h_next=True, c_next=True, **kw):
-    """ShardedSimulator.lstm_cell: every shard works its own rows on its own device.  gates, c_prev (and clear, when
-    given) have one tensor per shard; cell_params is one tensor for every shard (which then all have to be on its device)
-    or a list; the outputs and `stream` are True / None for all shards or a list with one entry per shard; returns the
-    list of the shards' results (entity_encoder.compute_sharded's conventions)."""
-    gs, cs, ps, cl = _shard_list(ssim, "gates", gates), _shard_list(ssim, "c_prev", c_prev), _shard_params(ssim, cell_params), _opt_list(ssim, "clear", clear)
-    ys, hs, cn = _per_shard(ssim, "y", y), _per_shard(ssim, "h_next", h_next), _per_shard(ssim, "c_next", c_next)
-    return _sharded(ssim, "hs_lstm_cell",
-                    lambda i, s: request(s.gpu_id, gs[i], cs[i], ps[i], clear=cl[i], y=ys[i], h_next=hs[i], c_next=cn[i], **kw), stream)
+    """ShardedSimulator.lstm_cell: every shard works its own rows on its own device."""
+    return _shard_calls(ssim, "hs_lstm_cell", request, stream, dict(gates=gates, c_prev=c_prev), dict(cell_params=cell_params),
+                        dict(clear=clear, y=y, h_next=h_next, c_next=c_next), kw)
 
 
 def compute_backward_sharded(ssim, gates, c_prev, cell_params, grad_y, stream=None, clear=None, grad_h_next=None, grad_c_next=None,
                              grad_gates=True, grad_c_prev=True, grad_cell_params=True, **kw):
     """ShardedSimulator.lstm_cell_backward: as compute_sharded; every shard's grad_cell_params holds the sum over its own
     rows (add them for shared parameters)."""
-    gs, cs, ps, cl = _shard_list(ssim, "gates", gates), _shard_list(ssim, "c_prev", c_prev), _shard_params(ssim, cell_params), _opt_list(ssim, "clear", clear)
-    gy, gh, gc = _shard_list(ssim, "grad_y", grad_y), _opt_list(ssim, "grad_h_next", grad_h_next), _opt_list(ssim, "grad_c_next", grad_c_next)
-    og, oc, op = _per_shard(ssim, "grad_gates", grad_gates), _per_shard(ssim, "grad_c_prev", grad_c_prev), _per_shard(ssim, "grad_cell_params", grad_cell_params)
-    return _sharded(ssim, "hs_lstm_cell_backward",
-                    lambda i, s: request_backward(s.gpu_id, gs[i], cs[i], ps[i], gy[i], clear=cl[i], grad_h_next=gh[i], grad_c_next=gc[i],
-                                                  grad_gates=og[i], grad_c_prev=oc[i], grad_cell_params=op[i], **kw), stream)
+    return _shard_calls(ssim, "hs_lstm_cell_backward", request_backward, stream, dict(gates=gates, c_prev=c_prev, grad_y=grad_y),
+                        dict(cell_params=cell_params), dict(clear=clear, grad_h_next=grad_h_next, grad_c_next=grad_c_next, grad_gates=grad_gates,
+                                                            grad_c_prev=grad_c_prev, grad_cell_params=grad_cell_params), kw)
 
 
 # ---- the autograd face ----
+@functools.lru_cache(maxsize=None)
 def _function():
     import torch
 
@@ -287,11 +224,6 @@ def _function():
                                    grad_cell_params=ctx.needs_input_grad[2] or None)
             return res.get("grad_gates"), res.get("grad_c_prev"), res.get("grad_cell_params"), None, None, None
     return _Cell
-
-
-def _module_base():
-    import torch
-    return torch.nn.Module
 
 
 class LSTMCore(_module_base()):

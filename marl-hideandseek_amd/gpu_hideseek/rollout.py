@@ -29,7 +29,7 @@ minibatch_eager() is the same result by torch indexing, for readers, the tests a
 """
 import ctypes as C
 
-from ._request import _disjoint, _run
+from ._request import _disjoint, _run, _tensor
 
 MAX_FIELDS = 16            # HS_GATHER_MAX_FIELDS
 MAX_ROW_BYTES = 1 << 20    # HS_GATHER_MAX_ROW_BYTES
@@ -102,15 +102,7 @@ def request(gpu_id, index, fields, chunks, chunk_steps, rows, bad=None):
     K, L, n = _positive("chunks", chunks), _positive("chunk_steps", chunk_steps), _positive("rows", rows)
     if K * n >= 2 ** 31:
         raise ValueError(f"chunks * rows = {K * n} must stay below 2^31")
-    if not isinstance(index, torch.Tensor):
-        raise ValueError("index must be a torch tensor")
-    what = f"index must be a contiguous int32 tensor of shape (m >= 1,) on {dev}"
-    if index.dim() != 1 or index.shape[0] < 1:
-        raise ValueError(f"{what}: its shape is {tuple(index.shape)}")
-    if index.dtype != torch.int32:
-        raise ValueError(f"{what}: its dtype is {index.dtype}")
-    if not index.is_contiguous():
-        raise ValueError(f"{what}: it is not contiguous")
+    _tensor("index", index, ("m >= 1",), ("int32",), dev)
     m = int(index.shape[0])
     fields = list(fields)
     if not 1 <= len(fields) <= MAX_FIELDS:
@@ -156,13 +148,7 @@ def request(gpu_id, index, fields, chunks, chunk_steps, rows, bad=None):
         inputs.append((f"field {i}: src", src))
         table.append([src, dst, row_bytes, per_chunk, shape])
     if bad is not None and bad is not False and bad is not True:
-        if not isinstance(bad, torch.Tensor):
-            raise ValueError("bad must be None, True or a torch tensor")
-        what = f"bad must be a contiguous int32 tensor of shape (1,) on {dev}"
-        if tuple(bad.shape) != (1,):
-            raise ValueError(f"{what}: its shape is {tuple(bad.shape)}")
-        if bad.dtype != torch.int32:
-            raise ValueError(f"{what}: its dtype is {bad.dtype}")
+        _tensor("bad", bad, (1,), ("int32",), dev, "None, True or a torch tensor")
         outputs.append(("bad", bad))
     _disjoint(outputs, inputs, dev)
     for i in made:

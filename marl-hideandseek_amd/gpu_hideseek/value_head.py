@@ -21,9 +21,8 @@ Both calls divide by the same count of active samples, so their gradients add to
 symlog(), symexp() and twohot() are the eager composition in plain torch, for readers and for tools/twohot_bench.py.
 """
 import ctypes as C
-import math
 
-from ._request import _DTYPES, _disjoint, _name, _per_shard, _rows, _run, _sharded, _vector
+from ._request import _DTYPES, _OUTPUT, _dtype_arg, _finite, _name, _outputs, _rows, _run, _shard_calls, _stride, _vector, _wanted
 
 STATS = 6             # HS_TWOHOT_STATS: sum ce, sum (v - R)^2, sum v, sum R, sum R^2, count
 MAX_BINS = 256        # HS_TWOHOT_MAX_BINS
@@ -100,19 +99,14 @@ def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=D
     if isinstance(bins, bool) or not isinstance(bins, int) or bins < 2 or bins > MAX_BINS:
         raise ValueError(f"bins must be an integer in [2, {MAX_BINS}], got {bins}")
     B = bins
-    coefs = dict(lo=float(lo), hi=float(hi), loss_coef=float(loss_coef), grad_scale=float(grad_scale))
-    for k, v in coefs.items():
-        if not math.isfinite(v) or not math.isfinite(C.c_float(v).value):
-            raise ValueError(f"{k} must be finite, got {v}")
+    coefs = {k: _finite(k, v) for k, v in (("lo", lo), ("hi", hi), ("loss_coef", loss_coef), ("grad_scale", grad_scale))}
     if not C.c_float(coefs["lo"]).value < C.c_float(coefs["hi"]).value:
         raise ValueError(f"lo must be below hi, got lo {lo}, hi {hi}")
     if grad_logits is None:
         grad_logits = returns is not None
     if stats is None:
         stats = returns is not None
-    outputs = {k: t for k, t in (("value", value), ("grad_logits", grad_logits), ("stats", stats)) if t is not None and t is not False}
-    if not outputs:
-        raise ValueError("nothing to do: none of value, grad_logits and stats requested")
+    outputs = _wanted((("value", value), ("grad_logits", grad_logits), ("stats", stats)), "none of value, grad_logits and stats requested")
     if returns is None and ("grad_logits" in outputs or "stats" in outputs):
         raise ValueError("grad_logits and stats need returns")
 
@@ -123,47 +117,23 @@ def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=D
     if mask is not None:
         _vector("mask", mask, n, dev, ("float32",))
     inputs = [(k, t) for k, t in (("logits", logits), ("returns", returns), ("mask", mask)) if t is not None]
-    given = {k: t for k, t in outputs.items() if t is not True}
-    gstride = B
-    for k, dt in (("value_dtype", value_dtype), ("grad_dtype", grad_dtype)):
-        if dt is not None and _name(dt) not in _DTYPES:
-            raise ValueError(f"{k} must be one of {', '.join(_DTYPES)}, got {dt}")
-    if "value" in given:
-        v = given["value"]
-        if not isinstance(v, torch.Tensor):
-            raise ValueError("value must be True, None or a torch tensor")
-        what = f"value must be a contiguous {' / '.join(_DTYPES)} tensor of shape ({n},) or ({n}, 1) on {dev}"
-        if tuple(v.shape) not in ((n,), (n, 1)):
-            raise ValueError(f"{what}: its shape is {tuple(v.shape)}")
-        if _name(v.dtype) not in _DTYPES:
-            raise ValueError(f"{what}: its dtype is {v.dtype}")
-        if not v.is_contiguous():
-            raise ValueError(f"{what}: it is not contiguous")
-    if "grad_logits" in given:
-        gstride = _rows("grad_logits", given["grad_logits"], n, B, dev, n)
-    if "stats" in given:
-        _vector("stats", given["stats"], STATS, dev, ("float64",))
-        if tuple(given["stats"].shape) != (STATS,):
-            raise ValueError(f"stats must have shape ({STATS},): its shape is {tuple(given['stats'].shape)}")
-    _disjoint(list(given.items()), inputs, dev)
-
-    res = dict(given)
-    if outputs.get("value") is True:
-        res["value"] = torch.empty(n, dtype=logits.dtype if value_dtype is None else value_dtype, device=dev)
-    if outputs.get("grad_logits") is True:        # as wide as the logits tensor, so that logits.backward() takes it
-        W = int(logits.shape[1])
-        res["grad_logits"] = (torch.zeros if W > B else torch.empty)((n, W), dtype=logits.dtype if grad_dtype is None else grad_dtype, device=dev)
-        gstride = max(W, B)
-    if outputs.get("stats") is True:
-        res["stats"] = torch.empty(STATS, dtype=torch.float64, device=dev)
-    res = {k: res[k] for k in outputs}
+    _dtype_arg("value_dtype", value_dtype)
+    _dtype_arg("grad_dtype", grad_dtype)
+    W = int(logits.shape[1])
+    # grad_logits is as wide as the logits tensor, so that logits.backward() takes it: zeros where it is wider than B
+    specs = {"value": ((n,), logits.dtype if value_dtype is None else value_dtype, lambda k, t: _vector(k, t, n, dev, _DTYPES, _OUTPUT)),
+             "grad_logits": ((n, W), logits.dtype if grad_dtype is None else grad_dtype, lambda k, t: _rows(k, t, n, B, dev, n), W > B),
+             "stats": ((STATS,), torch.float64)}
+    res, out = _outputs(outputs, specs, inputs, dev)
+    g = outputs.get("grad_logits")
+    gstride = B if g is None else max(W, B) if g is True else _stride(g, B)
 
     def ptr(t):
         return t.data_ptr() if t is not None else None
     req = HsTwohotRequest(ptr(logits), ptr(returns), ptr(mask), n, _DTYPES[_name(logits.dtype)], stride, B, coefs["lo"], coefs["hi"],
                           coefs["loss_coef"], coefs["grad_scale"], _DTYPES[_name(res["value"].dtype)] if "value" in res else 0,
                           _DTYPES[_name(res["grad_logits"].dtype)] if "grad_logits" in res else 0, gstride, 0,
-                          ptr(res.get("value")), ptr(res.get("grad_logits")), ptr(res.get("stats")))
+                          out("value"), out("grad_logits"), out("stats"))
     res["coefficients"] = {k: C.c_float(v).value for k, v in coefs.items()}       # as the kernel saw them (f32)
     return res, req
 
@@ -179,18 +149,10 @@ _PER_SHARD = ("mask", "value", "grad_logits", "stats")
 
 
 def compute_sharded(ssim, logits, returns=None, stream=None, **kw):
-    """ShardedSimulator.value_head: every shard computes its own samples on its own device.  `logits` has one tensor per
-    shard; returns, mask, each output and `stream` are True / None for all shards or a list with one entry per shard;
-    returns the list of the shards' results.  With stream=None every shard's call is enqueued on a side stream of its
-    device, ordered after that device's current stream, before any is waited for.  Every shard divides by its own count of
-    active samples."""
-    import torch
-    n = len(ssim.shards)
-    if isinstance(logits, torch.Tensor) or len(logits) != n:
-        raise ValueError(f"logits: one tensor per shard ({n}) expected")
-    rets = _per_shard(ssim, "returns", returns)
-    per = {k: _per_shard(ssim, k, kw.pop(k)) for k in _PER_SHARD if k in kw}
-    return _sharded(ssim, "hs_twohot_value", lambda i, s: request(s.gpu_id, logits[i], rets[i], **{k: v[i] for k, v in per.items()}, **kw), stream)
+    """ShardedSimulator.value_head: every shard computes its own samples on its own device.  Every shard divides by its
+    own count of active samples."""
+    return _shard_calls(ssim, "hs_twohot_value", request, stream, dict(logits=logits),
+                        per_shard=dict({k: kw.pop(k) for k in _PER_SHARD if k in kw}, returns=returns), kw=kw)
 
 
 def stats_to_metrics(stats):

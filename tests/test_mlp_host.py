@@ -605,3 +605,87 @@ def test_policy_sequence_is_the_step_loop():
     assert bool(cleared.any()) and bool(seq[2][0][0][cleared].any())                       # no clear at the last step: the state is carried on
     _, _, mid = net.sequence(None, x["actor"][:2], x["critic"][:2], state, x["clears"][:2])
     assert not mid[0][0][cleared].any() and not mid[1][1][cleared].any()
+
+
+# ---- what the request builders share (gpu_hideseek._request) ----
+def test_the_tensor_check():
+    """_request._tensor: a free leading dimension, alternative shapes, the 2^31 bound at n * width == 2^31 exactly and one
+    element below it (meta tensors: nothing that large is allocated), and the alignment of a view."""
+    from gpu_hideseek._request import _OUTPUT, _tensor
+    meta = lambda *shape, dtype=torch.bfloat16: torch.empty(*shape, dtype=dtype, device="meta")      # noqa: E731
+    lead, three = ("n >= 1", 256), ("float32", "bfloat16", "float16")
+    odd = torch.zeros(12 * 64 + 8)[1:1 + 12 * 64].view(12, 64)
+    assert odd.is_contiguous() and odd.data_ptr() % 16
+    table = [
+        # (tensor, shapes, dtypes, keywords, None or what the refusal says)
+        (torch.zeros(1, 256), lead, three, {}, None), (torch.zeros(7, 256), lead, three, {}, None),
+        (torch.zeros(0, 256), lead, three, {}, r"shape \(n >= 1, 256\) on cuda:0: its shape is \(0, 256\)"),
+        (torch.zeros(7, 255), lead, three, {}, "its shape is"), (torch.zeros(7, 256, 1), lead, three, {}, "its shape is"),
+        (torch.zeros(7), [(7,), (7, 1)], three, {}, None), (torch.zeros(7, 1), [(7,), (7, 1)], three, {}, None),
+        (torch.zeros(1, 7), [(7,), (7, 1)], three, {}, r"shape \(7,\) or \(7, 1\) on cuda:0: its shape is \(1, 7\)"),
+        (torch.zeros(7, 2), [(7,), (7, 1)], three, {}, "its shape is"),
+        (torch.zeros(7, dtype=torch.float64), (7,), three, {}, r"a contiguous float32 / bfloat16 / float16 tensor of shape \(7,\) on cuda:0: its dtype is torch.float64"),
+        (torch.zeros(14)[::2], (7,), three, {}, "it is not contiguous"), (torch.zeros(256, 7).t(), lead, three, {}, "it is not contiguous"),
+        (meta(2 ** 23, 256), lead, three, dict(bound=256), r"n \* 256 must stay below 2\^31"), (meta(2 ** 23 - 1, 256), lead, three, dict(bound=256), None),
+        (meta(2 ** 31, dtype=torch.int8), ("n >= 1",), ("int8",), dict(bound=1), r"must stay below 2\^31"),
+        (meta(2 ** 31 - 1, dtype=torch.int8), ("n >= 1",), ("int8",), dict(bound=1), None),
+        (meta(2 ** 22, 256), lead, three, dict(bound=512), r"n \* 512 must stay below 2\^31"),          # the bound's width is the caller's, not the tensor's
+        (meta(2 ** 23, 256), lead, three, {}, None),                                                    # no bound asked for
+        (odd, (12, 64), three, dict(align=16), "odd must be 16-byte aligned: its address is 0x"), (odd, (12, 64), three, dict(align=4), None),
+        (odd, (12, 64), three, {}, None), (odd, (12, 65), three, dict(align=16), "its shape is"),       # shape before alignment
+        (3.0, (7,), three, {}, "odd must be a torch tensor"), (None, (7,), three, dict(kind=_OUTPUT), "odd must be True, None or a torch tensor"),
+    ]
+    for i, (t, shapes, dtypes, kw, what) in enumerate(table):
+        if what is None:
+            _tensor("odd", t, shapes, dtypes, "cuda:0", **kw)              # the device is not this check's business
+        else:
+            with pytest.raises(ValueError, match=what):
+                _tensor("odd", t, shapes, dtypes, "cuda:0", **kw)
+            print(f"row {i}: refused")
+
+
+def test_each_autograd_function_is_defined_once():
+    from gpu_hideseek import entity_encoder, mlp, recurrent
+    for module in (entity_encoder, mlp, recurrent):
+        f = module._function()
+        assert f is module._function() and issubclass(f, torch.autograd.Function), module.__name__
+
+
+def test_the_sharded_face():
+    """_request._shard_calls against two fake shards: a list of the wrong length is refused by its name, None and True
+    go to every shard, one params tensor is handed to every shard, and every shard's call lands on its own stream."""
+    from gpu_hideseek._request import _shard_calls
+    calls = []
+
+    class Lib:
+        def __init__(self, shard):
+            self.shard = shard
+
+        def __getattr__(self, name):
+            return lambda h, stream, req: calls.append((self.shard, name, stream.value)) or 0
+
+    class Shard:
+        def __init__(self, i):
+            self.gpu_id, self.num_worlds, self.agents_per_world, self._L, self._h = i, 8 + i, 6, Lib(i), None
+
+    class SSim:
+        shards = [Shard(0), Shard(1)]
+
+    def request(gpu_id, **kw):
+        return dict(kw, gpu_id=gpu_id), C.c_int32(gpu_id)
+    z, params, y1 = [torch.zeros(2, 4), torch.zeros(3, 4)], torch.zeros(12), torch.zeros(3, 4)
+    res = _shard_calls(SSim(), "hs_fake", request, [11, 12], dict(z=z), dict(params=params), dict(y=True, mask=None, out=[None, y1]), dict(eps=0.5))
+    assert calls == [(0, "hs_fake_async", 11), (1, "hs_fake_async", 12)]
+    for i, r in enumerate(res):
+        assert r["gpu_id"] == i and r["z"] is z[i] and r["params"] is params and r["y"] is True and r["mask"] is None and r["eps"] == 0.5
+    assert res[0]["out"] is None and res[1]["out"] is y1
+    res = _shard_calls(SSim(), "hs_fake", request, [11, 12], dict(z=z), dict(params=[params, z[1]]), lead=lambda s: (s.num_worlds * s.agents_per_world,))
+    assert [r["gpu_id"] for r in res] == [48, 54] and res[1]["params"] is z[1]
+    for kw, what in ((dict(required=dict(z=z[:1])), r"z: one tensor per shard \(2\) expected"), (dict(required=dict(z=z[0])), "z: one tensor per shard"),
+                     (dict(required=dict(z=None)), "z: one tensor per shard"), (dict(shared=dict(params=[params] * 3)), r"params: one entry per shard \(2\) expected"),
+                     (dict(per_shard=dict(y=[True])), "y: one entry per shard"), (dict(per_shard=dict(mask=y1)), "mask: one entry per shard"),
+                     (dict(stream=[11]), "stream: one entry per shard")):
+        a = dict(dict(required=dict(z=z), stream=[11, 12]), **kw)
+        with pytest.raises(ValueError, match=what):
+            _shard_calls(SSim(), "hs_fake", request, a.pop("stream"), a.pop("required"), **a)
+    assert len(calls) == 4                                         # nothing was run by a refused call
