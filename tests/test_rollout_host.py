@@ -1,6 +1,9 @@
 """The rollout buffer and the minibatch gather without a GPU (gpu_hideseek.rollout, hs_gather_sequences): the refusals of
 request(), Rollout() and epoch_parts() before the library is involved, minibatch_eager() on a hand-written buffer against
-the id formula s = k n + r, an epoch's parts as a partition of the sequence ids, and the header against the ctypes mirror."""
+the id formula s = k n + r, an epoch's parts as a partition of the sequence ids, and the header against the ctypes mirror.
+The last part is shared with tests/test_gpu_rollout.py: the kernel's constants out of the header's text, launch_gather's
+deal of the work restated, the 40 seeded configurations of the sweep, and the reference of every GPU comparison, which is
+pinned here against a plain loop over rollout.sequence_rows."""
 import ctypes as C
 import os
 import re
@@ -233,3 +236,168 @@ def test_header_states_the_request(hideseek_lib):
     # a bandwidth kernel: no LDS, and the one atomic is the count of the bad ids
     assert "__shared__" not in kernel and len(re.findall(r"atomic\w*\(", kernel)) == 1 and "atomicAdd(a.bad, 1)" in kernel
     assert len(re.findall(r"__global__", kernel)) == len(re.findall(r"template <int kThreads = kGatherThreads>\n__global__", kernel)) == 1
+
+
+# ---- what tests/test_gpu_rollout.py shares: the kernel's constants, its deal of the work, the seeded configurations ----
+class _Constants:
+    pass
+
+
+def kernel_constants():
+    """kGatherInFlight, kGatherMaxGrid, kGatherWaves, kGatherVec and the 64 lanes of a wave, out of the text of
+    csrc/hs_k_gather.h: a test that claims a trip count asserts it with these, so that a changed constant fails it."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "marl-hideandseek_amd", "csrc", "hs_k_gather.h")).read()
+    c = _Constants()
+    threads = int(re.search(r"kGatherThreads = (\d+);", text).group(1))
+    c.lanes = int(re.search(r"kGatherWaves = kGatherThreads / (\d+);", text).group(1))
+    c.waves = threads // c.lanes
+    c.in_flight = int(re.search(r"kGatherInFlight = (\d+);", text).group(1))
+    c.max_grid = int(re.search(r"kGatherMaxGrid = (\d+);", text).group(1))
+    c.vec = int(re.search(r"kGatherVec = (\d+);", text).group(1))
+    # the strides of the three lane loops and of the grid are written with the same numbers
+    for phrase in (f"p += {c.lanes})", f"e += {c.lanes})", f"threadIdx.x % {c.lanes}", f"threadIdx.x / {c.lanes}", "t0 += kGatherInFlight", "gridDim.x * kGatherWaves",
+                   "u += stride"):
+        assert phrase in text, phrase
+    return c
+
+
+class _Geometry:
+    pass
+
+
+def geometry(fields, m, c=None):
+    """launch_gather's deal of a request, restated: `fields` is [(row_bytes, src address, dst address)].  .wide[i] says
+    whether field i moves as kGatherVec-byte pieces, .slots is the wide fields plus one for all the narrow ones, .units
+    = slots * m, .stride the waves of the capped grid and .trips how often the busiest wave goes round `u += stride`."""
+    c = c or kernel_constants()
+    g = _Geometry()
+    g.wide = [rb % c.vec == 0 and src % c.vec == 0 and dst % c.vec == 0 for rb, src, dst in fields]
+    g.n_wide = sum(g.wide)
+    g.slots = g.n_wide + (1 if g.n_wide < len(fields) else 0)
+    g.units = g.slots * m
+    g.stride = min(-(-g.units // c.waves), c.max_grid) * c.waves
+    g.trips = -(-g.units // g.stride)
+    return g
+
+
+SWEEP_ROW_BYTES = (4, 8, 20, 48, 512, 592, 1040)
+SWEEP_SHIFTS = (0, 4, 8, 12)
+SWEEP_DTYPES = {"float32": 4, "bfloat16": 2, "int32": 4}
+
+
+def outside(total):
+    """Ids that are no sequence of a rollout of `total`, on both sides."""
+    return [-1, total, total + 1, -total, -2 ** 31, 2 ** 31 - 1]
+
+
+def gather_configs(count=40, seed=20260):
+    """The seeded sweep: `count` configurations from one numpy generator.  K in [1, 4], L in [1, 9], n in [1, 70], m in
+    [1, 300]; 1 to 16 fields of a row width out of SWEEP_ROW_BYTES, per step or per chunk, src and dst each shifted by
+    0, 4, 8 or 12 bytes from a 16-byte boundary; ids that repeat, 0 to 3 of them out of range."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = []
+    for number in range(count):
+        K, L, n, m = (int(rng.integers(lo, hi + 1)) for lo, hi in ((1, 4), (1, 9), (1, 70), (1, 300)))
+        fields = []
+        for _ in range(int(rng.integers(1, 17))):
+            fields.append(dict(row_bytes=int(rng.choice(SWEEP_ROW_BYTES)), per_chunk=bool(rng.integers(2)), dtype=str(rng.choice(sorted(SWEEP_DTYPES))),
+                               src_shift=int(rng.choice(SWEEP_SHIFTS)), dst_shift=int(rng.choice(SWEEP_SHIFTS))))
+        ids = [int(s) for s in rng.integers(0, K * n, m)]
+        bad = min(int(rng.integers(0, 4)), m)
+        for j, s in zip(rng.choice(m, bad, replace=False), rng.choice(outside(K * n), bad)):
+            ids[int(j)] = int(s)
+        out.append(dict(number=number, K=K, L=L, n=n, m=m, fields=fields, ids=ids, bad=bad))
+    return out
+
+
+def source_shape(field, K, L, n):
+    """The shape of the src of a field of gather_configs()."""
+    elements = field["row_bytes"] // SWEEP_DTYPES[field["dtype"]]
+    return (K if field["per_chunk"] else K * L, n) + (() if elements == 1 else (elements,))
+
+
+def random_bits(shape, dtype, g):
+    """A CPU tensor of every bit pattern of the type, NaNs included."""
+    bits = torch.randint(-2 ** 31, 2 ** 31 - 1, shape, generator=g, dtype=torch.int64).to(torch.int32)
+    return bits if dtype == torch.int32 else bits.view(torch.float32) if dtype == torch.float32 else (bits >> 16).to(torch.int16).view(dtype)
+
+
+def expected(ids, src, chunks, chunk_steps, rows, per_chunk):
+    """The reference of every comparison: rollout.gather_eager (torch indexing) on the device of `src`, the ids out of
+    range replaced by a valid one and their rows zeroed."""
+    from gpu_hideseek import rollout
+    idx = torch.as_tensor(ids).long()
+    ok = (idx >= 0) & (idx < chunks * rows)
+    valid = torch.where(ok, idx, torch.zeros_like(idx)).to(torch.int32).to(src.device)
+    want = rollout.gather_eager(valid, src, chunks, chunk_steps, rows, per_chunk).clone()
+    gone = (~ok).nonzero().flatten().to(src.device)
+    if per_chunk:
+        want[gone] = 0
+    else:
+        want[:, gone] = 0
+    return want
+
+
+def _by_the_formula(ids, src, chunks, chunk_steps, rows, per_chunk):
+    """The same as bytes [L, m, row bytes] (or [m, row bytes]) by a plain loop over rollout.sequence_rows."""
+    import numpy as np
+    from gpu_hideseek import rollout
+    a = src.contiguous().view(-1).view(torch.uint8).numpy().reshape(src.shape[0], rows, -1)
+    dst = np.zeros(((len(ids),) if per_chunk else (chunk_steps, len(ids))) + (a.shape[2],), np.uint8)
+    for j, s in enumerate(ids):
+        if 0 <= s < chunks * rows:
+            (k, r, steps), = rollout.sequence_rows([s], chunks, chunk_steps, rows)
+            if per_chunk:
+                dst[j] = a[k, r]
+            else:
+                for t, step in enumerate(steps):
+                    dst[t, j] = a[step, r]
+    return dst
+
+
+def test_the_constants_and_the_deal_of_the_work():
+    c = kernel_constants()
+    assert (c.lanes, c.waves, c.in_flight, c.max_grid, c.vec) == (64, 4, 4, 2048, 16)
+    g = geometry([(592, 0x1000, 0x2000), (4, 0x1000, 0x2000), (592, 0x1004, 0x2000), (592, 0x1000, 0x2004), (600, 0x1000, 0x2000), (16, 0x10, 0x20)], 5, c)
+    assert g.wide == [True, False, False, False, False, True] and (g.n_wide, g.slots, g.units, g.stride, g.trips) == (2, 3, 15, 16, 1)
+    g = geometry([(16, 0, 0)] * 3, 3400, c)
+    assert (g.slots, g.units, g.stride, g.trips) == (3, 10200, 8192, 2)
+    g = geometry([(4, 0, 0)] * 3, 9, c)
+    assert (g.n_wide, g.slots, g.units, g.stride) == (0, 1, 9, 12)
+
+
+def test_the_sweep_reaches_what_it_is_for():
+    """The 40 configurations are the same on every machine, and between them they hold every row width, shift and count
+    of bad ids, requests of wide fields only and of narrow fields only, 16 fields, and chunks of one, two and three
+    passes of the rows in flight."""
+    c = kernel_constants()
+    configs = gather_configs()
+    assert len(configs) == 40 and configs == gather_configs()
+    fields = [f for cfg in configs for f in cfg["fields"]]
+    assert {f["row_bytes"] for f in fields} == set(SWEEP_ROW_BYTES)
+    assert {(f["src_shift"], f["dst_shift"]) for f in fields} == {(a, b) for a in SWEEP_SHIFTS for b in SWEEP_SHIFTS}
+    assert {f["per_chunk"] for f in fields} == {False, True} and {f["dtype"] for f in fields} == set(SWEEP_DTYPES)
+    assert {cfg["bad"] for cfg in configs} == {0, 1, 2, 3} and {len(cfg["fields"]) for cfg in configs} >= {1, 16}
+    assert all(1 <= cfg["K"] <= 4 and 1 <= cfg["L"] <= 9 and 1 <= cfg["n"] <= 70 and 1 <= cfg["m"] <= 300 for cfg in configs)
+    assert {-(-cfg["L"] // c.in_flight) for cfg in configs} == {1, 2, 3}
+    assert all(sum(not 0 <= s < cfg["K"] * cfg["n"] for s in cfg["ids"]) == cfg["bad"] for cfg in configs)
+    assert any(len(set(cfg["ids"])) < cfg["m"] for cfg in configs), "ids repeat"
+    kinds = {frozenset(geometry([(f["row_bytes"], f["src_shift"], f["dst_shift"]) for f in cfg["fields"]], cfg["m"], c).wide) for cfg in configs}
+    assert kinds == {frozenset([True]), frozenset([False]), frozenset([True, False])}
+
+
+def test_gather_eager_is_the_id_formula_on_the_sweep():
+    """The reference of the GPU tests, pinned without a GPU: for the 40 configurations, expected() (gather_eager with
+    the bad ids' rows zeroed) on CPU tensors is, byte for byte, a plain Python loop over rollout.sequence_rows."""
+    import numpy as np
+    g = torch.Generator().manual_seed(7)
+    for cfg in gather_configs():
+        K, L, n = cfg["K"], cfg["L"], cfg["n"]
+        for i, f in enumerate(cfg["fields"]):
+            src = random_bits(source_shape(f, K, L, n), getattr(torch, f["dtype"]), g)
+            want = expected(cfg["ids"], src, K, L, n, f["per_chunk"])
+            assert want.dtype == src.dtype and want.shape == ((cfg["m"],) if f["per_chunk"] else (L, cfg["m"])) + tuple(src.shape[2:]), (cfg, i)
+            got = want.contiguous().view(-1).view(torch.uint8).numpy()
+            assert np.array_equal(got, _by_the_formula(cfg["ids"], src, K, L, n, f["per_chunk"]).reshape(-1)), (cfg, i)
