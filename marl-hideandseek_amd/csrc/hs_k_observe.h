@@ -62,6 +62,8 @@ struct ObsShared : ObsStaged {
     unsigned short rampPairs[kWaves][kWaveRampPairs];
     int nPairs[kWaves], nRampPairs[kWaves];
     unsigned present;                                      // bit b: body slot b exists
+    int sawHider;                                          // pass 3, deferred worlds: a seeker's visibility ray reached a hider
+    int slot;                                              // the world's slot in the tiled columns, for the thread that moves the point
     // per (agent, OTHER body slot), shared by the agent's 46 rays: origin - body position, |.|^2 - bounding radius^2, and
     // the origin in the body's frame.  An agent's own row is never written or used.
     alignas(16) float rel[kAgents][kNumDSlots][8];
@@ -175,6 +177,29 @@ HSD unsigned stage_world(const SimState &S, int ps, ObsShared<NT> &sh, int tid) 
 HSD unsigned long long ray_key(float t, int id) { return ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)id; }
 constexpr unsigned kKeyMiss = 0xffffffffu;
 
+// The rewards of a DEFERRED world (hs_k_physics.h phase_post, kHdrDeferred in hs_state.h).  k_observe's seeker -> hider
+// visibility rays are the rays of rewardsVisSystem (sim.cpp:763-804): same state, origin, target, FOV test, t_max and tie
+// rule, and i < nAgents names the active agents, whose types make up the team lists.  k_physics wrote the step's rewards
+// and its point of the running scores as for "no hider seen".  A pass-3 thread whose ray sees a hider calls this: it
+// rewrites the rewards of the world's agents with outputRewardsDonesSystem's expressions (sim.cpp:806-841) for a hider
+// seen — every caller stores the same values —, and the first caller of the workgroup moves the point
+// (updateEpisodeResultsSystem, sim.cpp:843-893).  About 2 in 1000 world-steps come here.
+// `step`: the header's, i.e. the step after the reset's count; the physics step gave a point from kNumPrepSteps on.
+template <int NT>
+HSD void settle_deferred_reward(const SimState &S, ObsShared<NT> &sh, int w, int step, int counts, int teams) {
+    const int A = S.A, nAgents = cnt_agents(counts);
+    for (int a = 0; a < nAgents; ++a) {
+        float r = -1.f;
+        if (team_agent_type(teams, a) == AGENT_SEEKER) r *= -1.f;
+        if (fabsf(sh.g.pos[kAgentSlot0 + a][0]) >= 18.f || fabsf(sh.g.pos[kAgentSlot0 + a][1]) >= 18.f) r -= 10.f;
+        S.xReward[w * A + a] = r;
+    }
+    if (atomicExch(&sh.sawHider, 1) == 0 && step >= kNumPrepSteps + 1) {
+        const int ps = sh.slot, hiddenWin = cnt_seekers_first(counts) != 0 ? 1 : 0;
+        S.runningScores(hiddenWin, ps) -= 1; S.runningScores(1 - hiddenWin, ps) += 1;
+    }
+}
+
 // NT = threads per world = obs_threads(A) (192 for the 4-agent benchmark): a lane per ray.
 template <int NT>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWaves, kObsWaves))) k_observe(SimState S) {
@@ -210,11 +235,17 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
     const unsigned present = stage_world<NT>(S, p, sh, tid);
     const int w = hdr.x;
     if (w < 0) return;                                   // (empty slot of the last octet)
-    if (tid == 0) { sh.g.numWalls = hdr.y & 255; sh.g.numPlanes = (hdr.y >> 8) & 255; sh.present = present; }
+    if (tid == 0) { sh.g.numWalls = hdr.y & 255; sh.g.numPlanes = (hdr.y >> 8) & 255; sh.present = present; sh.sawHider = 0; sh.slot = p; }
     const int counts = hdr.z;
     const int teams = hdr.w;
-    const int step = hdr.y >> 16;
+    // the step, and above it the mark "the physics step that came before left the seeker -> hider rays of its rewards to
+    // this launch" (kHdrDeferred, hs_state.h): negative when marked
+    static_assert(kHdrDeferred == 1u << 31, "the mark is the sign of the header's second word");
+    const int stepMark = hdr.y >> 16;
     __syncthreads();
+    // The mark is consumed here, once every wave has read it: a launch with no physics step in front of it (Manager::init,
+    // a checkpoint load, a repeat) finds none and changes nothing.
+    if (tid == 0 && stepMark < 0) S.slotHdr[p].y = hdr.y & 0x7fffffff;
     const WorldGeom &g = sh.g;
     const int nAgents = cnt_agents(counts), nBoxes = cnt_boxes(counts), nRamps = cnt_ramps(counts);
     HS_OTICK(0)
@@ -404,8 +435,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
                 const int j = jj < i ? jj : jj + 1;
                 const float vis = (id == (unsigned)(kAgentSlot0 + j)) ? 1.f : 0.f;
                 // CPU-branch side effect (sim.cpp:700-705): all writers store the same value
-                if (vis != 0.f && team_agent_type(teams, i) == AGENT_SEEKER && team_agent_type(teams, j) == AGENT_HIDER)
+                if (vis != 0.f && team_agent_type(teams, i) == AGENT_SEEKER && team_agent_type(teams, j) == AGENT_HIDER) {
                     S.hiderTeamReward[w] = -1.f;
+                    if (stepMark < 0) settle_deferred_reward(S, sh, w, stepMark & 0x7fff, counts, teams);
+                }
                 S.xVisAgents[row * (kMaxAgents - 1) + jj] = vis;
             }
         }
@@ -427,6 +460,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(kObsWav
             const V3 mang = {sh.ang[slot][0], sh.ang[slot][1], sh.ang[slot][2]};
             const Q toF = qinv(mrot);
             if (e == 0) {
+                const int step = stepMark & 0x7fff;
                 if (step <= kNumPrepSteps) S.xPrep[row] = kNumPrepSteps - step;
                 float *so = S.xSelfObs + row * 13;
                 store_posvel(so, mpos, quat_to_euler(mrot), qrot(toF, mlin), qrot(toF, mang));

@@ -106,9 +106,11 @@ struct alignas(16) OctRes {
     unsigned int wallSeen[kTile];               // bit s: body slot s had a wall / extra-plane manifold (previous step's while the
                                                 // body list is built, then this step's: SimState::wallHist)
     unsigned char numWalls[kTile], numPlanes[kTile], ndd[kTile], nsc[kTile], seen[kTile], hasGrab[kTile];
+    // (seen, phase_post: 1 = a seeker's ray reached a hider, kSeenDeferred = the rays are left to this launch's k_observe)
     unsigned char spill[kTile];                 // this substep: bit 0 body-body, bit 1 body-static candidates beyond the LDS capacity
     int wid[kTile];                             // world id of each slot of the octet (SimState::worldOfSlot), -1 = empty slot
 };
+constexpr int kSeenDeferred = 2;
 static_assert(sizeof(OctRes) <= 20 * 1024, "8 waves of 8 worlds share the CU's 160 KiB of LDS");
 static_assert(offsetof(OctRes, u.sat.items) >= offsetof(OctRes, u.det.wall), "items must not overlap the AABBs");
 static_assert(sizeof(ManDD) / 4 * OctRes::kSlots <= OctRes::kVelOffsetWords, "manifold slots lie below the velocities");
@@ -1299,9 +1301,11 @@ HSD void phase_post(const SimState &S, OctRes &R) {
     const int A_ = S.A;
     const bool wok = w >= 0;
     const bool instant = (S.flags & FLAG_ZERO_AGENT_VELOCITY) == FLAG_ZERO_AGENT_VELOCITY;
-    int teams = 0, step = 0, counts = 0;
+    int teams = 0, step = 0, counts = 0, resetReq = 0;
+    float hider_reward = 0.f;
     if (wok) {
         teams = S.teams[w]; step = S.curEpisodeStep[w]; counts = S.counts[w];
+        hider_reward = S.hiderTeamReward[w]; resetReq = S.xReset[w];
         if (l == 0) R.seen[g] = 0;
         if (instant && l < kMaxAgents && R.meta[kAgentSlot0 + l][g] != 0) {
             const int slot = kAgentSlot0 + l;
@@ -1310,10 +1314,19 @@ HSD void phase_post(const SimState &S, OctRes &R) {
             rst3(R.u.vel.ang, slot, g, V3{0.f, 0.f, 0.f});
         }
     }
-    wave_sync();
     // The seen flag feeds the reward (from episode step 95 on) and the episode result (from 96 on); the reset overwrites
-    // hiderTeamReward every step, so during the preparation phase the rays would change nothing anyone can read.
-    for (int pr = l; wok && step >= kNumPrepSteps - 1 && pr < 9; pr += G) {      // (seeker, hider) pairs
+    // hiderTeamReward every step, so during the preparation phase the rays would change nothing anyone can read.  Nor can
+    // they where the previous step's k_observe has already seen a hider (hiderTeamReward is -1).  And where this launch's
+    // k_observe will cast the very same rays on the very same state — it follows, and the reset below only counts the
+    // step — the world is DEFERRED: everything is written as for "not seen" here, the reset marks the slot header
+    // (write_slot_hdr), and k_observe rewrites the rewards and moves the point should one of its rays see a hider.
+    // The rays below remain for the episode's last step, a requested reset and skipped observations.
+    const bool undecided = wok && step >= kNumPrepSteps - 1 && hider_reward != -1.f;
+    const bool defer = undecided && (S.flags & FLAG_EXT_SKIP_OBSERVATIONS) != FLAG_EXT_SKIP_OBSERVATIONS && resetReq == 0 &&
+                       !((S.flags & FLAG_IGNORE_EPISODE_LENGTH) != FLAG_IGNORE_EPISODE_LENGTH && step == kEpisodeLen - 1);
+    if (defer && l == 0) R.seen[g] = kSeenDeferred;
+    wave_sync();
+    for (int pr = l; undecided && !defer && pr < 9; pr += G) {      // (seeker, hider) pairs
         const int si = pr / 3, hi_ = pr % 3;
         if (si < cnt_seekers(counts) && hi_ < cnt_hiders(counts)) {
             const ResGeom geom = {R, S, g, p};
@@ -1330,8 +1343,7 @@ HSD void phase_post(const SimState &S, OctRes &R) {
     }
     wave_sync();
     if (!wok) return;
-    float hider_reward = S.hiderTeamReward[w];
-    if (R.seen[g]) hider_reward = -1.f;
+    if (R.seen[g] == 1) hider_reward = -1.f;
     if (l < A_ && team_agent_active(teams, l)) {
         const int agent = l, slot = kAgentSlot0 + agent, row = w * A_ + agent;
         if (step == 0) S.xDone[row] = 0;
@@ -1575,10 +1587,11 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
     {
         const int myWorld = L < kTile ? R.wid[L] : -1;
         const int mySeen = L < kTile ? (int)R.wallSeen[L] : 0;
+        const bool myDeferred = L < kTile && R.seen[L] == kSeenDeferred;      // (phase_post: k_observe settles the reward)
         wave_sync();                      // every lane has read what it needs from the resident set
         if (myWorld >= 0) {
             S.wallHist[myWorld] = mySeen;
-            reset_world(S, myWorld, gen[L]);
+            reset_world(S, myWorld, gen[L], myDeferred);
         }
     }
     if (L == 0) {

@@ -438,22 +438,26 @@ HSD void regenerate_world(const SimState &S, int w, int level, const hs_checkpoi
 }
 
 // Keeps SimState::slotHdr in step with the per-world scalars it mirrors.
-HSD void write_slot_hdr(const SimState &S, int w, int ps) {
+// `deferred`: kHdrDeferred (hs_state.h), set by the reset at the tail of a physics step only.
+HSD void write_slot_hdr(const SimState &S, int w, int ps, bool deferred = false) {
     // (the step counter is unbounded under IgnoreEpisodeLength, sim.cpp:196; k_observe only asks "step <= 96" and
-    // "96 - step", so the header carries it saturated at 0x7fff instead of letting it overflow the 16 bits)
+    // "96 - step", so the header carries it saturated at 0x7fff, 15 bits, instead of letting it overflow)
     const int step = S.curEpisodeStep[w];
-    S.slotHdr[ps] = make_int4(w, S.numWalls[w] | (S.numPlanes[w] << 8) | ((step < 0x7fff ? step : 0x7fff) << 16), S.counts[w], S.teams[w]);
+    const unsigned y = (unsigned)S.numWalls[w] | ((unsigned)S.numPlanes[w] << 8) | ((unsigned)(step < 0x7fff ? step : 0x7fff) << 16) |
+                       (deferred ? kHdrDeferred : 0u);
+    S.slotHdr[ps] = make_int4(w, (int)y, S.counts[w], S.teams[w]);
 }
 
-// resetSystem (src/sim.cpp:172-200) for one world
-HSD void reset_world(const SimState &S, int w, GenScratch &scratch) {
+// resetSystem (src/sim.cpp:172-200) for one world.  `deferred`: see write_slot_hdr; phase_post defers only where the
+// world is not regenerated here.
+HSD void reset_world(const SimState &S, int w, GenScratch &scratch, bool deferred = false) {
     int level = S.xReset[w];
     const int step = S.curEpisodeStep[w];
     if ((S.flags & FLAG_IGNORE_EPISODE_LENGTH) != FLAG_IGNORE_EPISODE_LENGTH && step == kEpisodeLen - 1) level = 1;
     if (level == 0) {
         S.curEpisodeStep[w] = step + 1;
         S.hiderTeamReward[w] = 1.f;
-        write_slot_hdr(S, w, S.slotOfWorld[w]);
+        write_slot_hdr(S, w, S.slotOfWorld[w], deferred);
         return;
     }
     regenerate_world<false>(S, w, level, nullptr, scratch);

@@ -42,8 +42,11 @@ struct SimState {
     int *loadAcc;          // [N] candidate pairs seen since the last k_balance
     int *wallHist;         // [N] bit s: body slot s had a wall / extra-plane manifold in the previous step (ordering hint only)
     // What k_observe needs to know about the world in a slot, in slot order so that no load waits for worldOfSlot:
-    // {world id (-1: empty), numWalls | numPlanes << 8 | curEpisodeStep << 16, counts, teams}.  Rewritten by whoever
-    // changes one of them (write_slot_hdr: reset / level generation, checkpoint load, k_balance_commit).
+    // {world id (-1: empty), numWalls | numPlanes << 8 | curEpisodeStep (saturated at 0x7fff) << 16 | deferred << 31,
+    // counts, teams}.  Rewritten by whoever changes one of them (write_slot_hdr: reset / level generation, checkpoint
+    // load, k_balance_commit).  `deferred` (kHdrDeferred below) is a message from a physics step to the k_observe of the
+    // same step: "the seeker -> hider rays of this step's rewards are yours" (hs_k_physics.h phase_post).  The reset at
+    // the tail of k_physics sets it, that k_observe clears it, every other writer of the header leaves it clear.
     int4 *slotHdr;         // [ceil(N / 8) * 8]
     // How long each physics wave took in the previous step (100 MHz ticks) and the sums over all waves of the last
     // three steps: a wave that was slower than the average raises its issue priority (hs_k_physics.h).
@@ -95,6 +98,8 @@ struct SimState {
     long long *phaseTicks; // [physics waves][10] accumulated per-phase ticks, then k_observe's sections from
                            // phase_ticks_obs_base() on (HS_PHASE_TIMING builds only)
 };
+
+constexpr unsigned kHdrDeferred = 1u << 31;       // SimState::slotHdr[p].y: the deferred mark
 
 // --- The split schedule of a blocking step (hideseek.hip launch_step): the octets predicted to be among the slowest ("late",
 // group 1) and the others ("early", group 0) run as two independent k_physics -> k_observe chains.  Each group is a compact
