@@ -13,9 +13,7 @@ all, and sequence id s = k n + r is chunk k of row r.  A minibatch is m ids, an 
 
 The time alignment, stated once.  Slot t holds
     actor[t], critic[t]     the observation o_t, packed (and normalised)
-    clear[t]                the done export of the sim.step() that produced o_t: the `clear` the recurrent core takes with
-                            o_t (hs_lstm_cell: "the done export of the step just taken"), so the state carried OUT of
-                            slot t is zero in the rows whose episode ended with that step
+    clear[t]                the done export of the sim.step() that produced o_t
     action[t], log_prob[t], value[t]     the action drawn from the policy's output on o_t, its log-probability, and the
                             critic's decoded value of o_t (hs_gae_request: "V(observation the action of step t was chosen
                             from)")
@@ -23,7 +21,18 @@ The time alignment, stated once.  Slot t holds
                             done export of step t; nonzero = the episode ended with step t")
     mask[t]                 the self_mask export with o_t
 so clear[t + 1] = done[t], and clear[0] is the done of the last step of the previous rollout.  actor_h / actor_c /
-critic_h / critic_c [k] are the carried LSTM states BEFORE the forward of slot k L: where a chunk's sequence starts.
+critic_h / critic_c [k] are the LSTM states as the forward of slot k L received them: where a chunk's sequence starts.
+
+Where an episode starts.  A step runs, in the reference's order (src/sim.cpp: outputRewardsDonesSystem, resetSystem,
+collectObservationsSystem), the rewards and dones, then the reset, then the observations: the observation exported
+together with done != 0 is already the FIRST one of the next episode (prep_counter = 96).  So the state that goes INTO
+the forward of slot t is zero where clear[t] != 0.  done is written for the agents active in the episode that ends: a row
+that joins with the new episode exports done = 0 with its first observation, and a row that leaves keeps a stale done = 1
+(and a stale reward) while it is out.  Hence the rule, state_zero_into(): the state into slot t is zero where
+clear[t] != 0, where mask[t] == 0 or where mask[t - 1] == 0, so a row that is out carries zero and a row that joins
+starts from zero.  The trainer applies it to the carried state after every sim.step(); the update gives it to the
+recurrent core, whose `clear` zeroes the state carried OUT of a step, as the clear of the step BEFORE: chunk_clears().
+Resets the host requests in mid-episode set no done and are not covered.
 
 minibatch_eager() is the same result by torch indexing, for readers, the tests and tools/gather_bench.py.
 """
@@ -73,6 +82,26 @@ def epoch_parts(perm, num_minibatches):
         raise ValueError(f"the {total} sequences (chunks * rows) do not divide into {num_minibatches} minibatches")
     m = total // num_minibatches
     return [perm[i * m:(i + 1) * m] for i in range(num_minibatches)]
+
+
+# ---- where an episode starts ----
+def state_zero_into(clear, mask, mask_before):
+    """The rows (bool, of the arguments' shape) whose LSTM state is zero as it goes INTO the forward of a slot: `clear` is
+    the done export that came with the slot's observation, `mask` its self_mask export and `mask_before` the self_mask of
+    the slot before (the module docstring states why).  The one statement of the rule: collect() and the update use it."""
+    return (clear != 0) | (mask == 0) | (mask_before == 0)
+
+
+def chunk_clears(clear, mask):
+    """The `clear` [L, m] int32 that the recurrent core takes over a chunk of L slots whose per-slot fields are `clear`
+    and `mask` [L, m]: the core zeroes the state carried OUT of a step, so step t < L - 1 takes state_zero_into() of slot
+    t + 1, and the last step none, because what it carries out is not used.  The state into the chunk's first slot is the
+    stored one, which collect() has put through the rule already."""
+    import torch
+    out = torch.zeros(clear.shape, dtype=torch.int32, device=clear.device)
+    if clear.shape[0] > 1:
+        out[:-1] = state_zero_into(clear[1:], mask[1:], mask[:-1])
+    return out
 
 
 # ---- the fused call ----

@@ -10,23 +10,26 @@ defaults are jax_train.py's, the order of the calls below is the project's.
 Composition only: every kernel is another module's (policy_inputs, policy, action_sampling, value_head, advantages,
 rollout, ppo_loss, optim).  Single device: there is no ShardedSimulator form (optim states the same limit).
 
-collect() fills the rollout (rollout.py states what slot t holds).  Per slot: sim.step() -> pack_policy_inputs into the
-slot (normalised, the raw moments into moments[t]) -> at a chunk's first slot a snapshot of the carried LSTM states -> the
-policy's forward under no_grad with clear[t] -> value_head's decode into value[t] -> sample_actions (seed = cfg.seed, a
-counter that grows by one per slot over the whole run) into the simulator's action tensor, action[t] and log_prob[t]; the
-next step's reward and done exports go into the slot it closes.
+collect() fills the rollout (rollout.py states what slot t holds).  Per slot: sim.step() -> the done and self_mask exports
+into clear[t] and mask[t] -> the carried LSTM states zeroed in the rows whose episode starts with this observation or which
+are out (rollout.state_zero_into: the step resets before it observes, so the observation that comes with done is the next
+episode's first; a row that joins comes with done = 0) -> pack_policy_inputs into the slot (normalised, the raw moments
+into moments[t]) -> at a chunk's first slot a snapshot of the carried states, as the forward receives them -> the policy's
+forward under no_grad, with no clear -> value_head's decode into value[t] -> sample_actions (seed = cfg.seed, a counter
+that grows by one per slot over the whole run) into the simulator's action tensor, action[t] and log_prob[t]; the next
+step's reward and done exports go into the slot it closes.
 The bootstrap.  After slot T - 1 the simulator is stepped once more, which closes slot T - 1 and leaves the observation
-o_T in the exports.  Its value comes from a CRITIC-ONLY forward (the critic's rows packed without moments, the critic
-backbone and head on the carried critic state) whose new state is dropped: the carried state is not advanced, the
-actor is not run.  The next collect() does not step before its slot 0: it packs the same exports with the normaliser as
+o_T in the exports; the carried states are zeroed by the same rule.  Its value comes from a CRITIC-ONLY forward (the
+critic's rows packed without moments, the critic backbone and head on the carried critic state) whose new state is
+dropped: the carried state is not advanced, the actor is not run.  The next collect() does not step before its slot 0: it packs the same exports with the normaliser as
 updated since, and runs the full forward with the policy as updated since, so log_prob[0] and value[0] belong to the
 policy that update() starts from, and every observation adds its moments once.  Then compute_advantages (moments=True)
 over the buffers, then ObsNormaliser.update with the T moments.
 
 update() runs num_epochs epochs: a fresh torch.randperm(K n) on the device from a seeded generator, cut into
-num_minibatches equal parts; per part Rollout.minibatch (one launch), net.sequence from the gathered chunk-start states
-with the gathered clears, ppo_loss (adv_moments, mask) and value_head (returns, mask, loss_coef = value_loss_coef) on the
-L m flattened samples, torch.autograd.backward with their two gradients (both are gradients of means over the same count
+num_minibatches equal parts; per part Rollout.minibatch (one launch), sequence_logits (net.sequence from the gathered
+chunk-start states under rollout.chunk_clears of the gathered clears and masks), ppo_loss (adv_moments, mask) and
+value_head (returns, mask, loss_coef = value_loss_coef) on the L m flattened samples, torch.autograd.backward with their two gradients (both are gradients of means over the same count
 of active samples, so they add into the gradient of policy_loss - entropy_coef * entropy + value_loss_coef * value_loss),
 and opt.step().  Every call is enqueued on torch's current stream (_request.on_current_stream); the statistics add up in
 device tensors and are read once, at the end.
@@ -36,7 +39,8 @@ fused=False runs the policy's eager pieces (set_fused(False)) and takes the mini
 
 state_dict() holds the flat parameters, Adam's m, v and state, the normaliser, the carried LSTM state and clear, the
 update index, the sampling counter and the permutation generator; not the simulator (save_checkpoints is for that).  After
-load_state_dict() the next collect() steps the simulator before its slot 0 and takes clear[0] from that step.
+load_state_dict() the next collect() steps the simulator before its slot 0, takes clear[0] from that step and zeroes the
+loaded states by it (the rows that were out when the state was saved carry zero already).
 """
 import dataclasses
 import time
@@ -171,6 +175,13 @@ class Trainer:
         self.rollout.reward[t].copy_(self._export("reward")[:, 0])
         self.rollout.done[t].copy_(self._export("done")[:, 0])
 
+    def _zero_carried(self, clear, mask, mask_before):
+        """After a sim.step(): zero the carried LSTM state in the rows that rollout.state_zero_into() names, given the done
+        and self_mask exports of that step and the self_mask of the slot before."""
+        zero = rollout.state_zero_into(clear, mask, mask_before).unsqueeze(1)
+        for x in (t for s in self.state for t in s):
+            x.masked_fill_(zero, 0)
+
     def collect(self):
         """Fill the rollout with steps_per_update slots, the bootstrap value, the advantages and returns, and fold the
         slots' moments into the normaliser."""
@@ -185,10 +196,13 @@ class Trainer:
                     if t > 0:
                         self._close_slot(t - 1)
                     buf.clear[t].copy_(self._export("done")[:, 0])
-                else:
+                    buf.mask[t].copy_(self._export("self_mask")[:, 0])
+                    with self._phase("rollout_forward"):
+                        self._zero_carried(buf.clear[t], buf.mask[t], buf.mask[t - 1] if t > 0 else buf.mask[t])
+                else:                                    # the closing step of the last collect() led here, and zeroed
                     buf.clear[0].copy_(self.clear)
+                    buf.mask[0].copy_(self._export("self_mask")[:, 0])
                 self.stepped = False
-                buf.mask[t].copy_(self._export("self_mask")[:, 0])
                 with self._phase("pack"):
                     sim.pack_policy_inputs(actor=buf.actor[t], critic=buf.critic[t], moments=buf.moments[t], normaliser=self.normaliser)
                 if t % L == 0:
@@ -196,7 +210,7 @@ class Trainer:
                     for dst, src in ((buf.actor_h, self.state[0][0]), (buf.actor_c, self.state[0][1]), (buf.critic_h, self.state[1][0]), (buf.critic_c, self.state[1][1])):
                         dst[k].copy_(src)
                 with self._phase("rollout_forward"):
-                    logits, critic_logits, self.state = net(sim, buf.actor[t], buf.critic[t], self.state, buf.clear[t])
+                    logits, critic_logits, self.state = net(sim, buf.actor[t], buf.critic[t], self.state, None)
                     sim.value_head(critic_logits, value=buf.value[t])
                     out = sim.sample_actions(logits, buckets=net.buckets, seed=(cfg.seed, 0), counter=self.counter, log_prob=buf.log_prob[t])
                     buf.action[t].copy_(out["action"].reshape(self.rows, -1))
@@ -206,6 +220,8 @@ class Trainer:
             self.stepped = True
             self._close_slot(T - 1)
             self.clear.copy_(buf.done[T - 1])
+            with self._phase("rollout_forward"):
+                self._zero_carried(self.clear, self._export("self_mask")[:, 0], buf.mask[T - 1])
             with self._phase("gae"):                     # the bootstrap's critic-only forward included
                 self.bootstrap_value()
                 sim.compute_advantages(buf.reward, buf.done, buf.value, self.bootstrap, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, mask=buf.mask,
@@ -235,6 +251,15 @@ class Trainer:
         self._mb = self.rollout.minibatch(index, out=self._mb)
         return self._mb
 
+    def sequence_logits(self, mb):
+        """The policy over the sequences of a minibatch (what minibatch() or Rollout.minibatch_eager() returned), as the
+        update recomputes them: from the gathered chunk-start states, every step's state zeroed where the next slot's
+        episode starts (rollout.chunk_clears), so that no memory and no gradient crosses an episode's end.  Returns
+        (logits [L, m, sum(buckets)], critic_logits [L, m, bins]), part of the autograd graph."""
+        state0 = ((mb["actor_h"], mb["actor_c"]), (mb["critic_h"], mb["critic_c"]))
+        logits, critic_logits, _ = self.net.sequence(self.sim, mb["actor"], mb["critic"], state0, rollout.chunk_clears(mb["clear"], mb["mask"]))
+        return logits, critic_logits
+
     def forward_backward(self, index, epoch=0):
         """One minibatch up to the optimiser's step: the gather, the forward, the two loss kernels and the backward, which
         adds into the flat gradient buffer.  The statistics of the two losses are added to row `epoch` of ppo_stats /
@@ -245,8 +270,7 @@ class Trainer:
             mb = self.minibatch(index)
         with on_current_stream(), self._phase("update_forward_backward"):
             S = mb["clear"].numel()
-            state0 = ((mb["actor_h"], mb["actor_c"]), (mb["critic_h"], mb["critic_c"]))
-            logits, critic_logits, _ = net.sequence(sim, mb["actor"], mb["critic"], state0, mb["clear"])
+            logits, critic_logits = self.sequence_logits(mb)
             logits, critic_logits = logits.reshape(S, -1), critic_logits.reshape(S, -1)
             mask = mb["mask"].reshape(S)
             pol = sim.ppo_loss(logits.detach(), mb["action"].reshape(S, -1), mb["log_prob"].reshape(S), mb["advantage"].reshape(S), buckets=net.buckets,

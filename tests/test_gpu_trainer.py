@@ -119,31 +119,38 @@ def test_replay_on_a_second_simulator(collected):
         s2.close()
 
 
+def _seq_to_slots(x):
+    """[L, K * ROWS, ...] of all sequences in order (id = k ROWS + r) -> [T, ROWS, ...]."""
+    return x.reshape(L, K, ROWS, *x.shape[2:]).transpose(0, 1).reshape(T, ROWS, *x.shape[2:])
+
+
 def test_stored_quantities_belong_to_the_stored_policy(collected):
+    """The reference is the episode loop of test_trainer_host from the stored states of chunk 0: it knows neither done nor
+    clear.  The recomputation is the trainer's own forward of a minibatch of all sequences, from the stored chunk starts."""
     import torch
+    from test_trainer_host import episode_loop, zero_in
     sim, tr, _ = collected
     buf, net = tr.rollout, tr.net
-    ref32 = _policy().set_fused(False)
-    ref64 = _policy().set_fused(False).double()
+    zero = zero_in(buf.mask.cpu(), buf.critic.cpu())
+    assert zero.any(dim=1).tolist() == (buf.clear != 0).any(dim=1).cpu().tolist()             # the done falls on the episode's first slot
     got, want = {}, {}
-    for k in range(K):
-        sl = slice(k * L, (k + 1) * L)
-        state0 = ((buf.actor_h[k], buf.actor_c[k]), (buf.critic_h[k], buf.critic_c[k]))
-        with torch.no_grad():
-            logits, critic_logits, _ = net.sequence(sim, buf.actor[sl], buf.critic[sl], state0, buf.clear[sl])
-            for t in range(L):
-                lp = sim.sample_actions(logits[t].contiguous(), mode="evaluate", action=buf.action[k * L + t].clone(), log_prob=True)["log_prob"]
-                v = sim.value_head(critic_logits[t].contiguous(), value_dtype=torch.float32)["value"]
-                got.setdefault("log_prob", []).append(lp.double().cpu())
-                got.setdefault("value", []).append(v.double().cpu())
-            for name, ref, ft in (("f32", ref32, torch.float32), ("f64", ref64, torch.float64)):
-                st = tuple(tuple(x.cpu().to(ft) for x in s) for s in state0)
-                lg, cl, _ = ref.sequence(None, buf.actor[sl].cpu().to(ft), buf.critic[sl].cpu().to(ft), st, buf.clear[sl].cpu())
-                want.setdefault(name, {}).setdefault("log_prob", []).append(_log_prob(lg, buf.action[sl].cpu(), net.buckets).double())
-                want[name].setdefault("value", []).append(_decode(cl).double())
+    index = torch.arange(K * ROWS, dtype=torch.int32, device="cuda")
+    with torch.no_grad():
+        logits, critic_logits = (_seq_to_slots(x) for x in tr.sequence_logits(buf.minibatch(index)))
+        for t in range(T):
+            lp = sim.sample_actions(logits[t].contiguous(), mode="evaluate", action=buf.action[t].clone(), log_prob=True)["log_prob"]
+            v = sim.value_head(critic_logits[t].contiguous(), value_dtype=torch.float32)["value"]
+            got.setdefault("log_prob", []).append(lp.double().cpu())
+            got.setdefault("value", []).append(v.double().cpu())
+        state0 = ((buf.actor_h[0], buf.actor_c[0]), (buf.critic_h[0], buf.critic_c[0]))
+        for name, ft in (("f32", torch.float32), ("f64", torch.float64)):
+            ref = _policy().set_fused(False).to(ft)
+            st = tuple(tuple(x.cpu().to(ft) for x in s) for s in state0)
+            lg, cl, _ = episode_loop(ref, buf.actor.cpu().to(ft), buf.critic.cpu().to(ft), zero, st)
+            want[name] = {"log_prob": _log_prob(lg, buf.action.cpu(), net.buckets).double(), "value": _decode(cl).double()}
     stored = {"log_prob": buf.log_prob.double().cpu(), "value": buf.value.double().cpu()}
     for q in ("log_prob", "value"):
-        f64, f32, again = torch.cat(want["f64"][q]), torch.cat(want["f32"][q]), torch.stack(got[q])
+        f64, f32, again = want["f64"][q], want["f32"][q], torch.stack(got[q])
         allow = 4.0 * float((f32 - f64).abs().max())
         es, ea = float((stored[q] - f64).abs().max()), float((again - f64).abs().max())
         print(f"trainer: {q}: stored {es:.3e}, recomputed from the chunk starts {ea:.3e} from float64 (allowance {allow:.3e}, "
@@ -177,22 +184,26 @@ def test_gradient_of_one_minibatch_fused_against_eager(collected):
         getattr(eager.rollout, k).copy_(t)
     eager.adv_moments.copy_(tr.adv_moments)
     index = torch.randperm(K * ROWS, generator=torch.Generator().manual_seed(41)).to(torch.int32).cuda()[:K * ROWS // 2]
-    grads = {}
-    for name, x in (("fused", tr), ("eager", eager)):
-        assert not x.opt.flat.grads.any().item()
-        pol, val = x.forward_backward(index)
-        grads[name] = x.opt.flat.grads.clone()
-        x.opt.zero_grad()
-        if name == "fused":
-            up = pol["grad_logits"].clone(), val["grad_logits"].clone()
-    # the allowance: the eager composition on the CPU in float64 and float32 on this minibatch's rows, under the fused
-    # trainer's upstream gradients
+    # the fused trainer's forward_backward gives the two losses' upstream gradients; the eager trainer's forward of the
+    # same minibatch is put under the same ones, so that the two flat gradients differ by the policy's backward alone
+    assert not tr.opt.flat.grads.any().item() and not eager.opt.flat.grads.any().item()
+    pol, val = tr.forward_backward(index)
+    up = pol["grad_logits"].clone(), val["grad_logits"].clone()
+    lg, cl = eager.sequence_logits(eager.minibatch(index))
+    torch.autograd.backward([lg.reshape(up[0].shape), cl.reshape(up[1].shape)], list(up))
+    grads = {"fused": tr.opt.flat.grads.clone(), "eager": eager.opt.flat.grads.clone()}
+    assert grads["eager"].any().item()
+    tr.opt.zero_grad()
+    eager.opt.zero_grad()
+    # the allowance: the trainer's own forward of a minibatch on the CPU in float64 and float32 (with eager pieces it needs
+    # the policy and no simulator), on this minibatch's rows, under the fused trainer's upstream gradients
+    import types
     mb = {k: v.cpu() for k, v in tr.rollout.minibatch_eager(index).items()}
     ref = {}
     for name, ft in (("f32", torch.float32), ("f64", torch.float64)):
         net = _policy().set_fused(False).to(ft)
-        st = ((mb["actor_h"].to(ft), mb["actor_c"].to(ft)), (mb["critic_h"].to(ft), mb["critic_c"].to(ft)))
-        lg, cl, _ = net.sequence(None, mb["actor"].to(ft), mb["critic"].to(ft), st, mb["clear"])
+        rows = {k: v.to(ft) if k in ("actor", "critic", "actor_h", "actor_c", "critic_h", "critic_c") else v for k, v in mb.items()}
+        lg, cl = trainer.Trainer.sequence_logits(types.SimpleNamespace(net=net, sim=None), rows)
         torch.autograd.backward([lg.reshape(up[0].shape), cl.reshape(up[1].shape)], [up[0].cpu().to(ft), up[1].cpu().to(ft)])
         ref[name] = {k: p.grad.double() for k, p in net.named_parameters()}
     layout = tr.opt.layout()
