@@ -896,6 +896,66 @@ typedef struct hs_gather_request {
 int32_t hs_gather_sequences(hs_sim *sim, const hs_gather_request *req);
 int32_t hs_gather_sequences_async(hs_sim *sim, void *hip_stream, const hs_gather_request *req);
 
+/* Episode statistics: how the game is going.  One call after a step advances a tracker per agent row (row = world * A +
+ * slot) and per world, and folds every episode that ended with that step into a table of f64 sums (csrc/hs_k_episode.h:
+ * one kernel over the rows, one lane per row, then the fixed-order add of the workgroups' partial sums onto the table).
+ * Inputs, each [rows] unless said otherwise, device memory of the handle's GPU; a null pointer means the handle's own:
+ *   reward f32, done i32, self_type i32 (0 = seeker, nonzero = hider), self_mask f32: the exports after the step;
+ *   episode_result [worlds][2] f32: the export; hider_team [worlds] i32: the team index (0 or 1) of the hiders in the
+ *   world's CURRENT episode, null = the handle's own team order (1 where the seekers are team 0).
+ * State, caller-owned device memory, read and written in place: per row ret, disc, gpow f32 and len, type, phase i32
+ * (phase: HS_EPISODE_OUT = 0, HS_EPISODE_TRACKED = 1, HS_EPISODE_WAITING = 2 = waiting for its next episode start);
+ * per world world_hider_team and world_phase i32 (0 = no team latched yet, 1 = latched).
+ * The arithmetic is the contract: IEEE f32, unfused, in exactly this order.  Per row, with R = reward, m = self_mask:
+ *   was = phase == 1
+ *   if was:    ret = ret + R;  disc = disc + gpow * R;  gpow = gpow * gamma;  len = len + 1
+ *   ended = was && done != 0
+ *   if ended:  the side of `type` (the latched one, not this step's self_type: 0 = seekers, nonzero = hiders) gains
+ *              1 episode, ret, ret^2, disc, len: each the f64 of the f32 / i32 value, the square taken in f64
+ *   restart = done != 0 || (phase != 2 && (!was || m == 0))          (phase as it was before this call)
+ *   if restart: ret = disc = +0.0, gpow = 1, len = 0, type = self_type, phase = m != 0 ? 1 : 0
+ * A row that was not tracked uses no reward (a select, not a product with zero): a row that is out or waiting adds
+ * nothing, whatever stale done or NaN reward it carries.  The observation exported together with done != 0 is the first of
+ * the NEXT episode (and so are self_type and self_mask, which HS_FLAG_RANDOM_FLIP_TEAMS and changing team sizes alter):
+ * hence the latched type.  `restart` is the rule by which the learner zeroes its recurrent state: a row that joins exports
+ * done = 0 and starts at zero, a row that leaves keeps a stale done and goes out; a waiting row starts on a done only.
+ * Per world, after its rows: the world ended if any of its rows ended.  Then, with h = world_hider_team (the latched one):
+ *   world_episodes gains 1;  if world_phase == 1 and h is 0 or 1, x = episode_result[w][h]:
+ *   x == 1.0 hider_wins gains 1, x == 0.0 seeker_wins gains 1, x == 0.5 draws gains 1 (any other x: none of them).
+ * Then, if the world ended or any of its rows restarted: world_hider_team = hider_team[w], world_phase = 1.
+ * table [HS_EPISODE_STATS] f64, for the seekers [0..4] and then the hiders [5..9]: episodes, sum ret, sum ret^2, sum disc,
+ * sum len; then [10] hider_wins, [11] seeker_wins, [12] draws, [13] world_episodes.  A call ADDS this step's sums to the
+ * table: zeroing it is the caller's business.  This step's sums are added without atomics, in an order that depends on the
+ * handle's (worlds, A) alone, starting from +0.0, and then added to the table once: the same inputs give the same bits on
+ * every call.  The partial sums go through a workspace of the handle, so two calls on one handle must not overlap.
+ * A reset the host requests in mid-episode sets no done and is not covered: the episode it cuts short runs on into the
+ * next one.  Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says
+ * which): a null request; a null state pointer or table; gamma not finite or outside [0, 1]; a pointer not aligned to
+ * its element size (table: 8 bytes); a state array or the table overlapping an input, another state array or the table; a
+ * call before hs_init or inside an open step.  Under HS_FLAG_EXT_SKIP_OBSERVATIONS a null self_type or self_mask is
+ * refused with HS_ERR_UNSUPPORTED (the observation stage refreshes them after a reset, and it does not run); with both
+ * given the call works there.  Writes no simulator state.  hs_episode_stats is ordered after the device's legacy default
+ * stream and blocking; hs_episode_stats_async enqueues on the caller's hipStream_t without synchronising (the caller
+ * orders it after the step that wrote the exports). */
+enum { HS_EPISODE_STATS = 14, HS_EPISODE_SIDE_STATS = 5 };
+enum { HS_EPISODE_OUT = 0, HS_EPISODE_TRACKED = 1, HS_EPISODE_WAITING = 2 };
+typedef struct hs_episode_request {
+    const float   *reward;        /* [rows] f32 or null = the reward export */
+    const int32_t *done;          /* [rows] i32 or null = the done export */
+    const int32_t *self_type;     /* [rows] i32 or null = the self_type export */
+    const float   *self_mask;     /* [rows] f32 or null = the self_mask export */
+    const float   *episode_result;        /* [worlds][2] f32 or null = the episode_result export */
+    const int32_t *hider_team;    /* [worlds] i32 or null = the handle's team order */
+    float gamma;                  /* finite, in [0, 1] */
+    int32_t reserved;
+    float   *ret, *disc, *gpow;   /* [rows] f32 each, read and written */
+    int32_t *len, *type, *phase;  /* [rows] i32 each, read and written */
+    int32_t *world_hider_team, *world_phase;      /* [worlds] i32 each, read and written */
+    double  *table;               /* [HS_EPISODE_STATS] f64, added to */
+} hs_episode_request;             /* 128 bytes */
+int32_t hs_episode_stats(hs_sim *sim, const hs_episode_request *req);
+int32_t hs_episode_stats_async(hs_sim *sim, void *hip_stream, const hs_episode_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

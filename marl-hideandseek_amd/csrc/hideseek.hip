@@ -33,6 +33,7 @@
 #include "hs_k_lstm.h"
 #include "hs_k_dense.h"
 #include "hs_k_gather.h"                  // ahead of hs_k_adam.h: its one kernel is a template, emitted where launch_gather (the last stage) names it
+#include "hs_k_episode.h"                 // likewise: its two kernels are templates, emitted where launch_episode (after launch_gather) names them
 #include "hs_k_adam.h"
 
 namespace {
@@ -101,6 +102,7 @@ struct hs_sim {
     float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
     float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
     double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]
+    double *episode_partials = nullptr;    // hs_episode_stats: the sums of each workgroup, [episode_grid][HS_EPISODE_STATS]
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -1100,6 +1102,61 @@ int launch_gather(hs_sim *, hipStream_t strm, const hs_gather_request *r) {
 }
 }  // namespace
 
+// ---- episode statistics (hs_k_episode.h) ----
+namespace {
+static_assert(HS_EPISODE_STATS == hs::kEpiStats && HS_EPISODE_SIDE_STATS == hs::kEpiSide && HS_EPISODE_OUT == hs::kEpiOut &&
+              HS_EPISODE_TRACKED == hs::kEpiTracked && HS_EPISODE_WAITING == hs::kEpiWaiting && 2 * hs::kEpiSide == hs::kEpiHiderWins &&
+              hs::kEpiWorldEpisodes == hs::kEpiStats - 1, "hs_episode_request and k_episode agree");
+static_assert(sizeof(hs_episode_request) == 128 && offsetof(hs_episode_request, gamma) == 48 && offsetof(hs_episode_request, ret) == 56 &&
+              offsetof(hs_episode_request, len) == 80 && offsetof(hs_episode_request, world_hider_team) == 104 && offsetof(hs_episode_request, table) == 120,
+              "hs_episode_request layout (gpu_hideseek/episodes.py mirrors it)");
+static_assert(kExports[HS_EXPORT_SELF_TYPE].dtype == HS_DTYPE_I32 && kExports[HS_EXPORT_SELF_TYPE].per_agent && kExports[HS_EXPORT_SELF_TYPE].tail[0] == 1 &&
+              kExports[HS_EXPORT_REWARD].tail[0] == 1 && kExports[HS_EXPORT_DONE].tail[0] == 1 && kExports[HS_EXPORT_SELF_MASK].tail[0] == 1 &&
+              kExports[HS_EXPORT_EPISODE_RESULT].dtype == HS_DTYPE_F32 && !kExports[HS_EXPORT_EPISODE_RESULT].per_agent &&
+              kExports[HS_EXPORT_EPISODE_RESULT].tail[0] == 2 && hs::AGENT_SEEKER == 0 && hs::AGENT_HIDER == 1,
+              "k_episode reads the reward, done, self_type, self_mask and episode_result exports");
+static_assert(hs::kEpiThreads >= hs::kMaxAgents && hs::kEpiStats * hs::kEpiSumSegs <= 1024, "a workgroup of k_episode holds a world, k_episode_fold is one workgroup");
+
+// The request with every null input replaced by the handle's own (the state and the table are left as given).
+hs::EpisodeArgs episode_args(const hs_sim *s, const hs_episode_request *r) {
+    const hs::SimState &S = s->S;
+    return {r->reward ? r->reward : S.xReward, r->done ? r->done : S.xDone, r->self_type ? r->self_type : S.xSelfType,
+            r->self_mask ? r->self_mask : S.xSelfMask, r->episode_result ? r->episode_result : S.xEpisodeResult, r->hider_team, S.counts,
+            r->ret, r->disc, r->gpow, r->len, r->type, r->phase, r->world_hider_team, r->world_phase, s->episode_partials, S.N, s->A, r->gamma};
+}
+
+int check_episode(hs_sim *s, const hs_episode_request *r) {
+    const Check c{"hs_episode_stats"};
+    if (!r) return c.bad("null request");
+    if (!r->ret || !r->disc || !r->gpow || !r->len || !r->type || !r->phase || !r->world_hider_team || !r->world_phase) return c.bad("null state pointer");
+    if (!r->table) return c.bad("null table");
+    if (!(r->gamma >= 0.f && r->gamma <= 1.f)) return c.bad("gamma must be finite and in [0, 1]");
+    if (!aligned(4, {r->reward, r->done, r->self_type, r->self_mask, r->episode_result, r->hider_team, r->ret, r->disc, r->gpow, r->len, r->type, r->phase,
+                     r->world_hider_team, r->world_phase}))
+        return c.bad("every input and state pointer must be 4-byte aligned");
+    if (!aligned(8, {r->table})) return c.bad("table must be 8-byte aligned");
+    if ((s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) && (!r->self_type || !r->self_mask))
+        return c.bad("a null self_type or self_mask needs the exports that HS_FLAG_EXT_SKIP_OBSERVATIONS leaves unwritten after a reset", HS_ERR_UNSUPPORTED);
+    const hs::EpisodeArgs a = episode_args(s, r);
+    const uintptr_t worlds = (uintptr_t)s->S.N, rows = worlds * (uintptr_t)s->A;
+    HS_TRY(c.disjoint({range("reward", a.reward, rows * 4), range("done", a.done, rows * 4), range("self_type", a.selfType, rows * 4),
+                       range("self_mask", a.selfMask, rows * 4), range("episode_result", a.episodeResult, worlds * 8), range("hider_team", a.hiderTeam, worlds * 4)},
+                      {range("ret", r->ret, rows * 4), range("disc", r->disc, rows * 4), range("gpow", r->gpow, rows * 4), range("len", r->len, rows * 4),
+                       range("type", r->type, rows * 4), range("phase", r->phase, rows * 4), range("world_hider_team", r->world_hider_team, worlds * 4),
+                       range("world_phase", r->world_phase, worlds * 4), range("table", r->table, HS_EPISODE_STATS * sizeof(double))}));
+    return c.handle_ready(s);
+}
+// One k_episode over every agent row (the request has passed check_episode), then the fixed-order add onto the table.
+int launch_episode(hs_sim *s, hipStream_t strm, const hs_episode_request *r) {
+    const hs::EpisodeArgs a = episode_args(s, r);
+    const int grid = hs::episode_grid(a.worlds, a.A);
+    hipLaunchKernelGGL(hs::k_episode<>, dim3(grid), dim3(hs::kEpiThreads), 0, strm, a);
+    hipLaunchKernelGGL(hs::k_episode_fold<>, dim3(1), dim3(hs::kEpiStats * hs::kEpiSumSegs), 0, strm, (const double *)s->episode_partials, grid, r->table);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1246,6 +1303,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->lstm_partials, (size_t)hs::kRowsMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
     HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
     HS_ALLOC(s->adam_workspace, hs::kAdamWorkspace);
+    HS_ALLOC(s->episode_partials, (size_t)hs::episode_grid((int)N, A) * hs::kEpiStats);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1580,6 +1638,8 @@ int32_t hs_adam_step(hs_sim *s, const hs_adam_request *req) { return call_blocki
 int32_t hs_adam_step_async(hs_sim *s, void *hip_stream, const hs_adam_request *req) { return call_async(s, hip_stream, check_adam, launch_adam, req); }
 int32_t hs_gather_sequences(hs_sim *s, const hs_gather_request *req) { return call_blocking(s, check_gather, launch_gather, req); }
 int32_t hs_gather_sequences_async(hs_sim *s, void *hip_stream, const hs_gather_request *req) { return call_async(s, hip_stream, check_gather, launch_gather, req); }
+int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call_blocking(s, check_episode, launch_episode, req); }
+int32_t hs_episode_stats_async(hs_sim *s, void *hip_stream, const hs_episode_request *req) { return call_async(s, hip_stream, check_episode, launch_episode, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

@@ -330,6 +330,18 @@ class HideAndSeekSimulator:
         from . import rollout as _rollout
         return _rollout.compute(self, index, fields, chunks, chunk_steps, rows, bad=bad, stream=stream)
 
+    def episode_stats(self, state, table, *, gamma=0.998, reward=None, done=None, self_type=None, self_mask=None, episode_result=None,
+                      hider_team=None, stream=None):
+        """After a step: advance the per-row and per-world episode trackers `state` (episodes.new_state) and add every
+        episode that ended with the step to `table` ([14] float64), in one kernel (gpu_hideseek.episodes;
+        hs_episode_stats, whose header comment states the arithmetic and the table).  An input left None is the
+        simulator's own export (hider_team: its team order); an explicit one is a contiguous tensor on the device.
+        stream=None blocks; a torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns
+        {"table": table, "state": state}.  episodes.EpisodeStats is the tracker built on this call."""
+        from . import episodes as _episodes
+        return _episodes.compute(self, state, table, stream, gamma=gamma, reward=reward, done=done, self_type=self_type, self_mask=self_mask,
+                                 episode_result=episode_result, hider_team=hider_team)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

@@ -24,7 +24,9 @@ critic's rows packed without moments, the critic backbone and head on the carrie
 dropped: the carried state is not advanced, the actor is not run.  The next collect() does not step before its slot 0: it packs the same exports with the normaliser as
 updated since, and runs the full forward with the policy as updated since, so log_prob[0] and value[0] belong to the
 policy that update() starts from, and every observation adds its moments once.  Then compute_advantages (moments=True)
-over the buffers, then ObsNormaliser.update with the T moments.
+over the buffers, then ObsNormaliser.update with the T moments.  With trainer.episodes set to an episodes.EpisodeStats
+(None by default), collect() calls its step() after every sim.step() it makes, the closing one included, so every step
+reaches the tracker once across rollouts; metrics() and state_dict() do not know about it.
 
 update() runs num_epochs epochs: a fresh torch.randperm(K n) on the device from a seeded generator, cut into
 num_minibatches equal parts; per part Rollout.minibatch (one launch), sequence_logits (net.sequence from the gathered
@@ -156,6 +158,7 @@ class Trainer:
         self.stepped = False              # the simulator has been stepped past the last slot: its exports are the next o_0
         self._mb = None
         self.phases = None                # a PhaseTimer, or None: no events
+        self.episodes = None              # an episodes.EpisodeStats, or None: collect() calls its step() after every sim.step()
         E = cfg.num_epochs
         self.ppo_stats = torch.zeros(E, PPO_STATS, dtype=torch.float64, device=dev)
         self.value_stats = torch.zeros(E, VALUE_STATS, dtype=torch.float64, device=dev)
@@ -193,6 +196,8 @@ class Trainer:
                 if t > 0 or not self.stepped:
                     with self._phase("sim"):
                         sim.step()
+                    if self.episodes is not None:
+                        self.episodes.step()
                     if t > 0:
                         self._close_slot(t - 1)
                     buf.clear[t].copy_(self._export("done")[:, 0])
@@ -217,6 +222,8 @@ class Trainer:
                 self.counter += 1
             with self._phase("sim"):
                 sim.step()
+            if self.episodes is not None:
+                self.episodes.step()
             self.stepped = True
             self._close_slot(T - 1)
             self.clear.copy_(buf.done[T - 1])

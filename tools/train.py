@@ -13,7 +13,12 @@ the trainer's state_dict goes to <ckpt-dir>/<run-name>/<update> at the end and e
 with the bootstrap, gather, update forward + backward, Adam), waits for the device once per update, and prints each
 phase's time per update and share, over the updates after the first (which warms up); what the phases leave out (copies
 of exports into slots, the permutation, Python between the calls) is the row "other".
-Not here: PBT, Elo evaluation, tensorboard / wandb, several GPUs.
+--episode-stats tracks the finished episodes on the device (gpu_hideseek.episodes: one launch after every simulator step)
+and prints, as a second JSON line at each `Update:` print, what has finished since the last one: per side the episodes,
+the mean and standard deviation of the return, the mean discounted return and length, and the hiders' and seekers' win
+rates.  On a fresh simulator the episodes are tracked from their start; after --restore the tracker waits for every row's
+next episode, because the simulator's state is not restored.  tools/infer.py runs a saved policy without learning.
+Not here: PBT, Elo ratings (the reference's eval_competitive), tensorboard / wandb, several GPUs.
 """
 import argparse
 import json
@@ -25,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import trainer  # noqa: E402
+from gpu_hideseek import episodes, trainer  # noqa: E402
 
 PRINT_EVERY = 10
 
@@ -54,6 +59,7 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--eager", action="store_true", help="the policy's eager pieces and the gather by torch indexing (Trainer(fused=False))")
     ap.add_argument("--phases", action="store_true")
+    ap.add_argument("--episode-stats", action="store_true", help="track finished episodes on the device and print them with the metrics")
     ap.add_argument("--out", type=str, help="with --phases: write the table here too")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
@@ -102,6 +108,8 @@ def main(argv=None):
         tr.load_state_dict(torch.load(os.path.join(run_dir, str(args.restore)), map_location=tr.device, weights_only=False))
     if args.phases:
         tr.phases = trainer.PhaseTimer()
+    if args.episode_stats:
+        tr.episodes = episodes.EpisodeStats(sim, gamma=args.gamma).arm(from_start=args.restore is None)
 
     def save():
         if run_dir is not None:
@@ -117,6 +125,8 @@ def main(argv=None):
             if last_time != 0:
                 print("  FPS:", args.num_worlds * args.steps_per_update * (tr.update_index - last_update) / (now - last_time))
                 print("  " + json.dumps({k: v for k, v in metrics.items() if not isinstance(v, list)}))
+                if tr.episodes is not None:
+                    print("  " + json.dumps(tr.episodes.read()))
             last_time, last_update = now, tr.update_index
         t0 = time.perf_counter()
         metrics = tr.update_iter()
@@ -132,6 +142,8 @@ def main(argv=None):
             save()
     print(f"Update: {tr.update_index}")
     print("  " + json.dumps({k: v for k, v in metrics.items() if not isinstance(v, list)}))
+    if tr.episodes is not None:
+        print("  " + json.dumps(tr.episodes.read()))
     save()
     if args.phases and timed:
         fps = args.num_worlds * args.steps_per_update * timed / (wall_ms * 1e-3)
