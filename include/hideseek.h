@@ -956,6 +956,84 @@ typedef struct hs_episode_request {
 int32_t hs_episode_stats(hs_sim *sim, const hs_episode_request *req);
 int32_t hs_episode_stats_async(hs_sim *sim, void *hip_stream, const hs_episode_request *req);
 
+/* The league: P policies play each other on one simulator, and are rated.  One call after a step routes every agent row
+ * (row = world * A + slot) to a policy, ranks it among that policy's rows, books the games that ended with the step in a
+ * P x P table and moves the Elo ratings (csrc/hs_k_league.h: one kernel over the rows, one lane per row, then a
+ * one-workgroup fold).  madrona_learn's matchmaking is not part of the reference's tree: this contract is the project's.
+ * A league is P = num_policies, 1 <= P <= HS_LEAGUE_MAX_POLICIES.  The teams are equal and fixed: A = 2 k agent rows per
+ * world, k = team_size hiders and k seekers (the reference asserts num_hiders == num_seekers for the same purpose), and
+ * the handle's number of worlds is a multiple of P^2.  R = worlds * A.
+ * Schedule: world w always plays pair q = w mod P^2: policy i = q / P the hiders, policy j = q % P the seekers.  Every
+ * ordered pair, i == j included, has worlds / P^2 worlds, and every policy owns exactly R / P rows at every step,
+ * whatever HS_FLAG_RANDOM_FLIP_TEAMS does to the order of a world's rows: the P forwards have fixed shapes and nothing is
+ * read back from the device to size them.  (A drawn or rotating matchup is balanced only while all worlds' episodes stay
+ * in step.)
+ * Inputs, device memory of the handle's GPU; a null pointer means the handle's own:
+ *   done i32, self_type i32 (0 = seeker, nonzero = hider), self_mask f32, each [R]: the exports after the step;
+ *   episode_result [worlds][2] f32: the export; hider_team [worlds] i32: the team index (0 or 1) of the hiders in the
+ *   world's CURRENT episode, null = the handle's own team order, as hs_episode_stats takes it.
+ * Sides: a row is a hider iff its self_type is nonzero: the export after the step, which belongs to the NEXT episode when
+ * it comes with done (hs_episode_stats above).  A world is malformed if its rows do not split into k hiders and k seekers
+ * or if one of its self_mask values is 0: it takes its rows 0 .. k-1 as hiders and k .. 2k-1 as seekers and adds 1 to
+ * bad ([1] i32 or null, written by every call: the malformed worlds of this call).  So everything below is a permutation
+ * in every case.
+ * Routing outputs, each [R] i32:
+ *   policy_assignments[row] = the policy of the row's side; null = the handle's policy_assignments export, which feeds
+ *     the simulator as the reference's is fed;
+ *   slot[row] = the row's rank in the stable sort of all rows by (policy, row); row_of_slot[slot] = row, its inverse;
+ *   clear_slot[slot] = done[row] of the row now at that slot.  slot, row_of_slot and clear_slot may each be null.
+ * Slots [p R / P, (p + 1) R / P) are policy p's block.  The rank needs no scan and no sort: with g = w / P^2, policy p's
+ * block gets 2 P k slots per group g, starting at p R / P + g 2 P k; the world's offset in them is k times the number of
+ * sides p holds in the worlds of the group before q; the rank inside the world is the number of earlier rows of the world
+ * with the same policy.  What a caller that keeps state per slot relies on: the SET of slots a world owns does not change
+ * when its teams flip (a policy's rows of a world are one run of k, or with i == j of 2 k, slots), and a row changes slot
+ * only at an episode start, where recurrent state is zero anyway.
+ * Per-world state, caller-owned, read and written in place: world_hider_team i32 and world_phase i32 (0 = nothing
+ * latched, 1 = latched), [worlds] each.  With fixed teams a world's rows carry one done: the world ended with this step
+ * iff the done of its first row is nonzero.  In this order:
+ *   if the world ended and world_phase == 1: h = world_hider_team (the latched one); x = episode_result[w][h];
+ *     outcome o = 0 if x == 1.0 (the hiders win), 1 if x == 0.0 (the seekers win), 2 if x == 0.5 (a draw), 3 for any
+ *     other x, NaN included, and (without a read) for h outside {0, 1}: played, no outcome.  counts[i][j][o] gains 1.
+ *   if the world ended or world_phase == 0: world_hider_team = hider_team[w], world_phase = 1.
+ * counts [P][P][HS_LEAGUE_OUTCOMES] i64 is ADDED to (integers: the order of addition cannot show).
+ * Elo: elo [P] f64, read and written.  Ratings are batched by step: with D the counts this call added, and elo as it
+ * stood BEFORE the call, every ordered pair i != j has
+ *   n = D[i][j][0] + D[i][j][1] + D[i][j][2];   S = D[i][j][0] + 0.5 D[i][j][2]
+ *   E = 1 / (1 + 10^((elo[j] - elo[i]) / 400));   d = k_factor (S - n E), and d = +0.0 where n == 0 (E is not formed)
+ * and then, in ascending (i, j), elo[i] = elo[i] + d and elo[j] = elo[j] - d.  All f64, unfused.  The games that end with
+ * one step are all rated against the ratings before it, so their order within the step cannot matter; pairs with i == j
+ * and games with o == 3 move nothing; a call in which every d is zero writes no rating.  The same inputs give the same
+ * bits on every call.  The step's counts go through a table of the handle, so two calls on one handle must not overlap.
+ * Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a
+ * null request; null world_hider_team, world_phase, counts or elo; num_policies outside [1, HS_LEAGUE_MAX_POLICIES];
+ * team_size < 1 or the handle's A != 2 team_size; worlds not a multiple of P^2; k_factor not finite or not above 0; a
+ * pointer not aligned to its element size; an output overlapping an input or another output (the handle's exports
+ * included where a null pointer names them); a call before hs_init or inside an open step.  Under
+ * HS_FLAG_EXT_SKIP_OBSERVATIONS a null self_type or self_mask is refused with HS_ERR_UNSUPPORTED; with both given the
+ * call works there.  Writes no simulator state other than the policy_assignments export when that pointer is null.
+ * hs_league_step is ordered after the device's legacy default stream and blocking; hs_league_step_async enqueues on the
+ * caller's hipStream_t without synchronising (the caller orders it after the step that wrote the exports). */
+enum { HS_LEAGUE_MAX_POLICIES = 16, HS_LEAGUE_OUTCOMES = 4 };
+enum { HS_LEAGUE_HIDERS_WIN = 0, HS_LEAGUE_SEEKERS_WIN = 1, HS_LEAGUE_DRAW = 2, HS_LEAGUE_NO_OUTCOME = 3 };
+typedef struct hs_league_request {
+    const int32_t *done;          /* [R] i32 or null = the done export */
+    const int32_t *self_type;     /* [R] i32 or null = the self_type export */
+    const float   *self_mask;     /* [R] f32 or null = the self_mask export */
+    const float   *episode_result;        /* [worlds][2] f32 or null = the episode_result export */
+    const int32_t *hider_team;    /* [worlds] i32 or null = the handle's team order */
+    int32_t num_policies;         /* P in [1, HS_LEAGUE_MAX_POLICIES]; worlds % P^2 == 0 */
+    int32_t team_size;            /* k >= 1; the handle's A == 2 k */
+    double k_factor;              /* finite, > 0 */
+    int32_t *policy_assignments;  /* [R] i32 or null = the policy_assignments export */
+    int32_t *slot, *row_of_slot, *clear_slot;     /* [R] i32 each, or null */
+    int32_t *world_hider_team, *world_phase;      /* [worlds] i32 each, read and written */
+    int32_t *bad;                 /* [1] i32 or null: the malformed worlds of this call */
+    int64_t *counts;              /* [P][P][HS_LEAGUE_OUTCOMES] i64, added to */
+    double  *elo;                 /* [P] f64, read and written */
+} hs_league_request;              /* 128 bytes */
+int32_t hs_league_step(hs_sim *sim, const hs_league_request *req);
+int32_t hs_league_step_async(hs_sim *sim, void *hip_stream, const hs_league_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

@@ -34,6 +34,7 @@
 #include "hs_k_dense.h"
 #include "hs_k_gather.h"                  // ahead of hs_k_adam.h: its one kernel is a template, emitted where launch_gather (the last stage) names it
 #include "hs_k_episode.h"                 // likewise: its two kernels are templates, emitted where launch_episode (after launch_gather) names them
+#include "hs_k_league.h"                  // likewise: emitted where launch_league (after launch_episode) names them
 #include "hs_k_adam.h"
 
 namespace {
@@ -103,6 +104,7 @@ struct hs_sim {
     float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
     double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]
     double *episode_partials = nullptr;    // hs_episode_stats: the sums of each workgroup, [episode_grid][HS_EPISODE_STATS]
+    int32_t *league_step = nullptr;        // hs_league_step: the counts of the step and its malformed worlds, [kLeagueMaxBins + 1], zero between calls
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -1157,6 +1159,71 @@ int launch_episode(hs_sim *s, hipStream_t strm, const hs_episode_request *r) {
 }
 }  // namespace
 
+// ---- the league (hs_k_league.h) ----
+namespace {
+static_assert(HS_LEAGUE_MAX_POLICIES == hs::kLeagueMaxPolicies && HS_LEAGUE_OUTCOMES == hs::kLeagueOutcomes && HS_LEAGUE_HIDERS_WIN == hs::kLeagueHidersWin &&
+              HS_LEAGUE_SEEKERS_WIN == hs::kLeagueSeekersWin && HS_LEAGUE_DRAW == hs::kLeagueDraw && HS_LEAGUE_NO_OUTCOME == hs::kLeagueNoOutcome,
+              "hs_league_request and k_league agree");
+static_assert(sizeof(hs_league_request) == 128 && offsetof(hs_league_request, num_policies) == 40 && offsetof(hs_league_request, team_size) == 44 &&
+              offsetof(hs_league_request, k_factor) == 48 && offsetof(hs_league_request, policy_assignments) == 56 && offsetof(hs_league_request, slot) == 64 &&
+              offsetof(hs_league_request, world_hider_team) == 88 && offsetof(hs_league_request, bad) == 104 && offsetof(hs_league_request, counts) == 112 &&
+              offsetof(hs_league_request, elo) == 120,
+              "hs_league_request layout (gpu_hideseek/league.py mirrors it)");
+static_assert(kExports[HS_EXPORT_AGENT_POLICY].dtype == HS_DTYPE_I32 && kExports[HS_EXPORT_AGENT_POLICY].per_agent && kExports[HS_EXPORT_AGENT_POLICY].tail[0] == 1 &&
+              kExports[HS_EXPORT_SELF_TYPE].dtype == HS_DTYPE_I32 && kExports[HS_EXPORT_SELF_TYPE].tail[0] == 1 && kExports[HS_EXPORT_DONE].dtype == HS_DTYPE_I32 &&
+              kExports[HS_EXPORT_DONE].tail[0] == 1 && kExports[HS_EXPORT_SELF_MASK].dtype == HS_DTYPE_F32 && kExports[HS_EXPORT_SELF_MASK].tail[0] == 1 &&
+              kExports[HS_EXPORT_EPISODE_RESULT].dtype == HS_DTYPE_F32 && kExports[HS_EXPORT_EPISODE_RESULT].tail[0] == 2,
+              "k_league reads the done, self_type, self_mask and episode_result exports and writes policy_assignments");
+static_assert(hs::kLeagueThreads >= hs::kMaxAgents && hs::kLeagueMaxPolicies * hs::kLeagueMaxPolicies <= 1024, "a workgroup of k_league holds a world, k_league_fold is one workgroup");
+
+// The request with every null input, and a null policy_assignments, replaced by the handle's own.
+hs::LeagueArgs league_args(const hs_sim *s, const hs_league_request *r) {
+    const hs::SimState &S = s->S;
+    return {r->done ? r->done : S.xDone, r->self_type ? r->self_type : S.xSelfType, r->self_mask ? r->self_mask : S.xSelfMask,
+            r->episode_result ? r->episode_result : S.xEpisodeResult, r->hider_team, S.counts,
+            r->policy_assignments ? r->policy_assignments : S.xPolicy, r->slot, r->row_of_slot, r->clear_slot, r->world_hider_team, r->world_phase,
+            s->league_step, S.N, s->A, r->num_policies, r->team_size};
+}
+
+int check_league(hs_sim *s, const hs_league_request *r) {
+    const Check c{"hs_league_step"};
+    if (!r) return c.bad("null request");
+    if (!r->world_hider_team || !r->world_phase) return c.bad("null state pointer");
+    if (!r->counts) return c.bad("null counts");
+    if (!r->elo) return c.bad("null elo");
+    if (r->num_policies < 1 || r->num_policies > HS_LEAGUE_MAX_POLICIES) return c.bad("num_policies must be in [1, HS_LEAGUE_MAX_POLICIES]");
+    if (r->team_size < 1 || s->A != 2 * r->team_size) return c.bad("team_size must be at least 1 and the handle's agents per world 2 * team_size");
+    const int64_t P = r->num_policies;
+    if ((int64_t)s->S.N % (P * P)) return c.bad("the number of worlds must be a multiple of num_policies^2");
+    if ((int64_t)s->S.N * s->A >= (int64_t)1 << 31) return c.bad("worlds * agents must stay below 2^31");
+    if (!std::isfinite(r->k_factor) || !(r->k_factor > 0.0)) return c.bad("k_factor must be finite and above 0");
+    if (!aligned(4, {r->done, r->self_type, r->self_mask, r->episode_result, r->hider_team, r->policy_assignments, r->slot, r->row_of_slot, r->clear_slot,
+                     r->world_hider_team, r->world_phase, r->bad}))
+        return c.bad("every input, routing and state pointer must be 4-byte aligned");
+    if (!aligned(8, {r->counts, r->elo})) return c.bad("counts and elo must be 8-byte aligned");
+    if ((s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) && (!r->self_type || !r->self_mask))
+        return c.bad("a null self_type or self_mask needs the exports that HS_FLAG_EXT_SKIP_OBSERVATIONS leaves unwritten after a reset", HS_ERR_UNSUPPORTED);
+    const hs::LeagueArgs a = league_args(s, r);
+    const uintptr_t worlds = (uintptr_t)s->S.N, rows = worlds * (uintptr_t)s->A;
+    HS_TRY(c.disjoint({range("done", a.done, rows * 4), range("self_type", a.selfType, rows * 4), range("self_mask", a.selfMask, rows * 4),
+                       range("episode_result", a.episodeResult, worlds * 8), range("hider_team", a.hiderTeam, worlds * 4)},
+                      {range("policy_assignments", a.policy, rows * 4), range("slot", r->slot, rows * 4), range("row_of_slot", r->row_of_slot, rows * 4),
+                       range("clear_slot", r->clear_slot, rows * 4), range("world_hider_team", r->world_hider_team, worlds * 4),
+                       range("world_phase", r->world_phase, worlds * 4), range("bad", r->bad, 4),
+                       range("counts", r->counts, (uintptr_t)(P * P) * HS_LEAGUE_OUTCOMES * sizeof(int64_t)), range("elo", r->elo, (uintptr_t)P * sizeof(double))}));
+    return c.handle_ready(s);
+}
+// One k_league over every agent row (the request has passed check_league), then the fold of the step's counts and ratings.
+int launch_league(hs_sim *s, hipStream_t strm, const hs_league_request *r) {
+    const hs::LeagueArgs a = league_args(s, r);
+    hipLaunchKernelGGL(hs::k_league<>, dim3(hs::league_grid(a.worlds, a.A)), dim3(hs::kLeagueThreads), 0, strm, a);
+    hipLaunchKernelGGL(hs::k_league_fold<>, dim3(1), dim3(hs::kLeagueMaxPolicies * hs::kLeagueMaxPolicies), 0, strm, s->league_step, a.P, r->k_factor,
+                       (long long *)r->counts, r->elo, r->bad);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1304,6 +1371,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
     HS_ALLOC(s->adam_workspace, hs::kAdamWorkspace);
     HS_ALLOC(s->episode_partials, (size_t)hs::episode_grid((int)N, A) * hs::kEpiStats);
+    HS_ALLOC(s->league_step, hs::kLeagueMaxBins + 1);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1640,6 +1708,8 @@ int32_t hs_gather_sequences(hs_sim *s, const hs_gather_request *req) { return ca
 int32_t hs_gather_sequences_async(hs_sim *s, void *hip_stream, const hs_gather_request *req) { return call_async(s, hip_stream, check_gather, launch_gather, req); }
 int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call_blocking(s, check_episode, launch_episode, req); }
 int32_t hs_episode_stats_async(hs_sim *s, void *hip_stream, const hs_episode_request *req) { return call_async(s, hip_stream, check_episode, launch_episode, req); }
+int32_t hs_league_step(hs_sim *s, const hs_league_request *req) { return call_blocking(s, check_league, launch_league, req); }
+int32_t hs_league_step_async(hs_sim *s, void *hip_stream, const hs_league_request *req) { return call_async(s, hip_stream, check_league, launch_league, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

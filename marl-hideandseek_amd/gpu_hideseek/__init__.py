@@ -342,6 +342,22 @@ class HideAndSeekSimulator:
         return _episodes.compute(self, state, table, stream, gamma=gamma, reward=reward, done=done, self_type=self_type, self_mask=self_mask,
                                  episode_result=episode_result, hider_team=hider_team)
 
+    def league_step(self, num_policies, team_size, state, counts, elo, *, k_factor=32.0, policy_assignments=None, slot=None, row_of_slot=None,
+                    clear_slot=None, bad=None, done=None, self_type=None, self_mask=None, episode_result=None, hider_team=None, stream=None):
+        """After a step, for a league of `num_policies` policies with `team_size` hiders and seekers per world: route every
+        agent row to the policy of its side under the fixed schedule (world w plays pair w mod P^2), rank it among that
+        policy's rows, add the games that ended with the step to `counts` ([P, P, 4] int64) and move the ratings `elo`
+        ([P] float64), in one kernel and a one-workgroup fold (gpu_hideseek.league; hs_league_step, whose header comment
+        is the contract).  `state` is league.new_state's.  policy_assignments None writes the simulator's own
+        policy_assignments export; slot, row_of_slot, clear_slot (int32 [rows]) and bad (int32 [1]) are each None or a
+        tensor.  An input left None is the simulator's own export (hider_team: its team order).  stream=None blocks; a
+        torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {"counts", "elo", "state"} and the
+        outputs given.  league.League is the evaluator built on this call."""
+        from . import league as _league
+        return _league.compute(self, num_policies, team_size, state, counts, elo, stream, k_factor=k_factor, policy_assignments=policy_assignments,
+                               slot=slot, row_of_slot=row_of_slot, clear_slot=clear_slot, bad=bad, done=done, self_type=self_type,
+                               self_mask=self_mask, episode_result=episode_result, hider_team=hider_team)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

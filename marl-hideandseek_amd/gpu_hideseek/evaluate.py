@@ -11,8 +11,8 @@ state, pack_policy_inputs, the policy's forward under no_grad, sample_actions in
 sim.step(), EpisodeStats.step().  The normaliser is frozen: no moments are collected and update() is never called, so a
 run leaves the policy and the normaliser as it found them.
 
-Not here: ensembles of PBT policies playing each other and their Elo ratings (the reference's eval_competitive with
-num_policies > 1, which needs madrona_learn's matchmaking); one policy plays both sides.
+One policy plays both sides here.  Several policies playing each other, with their Elo ratings (the reference's
+eval_competitive with num_policies > 1), is gpu_hideseek.league and tools/league.py.  PBT training itself is not here.
 """
 from . import episodes, replay, rollout
 from ._request import on_current_stream

@@ -1,0 +1,334 @@
+"""Competitive evaluation: several policies play each other on one simulator and are rated (the function of the
+reference's eval_competitive with num_policies > 1 and of its print_elos).  One call after every step, hs_league_step
+(csrc/hs_k_league.h), routes every agent row to a policy, books the games that ended with the step in a P x P table and
+moves the Elo ratings; include/hideseek.h states the schedule, the routing, the outcomes and the rating arithmetic.
+madrona_learn's matchmaking is not in the reference's tree: the contract is the project's own.
+
+    lg = league.League(sim, [(net_a, norm_a), (net_b, norm_b)], team_size=3, mode="draw")     # sim right after sim.init()
+    lg.run(2400)
+    out = lg.read()                                   # {"counts": [P][P][4], "games": n, "elo": [...], "bad": 0}
+    league.print_elos(out["elo"])
+
+The schedule is fixed: world w plays pair q = w mod P^2, policy q // P the hiders and policy q % P the seekers, so every
+policy owns exactly R / P of the R agent rows at every step whatever RandomFlipTeams does, the P forwards have fixed
+shapes, and nothing is read back from the device to size them.  counts[i][j] = (hider wins, seeker wins, draws, played
+without an outcome) of hiders i against seekers j.  Ratings are batched by step: the games that end with one step are all
+rated against the ratings before it.
+
+host_step is the contract in plain numpy (int64 counts, float64 ratings, the same pair order): the tests' reference, and
+it needs no GPU.  Single device: there is no ShardedSimulator form, because the ratings would have to cross the shards.
+PBT training itself (several train states, hyper-parameter exploration, past-policy pools) is not here.
+"""
+import ctypes as C
+import math
+
+from . import replay, rollout
+from ._request import _disjoint, _run, _tensor, on_current_stream
+
+MAX_POLICIES = 16         # HS_LEAGUE_MAX_POLICIES
+OUTCOMES = 4              # HS_LEAGUE_OUTCOMES
+HIDERS_WIN, SEEKERS_WIN, DRAW, NO_OUTCOME = 0, 1, 2, 3
+DEFAULT_K_FACTOR = 32.0
+INITIAL_ELO = 1500.0
+MODES = ("draw", "greedy")
+WORLD_STATE = (("world_hider_team", "int32"), ("world_phase", "int32"))
+ROW_INPUTS = (("done", "int32"), ("self_type", "int32"), ("self_mask", "float32"))
+ROUTING = ("policy_assignments", "slot", "row_of_slot", "clear_slot")
+
+
+class HsLeagueRequest(C.Structure):
+    """hs_league_request (include/hideseek.h)."""
+    _fields_ = [("done", C.c_void_p), ("self_type", C.c_void_p), ("self_mask", C.c_void_p), ("episode_result", C.c_void_p),
+                ("hider_team", C.c_void_p), ("num_policies", C.c_int32), ("team_size", C.c_int32), ("k_factor", C.c_double),
+                ("policy_assignments", C.c_void_p), ("slot", C.c_void_p), ("row_of_slot", C.c_void_p), ("clear_slot", C.c_void_p),
+                ("world_hider_team", C.c_void_p), ("world_phase", C.c_void_p), ("bad", C.c_void_p), ("counts", C.c_void_p), ("elo", C.c_void_p)]
+
+
+def _league_shape(num_worlds, agents, num_policies, team_size):
+    for name, v in (("num_policies", num_policies), ("team_size", team_size)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 1 <= num_policies <= MAX_POLICIES:
+        raise ValueError(f"num_policies must be in [1, {MAX_POLICIES}], got {num_policies}")
+    if team_size < 1 or agents != 2 * team_size:
+        raise ValueError(f"team_size must be at least 1 and the simulator's agents per world 2 * team_size: team_size {team_size}, {agents} agents")
+    if num_worlds < 1 or num_worlds % (num_policies * num_policies):
+        raise ValueError(f"num_worlds must be a multiple of num_policies^2 = {num_policies * num_policies}, got {num_worlds}")
+    if num_worlds * agents >= 2 ** 31:
+        raise ValueError("num_worlds * agents must stay below 2^31")
+
+
+def _k_factor(k_factor):
+    k = float(k_factor)
+    if not (math.isfinite(k) and k > 0.0):
+        raise ValueError(f"k_factor must be finite and above 0, got {k_factor}")
+    return k
+
+
+def schedule(num_worlds, num_policies):
+    """(hider_policy[w], seeker_policy[w]) as lists: world w plays pair q = w mod P^2, q // P against q % P."""
+    P = int(num_policies)
+    if not 1 <= P <= MAX_POLICIES or num_worlds < 1 or num_worlds % (P * P):
+        raise ValueError(f"num_worlds must be a multiple of num_policies^2 with num_policies in [1, {MAX_POLICIES}]: {num_worlds} worlds, {num_policies} policies")
+    return [(w % (P * P)) // P for w in range(num_worlds)], [(w % (P * P)) % P for w in range(num_worlds)]
+
+
+def new_state(num_worlds, device):
+    """The per-world state, {name: tensor}: no world's team order latched."""
+    import torch
+    return {k: torch.zeros(num_worlds, dtype=getattr(torch, d), device=device) for k, d in WORLD_STATE}
+
+
+def print_elos(elos, file=None):
+    """The ratings four to a line, each as f"{idx:>3}: {elo:>8.2f}": the layout of the reference's table."""
+    vals = [float(e) for e in (elos.tolist() if hasattr(elos, "tolist") else elos)]
+    for lo in range(0, len(vals), 4):
+        print("".join(f"{idx:>3}: {elo:>8.2f}       " for idx, elo in enumerate(vals[lo:lo + 4], lo)), file=file)
+
+
+def host_step(state, counts, elo, num_policies, team_size, done, self_type, self_mask, episode_result, hider_team, k_factor=DEFAULT_K_FACTOR):
+    """The contract of hs_league_step in plain numpy, one world at a time.  `state` {"world_hider_team", "world_phase"}
+    (int32 [worlds]), `counts` (int64 [P, P, 4]) and `elo` (float64 [P]) are updated in place; done, self_type, self_mask
+    are [R], episode_result [worlds, 2], hider_team [worlds].  Returns {"policy_assignments", "slot", "row_of_slot",
+    "clear_slot": int32 [R], "bad": int}."""
+    import numpy as np
+    P, k = int(num_policies), int(team_size)
+    A = 2 * k
+    done, self_type, self_mask = (np.asarray(x).reshape(-1) for x in (done, self_type, self_mask))
+    worlds = done.shape[0] // A
+    R = worlds * A
+    episode_result, hider_team = np.asarray(episode_result).reshape(worlds, 2), np.asarray(hider_team).reshape(worlds)
+    policy, slot = np.zeros(R, np.int32), np.zeros(R, np.int32)
+    delta = np.zeros((P, P, OUTCOMES), np.int64)
+    bad = 0
+    held = [[sum((qq // P == p) + (qq % P == p) for qq in range(q)) for p in range(P)] for q in range(P * P)]
+    for w in range(worlds):
+        rows = slice(w * A, (w + 1) * A)
+        hider = self_type[rows] != 0
+        if int(hider.sum()) != k or bool((self_mask[rows] == 0).any()):
+            bad += 1
+            hider = np.arange(A) < k
+        g, q = divmod(w, P * P)
+        i, j = divmod(q, P)
+        for r in range(A):
+            p = i if hider[r] else j
+            sides = held[q][p]                  # the sides p holds in the worlds of the group before q
+            rank = sum(1 for b in range(r) if (i if hider[b] else j) == p)
+            policy[w * A + r] = p
+            slot[w * A + r] = p * (R // P) + g * 2 * P * k + k * sides + rank
+        ended = done[w * A] != 0
+        if ended and state["world_phase"][w] == 1:
+            h = int(state["world_hider_team"][w])
+            o = NO_OUTCOME
+            if h in (0, 1):
+                x = float(episode_result[w, h])
+                o = HIDERS_WIN if x == 1.0 else SEEKERS_WIN if x == 0.0 else DRAW if x == 0.5 else NO_OUTCOME
+            delta[i, j, o] += 1
+        if ended or state["world_phase"][w] == 0:
+            state["world_hider_team"][w] = hider_team[w]
+            state["world_phase"][w] = 1
+    row_of_slot, clear_slot = np.zeros(R, np.int32), np.zeros(R, np.int32)
+    row_of_slot[slot] = np.arange(R, dtype=np.int32)
+    clear_slot[slot] = done
+    counts += delta
+    before = np.array(elo, np.float64)
+    kf = np.float64(k_factor)
+    for i in range(P):
+        for j in range(P):
+            n = int(delta[i, j, 0] + delta[i, j, 1] + delta[i, j, 2])
+            if i == j or n == 0:
+                continue
+            S = np.float64(delta[i, j, 0]) + np.float64(0.5) * np.float64(delta[i, j, 2])
+            E = np.float64(1.0) / (np.float64(1.0) + np.float64(10.0) ** ((before[j] - before[i]) / np.float64(400.0)))
+            d = kf * (S - np.float64(n) * E)
+            elo[i] = elo[i] + d
+            elo[j] = elo[j] - d
+    return dict(policy_assignments=policy, slot=slot, row_of_slot=row_of_slot, clear_slot=clear_slot, bad=bad)
+
+
+def request(num_worlds, agents, gpu_id, num_policies, team_size, state, counts, elo, k_factor=DEFAULT_K_FACTOR, policy_assignments=None, slot=None,
+            row_of_slot=None, clear_slot=None, bad=None, done=None, self_type=None, self_mask=None, episode_result=None, hider_team=None):
+    """Validate a call over num_worlds x agents agent rows on GPU `gpu_id` for a league of `num_policies` with teams of
+    `team_size`: `state` as new_state() makes it, `counts` [P, P, 4] int64, `elo` [P] float64; the routing outputs
+    policy_assignments, slot, row_of_slot, clear_slot (int32 [rows], [rows, 1] or [num_worlds, agents]) and bad (int32 [1])
+    are each None or a tensor (policy_assignments None: the simulator's own export is written); the inputs given
+    explicitly as in episodes.request, None meaning the simulator's own.  Returns ({"counts", "elo", "state" and the
+    outputs given}, HsLeagueRequest).  Raises ValueError before the library is involved."""
+    import torch
+    dev = torch.device("cuda", gpu_id)
+    _league_shape(num_worlds, agents, num_policies, team_size)
+    k_factor = _k_factor(k_factor)
+    P, rows = num_policies, num_worlds * agents
+    if not isinstance(state, dict) or set(state) != {k for k, _ in WORLD_STATE}:
+        raise ValueError("state must be a dict of " + ", ".join(k for k, _ in WORLD_STATE) + " (league.new_state)")
+    per_row, per_world = [(rows,), (rows, 1), (num_worlds, agents)], [(num_worlds,), (num_worlds, 1)]
+    given = dict(done=done, self_type=self_type, self_mask=self_mask)
+    inputs = []
+    for k, d in ROW_INPUTS:
+        if given[k] is not None:
+            _tensor(k, given[k], per_row, (d,), dev, "None or a torch tensor")
+            inputs.append((k, given[k]))
+    if episode_result is not None:
+        _tensor("episode_result", episode_result, (num_worlds, 2), ("float32",), dev, "None or a torch tensor")
+        inputs.append(("episode_result", episode_result))
+    if hider_team is not None:
+        _tensor("hider_team", hider_team, per_world, ("int32",), dev, "None or a torch tensor")
+        inputs.append(("hider_team", hider_team))
+    outputs = []
+    routing = dict(policy_assignments=policy_assignments, slot=slot, row_of_slot=row_of_slot, clear_slot=clear_slot)
+    for k in ROUTING:
+        if routing[k] is not None:
+            _tensor(k, routing[k], per_row, ("int32",), dev, "None or a torch tensor")
+            outputs.append((k, routing[k]))
+    for k, d in WORLD_STATE:
+        _tensor(k, state[k], per_world, (d,), dev)
+        outputs.append((k, state[k]))
+    if bad is not None:
+        _tensor("bad", bad, (1,), ("int32",), dev, "None or a torch tensor")
+        outputs.append(("bad", bad))
+    _tensor("counts", counts, (P, P, OUTCOMES), ("int64",), dev, align=8)
+    _tensor("elo", elo, (P,), ("float64",), dev, align=8)
+    outputs += [("counts", counts), ("elo", elo)]
+    _disjoint(outputs, inputs, dev)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    req = HsLeagueRequest(ptr(done), ptr(self_type), ptr(self_mask), ptr(episode_result), ptr(hider_team), P, team_size, k_factor,
+                          *(ptr(routing[k]) for k in ROUTING), *(state[k].data_ptr() for k, _ in WORLD_STATE), ptr(bad), counts.data_ptr(), elo.data_ptr())
+    res = {"counts": counts, "elo": elo, "state": state}
+    res.update({k: t for k, t in routing.items() if t is not None})
+    if bad is not None:
+        res["bad"] = bad
+    return res, req
+
+
+def compute(sim, num_policies, team_size, state, counts, elo, stream=None, **kw):
+    """HideAndSeekSimulator.league_step."""
+    res, req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, num_policies, team_size, state, counts, elo, **kw)
+    _run(sim, "hs_league_step", req, stream)
+    return res
+
+
+class League:
+    """`policies`, a list of (net, normaliser or None) with net a policy.ActorCritic on the simulator's device, playing
+    each other on `sim` under the fixed schedule: the multi-policy sibling of evaluate.Evaluator.  The simulator has
+    team_size hiders and team_size seekers in every world and a number of worlds that is a multiple of len(policies)^2,
+    and comes right from sim.init().  mode "draw" samples the actions with the uniforms keyed by (seed, step, global agent
+    row), as the Evaluator's are; "greedy" takes every head's first maximum.  Nothing in a run changes a policy or a
+    normaliser.  Single device: there is no ShardedSimulator form, because the ratings would have to cross the shards.
+    `episodes`, None by default: an episodes.EpisodeStats of the same simulator whose step() run() calls after every step."""
+
+    def __init__(self, sim, policies, team_size, mode="draw", seed=0, k_factor=DEFAULT_K_FACTOR):
+        import torch
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        policies = [tuple(p) for p in policies]
+        if not policies or any(len(p) != 2 for p in policies):
+            raise ValueError("policies must be a list of (net, normaliser or None)")
+        P = len(policies)
+        _league_shape(sim.num_worlds, sim.agents_per_world, P, team_size)
+        self.k_factor = _k_factor(k_factor)
+        nets = [net for net, _ in policies]
+        if any(net.buckets != nets[0].buckets for net in nets):
+            raise ValueError("every policy must have the same action heads")
+        self.sim, self.policies, self.team_size, self.mode, self.seed = sim, policies, int(team_size), mode, int(seed)
+        self.num_policies = P
+        self.rows = R = sim.num_worlds * sim.agents_per_world
+        self.block = m = R // P                   # the rows of a policy, and the length of its block of slots
+        self.device = dev = torch.device("cuda", sim.gpu_id)
+        self.logit_width = L = sum(nets[0].buckets)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.slot, self.row_of_slot, self.clear_slot = (torch.zeros(R, **i32) for _ in range(3))
+        self.bad = torch.zeros(1, **i32)
+        self.world = new_state(sim.num_worlds, dev)
+        # counts [P, P, 4] i64 | elo [P] f64 | the malformed worlds of all calls, in one buffer: read() is one copy
+        self._table = torch.zeros(P * P * OUTCOMES + P + 1, dtype=torch.int64, device=dev)
+        self.counts = self._table[:P * P * OUTCOMES].view(P, P, OUTCOMES)
+        self.elo = self._table[P * P * OUTCOMES:P * P * OUTCOMES + P].view(torch.float64)
+        self.bad_total = self._table[P * P * OUTCOMES + P:]
+        self.elo.fill_(INITIAL_ELO)
+        # every policy packs all rows with its own normaliser and gathers its block: one pair of buffers per compute dtype
+        self.packed = {net.dtype: torch.zeros(R, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
+        self.gathered = {net.dtype: torch.zeros(1, m, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
+        self.logits_by_slot = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
+        self.logits = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
+        self.state = [net.actor.init_state(m, dev, net.dtype) for net in nets]
+        self.counter = 0
+        self.episodes = None
+        # the tensors above stay where they are: the request is checked and built once
+        self._req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, P, self.team_size, self.world, self.counts, self.elo, self.k_factor,
+                            slot=self.slot, row_of_slot=self.row_of_slot, clear_slot=self.clear_slot, bad=self.bad)[1]
+        self.arm()
+
+    def _league_step(self):
+        with on_current_stream():
+            _run(self.sim, "hs_league_step", self._req, None)
+        self.bad_total.add_(self.bad)
+
+    def arm(self):
+        """Right after sim.init(): no world's team order is latched, every carried LSTM state is zero, and the rows are
+        routed from the simulator as it stands (which latches the team orders; no game is booked).  counts and elo are
+        left as they are."""
+        for t in self.world.values():
+            t.zero_()
+        for s in self.state:
+            for x in s:
+                x.zero_()
+        self._league_step()
+        return self
+
+    def act(self):
+        """The observation in the simulator's exports -> the action tensor: every policy's forward over its own block of
+        slots, its carried state advanced."""
+        import torch
+        sim, R, m = self.sim, self.rows, self.block
+        with on_current_stream(), torch.no_grad():
+            for p, (net, normaliser) in enumerate(self.policies):
+                block = slice(p * m, (p + 1) * m)
+                packed, mine = self.packed[net.dtype], self.gathered[net.dtype]
+                sim.pack_policy_inputs(actor=packed, normaliser=normaliser)
+                sim.gather_sequences(self.row_of_slot[block], [(packed.view(1, R, -1), mine, False)], chunks=1, chunk_steps=1, rows=R)
+                zero = (self.clear_slot[block] != 0).unsqueeze(1)
+                for x in self.state[p]:
+                    x.masked_fill_(zero, 0)
+                y, self.state[p] = net.actor(sim, mine[0], self.state[p], None)
+                head = net.actor_head
+                self.logits_by_slot[0, block] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype)).float()
+            sim.gather_sequences(self.slot, [(self.logits_by_slot, self.logits, False)], chunks=1, chunk_steps=1, rows=R)
+            sim.sample_actions(self.logits[0], buckets=self.policies[0][0].buckets, mode=self.mode, seed=(self.seed, 0), counter=self.counter)
+        self.counter += 1
+
+    def run(self, num_steps, record_log=None, on_step=None):
+        """num_steps times: act(), sim.step(), the league's step, the attached episode tracker's; with `record_log` (a
+        binary file open for writing) replay.record_step after every step; on_step(i, self), if given, after that.
+        Returns read()."""
+        for i in range(int(num_steps)):
+            self.act()
+            self.sim.step()
+            self._league_step()
+            if self.episodes is not None:
+                self.episodes.step()
+            if record_log is not None:
+                replay.record_step(self.sim, record_log)
+            if on_step is not None:
+                on_step(i, self)
+        return self.read()
+
+    def read(self):
+        """{"counts": [P][P][4] lists (hider wins, seeker wins, draws, played without an outcome, of hiders i against
+        seekers j), "games": their sum, "elo": [P], "bad": the malformed worlds seen} by one copy to the host (which waits
+        for the device).  Nothing is reset."""
+        import torch
+        P = self.num_policies
+        host = self._table.cpu()
+        n = P * P * OUTCOMES
+        counts = host[:n].view(P, P, OUTCOMES)
+        return {"counts": counts.tolist(), "games": int(counts.sum()), "elo": host[n:n + P].view(torch.float64).tolist(), "bad": int(host[n + P])}
+
+
+def hider_win_rates(counts):
+    """[P][P]: the share of the games with an outcome that hiders i won against seekers j (0.0 where there were none)."""
+    out = []
+    for row in counts:
+        out.append([(c[HIDERS_WIN] / (c[HIDERS_WIN] + c[SEEKERS_WIN] + c[DRAW])) if (c[HIDERS_WIN] + c[SEEKERS_WIN] + c[DRAW]) else 0.0 for c in row])
+    return out

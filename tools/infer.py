@@ -9,8 +9,8 @@ reference's scripts/jax_infer.py that make sense here.
 optimiser's state is not needed.  The simulator runs with UseFixedWorld | ZeroAgentVelocity, as the reference's script
 does.  --record-log appends a checkpoint of every world after every step.  --print-rewards prints every step's reward
 tensor.  At the end it prints the per-side table of the episodes that finished (240 steps each) and one JSON line.
-Not here: --single-policy, PBT ensembles and Elo ratings (the reference's eval_competitive), --print-obs and
---print-action-probs.
+Several checkpoints playing each other, with Elo ratings (the reference's eval_competitive), is tools/league.py.
+Not here: --single-policy, PBT training, --print-obs and --print-action-probs.
 """
 import argparse
 import json

@@ -18,7 +18,8 @@ and prints, as a second JSON line at each `Update:` print, what has finished sin
 the mean and standard deviation of the return, the mean discounted return and length, and the hiders' and seekers' win
 rates.  On a fresh simulator the episodes are tracked from their start; after --restore the tracker waits for every row's
 next episode, because the simulator's state is not restored.  tools/infer.py runs a saved policy without learning.
-Not here: PBT, Elo ratings (the reference's eval_competitive), tensorboard / wandb, several GPUs.
+Saved checkpoints play each other, with Elo ratings (the reference's eval_competitive), in tools/league.py.
+Not here: PBT, tensorboard / wandb, several GPUs.
 """
 import argparse
 import json
