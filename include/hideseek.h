@@ -1034,6 +1034,41 @@ typedef struct hs_league_request {
 int32_t hs_league_step(hs_sim *sim, const hs_league_request *req);
 int32_t hs_league_step_async(hs_sim *sim, void *hip_stream, const hs_league_request *req);
 
+/* The routed pack: hs_pack_policy_inputs_normalized for a league or a population (one kernel, csrc/hs_k_pack_routed.h).
+ * One launch packs every agent row into SLOT order, each row normalised with the table of the policy that owns the slot,
+ * and collects the moments per policy.  With R = worlds * A rows and N = num_policies (R % N == 0), policy p owns slots
+ * [p R / N, (p + 1) R / N), as hs_league_step lays them out; row_of_slot [R] i32 is what that call writes.
+ *   Output row s (of actor and of critic, [R][HS_PACK_ROW], indexed by slot) has the BITS of row row_of_slot[s] of
+ *   hs_pack_policy_inputs_normalized called with tables + (s / (R / N)) * HS_NORM_TABLE; with null tables, of
+ *   hs_pack_policy_inputs.
+ *   moments + p * moments_stride [HS_PACK_MOMENTS] f64, for every p: the sums over policy p's slots of m x, m x x and m of
+ *   the raw f32 critic values, in f64, as hs_pack_policy_inputs states them.  No float atomics: the same inputs give the
+ *   same bits on every call; with N == 1 and the identity routing they are the bits of hs_pack_policy_inputs.
+ *   moments_stride is in doubles, >= HS_PACK_MOMENTS; nothing between the vectors is written.  A caller that keeps
+ *   [N][T][HS_PACK_MOMENTS] hands base + t * HS_PACK_MOMENTS with stride T * HS_PACK_MOMENTS, so that each policy's T
+ *   vectors are contiguous for hs_obs_norm_update.
+ *   bad [1] i32 or null: zeroed by the call, then the number of slots whose row_of_slot is outside [0, R).  Such a slot's
+ *   output rows are all-zero bits and it adds nothing to the moments; no export is read for it.
+ * Validation as hs_pack_policy_inputs_normalized (HS_ERR_INVALID_ARG, nothing written), and in addition: null
+ * row_of_slot; num_policies outside [1, HS_LEAGUE_MAX_POLICIES] or not a divisor of R; tables not 16-byte aligned;
+ * moments given with moments_stride < HS_PACK_MOMENTS; row_of_slot or bad not 4-byte aligned; an output overlapping
+ * row_of_slot, tables or another output.  The partial sums go through a workspace of the handle, so two calls with moments
+ * on one handle must not overlap.  Ordering and streams as hs_pack_policy_inputs. */
+typedef struct hs_pack_routed_request {
+    void *actor;                  /* [R][HS_PACK_ROW] of actor_dtype, indexed by slot, or null */
+    int32_t actor_dtype;          /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    void *critic;
+    int32_t critic_dtype;
+    const int32_t *row_of_slot;   /* [R] i32 */
+    int32_t num_policies;         /* N in [1, HS_LEAGUE_MAX_POLICIES]; R % N == 0 */
+    const float *tables;          /* [N][HS_NORM_TABLE] f32, 16-byte aligned, or null = no normalisation */
+    double *moments;              /* policy p's [HS_PACK_MOMENTS] at moments + p * moments_stride, or null */
+    int64_t moments_stride;       /* in doubles, >= HS_PACK_MOMENTS (read only with moments) */
+    int32_t *bad;                 /* [1] i32 or null */
+} hs_pack_routed_request;         /* 80 bytes */
+int32_t hs_pack_policy_inputs_routed(hs_sim *sim, const hs_pack_routed_request *req);
+int32_t hs_pack_policy_inputs_routed_async(hs_sim *sim, void *hip_stream, const hs_pack_routed_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

@@ -35,6 +35,7 @@
 #include "hs_k_gather.h"                  // ahead of hs_k_adam.h: its one kernel is a template, emitted where launch_gather (the last stage) names it
 #include "hs_k_episode.h"                 // likewise: its two kernels are templates, emitted where launch_episode (after launch_gather) names them
 #include "hs_k_league.h"                  // likewise: emitted where launch_league (after launch_episode) names them
+#include "hs_k_pack_routed.h"             // likewise: emitted where launch_pack_routed (after launch_league) names it
 #include "hs_k_adam.h"
 
 namespace {
@@ -94,6 +95,7 @@ struct hs_sim {
     hs::SpectateCam *cams = nullptr;       // hs_render_cameras: the device copy of the cameras, grown on demand
     int cam_cap = 0;
     double *pack_partials = nullptr;       // hs_pack_policy_inputs: the moments of each workgroup, [pack_grid][HS_PACK_MOMENTS]
+    double *pack_routed_partials = nullptr;        // hs_pack_policy_inputs_routed: [N][pack_routed_grid][HS_PACK_MOMENTS], N G <= kPackMaxGrid for every N
     double *gae_partials = nullptr;        // hs_compute_gae: the moments of each workgroup, [gae_grid][HS_GAE_MOMENTS]
     double *ppo_partials = nullptr;        // hs_ppo_loss: the statistics of each workgroup, [kPpoMaxGrid][HS_PPO_STATS]
     int32_t *ppo_counts = nullptr;         // hs_ppo_loss: the active samples each workgroup of k_ppo_count saw, [kPpoCountGrid]
@@ -1224,6 +1226,78 @@ int launch_league(hs_sim *s, hipStream_t strm, const hs_league_request *r) {
 }
 }  // namespace
 
+// ---- the routed pack (hs_k_pack_routed.h) ----
+namespace {
+static_assert(sizeof(hs_pack_routed_request) == 80 && offsetof(hs_pack_routed_request, actor_dtype) == 8 && offsetof(hs_pack_routed_request, critic) == 16 &&
+              offsetof(hs_pack_routed_request, critic_dtype) == 24 && offsetof(hs_pack_routed_request, row_of_slot) == 32 &&
+              offsetof(hs_pack_routed_request, num_policies) == 40 && offsetof(hs_pack_routed_request, tables) == 48 &&
+              offsetof(hs_pack_routed_request, moments) == 56 && offsetof(hs_pack_routed_request, moments_stride) == 64 && offsetof(hs_pack_routed_request, bad) == 72,
+              "hs_pack_routed_request layout (gpu_hideseek/policy_inputs.py mirrors it)");
+static_assert(hs::kLeagueMaxPolicies <= hs::kPackMaxGrid, "every policy has a workgroup");
+
+int check_pack_routed(hs_sim *s, const hs_pack_routed_request *r) {
+    const Check c{"hs_pack_policy_inputs_routed"};
+    if (!r) return c.bad("null request");
+    if (s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) return c.bad("HS_FLAG_EXT_SKIP_OBSERVATIONS leaves no observations to pack", HS_ERR_UNSUPPORTED);
+    HS_TRY(c.handle_ready(s));
+    if (!r->actor && !r->critic && !r->moments) return c.bad("every output is null");
+    if (r->actor) HS_TRY(c.dtype(r->actor_dtype, "output"));
+    if (r->critic) HS_TRY(c.dtype(r->critic_dtype, "output"));
+    if (!r->row_of_slot) return c.bad("null row_of_slot");
+    const int64_t R = (int64_t)s->S.N * s->A;
+    if (r->num_policies < 1 || r->num_policies > HS_LEAGUE_MAX_POLICIES) return c.bad("num_policies must be in [1, HS_LEAGUE_MAX_POLICIES]");
+    if (R % r->num_policies) return c.bad("the number of agent rows must be a multiple of num_policies");
+    if (r->moments && r->moments_stride < HS_PACK_MOMENTS) return c.bad("moments_stride must be at least HS_PACK_MOMENTS");
+    if (!aligned(16, {r->actor, r->critic})) return c.bad("outputs must be 16-byte aligned");
+    if (!aligned(16, {r->tables})) return c.bad("tables must be 16-byte aligned");
+    if (!aligned(8, {r->moments})) return c.bad("moments must be 8-byte aligned");
+    if (!aligned(4, {r->row_of_slot, r->bad})) return c.bad("row_of_slot and bad must be 4-byte aligned");
+    const uintptr_t N = (uintptr_t)r->num_policies, rows = (uintptr_t)R;
+    return c.disjoint({range("row_of_slot", r->row_of_slot, rows * 4), range("tables", r->tables, N * HS_NORM_TABLE * sizeof(float))},
+                      {range("actor", r->actor, rows * HS_PACK_ROW * elem_size(r->actor_dtype)), range("critic", r->critic, rows * HS_PACK_ROW * elem_size(r->critic_dtype)),
+                       range("moments", r->moments, r->moments ? ((N - 1) * (uintptr_t)r->moments_stride + HS_PACK_MOMENTS) * sizeof(double) : 0), range("bad", r->bad, 4)});
+}
+// The fixed-order sum of every policy's G workspace rows, after a k_pack_routed that wrote them.  A template, as
+// launch_pack_moments_sum is and for its reason: k_partials_sum stays where launch_pack's instantiates it.
+template <int kSegs = hs::kPackSumSegs>
+int launch_pack_routed_sums(hs_sim *s, hipStream_t strm, const hs_pack_routed_request *r, int G) {
+    if (r->moments)
+        for (int p = 0; p < r->num_policies; ++p)
+            launch_partials_sum<double, hs::kPackThreads / kSegs, kSegs>(strm, s->pack_routed_partials + (size_t)p * G * hs::kPackMoments, G, hs::kPackMoments,
+                                                                         r->moments + (size_t)p * r->moments_stride);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+// bad zeroed, one k_pack_routed over every slot (the request has passed check_pack_routed), then the fixed-order sum of each
+// policy's moments.  With no rows requested the table is not read.
+int launch_pack_routed(hs_sim *s, hipStream_t strm, const hs_pack_routed_request *r) {
+    const hs_pack_request plain = {r->actor, r->actor_dtype, r->critic, r->critic_dtype, r->moments};
+    hs::PackRoutedArgs a = {pack_args(s, &plain), r->row_of_slot, r->tables, r->bad, 0};
+    a.p.partials = s->pack_routed_partials;
+    a.perPolicy = a.p.rows / r->num_policies;
+    const int G = hs::pack_routed_grid(a.perPolicy, r->num_policies);
+    const dim3 grid(G, r->num_policies), blk(hs::kPackThreads);
+    const bool norm = r->tables && (r->actor || r->critic);
+    if (r->bad) HS_HIP(hipMemsetAsync(r->bad, 0, sizeof(int32_t), strm));
+    with_pack_type(r->actor, r->actor_dtype, [&](auto ta) {
+        with_pack_type(r->critic, r->critic_dtype, [&](auto tc) {
+            typedef decltype(ta) TA;
+            typedef decltype(tc) TC;
+            constexpr bool rows = !(std::is_same<TA, hs::PackAbsent>::value && std::is_same<TC, hs::PackAbsent>::value);
+            if constexpr (rows) {
+                if (r->moments && norm) hipLaunchKernelGGL((hs::k_pack_routed<TA, TC, true, true>), grid, blk, 0, strm, a);
+                else if (r->moments) hipLaunchKernelGGL((hs::k_pack_routed<TA, TC, true, false>), grid, blk, 0, strm, a);
+                else if (norm) hipLaunchKernelGGL((hs::k_pack_routed<TA, TC, false, true>), grid, blk, 0, strm, a);
+                else hipLaunchKernelGGL((hs::k_pack_routed<TA, TC, false, false>), grid, blk, 0, strm, a);
+            } else {
+                hipLaunchKernelGGL((hs::k_pack_routed<TA, TC, true, false>), grid, blk, 0, strm, a);       // the moments alone (check_pack_routed)
+            }
+        });
+    });
+    return launch_pack_routed_sums<>(s, strm, r, G);
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1362,7 +1436,10 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     }
     HS_ALLOC(s->bal_hist, hs::kBalanceBins); HS_ALLOC(s->bal_cursor, hs::kBalanceBins); HS_ALLOC(s->bal_new_slot, N);
     HS_ALLOC(S.status, 4);
-    if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
+    if (!(S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS)) {
+        HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
+        HS_ALLOC(s->pack_routed_partials, std::min<size_t>(hs::kPackMaxGrid, R / hs::kPackRows + hs::kLeagueMaxPolicies) * hs::kPackMoments);   // N G <= both, for every N
+    }
     HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
     HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
@@ -1710,6 +1787,8 @@ int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call
 int32_t hs_episode_stats_async(hs_sim *s, void *hip_stream, const hs_episode_request *req) { return call_async(s, hip_stream, check_episode, launch_episode, req); }
 int32_t hs_league_step(hs_sim *s, const hs_league_request *req) { return call_blocking(s, check_league, launch_league, req); }
 int32_t hs_league_step_async(hs_sim *s, void *hip_stream, const hs_league_request *req) { return call_async(s, hip_stream, check_league, launch_league, req); }
+int32_t hs_pack_policy_inputs_routed(hs_sim *s, const hs_pack_routed_request *req) { return call_blocking(s, check_pack_routed, launch_pack_routed, req); }
+int32_t hs_pack_policy_inputs_routed_async(hs_sim *s, void *hip_stream, const hs_pack_routed_request *req) { return call_async(s, hip_stream, check_pack_routed, launch_pack_routed, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

@@ -182,11 +182,16 @@ template <typename T, bool MASKED, bool NORM> HSD void pack_write(T *out, size_t
     }
 }
 
+struct PackDirect {};                     // the staging of k_pack and k_pack_norm: row r of the output is agent row r (pack_load)
+
 // The body of k_pack and of k_pack_norm (hs_k_norm.h), one instantiation per kernel, so the image is that kernel's LDS:
 // the row blocks of one workgroup staged, written as the actor's and the critic's rows, and the moments of the raw image.
-template <typename TA, typename TC, bool MOM, bool NORM>
-HSD void pack_blocks(const PackArgs a, const float *__restrict__ table) {
+// With a Route other than PackDirect (k_pack_routed, hs_k_pack_routed.h) the image is staged by route.load() instead, and
+// route.finish() runs after the rows are written; everything else is this body as it is.
+template <typename TA, typename TC, bool MOM, bool NORM, typename Route = PackDirect>
+HSD void pack_blocks(const PackArgs a, const float *__restrict__ table, Route route = Route{}) {
     constexpr bool kActor = !std::is_same<TA, PackAbsent>::value;
+    constexpr bool kRouted = !std::is_same<Route, PackDirect>::value;
     __shared__ PackImage im;
     if (kActor)
         for (int c = kPackColAgents + threadIdx.x; c < kPackRow; c += kPackThreads) im.maskOf[c] = (unsigned char)pack_mask_index(c);
@@ -201,11 +206,13 @@ HSD void pack_blocks(const PackArgs a, const float *__restrict__ table) {
         const size_t row0 = (size_t)b * kPackRows;
         const int nrows = a.rows - (int)row0 < kPackRows ? a.rows - (int)row0 : kPackRows;
         if (b != blockIdx.x) __syncthreads();             // the previous block's readers are done with the image
-        if (nrows == kPackRows) pack_load<true>(a, row0, nrows, im, kActor, MOM);
+        if constexpr (kRouted) route.load(a, row0, nrows, im, kActor, MOM);
+        else if (nrows == kPackRows) pack_load<true>(a, row0, nrows, im, kActor, MOM);
         else pack_load<false>(a, row0, nrows, im, kActor, MOM);
         __syncthreads();
         if constexpr (kActor) pack_write<TA, true, NORM>((TA *)a.actor, row0, nrows, im, table);
         if constexpr (!std::is_same<TC, PackAbsent>::value) pack_write<TC, false, NORM>((TC *)a.critic, row0, nrows, im, table);
+        if constexpr (kRouted) route.template finish<TA, TC>(a, row0, nrows);
         if (MOM) {
 #pragma unroll
             for (int j = 0; j < kOwn; ++j) {

@@ -162,6 +162,18 @@ class HideAndSeekSimulator:
         from . import policy_inputs
         return policy_inputs.pack(self, actor, critic, moments, dtype, stream, normaliser)
 
+    def pack_policy_inputs_routed(self, row_of_slot, num_policies, *, actor=None, critic=None, moments=None, moments_stride=None, tables=None,
+                                  bad=None, dtype=None, stream=None):
+        """pack_policy_inputs for `num_policies` policies that share this simulator, in one kernel
+        (gpu_hideseek.policy_inputs.pack_routed; hs_pack_policy_inputs_routed): output row s of `actor` / `critic` is agent
+        row row_of_slot[s] (int32 [rows], as league_step writes it), normalised with row s // (rows // num_policies) of
+        `tables` (float32 [N, 592], or None for none), bit for bit what pack_policy_inputs gives for that row and table.
+        `moments` is None, True or a float64 [N, 593] tensor or view (mom[:, t] of [N, T, 593]): policy p's moments are
+        those of its slots; `moments_stride` is its stride in doubles (by default the tensor's own).  `bad`, int32 [1] or
+        None, receives the number of slots whose row is out of range (their rows are zeros).  Returns {name: tensor}."""
+        from . import policy_inputs
+        return policy_inputs.pack_routed(self, row_of_slot, num_policies, actor, critic, moments, moments_stride, tables, bad, dtype, stream)
+
     def sample_actions(self, logits, *, buckets=(5, 5, 5, 2, 2), mode="draw", seed=(0, 0), counter=0, action=None,
                        log_prob=None, entropy=None, head_log_prob=None, zero_inactive=False, stream=None):
         """Turn the actor's logits [num_worlds * agents_per_world, W >= sum(buckets)] (float32, bfloat16 or float16,

@@ -22,7 +22,7 @@ PBT training itself (several train states, hyper-parameter exploration, past-pol
 import ctypes as C
 import math
 
-from . import replay, rollout
+from . import policy_inputs, replay, rollout
 from ._request import _disjoint, _run, _tensor, on_current_stream
 
 MAX_POLICIES = 16         # HS_LEAGUE_MAX_POLICIES
@@ -247,9 +247,14 @@ class League:
         self.elo = self._table[P * P * OUTCOMES:P * P * OUTCOMES + P].view(torch.float64)
         self.bad_total = self._table[P * P * OUTCOMES + P:]
         self.elo.fill_(INITIAL_ELO)
-        # every policy packs all rows with its own normaliser and gathers its block: one pair of buffers per compute dtype
+        # With one compute dtype (always, from tools/league.py) one routed pack writes every policy's block of slots under
+        # that policy's table (hs_pack_policy_inputs_routed): `tables` holds a copy of each normaliser's table, the identity
+        # for a policy without one, refreshed by arm() and at the start of run().  With several dtypes every policy packs
+        # all rows with its own normaliser and gathers its block: one pair of buffers per compute dtype.
+        self.routed = len({net.dtype for net in nets}) == 1
         self.packed = {net.dtype: torch.zeros(R, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
-        self.gathered = {net.dtype: torch.zeros(1, m, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
+        self.gathered = {} if self.routed else {net.dtype: torch.zeros(1, m, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
+        self.tables = torch.zeros(P, policy_inputs.NORM_TABLE, dtype=torch.float32, device=dev)
         self.logits_by_slot = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
         self.logits = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
         self.state = [net.actor.init_state(m, dev, net.dtype) for net in nets]
@@ -265,10 +270,22 @@ class League:
             _run(self.sim, "hs_league_step", self._req, None)
         self.bad_total.add_(self.bad)
 
+    def refresh_tables(self):
+        """Copy every normaliser's table as it stands into `tables` (the identity for a policy without normaliser): what
+        the routed pack of act() reads.  arm() and run() call it; a caller that updates a normaliser between two act()
+        calls of its own calls it too."""
+        for p, (_, normaliser) in enumerate(self.policies):
+            if normaliser is None:
+                self.tables[p, :policy_inputs.ROW] = 0.0
+                self.tables[p, policy_inputs.ROW:] = 1.0
+            else:
+                self.tables[p].copy_(policy_inputs.norm_table(normaliser, self.sim.gpu_id))
+
     def arm(self):
         """Right after sim.init(): no world's team order is latched, every carried LSTM state is zero, and the rows are
         routed from the simulator as it stands (which latches the team orders; no game is booked).  counts and elo are
         left as they are."""
+        self.refresh_tables()
         for t in self.world.values():
             t.zero_()
         for s in self.state:
@@ -283,15 +300,22 @@ class League:
         import torch
         sim, R, m = self.sim, self.rows, self.block
         with on_current_stream(), torch.no_grad():
+            if self.routed:
+                by_slot = self.packed[self.policies[0][0].dtype]
+                sim.pack_policy_inputs_routed(self.row_of_slot, self.num_policies, actor=by_slot, tables=self.tables)
             for p, (net, normaliser) in enumerate(self.policies):
                 block = slice(p * m, (p + 1) * m)
-                packed, mine = self.packed[net.dtype], self.gathered[net.dtype]
-                sim.pack_policy_inputs(actor=packed, normaliser=normaliser)
-                sim.gather_sequences(self.row_of_slot[block], [(packed.view(1, R, -1), mine, False)], chunks=1, chunk_steps=1, rows=R)
+                if self.routed:
+                    mine = by_slot[block]
+                else:
+                    packed, gathered = self.packed[net.dtype], self.gathered[net.dtype]
+                    sim.pack_policy_inputs(actor=packed, normaliser=normaliser)
+                    sim.gather_sequences(self.row_of_slot[block], [(packed.view(1, R, -1), gathered, False)], chunks=1, chunk_steps=1, rows=R)
+                    mine = gathered[0]
                 zero = (self.clear_slot[block] != 0).unsqueeze(1)
                 for x in self.state[p]:
                     x.masked_fill_(zero, 0)
-                y, self.state[p] = net.actor(sim, mine[0], self.state[p], None)
+                y, self.state[p] = net.actor(sim, mine, self.state[p], None)
                 head = net.actor_head
                 self.logits_by_slot[0, block] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype)).float()
             sim.gather_sequences(self.slot, [(self.logits_by_slot, self.logits, False)], chunks=1, chunk_steps=1, rows=R)
@@ -302,6 +326,7 @@ class League:
         """num_steps times: act(), sim.step(), the league's step, the attached episode tracker's; with `record_log` (a
         binary file open for writing) replay.record_step after every step; on_step(i, self), if given, after that.
         Returns read()."""
+        self.refresh_tables()
         for i in range(int(num_steps)):
             self.act()
             self.sim.step()

@@ -20,10 +20,18 @@ with its table and collects the moments of the raw rows in the same launch, and 
     norm = policy_inputs.ObsNormaliser(gpu_id)
     out = sim.pack_policy_inputs(actor=rollout_actor[t], critic=rollout_critic[t], moments=mom[t], normaliser=norm)
     norm.update(sim, mom)                                # [T, 593], after the rollout
+
+For a league or a population (gpu_hideseek.league, gpu_hideseek.population) pack_routed does the same in one launch for
+N policies that share the simulator: every row goes to its slot (row_of_slot of hs_league_step), is normalised with the
+table of the policy that owns the slot (the rows of one [N, 592] buffer: ObsNormaliser(..., table=tables[p])), and the
+moments are collected per policy (hs_pack_policy_inputs_routed, csrc/hs_k_pack_routed.h).
+
+    sim.pack_policy_inputs_routed(row_of_slot, N, actor=buf_actor[t], critic=buf_critic[t], moments=mom[:, t],
+                                  moments_stride=T * 593, tables=tables)          # mom [N, T, 593]
 """
 import ctypes as C
 
-from ._request import _DTYPES, _per_shard, _run, _sharded, stream_handle      # noqa: F401 (stream_handle: part of this module's face)
+from ._request import _DTYPES, _overlap, _per_shard, _run, _sharded, _tensor, stream_handle      # noqa: F401 (stream_handle: part of this module's face)
 
 ROW = 296            # HS_PACK_ROW
 MOMENTS = 593        # HS_PACK_MOMENTS: sum m x [296], sum m x x [296], sum m
@@ -51,6 +59,16 @@ class HsPackRequest(C.Structure):
     """hs_pack_request (include/hideseek.h)."""
     _fields_ = [("actor", C.c_void_p), ("actor_dtype", C.c_int32), ("critic", C.c_void_p), ("critic_dtype", C.c_int32),
                 ("moments", C.c_void_p)]
+
+
+class HsPackRoutedRequest(C.Structure):
+    """hs_pack_routed_request (include/hideseek.h)."""
+    _fields_ = [("actor", C.c_void_p), ("actor_dtype", C.c_int32), ("critic", C.c_void_p), ("critic_dtype", C.c_int32),
+                ("row_of_slot", C.c_void_p), ("num_policies", C.c_int32), ("tables", C.c_void_p), ("moments", C.c_void_p),
+                ("moments_stride", C.c_int64), ("bad", C.c_void_p)]
+
+
+MAX_POLICIES = 16    # HS_LEAGUE_MAX_POLICIES
 
 
 class HsObsNormRequest(C.Structure):
@@ -183,6 +201,84 @@ def pack_sharded(ssim, actor=None, critic=None, moments=None, dtype=None, stream
     return _sharded(ssim, lambda s, rt, st: _launch(s, *rt, st), make, stream)
 
 
+def request_routed(rows, gpu_id, row_of_slot, num_policies, actor=None, critic=None, moments=None, moments_stride=None, tables=None, bad=None,
+                   dtype=None):
+    """Validate a routed pack of `rows` agent rows on GPU `gpu_id` for `num_policies` policies: `row_of_slot` int32 [rows]
+    (or [rows, 1]); `actor` / `critic` as request() takes them, indexed by slot; `moments` None, True (a new [N, 593]) or a
+    float64 tensor whose first dimension is the policy, [N, 593] or a view such as mom[:, t] of [N, T, 593]: policy p's
+    vector is read at p * moments_stride doubles (by default the tensor's own stride(0)); `tables` None or a contiguous,
+    16-byte aligned float32 [N, 592]; `bad` None or int32 [1].  Returns ({name: tensor}, HsPackRoutedRequest).  Raises
+    ValueError before the library is involved."""
+    import torch
+    dev = torch.device("cuda", gpu_id)
+    N = num_policies
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= MAX_POLICIES:
+        raise ValueError(f"num_policies must be an integer in [1, {MAX_POLICIES}], got {N!r}")
+    if rows < 1 or rows % N:
+        raise ValueError(f"the number of agent rows ({rows}) must be a multiple of num_policies ({N})")
+    _tensor("row_of_slot", row_of_slot, [(rows,), (rows, 1)], ("int32",), dev)
+    if tables is not None:
+        _tensor("tables", tables, (N, NORM_TABLE), ("float32",), dev, "None or a torch tensor", align=16)
+    if bad is not None:
+        _tensor("bad", bad, (1,), ("int32",), dev, "None or a torch tensor")
+    res = {k: _output(k, t, rows, dev, dtype) for k, t in (("actor", actor), ("critic", critic)) if t is not None and t is not False}
+    stride = 0
+    if moments is True:
+        res["moments"] = torch.empty(N, MOMENTS, dtype=torch.float64, device=dev)
+    elif moments is not None and moments is not False:
+        what = f"moments must be True, None or a float64 tensor of shape ({N}, {MOMENTS}) on {dev} whose rows are contiguous and 8-byte aligned"
+        if not isinstance(moments, torch.Tensor):
+            raise ValueError(what)
+        if tuple(moments.shape) != (N, MOMENTS):
+            raise ValueError(f"{what}: its shape is {tuple(moments.shape)}")
+        if moments.dtype != torch.float64:
+            raise ValueError(f"{what}: its dtype is {moments.dtype}")
+        if moments.stride(1) != 1:
+            raise ValueError(f"{what}: its stride is {tuple(moments.stride())}")
+        if moments.device != dev:
+            raise ValueError(f"{what}: it is on {moments.device}")
+        if moments.data_ptr() % 8:
+            raise ValueError(f"{what}: it starts {moments.data_ptr() % 8} bytes past an 8-byte boundary")
+        res["moments"] = moments
+    if "moments" in res:
+        own = int(res["moments"].stride(0)) if N > 1 else MOMENTS
+        stride = own if moments_stride is None else moments_stride
+        if isinstance(stride, bool) or not isinstance(stride, int) or stride < MOMENTS:
+            raise ValueError(f"moments_stride must be an integer of at least {MOMENTS} doubles, got {stride!r}")
+        if N > 1 and stride != own:
+            raise ValueError(f"moments_stride is {stride}, the moments tensor has {own} doubles between its policies")
+    if not res:
+        raise ValueError("no output requested")
+    for k, t in (("row_of_slot", row_of_slot), ("tables", tables), ("bad", bad)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{k} must be on {dev}: it is on {t.device}")
+    if bad is not None:
+        res["bad"] = bad
+    inputs = [("row_of_slot", row_of_slot)] + ([("tables", tables)] if tables is not None else [])
+    outs = [(k, res[k]) for k in ("actor", "critic", "moments", "bad") if k in res]
+    for i, (k, t) in enumerate(outs):
+        for k2, t2 in inputs + outs[:i]:
+            if _overlap(t, t2):
+                raise ValueError(f"{k} overlaps {k2}")
+
+    def code(k):
+        return _DTYPES[str(res[k].dtype).replace("torch.", "")] if k in res else 0
+
+    def ptr(k):
+        return res[k].data_ptr() if k in res else None
+    return res, HsPackRoutedRequest(ptr("actor"), code("actor"), ptr("critic"), code("critic"), row_of_slot.data_ptr(), N,
+                                    None if tables is None else tables.data_ptr(), ptr("moments"), stride, ptr("bad"))
+
+
+def pack_routed(sim, row_of_slot, num_policies, actor=None, critic=None, moments=None, moments_stride=None, tables=None, bad=None, dtype=None,
+                stream=None):
+    """HideAndSeekSimulator.pack_policy_inputs_routed."""
+    res, req = request_routed(sim.num_worlds * sim.agents_per_world, sim.gpu_id, row_of_slot, num_policies, actor, critic, moments, moments_stride,
+                              tables, bad, dtype)
+    _run(sim, "hs_pack_policy_inputs_routed", req, stream)
+    return res
+
+
 def table_of_state(state, eps):
     """The table [592] float32 (numpy) of a state [593] float64 (numpy), by the formula of hs_obs_norm_update."""
     import numpy as np
@@ -213,15 +309,17 @@ class ObsNormaliser:
     moving average of the first and second moments of every column of the packed row, bias-corrected, kept in `state`
     (float64 [593]: m1, m2, N) and turned into `table` (float32 [592]: mean, 1 / sqrt(var + eps); 0 and 1 for
     prep_counter and self_type) by update().  Hand it to pack_policy_inputs(normaliser=...).  The arithmetic is stated
-    with hs_obs_norm_request in include/hideseek.h."""
+    with hs_obs_norm_request in include/hideseek.h.  `table`, if given, is the float32 [592] tensor (contiguous, 16-byte
+    aligned, on the GPU) the table is kept in, instead of one allocated here: the tables of N normalisers are then the
+    rows of one [N, 592] buffer, which is what pack_routed reads."""
 
-    def __init__(self, gpu_id, decay=0.99999, eps=1e-5):
+    def __init__(self, gpu_id, decay=0.99999, eps=1e-5, table=None):
         import torch
         self.gpu_id = int(gpu_id)
         self.decay, self.eps = _decay_eps(decay, eps)
         dev = torch.device("cuda", self.gpu_id)
+        self.table = torch.empty(NORM_TABLE, dtype=torch.float32, device=dev) if table is None else norm_table(table, self.gpu_id)
         self.state = torch.zeros(NORM_STATE, dtype=torch.float64, device=dev)
-        self.table = torch.empty(NORM_TABLE, dtype=torch.float32, device=dev)
         self.reset()
 
     def reset(self):
