@@ -1069,6 +1069,58 @@ typedef struct hs_pack_routed_request {
 int32_t hs_pack_policy_inputs_routed(hs_sim *sim, const hs_pack_routed_request *req);
 int32_t hs_pack_policy_inputs_routed_async(hs_sim *sim, void *hip_stream, const hs_pack_routed_request *req);
 
+/* The routed sampler: hs_sample_actions for a league or a population (one kernel, csrc/hs_k_sample_routed.h).  The logits
+ * are in SLOT order (the P forwards write blocks of one buffer), the actions the next step reads go out in ROW order, and
+ * what a learner stores stays in slot order.  With R = worlds * A rows and row_of_slot [R] i32 as hs_league_step writes it:
+ *   For slot s with r = row_of_slot[s] in [0, R), action_rows[r] and action[s], log_prob[s], entropy[s], head_log_prob[s]
+ *   have the BITS hs_sample_actions gives row r when it is handed a logits array whose row r is slot s's logits.
+ *   The uniform is keyed by the global agent row world_offset * A + r, not by the slot: a draw does not depend on the
+ *   routing.
+ *   A slot whose row is outside [0, R) writes all-zero bits to its slot-order outputs, writes no row, and is counted in
+ *   bad [1] i32 (or null), which the call zeroes first.  Rows named by no slot are left untouched.
+ *   row_of_slot from hs_league_step is a permutation.  With duplicates the row holds one of its writers' quintuples;
+ *   which one is unspecified.
+ * mode is HS_SAMPLE_DRAW or HS_SAMPLE_GREEDY; HS_SAMPLE_EVALUATE is refused (an update scores stored actions with
+ * hs_ppo_loss, which needs no routing).  flags must be 0.  action_rows null = the handle's action export.  action,
+ * log_prob, entropy and head_log_prob may each be null.
+ * Validation as hs_sample_actions (HS_ERR_INVALID_ARG, nothing written), and in addition: a null row_of_slot; a pointer
+ * not 4-byte aligned (logits: their element size); an output overlapping logits, row_of_slot or another output, the
+ * action export included when action_rows is null; every slot-order output null together with a non-null action_rows
+ * (hs_sample_actions on gathered logits does that).  Ordering and streams as hs_sample_actions. */
+typedef struct hs_sample_routed_request {
+    const void *logits;           /* [R][logits_stride] of logits_dtype, indexed by slot */
+    int32_t logits_dtype;         /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t logits_stride;        /* elements, >= sum of buckets */
+    int32_t buckets[HS_SAMPLE_HEADS];
+    int32_t mode;                 /* HS_SAMPLE_DRAW | HS_SAMPLE_GREEDY */
+    uint32_t flags;               /* 0 */
+    uint32_t seed[2];
+    uint32_t counter;
+    const int32_t *row_of_slot;   /* [R] i32 */
+    int32_t *action_rows;         /* [R][5] indexed by ROW; null = the simulator's own action export */
+    int32_t *action;              /* [R][5] indexed by slot, or null */
+    float *log_prob, *entropy;    /* [R] indexed by slot, either may be null */
+    float *head_log_prob;         /* [R][5] indexed by slot, or null */
+    int32_t *bad;                 /* [1] i32 or null */
+} hs_sample_routed_request;       /* 112 bytes */
+int32_t hs_sample_actions_routed(hs_sim *sim, const hs_sample_routed_request *req);
+int32_t hs_sample_actions_routed_async(hs_sim *sim, void *hip_stream, const hs_sample_routed_request *req);
+
+/* Grouped advantages: hs_compute_gae with one moments vector per group of rows (csrc/hs_k_gae.h).  The rows are
+ * `groups` = G groups of m = R / G consecutive rows: the slots of a population's policies.  advantage and returns are
+ * exactly hs_compute_gae's (per-row chains).  moments is [G][HS_GAE_MOMENTS] f64: vector g has the BITS hs_compute_gae
+ * writes on a handle of m rows that is given group g's columns as contiguous arrays (the grid is cut per group and each
+ * group's partial sums are added in that call's order).  Validation as hs_compute_gae, the moments range being
+ * G vectors, and in addition: groups outside [1, HS_LEAGUE_MAX_POLICIES] or not a divisor of R.  Workspace, ordering
+ * and streams as hs_compute_gae. */
+typedef struct hs_gae_grouped_request {
+    hs_gae_request gae;           /* moments: [groups][HS_GAE_MOMENTS] f64 or null */
+    int32_t groups;               /* G in [1, HS_LEAGUE_MAX_POLICIES]; R % G == 0 */
+    int32_t reserved;             /* 0 */
+} hs_gae_grouped_request;         /* 88 bytes */
+int32_t hs_compute_gae_grouped(hs_sim *sim, const hs_gae_grouped_request *req);
+int32_t hs_compute_gae_grouped_async(hs_sim *sim, void *hip_stream, const hs_gae_grouped_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

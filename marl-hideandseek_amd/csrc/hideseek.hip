@@ -36,6 +36,7 @@
 #include "hs_k_episode.h"                 // likewise: its two kernels are templates, emitted where launch_episode (after launch_gather) names them
 #include "hs_k_league.h"                  // likewise: emitted where launch_league (after launch_episode) names them
 #include "hs_k_pack_routed.h"             // likewise: emitted where launch_pack_routed (after launch_league) names it
+#include "hs_k_sample_routed.h"           // likewise: emitted where launch_sample_routed (after launch_pack_routed) names it
 #include "hs_k_adam.h"
 
 namespace {
@@ -96,7 +97,7 @@ struct hs_sim {
     int cam_cap = 0;
     double *pack_partials = nullptr;       // hs_pack_policy_inputs: the moments of each workgroup, [pack_grid][HS_PACK_MOMENTS]
     double *pack_routed_partials = nullptr;        // hs_pack_policy_inputs_routed: [N][pack_routed_grid][HS_PACK_MOMENTS], N G <= kPackMaxGrid for every N
-    double *gae_partials = nullptr;        // hs_compute_gae: the moments of each workgroup, [gae_grid][HS_GAE_MOMENTS]
+    double *gae_partials = nullptr;        // hs_compute_gae: the moments of each workgroup, [gae_grid][HS_GAE_MOMENTS]; grouped: [G][gae_grid(R / G)][..]
     double *ppo_partials = nullptr;        // hs_ppo_loss: the statistics of each workgroup, [kPpoMaxGrid][HS_PPO_STATS]
     int32_t *ppo_counts = nullptr;         // hs_ppo_loss: the active samples each workgroup of k_ppo_count saw, [kPpoCountGrid]
     double *twohot_partials = nullptr;     // hs_twohot_value: the statistics of each workgroup, [kTwMaxGrid][HS_TWOHOT_STATS]
@@ -511,9 +512,8 @@ static_assert(kExports[HS_EXPORT_REWARD].dtype == HS_DTYPE_F32 && kExports[HS_EX
               kExports[HS_EXPORT_REWARD].per_agent && kExports[HS_EXPORT_DONE].per_agent && kExports[HS_EXPORT_SELF_MASK].per_agent,
               "k_gae reads copies of the reward, done and self_mask exports");
 
-int check_gae(hs_sim *s, const hs_gae_request *r) {
-    const Check c{"hs_compute_gae"};
-    if (!r) return c.bad("null request");
+// What hs_compute_gae and hs_compute_gae_grouped check of a request: `groups` moments vectors.
+int check_gae_request(const Check &c, hs_sim *s, const hs_gae_request *r, int groups) {
     if (!r->reward) return c.bad("null reward");
     if (!r->done) return c.bad("null done");
     if (!r->value) return c.bad("null value");
@@ -531,8 +531,13 @@ int check_gae(hs_sim *s, const hs_gae_request *r) {
     HS_TRY(c.disjoint({range("reward", r->reward, n * 4), range("done", r->done, n * 4), range("value", r->value, n * vsize),
                        range("bootstrap", r->bootstrap, rows * vsize), range("mask", r->mask, n * 4)},
                       {range("advantage", r->advantage, n * 4), range("returns", r->returns, n * 4),
-                       range("moments", r->moments, HS_GAE_MOMENTS * sizeof(double))}));
+                       range("moments", r->moments, (uintptr_t)groups * HS_GAE_MOMENTS * sizeof(double))}));
     return c.handle_ready(s);
+}
+int check_gae(hs_sim *s, const hs_gae_request *r) {
+    const Check c{"hs_compute_gae"};
+    if (!r) return c.bad("null request");
+    return check_gae_request(c, s, r, 1);
 }
 // One k_gae over every agent row (the request has passed check_gae), then the fixed-order sum of the moments.
 int launch_gae(hs_sim *s, hipStream_t strm, const hs_gae_request *r) {
@@ -1298,6 +1303,88 @@ int launch_pack_routed(hs_sim *s, hipStream_t strm, const hs_pack_routed_request
 }
 }  // namespace
 
+// ---- the routed sampler (hs_k_sample_routed.h) ----
+namespace {
+static_assert(sizeof(hs_sample_routed_request) == 112 && offsetof(hs_sample_routed_request, logits_stride) == 12 && offsetof(hs_sample_routed_request, buckets) == 16 &&
+              offsetof(hs_sample_routed_request, mode) == 36 && offsetof(hs_sample_routed_request, seed) == 44 && offsetof(hs_sample_routed_request, counter) == 52 &&
+              offsetof(hs_sample_routed_request, row_of_slot) == 56 && offsetof(hs_sample_routed_request, action_rows) == 64 &&
+              offsetof(hs_sample_routed_request, action) == 72 && offsetof(hs_sample_routed_request, head_log_prob) == 96 && offsetof(hs_sample_routed_request, bad) == 104,
+              "hs_sample_routed_request layout (gpu_hideseek/action_sampling.py mirrors it)");
+
+int check_sample_routed(hs_sim *s, const hs_sample_routed_request *r) {
+    const Check c{"hs_sample_actions_routed"};
+    if (!r) return c.bad("null request");
+    if (!r->logits) return c.bad("null logits");
+    if (!r->row_of_slot) return c.bad("null row_of_slot");
+    HS_TRY(c.dtype(r->logits_dtype, "logits"));
+    if (r->mode != HS_SAMPLE_DRAW && r->mode != HS_SAMPLE_GREEDY) return c.bad("mode must be HS_SAMPLE_DRAW or HS_SAMPLE_GREEDY");
+    if (r->flags) return c.bad("flags must be 0");
+    int L;
+    HS_TRY(c.buckets(r->buckets, &L));
+    if (r->logits_stride < L) return c.bad("logits_stride is below the sum of the buckets");
+    if (!aligned(elem_size(r->logits_dtype), {r->logits})) return c.bad("logits must be aligned to their element size");
+    if (!aligned(4, {r->row_of_slot, r->action_rows, r->action, r->log_prob, r->entropy, r->head_log_prob, r->bad}))
+        return c.bad("row_of_slot, action_rows, action, log_prob, entropy, head_log_prob and bad must be 4-byte aligned");
+    if (r->action_rows && !r->action && !r->log_prob && !r->entropy && !r->head_log_prob)
+        return c.bad("every slot-order output is null and action_rows is given: hs_sample_actions on the gathered logits does that");
+    HS_TRY(c.handle_ready(s));
+    const uintptr_t rows = (uintptr_t)s->S.N * (uintptr_t)s->A;
+    if ((int64_t)rows * r->logits_stride >= (int64_t)1 << 31) return c.bad("rows * logits_stride must stay below 2^31");
+    return c.disjoint({range("logits", r->logits, ((rows - 1) * (uintptr_t)r->logits_stride + (uintptr_t)L) * elem_size(r->logits_dtype)),
+                       range("row_of_slot", r->row_of_slot, rows * 4)},
+                      {range("action_rows", r->action_rows ? r->action_rows : s->S.xAction, rows * HS_SAMPLE_HEADS * 4),
+                       range("action", r->action, rows * HS_SAMPLE_HEADS * 4), range("log_prob", r->log_prob, rows * 4), range("entropy", r->entropy, rows * 4),
+                       range("head_log_prob", r->head_log_prob, rows * HS_SAMPLE_HEADS * 4), range("bad", r->bad, 4)});
+}
+// bad zeroed, then one k_sample_routed over every slot (the request has passed check_sample_routed).
+int launch_sample_routed(hs_sim *s, hipStream_t strm, const hs_sample_routed_request *r) {
+    const hs::SimState &S = s->S;
+    hs::SampleRoutedArgs a = {};
+    a.s.logits = r->logits;
+    a.s.action = r->action_rows ? r->action_rows : S.xAction;
+    a.s.logProb = r->log_prob; a.s.entropy = r->entropy; a.s.headLogProb = r->head_log_prob;
+    a.s.L = pack_buckets(r->buckets, &a.s.bucketK, &a.s.bucketOff);
+    a.s.rows = S.N * s->A; a.s.stride = r->logits_stride; a.s.mode = r->mode;
+    a.s.seed0 = r->seed[0]; a.s.seed1 = r->seed[1]; a.s.counter = r->counter;
+    a.s.row0Global = (uint32_t)S.worldOffset * (uint32_t)s->A;
+    a.rowOfSlot = r->row_of_slot; a.actionSlots = r->action; a.bad = r->bad;
+    if (r->bad) HS_HIP(hipMemsetAsync(r->bad, 0, sizeof(int32_t), strm));
+    const dim3 grid(hs::sample_grid(a.s.rows)), blk(hs::kSampleThreads);
+    with_elem(r->logits_dtype, [&](auto t) { hipLaunchKernelGGL(hs::k_sample_routed<decltype(t)>, grid, blk, 0, strm, a); });
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
+// ---- grouped advantages (hs_k_gae.h) ----
+namespace {
+static_assert(sizeof(hs_gae_grouped_request) == 88 && offsetof(hs_gae_grouped_request, groups) == 80, "hs_gae_grouped_request layout (gpu_hideseek/advantages.py mirrors it)");
+
+int check_gae_grouped(hs_sim *s, const hs_gae_grouped_request *r) {
+    const Check c{"hs_compute_gae_grouped"};
+    if (!r) return c.bad("null request");
+    if (r->groups < 1 || r->groups > HS_LEAGUE_MAX_POLICIES) return c.bad("groups must be in [1, HS_LEAGUE_MAX_POLICIES]");
+    if (((int64_t)s->S.N * s->A) % r->groups) return c.bad("the number of agent rows must be a multiple of groups");
+    return check_gae_request(c, s, &r->gae, r->groups);
+}
+// One k_gae_grouped over every agent row (the request has passed check_gae_grouped), then the fixed-order sum of each
+// group's moments: k_partials_sum as launch_gae instantiates it.
+int launch_gae_grouped(hs_sim *s, hipStream_t strm, const hs_gae_grouped_request *g) {
+    const hs_gae_request *r = &g->gae;
+    const int rows = s->S.N * s->A, m = rows / g->groups, parts = hs::gae_grid(m);
+    const hs::GaeGroupedArgs a = {{r->reward, r->done, r->value, r->bootstrap, r->mask, r->advantage, r->returns,
+                                   r->moments ? s->gae_partials : nullptr, rows, r->steps, r->gamma, r->lambda}, m};
+    const dim3 grid(parts, g->groups), blk(hs::kGaeThreads);
+    with_elem(r->value_dtype, [&](auto t) { hipLaunchKernelGGL(hs::k_gae_grouped<decltype(t)>, grid, blk, 0, strm, a); });
+    if (r->moments)
+        for (int q = 0; q < g->groups; ++q)
+            launch_partials_sum<double, hs::kGaeMoments, hs::kGaeSumSegs>(strm, s->gae_partials + (size_t)q * parts * hs::kGaeMoments, parts, hs::kGaeMoments,
+                                                                          r->moments + (size_t)q * hs::kGaeMoments);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1440,7 +1527,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
         HS_ALLOC(s->pack_partials, (size_t)hs::pack_grid((int)R) * hs::kPackMoments);
         HS_ALLOC(s->pack_routed_partials, std::min<size_t>(hs::kPackMaxGrid, R / hs::kPackRows + hs::kLeagueMaxPolicies) * hs::kPackMoments);   // N G <= both, for every N
     }
-    HS_ALLOC(s->gae_partials, (size_t)hs::gae_grid((int)R) * hs::kGaeMoments);
+    HS_ALLOC(s->gae_partials, (size_t)(hs::gae_grid((int)R) + hs::kLeagueMaxPolicies) * hs::kGaeMoments);      // G gae_grid(R / G) <= that, for every G
     HS_ALLOC(s->ppo_partials, (size_t)hs::kPpoMaxGrid * hs::kPpoStats); HS_ALLOC(s->ppo_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->twohot_partials, (size_t)hs::kTwMaxGrid * hs::kTwStats); HS_ALLOC(s->twohot_counts, hs::kPpoCountGrid);
     HS_ALLOC(s->embed_partials, (size_t)hs::kRowsMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
@@ -1789,6 +1876,10 @@ int32_t hs_league_step(hs_sim *s, const hs_league_request *req) { return call_bl
 int32_t hs_league_step_async(hs_sim *s, void *hip_stream, const hs_league_request *req) { return call_async(s, hip_stream, check_league, launch_league, req); }
 int32_t hs_pack_policy_inputs_routed(hs_sim *s, const hs_pack_routed_request *req) { return call_blocking(s, check_pack_routed, launch_pack_routed, req); }
 int32_t hs_pack_policy_inputs_routed_async(hs_sim *s, void *hip_stream, const hs_pack_routed_request *req) { return call_async(s, hip_stream, check_pack_routed, launch_pack_routed, req); }
+int32_t hs_sample_actions_routed(hs_sim *s, const hs_sample_routed_request *req) { return call_blocking(s, check_sample_routed, launch_sample_routed, req); }
+int32_t hs_sample_actions_routed_async(hs_sim *s, void *hip_stream, const hs_sample_routed_request *req) { return call_async(s, hip_stream, check_sample_routed, launch_sample_routed, req); }
+int32_t hs_compute_gae_grouped(hs_sim *s, const hs_gae_grouped_request *req) { return call_blocking(s, check_gae_grouped, launch_gae_grouped, req); }
+int32_t hs_compute_gae_grouped_async(hs_sim *s, void *hip_stream, const hs_gae_grouped_request *req) { return call_async(s, hip_stream, check_gae_grouped, launch_gae_grouped, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

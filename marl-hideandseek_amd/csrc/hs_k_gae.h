@@ -135,4 +135,50 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(GaeArgs a) {
     }
 }
 
+// The grouped form (hs_compute_gae_grouped): the rows are G groups of m = rows / G consecutive rows (the slots of a
+// population's policies), the chains are k_gae's, and the moments are one vector per group.  The grid is cut per group:
+// blockIdx.y is the group and has gae_grid(m) workgroups, workgroup x of group g takes the rows g m + 64 x .. and a lane
+// past m is idle, so the lanes a workgroup adds, and the gae_grid(m) partials k_partials_sum adds per group, are those of
+// k_gae on a handle of m rows that is given the group's columns: the moments of a group have that call's bits.  The
+// partials are [G][gae_grid(m)][kGaeMoments].  The body repeats k_gae's text around gae_row, which stays as it is there
+// so that k_gae compiles to the code it had.
+struct GaeGroupedArgs {
+    GaeArgs a;                            // rows = all rows
+    int perGroup;                         // m
+};
+
+template <typename T>
+__global__ __launch_bounds__(kGaeThreads) void k_gae_grouped(GaeGroupedArgs g) {
+    GaeArgs a = g.a;                                      // the group's view: its first row is row 0, a time slice is still a.rows long
+    const size_t first = (size_t)blockIdx.y * (size_t)g.perGroup;
+    a.reward += first; a.done += first;
+    a.value = (const T *)a.value + first; a.bootstrap = (const T *)a.bootstrap + first;
+    if (a.mask) a.mask += first;
+    if (a.advantage) a.advantage += first;
+    if (a.returns) a.returns += first;
+    const uint32_t row = blockIdx.x * kGaeThreads + threadIdx.x;
+    GaeSums sum = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (row < (uint32_t)g.perGroup) {
+        const bool both = a.advantage && a.returns;
+        if (a.mask) {
+            if (a.partials) { if (both) gae_row<T, true, true, true>(a, row, sum); else gae_row<T, true, true, false>(a, row, sum); }
+            else { if (both) gae_row<T, true, false, true>(a, row, sum); else gae_row<T, true, false, false>(a, row, sum); }
+        } else {
+            if (a.partials) { if (both) gae_row<T, false, true, true>(a, row, sum); else gae_row<T, false, true, false>(a, row, sum); }
+            else { if (both) gae_row<T, false, false, true>(a, row, sum); else gae_row<T, false, false, false>(a, row, sum); }
+        }
+    }
+    if (a.partials) {                                     // lane q < kGaeMoments adds moment q of the lanes in lane order
+        __shared__ double red[kGaeMoments][kGaeThreads];
+        const int tid = threadIdx.x;
+        red[0][tid] = sum.adv; red[1][tid] = sum.adv2; red[2][tid] = sum.ret; red[3][tid] = sum.ret2; red[4][tid] = sum.n;
+        __syncthreads();
+        if (tid < kGaeMoments) {
+            double s = red[tid][0];
+            for (int k = 1; k < kGaeThreads; ++k) s += red[tid][k];
+            a.partials[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kGaeMoments + tid] = s;
+        }
+    }
+}
+
 }  // namespace hs

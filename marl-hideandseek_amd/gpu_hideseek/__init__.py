@@ -190,8 +190,23 @@ class HideAndSeekSimulator:
                                       action=action, log_prob=log_prob, entropy=entropy, head_log_prob=head_log_prob,
                                       zero_inactive=zero_inactive)
 
+    def sample_actions_routed(self, logits, row_of_slot, *, buckets=(5, 5, 5, 2, 2), mode="draw", seed=(0, 0), counter=0, action_rows=None,
+                              action=None, log_prob=None, entropy=None, head_log_prob=None, bad=None, stream=None):
+        """sample_actions for policies that share this simulator, in one kernel (gpu_hideseek.action_sampling.sample_routed;
+        hs_sample_actions_routed): `logits` [rows, W >= sum(buckets)] are indexed by SLOT and `row_of_slot` (int32 [rows], as
+        league_step writes it) names each slot's agent row.  The actions go to `action_rows`, indexed by row (None: in
+        place into action_tensor(), ready for the next step); `action` [rows, 5], `log_prob`, `entropy` [rows] and
+        `head_log_prob` [rows, 5], each True, a tensor or None, stay indexed by slot.  Every value has the bits
+        sample_actions gives the row from the same logits, seed and counter.  mode is "draw" or "greedy".  `bad`, True,
+        int32 [1] or None, receives the number of slots whose row is out of range (their outputs are zeros and no row is
+        written).  Returns {name: tensor}."""
+        from . import action_sampling
+        return action_sampling.sample_routed(self, logits, row_of_slot, stream, buckets=buckets, mode=mode, seed=seed, counter=counter,
+                                             action_rows=action_rows, action=action, log_prob=log_prob, entropy=entropy,
+                                             head_log_prob=head_log_prob, bad=bad)
+
     def compute_advantages(self, rewards, dones, values, bootstrap, *, gamma=0.998, gae_lambda=0.95, mask=None,
-                           advantages=True, returns=True, moments=None, stream=None):
+                           advantages=True, returns=True, moments=None, groups=None, stream=None):
         """GAE advantages and value targets of a rollout in one kernel (gpu_hideseek.advantages; hs_compute_gae, whose
         header comment states the arithmetic: IEEE f32 in a fixed order, the same bits on every call).  `rewards`
         (float32), `dones` (int32: nonzero = the episode ended with step t), `values` (float32, bfloat16 or float16: the
@@ -200,11 +215,13 @@ class HideAndSeekSimulator:
         `bootstrap` [rows] is the value of the observation after the last step, in the dtype of `values`.
         `advantages` and `returns` are each True (a new float32 tensor shaped like `rewards`), a preallocated tensor or
         None; `moments` likewise, [5] float64: sum and sum of squares of the advantages and of the returns and the count,
-        over the active steps (advantages.moments_to_mean_std).  stream=None blocks; a torch.cuda.Stream or raw handle
+        over the active steps (advantages.moments_to_mean_std).  With `groups` = G the rows are G groups of rows / G
+        consecutive rows (the slots of a population's policies) and `moments` is [G, 5], vector g with the bits of this call
+        on group g's columns alone (hs_compute_gae_grouped).  stream=None blocks; a torch.cuda.Stream or raw handle
         enqueues there without synchronising.  Returns {name: tensor} of what was written."""
         from . import advantages as _advantages
         return _advantages.compute(self, rewards, dones, values, bootstrap, stream, gamma=gamma, gae_lambda=gae_lambda,
-                                   mask=mask, advantages=advantages, returns=returns, moments=moments)
+                                   mask=mask, advantages=advantages, returns=returns, moments=moments, groups=groups)
 
     def ppo_loss(self, logits, action, old_log_prob, advantage, *, buckets=(5, 5, 5, 2, 2), adv_moments=None, mask=None, value=None,
                  returns=None, old_value=None, clip_coef=0.2, value_loss_coef=0.5, entropy_coef=0.01, grad_scale=1.0,

@@ -29,6 +29,14 @@ class HsGaeRequest(C.Structure):
                 ("lambda", C.c_float), ("advantage", C.c_void_p), ("returns", C.c_void_p), ("moments", C.c_void_p)]
 
 
+class HsGaeGroupedRequest(C.Structure):
+    """hs_gae_grouped_request (include/hideseek.h)."""
+    _fields_ = [("gae", HsGaeRequest), ("groups", C.c_int32), ("reserved", C.c_int32)]
+
+
+MAX_GROUPS = 16       # HS_LEAGUE_MAX_POLICIES
+
+
 def moments_to_mean_std(moments):
     """{"count": n, "advantages": (mean, std), "returns": (mean, std)} in float64 from the moments of
     compute_advantages: the statistics (biased standard deviation) of the active (t, row) pairs, for the advantage
@@ -47,12 +55,20 @@ def moments_to_mean_std(moments):
 
 
 def request(num_worlds, agents, gpu_id, rewards, dones, values, bootstrap, gamma=DEFAULT_GAMMA, gae_lambda=DEFAULT_LAMBDA,
-            mask=None, advantages=True, returns=True, moments=None):
+            mask=None, advantages=True, returns=True, moments=None, groups=None):
     """Validate a call over num_worlds x agents agent rows on GPU `gpu_id`, allocate the outputs given as True, and
-    return ({name: tensor}, HsGaeRequest).  Raises ValueError before the library is involved."""
+    return ({name: tensor}, HsGaeRequest).  With `groups` = G (an integer in [1, MAX_GROUPS] that divides the rows) the
+    rows are G groups of rows / G consecutive rows, `moments` is [G, 5], one vector per group, and the request is an
+    HsGaeGroupedRequest (hs_compute_gae_grouped).  Raises ValueError before the library is involved."""
     import torch
     dev = torch.device("cuda", gpu_id)
     rows = num_worlds * agents
+    if groups is not None:
+        if isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups <= MAX_GROUPS:
+            raise ValueError(f"groups must be None or an integer in [1, {MAX_GROUPS}], got {groups!r}")
+        if rows % groups:
+            raise ValueError(f"the number of agent rows ({rows}) must be a multiple of groups ({groups})")
+    mshape = (MOMENTS,) if groups is None else (groups, MOMENTS)
     gamma, gae_lambda = float(gamma), float(gae_lambda)
     if not (math.isfinite(gamma) and 0.0 <= gamma <= 1.0):
         raise ValueError(f"gamma must be finite and in [0, 1], got {gamma}")
@@ -75,13 +91,13 @@ def request(num_worlds, agents, gpu_id, rewards, dones, values, bootstrap, gamma
     given = {k: t for k, t in outputs.items() if t is not True}
     for k, t in given.items():
         if k == "moments":
-            _tensor(k, t, (MOMENTS,), ("float64",), dev, _OUTPUT)
+            _tensor(k, t, mshape, ("float64",), dev, _OUTPUT)
         else:
             _tensor(k, t, per_step(steps), ("float32",), dev, _OUTPUT)
     # overlaps are left to the library, which refuses them: only the devices are looked at here, and last
     _disjoint([], [(k, t) for k, t in (("rewards", rewards), ("dones", dones), ("values", values), ("bootstrap", bootstrap), ("mask", mask),
                                        *given.items()) if t is not None], dev)
-    res = {k: given[k] if k in given else torch.empty((MOMENTS,) if k == "moments" else tuple(rewards.shape),
+    res = {k: given[k] if k in given else torch.empty(mshape if k == "moments" else tuple(rewards.shape),
                                                       dtype=torch.float64 if k == "moments" else torch.float32, device=dev) for k in outputs}
 
     def ptr(k):
@@ -89,13 +105,15 @@ def request(num_worlds, agents, gpu_id, rewards, dones, values, bootstrap, gamma
     req = HsGaeRequest(rewards.data_ptr(), dones.data_ptr(), values.data_ptr(), bootstrap.data_ptr(),
                        mask.data_ptr() if mask is not None else None, _DTYPES[_name(values.dtype)], steps, gamma,
                        gae_lambda, ptr("advantages"), ptr("returns"), ptr("moments"))
+    if groups is not None:
+        req = HsGaeGroupedRequest(req, groups, 0)
     return res, req
 
 
 def compute(sim, rewards, dones, values, bootstrap, stream=None, **kw):
     """HideAndSeekSimulator.compute_advantages."""
     res, req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, rewards, dones, values, bootstrap, **kw)
-    _run(sim, "hs_compute_gae", req, stream)
+    _run(sim, "hs_compute_gae_grouped" if isinstance(req, HsGaeGroupedRequest) else "hs_compute_gae", req, stream)
     return res
 
 

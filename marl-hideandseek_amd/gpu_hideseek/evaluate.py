@@ -12,7 +12,8 @@ sim.step(), EpisodeStats.step().  The normaliser is frozen: no moments are colle
 run leaves the policy and the normaliser as it found them.
 
 One policy plays both sides here.  Several policies playing each other, with their Elo ratings (the reference's
-eval_competitive with num_policies > 1), is gpu_hideseek.league and tools/league.py.  PBT training itself is not here.
+eval_competitive with num_policies > 1), is gpu_hideseek.league and tools/league.py.  Training several policies at once is
+gpu_hideseek.population.
 """
 from . import episodes, replay, rollout
 from ._request import on_current_stream
@@ -20,15 +21,27 @@ from ._request import on_current_stream
 MODES = ("draw", "greedy")
 
 
-def load_policy(path_or_dict, dtype=None, device=None):
+def members(d):
+    """The trainer state_dicts in a checkpoint: the members of a population's (population.Population.state_dict), or the
+    one of a trainer's."""
+    return list(d["members"]) if "members" in d else [d]
+
+
+def load_policy(path_or_dict, dtype=None, device=None, member=None):
     """(net, normaliser or None) from a trainer state_dict (a file torch.save wrote, or the dict): a policy.make_policy
     of `dtype` whose parameters are the state's flat "params" buffer, laid out as the state's optimiser says, and an
-    ObsNormaliser with the state's moments where the trainer had one."""
+    ObsNormaliser with the state's moments where the trainer had one.  Of a population's checkpoint, `member` i."""
     import torch
     from . import optim, policy
     from .policy_inputs import ObsNormaliser
     device = torch.device("cuda", 0) if device is None else torch.device(device)
     d = torch.load(path_or_dict, map_location=device, weights_only=False) if not isinstance(path_or_dict, dict) else path_or_dict
+    if "members" in d:
+        if member is None or not 0 <= member < len(d["members"]):
+            raise ValueError(f"a population checkpoint of {len(d['members'])} members: member must be in [0, {len(d['members'])}), got {member!r}")
+        d = d["members"][member]
+    elif member not in (None, 0):
+        raise ValueError(f"a trainer checkpoint has one policy: member must be None or 0, got {member!r}")
     net = policy.make_policy(dtype).to(device)
     flat = optim.flatten(net.named_parameters(), device)
     theirs = {k: (int(lo), int(hi), tuple(shape)) for k, (lo, hi, shape) in d["optimizer"]["layout"].items()}

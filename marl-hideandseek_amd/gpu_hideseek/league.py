@@ -17,7 +17,8 @@ rated against the ratings before it.
 
 host_step is the contract in plain numpy (int64 counts, float64 ratings, the same pair order): the tests' reference, and
 it needs no GPU.  Single device: there is no ShardedSimulator form, because the ratings would have to cross the shards.
-PBT training itself (several train states, hyper-parameter exploration, past-policy pools) is not here.
+Training several policies at once on this schedule (several train states, live ratings, hyper-parameter exploration) is
+gpu_hideseek.population; pools of past policies are not implemented.
 """
 import ctypes as C
 import math
@@ -256,7 +257,7 @@ class League:
         self.gathered = {} if self.routed else {net.dtype: torch.zeros(1, m, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
         self.tables = torch.zeros(P, policy_inputs.NORM_TABLE, dtype=torch.float32, device=dev)
         self.logits_by_slot = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
-        self.logits = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
+        self._acted_slot = torch.zeros(R, **i32)          # `slot` as the last act() had it: the routing its logits belong to
         self.state = [net.actor.init_state(m, dev, net.dtype) for net in nets]
         self.counter = 0
         self.episodes = None
@@ -318,9 +319,17 @@ class League:
                 y, self.state[p] = net.actor(sim, mine, self.state[p], None)
                 head = net.actor_head
                 self.logits_by_slot[0, block] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype)).float()
-            sim.gather_sequences(self.slot, [(self.logits_by_slot, self.logits, False)], chunks=1, chunk_steps=1, rows=R)
-            sim.sample_actions(self.logits[0], buckets=self.policies[0][0].buckets, mode=self.mode, seed=(self.seed, 0), counter=self.counter)
+            # slot-order logits -> row-order actions in one launch, with the bits sample_actions gives the gathered logits
+            sim.sample_actions_routed(self.logits_by_slot[0], self.row_of_slot, buckets=self.policies[0][0].buckets, mode=self.mode, seed=(self.seed, 0),
+                                      counter=self.counter)
+            self._acted_slot.copy_(self.slot)
         self.counter += 1
+
+    @property
+    def logits(self):
+        """The logits of the last act() in ROW order, [1, R, L] float32: gathered from logits_by_slot on request (act()
+        itself samples from the slot order)."""
+        return self.logits_by_slot[:, self._acted_slot.long()]
 
     def run(self, num_steps, record_log=None, on_step=None):
         """num_steps times: act(), sim.step(), the league's step, the attached episode tracker's; with `record_log` (a

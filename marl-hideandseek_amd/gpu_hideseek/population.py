@@ -1,0 +1,432 @@
+"""Population training: P policies learn at once on one simulator under the league's fixed schedule (the function of the
+reference's scripts/jax_train.py --pbt-ensemble-size N): the two sides improve against each other, not against a copy of
+themselves.  Composition only, as gpu_hideseek.trainer is: the league's routing (hs_league_step), the routed pack, the
+routed sampler, grouped advantages, and per policy the trainer's update.  Single device, like Trainer and League.
+
+    sim.init()
+    pop = population.Population(sim, population.PopulationConfig(num_policies=4, team_size=3, pbt_interval=10))
+    for _ in range(updates):
+        out = pop.update_iter()             # {"policies": [metrics per policy], "elo": [...], "games": n, "bad": n, "update": i, "fps": ...}
+
+Everything is in SLOT order.  With R agent rows and m = R / P, policy p owns slots [p m, (p + 1) m) at every step,
+whatever RandomFlipTeams does (league.py states the schedule), so the rollout is one shared rollout.Rollout of R rows whose
+columns are slots, a policy's part of every [T, R, ...] buffer is the column block p, its forward is one call of fixed
+shape on a block of one [R, 296] buffer, and its sequence ids are k R + p m + r' for a permutation of K m.
+
+collect() follows Trainer.collect()'s time alignment (rollout.py states it).  Per slot t: sim.step() -> the attached
+episode tracker's step() -> slot t - 1 is CLOSED: the reward and done exports are gathered into reward[t - 1] and
+done[t - 1] with the routing of BEFORE this step (one gather_sequences call with two fields), because the reward of an
+episode's last step belongs to the slot the row held when it acted, and the step that ends an episode may flip the teams
+-> hs_league_step: the new routing, the games that ended, the ratings -> clear[t] = clear_slot -> the carried LSTM states
+zeroed where clear_slot != 0 (the teams are full, so mask is 1 everywhere; a malformed world is counted in "bad") -> the
+routed pack into actor[t], critic[t] and moments[:, t] -> at a chunk's first slot the snapshots of the carried states -> P
+forwards on blocks -> one value_head decode over R rows -> one sample_actions_routed into the action export (row order),
+action[t] and log_prob[t] (slot order).  A world's rows hold the same set of slots before and after a flip and done is the
+same for every row of a world, so clear[t + 1] == done[t] holds slot for slot.
+The league step runs EXACTLY ONCE per sim.step(): after the closing step of a rollout it is run there, and the next
+collect() reuses that routing and clear_slot as Trainer reuses the exports, otherwise the games of that step would be
+booked twice.  After the rollout: the bootstrap (a critic-only routed pack without moments, P critic forwards on the
+carried critic states, which stay as they are, one decode), one compute_advantages(groups=P) whose moments [P, 5] are per
+policy, and P normaliser updates from moments[p].
+
+update() runs, per policy in turn, the trainer's epochs (Trainer.run_epochs: the gather with rows = R, net.sequence,
+ppo_loss with adv_moments[p] and the policy's entropy_coef, value_head, backward, Adam with the policy's lr), then reads
+every policy's metrics, the ratings and the counts in ONE copy to the host.
+
+Exploit / explore.  madrona_learn's PBT is not in the reference's tree: this contract is the project's own.  With
+pbt_interval = N > 0, after every N-th update and on the ratings just read, plan_exploit ranks the policies by rating
+(highest first, ties to the lower index); the lowest n = max(1, floor(P * exploit_fraction)) are replaced, each by a source
+drawn uniformly from the top n (exploit_fraction <= 0.5, so dst == src never occurs; with P < 2 nothing happens).  Applying
+(dst, src): dst takes src's flat parameters, Adam's m, v and state, the normaliser's state and table row, and src's
+rating; dst's lr and entropy_coef each become src's times a scale drawn from explore_scales, clamped to the base value
+times explore_range (the reference's ParamExplore bounds, 0.1 .. 10).  The carried LSTM states stay.  One
+numpy.random.Generator(cfg.seed) draws everything, on the host; nothing beyond the metrics read waits for the device.
+Pools of past policies (--pbt-past-policies) are out of scope.
+
+state_dict() is {"members": [...], "league", "hyper", "update_index", "counter"}; a member has Trainer.state_dict()'s
+keys, so evaluate.load_policy(state["members"][i]) reads it.  After load_state_dict() the next collect() steps the
+simulator before its slot 0, as the Trainer's does.
+"""
+import dataclasses
+import math
+import time
+
+from . import advantages, league, optim, policy, policy_inputs, rollout, trainer
+from ._request import _run, on_current_stream
+from .policy_inputs import ObsNormaliser
+
+
+@dataclasses.dataclass
+class PopulationConfig(trainer.TrainConfig):
+    """TrainConfig's knobs (lr and entropy_coef are the base values every policy starts from) and the population's."""
+    num_policies: int = 2
+    team_size: int = 3
+    k_factor: float = league.DEFAULT_K_FACTOR
+    pbt_interval: int = 0                 # exploit / explore after every N-th update; 0: never
+    exploit_fraction: float = 0.25
+    explore_scales: tuple = (0.8, 1.25)
+    explore_range: tuple = (0.1, 10.0)
+
+
+def check_population_config(cfg, num_worlds, agents):
+    """Raise ValueError for a config that does not fit the simulator: the league's shape rules, trainer.check_config with
+    rows = m (a policy's slots), and the exploit / explore knobs."""
+    league._league_shape(num_worlds, agents, cfg.num_policies, cfg.team_size)
+    league._k_factor(cfg.k_factor)
+    trainer.check_config(cfg, num_worlds * agents // cfg.num_policies)
+    if isinstance(cfg.pbt_interval, bool) or not isinstance(cfg.pbt_interval, int) or cfg.pbt_interval < 0:
+        raise ValueError(f"pbt_interval must be an integer of at least 0, got {cfg.pbt_interval!r}")
+    _fraction(cfg.exploit_fraction)
+    scales = tuple(cfg.explore_scales)
+    if not scales or any(not (math.isfinite(float(s)) and float(s) > 0.0) for s in scales):
+        raise ValueError(f"explore_scales must be a non-empty tuple of finite factors above 0, got {cfg.explore_scales!r}")
+    _range(cfg.explore_range)
+
+
+def _fraction(fraction):
+    f = float(fraction)
+    if not 0.0 < f <= 0.5:
+        raise ValueError(f"exploit_fraction must be in (0, 0.5], got {fraction!r}")
+    return f
+
+
+def _range(explore_range):
+    try:
+        lo, hi = (float(x) for x in explore_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"explore_range must be a pair (low, high), got {explore_range!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= 1.0 <= hi):
+        raise ValueError(f"explore_range must be finite with 0 < low <= 1 <= high, got {explore_range!r}")
+    return lo, hi
+
+
+def plan_exploit(elo, fraction, rng):
+    """[(dst, src)] for ratings `elo` (a list of P numbers): the module docstring states the rule.  A pure host function;
+    `rng` is a numpy.random.Generator and draws one integer per pair."""
+    f = _fraction(fraction)
+    vals = [float(e) for e in elo]
+    P = len(vals)
+    if P < 2:
+        return []
+    order = sorted(range(P), key=lambda i: (-vals[i], i))
+    n = max(1, int(math.floor(P * f)))
+    return [(dst, order[int(rng.integers(n))]) for dst in order[P - n:]]
+
+
+def explore(value, base, scales, explore_range, rng):
+    """`value` times a scale drawn from `scales` by `rng`, clamped to [base * low, base * high]."""
+    lo, hi = _range(explore_range)
+    scale = float(scales[int(rng.integers(len(scales)))])
+    return min(max(float(value) * scale, float(base) * lo), float(base) * hi)
+
+
+class _Member(trainer.Trainer):
+    """One policy of a population as the Trainer's update sees it: its net, optimiser, normaliser, permutation generator,
+    statistics and config (with its own lr and entropy_coef), on the SHARED rollout, of which it owns the column block
+    [first, first + rows).  collect() is the population's."""
+
+    def __init__(self, pop, index, net, table):
+        import torch
+        sim, cfg, dev = pop.sim, pop.cfg, pop.device
+        self.sim, self.fused, self.index = sim, pop.fused, index
+        self.cfg = dataclasses.replace(cfg)               # lr and entropy_coef change under exploration
+        self.rows, self.first, self.total_rows = pop.block, index * pop.block, pop.rows
+        self.dtype, self.device = pop.dtype, dev
+        if net is None:
+            net = policy.make_policy(self.dtype, generator=torch.Generator().manual_seed(cfg.seed + index))
+        self.net = net.to(dev).set_fused(self.fused)
+        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm)
+        self.normaliser = ObsNormaliser(sim.gpu_id, table=table) if cfg.normalise_obs else None
+        self.rollout = pop.rollout
+        self.state = self.net.init_state(self.rows, dev, self.dtype)
+        self.clear = pop.clear[self.first:self.first + self.rows]
+        self.adv_moments = pop.adv_moments[index]
+        self.generator = torch.Generator(device=dev).manual_seed(cfg.seed + index)
+        self.update_index, self.counter, self.stepped = 0, 0, False
+        self._mb, self.phases, self.episodes = None, None, None
+        E = cfg.num_epochs
+        self.ppo_stats = torch.zeros(E, trainer.PPO_STATS, dtype=torch.float64, device=dev)
+        self.value_stats = torch.zeros(E, trainer.VALUE_STATS, dtype=torch.float64, device=dev)
+        self.adam_stats = torch.zeros(3, dtype=torch.float64, device=dev)
+        self._ppo_out = torch.zeros(trainer.PPO_STATS, dtype=torch.float64, device=dev)
+        self._value_out = torch.zeros(trainer.VALUE_STATS, dtype=torch.float64, device=dev)
+
+    lr = property(lambda self: self.opt.param_groups[0]["lr"])
+    entropy_coef = property(lambda self: self.cfg.entropy_coef)
+
+    def set_hyper(self, lr, entropy_coef):
+        self.opt.param_groups[0]["lr"] = float(lr)
+        self.cfg.entropy_coef = float(entropy_coef)
+
+    def permutation(self):
+        """A permutation of the policy's K m sequences, mapped on the device to the ids k R + first + r' of the shared rollout."""
+        import torch
+        m, R = self.rows, self.total_rows
+        perm = torch.randperm(self.rollout.chunks * m, generator=self.generator, device=self.device, dtype=torch.int32)
+        if m == R:
+            return perm
+        return torch.div(perm, m, rounding_mode="floor") * R + (self.first + perm % m)
+
+    def collect(self):
+        raise NotImplementedError("a member's rollout is Population.collect()'s")
+
+
+class Population:
+    """cfg.num_policies policies (policy.make_policy, policy p seeded cfg.seed + p, unless `nets` gives them), each with its
+    optim.Adam, ObsNormaliser and permutation generator, on one simulator right after sim.init(): equal fixed teams of
+    cfg.team_size and a number of worlds that is a multiple of num_policies^2.  The module docstring states the loop.
+    `phases` (a trainer.PhaseTimer) and `episodes` (an episodes.EpisodeStats) work as on Trainer."""
+
+    def __init__(self, sim, cfg=None, nets=None, fused=True):
+        import numpy as np
+        import torch
+        self.sim, self.cfg, self.fused = sim, PopulationConfig() if cfg is None else cfg, bool(fused)
+        cfg = self.cfg
+        check_population_config(cfg, sim.num_worlds, sim.agents_per_world)
+        self.num_policies = P = cfg.num_policies
+        self.rows = R = sim.num_worlds * sim.agents_per_world
+        self.block = m = R // P
+        if nets is not None and len(nets) != P:
+            raise ValueError(f"nets must be None or {P} policies, got {len(nets)}")
+        self.dtype = torch.float32 if cfg.dtype is None else cfg.dtype
+        self.device = dev = torch.device("cuda", sim.gpu_id)
+        T = cfg.steps_per_update
+        i32 = dict(dtype=torch.int32, device=dev)
+        # the league's state, as League holds it: counts | elo | the malformed worlds of all calls in one buffer
+        self.slot, self.row_of_slot, self.clear_slot = (torch.zeros(R, **i32) for _ in range(3))
+        self.bad = torch.zeros(1, **i32)
+        self.world = league.new_state(sim.num_worlds, dev)
+        n = P * P * league.OUTCOMES
+        self._table = torch.zeros(n + P + 1, dtype=torch.int64, device=dev)
+        self.counts = self._table[:n].view(P, P, league.OUTCOMES)
+        self.elo = self._table[n:n + P].view(torch.float64)
+        self.bad_total = self._table[n + P:]
+        self.elo.fill_(league.INITIAL_ELO)
+        self._league_req = league.request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, P, cfg.team_size, self.world, self.counts, self.elo, cfg.k_factor,
+                                          slot=self.slot, row_of_slot=self.row_of_slot, clear_slot=self.clear_slot, bad=self.bad)[1]
+        self.tables = torch.zeros(P, policy_inputs.NORM_TABLE, dtype=torch.float32, device=dev)
+        self.tables[:, policy_inputs.ROW:] = 1.0
+        self.clear = torch.zeros(R, **i32)                # clear_slot of a rollout's closing step: clear[0] of the next
+        self.adv_moments = torch.zeros(P, advantages.MOMENTS, dtype=torch.float64, device=dev)
+        nets = [None] * P if nets is None else list(nets)
+        if nets[0] is None:                               # the rollout needs the hidden width before the members need the rollout
+            nets[0] = policy.make_policy(self.dtype, generator=torch.Generator().manual_seed(cfg.seed))
+        hidden = nets[0].actor.core.hidden
+        self.rollout = rollout.Rollout(sim, T, cfg.num_bptt_chunks, self.dtype, hidden=hidden)
+        self.rollout.mask.fill_(1.0)                      # the teams are full
+        self.members = [_Member(self, p, nets[p], self.tables[p]) for p in range(P)]
+        if any(mb.net.buckets != self.members[0].net.buckets or mb.net.actor.core.hidden != hidden for mb in self.members):
+            raise ValueError("every policy must have the same action heads and hidden width")
+        self.buckets = self.members[0].net.buckets
+        self.moments = torch.zeros(P, T, rollout.MOMENTS, dtype=torch.float64, device=dev)
+        self.logits = torch.zeros(R, sum(self.buckets), dtype=self.dtype, device=dev)
+        self.critic_logits = torch.zeros(R, self.members[0].net.bins, dtype=self.dtype, device=dev)
+        self.boot_rows = torch.zeros(R, rollout.ROW, dtype=self.dtype, device=dev)
+        self.bootstrap = torch.zeros(R, dtype=torch.float32, device=dev)
+        self.rng = np.random.Generator(np.random.PCG64(cfg.seed))
+        self.update_index, self.counter = 0, 0
+        self.stepped = False
+        self.phases, self.episodes = None, None
+        self.league_step()                                # routes the rows as they stand and latches the team orders; books no game
+
+    # ---- what the policies hold ----
+    nets = property(lambda self: [mb.net for mb in self.members])
+    lr = property(lambda self: [mb.lr for mb in self.members])
+    entropy_coef = property(lambda self: [mb.entropy_coef for mb in self.members])
+
+    def _phase(self, name):
+        return trainer._NoSpan() if self.phases is None else self.phases(name)
+
+    def _export(self, name):
+        return getattr(self.sim, name + "_tensor")().to_torch()
+
+    def league_step(self):
+        """hs_league_step on the simulator's exports as they stand: once after every sim.step()."""
+        with on_current_stream():
+            _run(self.sim, "hs_league_step", self._league_req, None)
+        self.bad_total.add_(self.bad)
+
+    # ---- the rollout ----
+    def _close_slot(self, t):
+        """The reward and done exports of the step just taken into slot t, under the routing that slot t acted with."""
+        R, buf = self.rows, self.rollout
+        self.sim.gather_sequences(self.row_of_slot, [(self._export("reward").view(1, R, 1), buf.reward[t].view(1, R, 1), False),
+                                                     (self._export("done").view(1, R, 1), buf.done[t].view(1, R, 1), False)],
+                                  chunks=1, chunk_steps=1, rows=R)
+
+    def _zero_carried(self, clear):
+        zero = (clear != 0).unsqueeze(1)
+        m = self.block
+        for p, mb in enumerate(self.members):
+            for x in (t for s in mb.state for t in s):
+                x.masked_fill_(zero[p * m:(p + 1) * m], 0)
+
+    def _after_step(self, t):
+        """What follows every sim.step(): the tracker, the close of slot `t` (None: there is none), the league step."""
+        if self.episodes is not None:
+            self.episodes.step()
+        if t is not None:
+            self._close_slot(t)
+        self.league_step()
+
+    def collect(self):
+        """Fill the shared rollout with steps_per_update slots in slot order, the bootstrap values, the advantages and
+        returns with their moments per policy, and fold every policy's moments into its normaliser."""
+        import torch
+        sim, buf, cfg, P, m = self.sim, self.rollout, self.cfg, self.num_policies, self.block
+        T, L = buf.steps, buf.chunk_steps
+        tables = self.tables if cfg.normalise_obs else None
+        with on_current_stream(), torch.no_grad():
+            for t in range(T):
+                if t > 0 or not self.stepped:
+                    with self._phase("sim"):
+                        sim.step()
+                    self._after_step(t - 1 if t > 0 else None)
+                    buf.clear[t].copy_(self.clear_slot)
+                    with self._phase("rollout_forward"):
+                        self._zero_carried(self.clear_slot)
+                else:                                    # the closing step of the last collect() led here, routed and zeroed
+                    buf.clear[0].copy_(self.clear)
+                self.stepped = False
+                with self._phase("pack"):
+                    sim.pack_policy_inputs_routed(self.row_of_slot, P, actor=buf.actor[t], critic=buf.critic[t], moments=self.moments[:, t], tables=tables)
+                if t % L == 0:
+                    k = t // L
+                    for p, mb in enumerate(self.members):
+                        cols = slice(p * m, (p + 1) * m)
+                        for dst, src in ((buf.actor_h, mb.state[0][0]), (buf.actor_c, mb.state[0][1]), (buf.critic_h, mb.state[1][0]), (buf.critic_c, mb.state[1][1])):
+                            dst[k, cols].copy_(src)
+                with self._phase("rollout_forward"):
+                    for p, mb in enumerate(self.members):
+                        cols = slice(p * m, (p + 1) * m)
+                        self.logits[cols], self.critic_logits[cols], mb.state = mb.net(sim, buf.actor[t, cols], buf.critic[t, cols], mb.state, None)
+                    sim.value_head(self.critic_logits, value=buf.value[t])
+                    sim.sample_actions_routed(self.logits, self.row_of_slot, buckets=self.buckets, seed=(cfg.seed, 0), counter=self.counter,
+                                              action=buf.action[t], log_prob=buf.log_prob[t])
+                self.counter += 1
+            with self._phase("sim"):
+                sim.step()
+            self._after_step(T - 1)
+            self.stepped = True
+            self.clear.copy_(self.clear_slot)
+            with self._phase("rollout_forward"):
+                self._zero_carried(self.clear_slot)
+            with self._phase("gae"):                     # the bootstrap's critic-only forwards included
+                self.bootstrap_value()
+                sim.compute_advantages(buf.reward, buf.done, buf.value, self.bootstrap, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, mask=buf.mask,
+                                       advantages=buf.advantage, returns=buf.returns, moments=self.adv_moments, groups=P)
+                for p, mb in enumerate(self.members):
+                    if mb.normaliser is not None:
+                        mb.normaliser.update(sim, self.moments[p])
+
+    def bootstrap_value(self):
+        """The critics' values of the observation in the simulator's exports into self.bootstrap (slot order): a critic-only
+        routed pack, every policy's critic forward on its carried critic state, which stays as it is, one decode."""
+        import torch
+        sim, m = self.sim, self.block
+        with on_current_stream(), torch.no_grad():
+            sim.pack_policy_inputs_routed(self.row_of_slot, self.num_policies, critic=self.boot_rows, tables=self.tables if self.cfg.normalise_obs else None)
+            for p, mb in enumerate(self.members):
+                cols = slice(p * m, (p + 1) * m)
+                y, _ = mb.net.critic(sim, self.boot_rows[cols], mb.state[1], None)
+                head = mb.net.critic_head
+                self.critic_logits[cols] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype))
+            sim.value_head(self.critic_logits, value=self.bootstrap)
+        return self.bootstrap
+
+    # ---- the update ----
+    def update(self):
+        """Every policy's epochs over its part of the rollout, in turn, then the metrics (the one read of the device), then,
+        every pbt_interval-th update, exploit / explore on the ratings just read."""
+        for mb in self.members:
+            mb.phases = self.phases
+            mb.run_epochs()
+        self.update_index += 1
+        out = self.metrics()
+        n = self.cfg.pbt_interval
+        if n and self.update_index % n == 0:
+            out["exploit"] = self.exploit(out["elo"])
+        return out
+
+    def metrics(self):
+        """{"policies": [a Trainer.metrics()-shaped dict per policy, with its "lr" and "entropy_coef"], "elo": [P], "games",
+        "bad", "update"}: one stacked copy to the host, which waits for the device."""
+        import torch
+        P = self.num_policies
+        rows = torch.stack([torch.stack(mb.metric_tensors()) for mb in self.members]).reshape(-1)
+        host = torch.cat([rows, self.elo, self.counts.sum().to(torch.float64).reshape(1), self.bad_total.to(torch.float64)]).cpu().tolist()
+        per = len(rows) // P
+        policies = []
+        for p, mb in enumerate(self.members):
+            d = mb.metrics_from(host[p * per:(p + 1) * per])
+            d["lr"], d["entropy_coef"] = mb.lr, mb.entropy_coef
+            policies.append(d)
+        return {"policies": policies, "elo": host[P * per:P * per + P], "games": int(host[-2]), "bad": int(host[-1]), "update": self.update_index}
+
+    def update_iter(self):
+        """collect() then update(): the metrics, with "fps" = rows * steps_per_update / the wall time of both."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        self.collect()
+        out = self.update()
+        out["fps"] = self.rows * self.cfg.steps_per_update / (time.perf_counter() - t0)
+        return out
+
+    # ---- exploit / explore ----
+    def exploit(self, elo):
+        """plan_exploit on the ratings `elo` (host numbers), applied pair by pair.  Returns the pairs."""
+        cfg = self.cfg
+        pairs = plan_exploit(elo, cfg.exploit_fraction, self.rng)
+        for dst, src in pairs:
+            self.apply_exploit(dst, src)
+        return pairs
+
+    def apply_exploit(self, dst, src):
+        """Policy `dst` takes policy `src`'s parameters, optimiser state, normaliser and rating, and explored lr and
+        entropy_coef.  Device-to-device copies: nothing waits."""
+        import torch
+        cfg, a, b = self.cfg, self.members[dst], self.members[src]
+        if dst == src:
+            raise ValueError("dst and src must differ")
+        with torch.no_grad():
+            a.opt.flat.params.copy_(b.opt.flat.params)
+            a.opt.m.copy_(b.opt.m)
+            a.opt.v.copy_(b.opt.v)
+            a.opt.adam_state.copy_(b.opt.adam_state)
+            if a.normaliser is not None:
+                a.normaliser.state.copy_(b.normaliser.state)
+                a.normaliser.table.copy_(b.normaliser.table)
+            self.elo[dst] = self.elo[src]
+        a.set_hyper(explore(b.lr, cfg.lr, cfg.explore_scales, cfg.explore_range, self.rng),
+                    explore(b.entropy_coef, cfg.entropy_coef, cfg.explore_scales, cfg.explore_range, self.rng))
+
+    # ---- checkpoints ----
+    def state_dict(self):
+        """{"members": [Trainer.state_dict()'s keys per policy], "league": the world state, counts, ratings and malformed
+        worlds, "hyper": {"lr", "entropy_coef"} per policy and the exploration generator, "update_index", "counter"}."""
+        for mb in self.members:
+            mb.update_index, mb.counter = self.update_index, self.counter
+        return {"members": [mb.state_dict() for mb in self.members],
+                "league": {"world": {k: t.clone() for k, t in self.world.items()}, "table": self._table.clone()},
+                "hyper": {"lr": self.lr, "entropy_coef": self.entropy_coef, "rng": self.rng.bit_generator.state},
+                "update_index": self.update_index, "counter": self.counter}
+
+    def load_state_dict(self, d):
+        """Load what state_dict() returned into a population of the same policies, config and simulator shape."""
+        import torch
+        if len(d["members"]) != self.num_policies:
+            raise ValueError(f"the state has {len(d['members'])} members: expected {self.num_policies}")
+        if tuple(d["league"]["table"].shape) != tuple(self._table.shape):
+            raise ValueError("the state's league table does not fit this population")
+        for mb, md in zip(self.members, d["members"]):
+            mb.load_state_dict(md)
+        for mb, lr, ec in zip(self.members, d["hyper"]["lr"], d["hyper"]["entropy_coef"]):
+            mb.set_hyper(lr, ec)
+        with torch.no_grad():
+            self._table.copy_(d["league"]["table"])
+            for k, t in self.world.items():
+                t.copy_(d["league"]["world"][k])
+        self.rng.bit_generator.state = d["hyper"]["rng"]
+        self.update_index, self.counter = int(d["update_index"]), int(d["counter"])
+        self.stepped = False

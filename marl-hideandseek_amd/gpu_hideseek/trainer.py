@@ -289,17 +289,21 @@ class Trainer:
             self.value_stats[epoch] += self._value_out
         return pol, val
 
-    def update(self):
-        """num_epochs epochs of num_minibatches minibatches over the rollout collect() filled.  Returns the metrics (the
-        one read of the device)."""
+    def permutation(self):
+        """The sequence ids of one epoch in a fresh order, int32 on the device, from the seeded generator."""
         import torch
-        cfg, buf = self.cfg, self.rollout
+        return torch.randperm(self.rollout.sequences, generator=self.generator, device=self.device, dtype=torch.int32)
+
+    def run_epochs(self):
+        """num_epochs epochs of num_minibatches minibatches over the rollout collect() filled: update() without the read
+        of the metrics (gpu_hideseek.population runs several policies' epochs before its one read)."""
+        cfg = self.cfg
         self.ppo_stats.zero_()
         self.value_stats.zero_()
         self.adam_stats.zero_()
         with on_current_stream():
             for epoch in range(cfg.num_epochs):
-                perm = torch.randperm(buf.sequences, generator=self.generator, device=self.device, dtype=torch.int32)
+                perm = self.permutation()
                 for part in rollout.epoch_parts(perm, cfg.num_minibatches):
                     self.forward_backward(part, epoch)
                     with self._phase("adam"):
@@ -307,10 +311,18 @@ class Trainer:
                     self.adam_stats[:2] += stats[::2]            # the norm and whether the step was skipped
                     self.adam_stats[2] = stats[3]
         self.update_index += 1
+
+    def update(self):
+        """run_epochs(), then the metrics (the one read of the device)."""
+        self.run_epochs()
         return self.metrics()
 
-    def metrics(self):
-        """The statistics of the last update() as Python numbers: one copy to the host, which waits for the device."""
+    METRIC_NAMES = ("policy_loss", "entropy", "approx_kl", "clip_fraction", "value_loss", "explained_variance", "mean_value", "advantage_mean",
+                    "advantage_std", "returns_mean", "returns_std", "grad_norm", "skipped", "adam_step")
+
+    def metric_tensors(self):
+        """The statistics of the last update as float64 scalars on the device, without synchronising: METRIC_NAMES, then
+        the value loss of every epoch."""
         import torch
         cfg = self.cfg
         steps = cfg.num_epochs * cfg.num_minibatches
@@ -318,17 +330,24 @@ class Trainer:
         pol = ppo_loss.stats_to_metrics(self.ppo_stats.sum(0), cfg.entropy_coef, cfg.value_loss_coef)
         val = value_head.stats_to_metrics(self.value_stats.sum(0))
         per_epoch = [value_head.stats_to_metrics(self.value_stats[e])["value_loss"] for e in range(cfg.num_epochs)]
-        names = ["policy_loss", "entropy", "approx_kl", "clip_fraction", "value_loss", "explained_variance", "mean_value", "advantage_mean", "advantage_std",
-                 "returns_mean", "returns_std", "grad_norm", "skipped", "adam_step"]
         vals = [pol["policy_loss"], pol["entropy"], pol["approx_kl"], pol["clip_fraction"], val["value_loss"], val["explained_variance"], val["mean_value"],
                 adv["advantages"][0], adv["advantages"][1], adv["returns"][0], adv["returns"][1], self.adam_stats[0] / steps, self.adam_stats[1], self.adam_stats[2]]
-        host = torch.stack([v.to(torch.float64) for v in vals + per_epoch]).cpu().tolist()
+        return [v.to(torch.float64) for v in vals + per_epoch]
+
+    def metrics_from(self, host):
+        """The metrics dict from the values of metric_tensors() as Python numbers."""
+        cfg, names = self.cfg, self.METRIC_NAMES
         out = dict(zip(names, host))
         out["skipped"], out["adam_step"] = int(out["skipped"]), int(out["adam_step"])
         out["value_loss_epochs"] = host[len(names):]
         out["loss"] = out["policy_loss"] - cfg.entropy_coef * out["entropy"] + cfg.value_loss_coef * out["value_loss"]
         out["update"] = self.update_index
         return out
+
+    def metrics(self):
+        """The statistics of the last update() as Python numbers: one copy to the host, which waits for the device."""
+        import torch
+        return self.metrics_from(torch.stack(self.metric_tensors()).cpu().tolist())
 
     def update_iter(self):
         """collect() then update(): the metrics, with "fps" = rows * steps_per_update / the wall time of both."""
@@ -366,6 +385,6 @@ class Trainer:
                 mine.copy_(theirs)
         if self.normaliser is not None:
             self.normaliser.load_state_dict(d["normaliser"])
-        self.generator.set_state(d["generator"])
+        self.generator.set_state(d["generator"].cpu())      # a state loaded with map_location is on the device
         self.update_index, self.counter = int(d["update_index"]), int(d["counter"])
         self.stepped = False

@@ -6,11 +6,13 @@ reference's scripts/jax_infer.py that make sense here.
     python tools/render_replay.py run.log --worlds 16 --out frames              # and watch it (flags 9, seed 5: the defaults there)
 
 --ckpt-path is a file tools/train.py saved (the trainer's state_dict): its "params" and "normaliser" are loaded, the
-optimiser's state is not needed.  The simulator runs with UseFixedWorld | ZeroAgentVelocity, as the reference's script
+optimiser's state is not needed; of a population's checkpoint (tools/train.py --pbt-ensemble-size) --member i picks one
+policy.  The simulator runs with UseFixedWorld | ZeroAgentVelocity, as the reference's script
 does.  --record-log appends a checkpoint of every world after every step.  --print-rewards prints every step's reward
 tensor.  At the end it prints the per-side table of the episodes that finished (240 steps each) and one JSON line.
 Several checkpoints playing each other, with Elo ratings (the reference's eval_competitive), is tools/league.py.
-Not here: --single-policy, PBT training, --print-obs and --print-action-probs.
+Training several policies at once is tools/train.py --pbt-ensemble-size.  Not here: --single-policy, --print-obs and
+--print-action-probs.
 """
 import argparse
 import json
@@ -29,6 +31,7 @@ def parse(argv=None):
     ap.add_argument("--num-worlds", type=int, required=True)
     ap.add_argument("--num-steps", type=int, default=200)
     ap.add_argument("--ckpt-path", type=str, required=True)
+    ap.add_argument("--member", type=int, help="the policy of a population checkpoint to run")
     ap.add_argument("--record-log", type=str)
     ap.add_argument("--print-rewards", action="store_true")
     ap.add_argument("--num-hiders", type=int, default=3)
@@ -59,7 +62,7 @@ def main(argv=None):
     args = parse(argv)
     F = gpu_hideseek.SimFlags
     dtype = torch.float16 if args.fp16 else torch.bfloat16 if args.bf16 else torch.float32
-    net, normaliser = evaluate.load_policy(args.ckpt_path, dtype, torch.device("cuda", args.gpu_id))
+    net, normaliser = evaluate.load_policy(args.ckpt_path, dtype, torch.device("cuda", args.gpu_id), member=args.member)
     sim = gpu_hideseek.HideAndSeekSimulator(
         exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
         sim_flags=F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders, max_hiders=args.num_hiders,

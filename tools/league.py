@@ -3,13 +3,15 @@ reference's scripts/jax_infer.py with more than one policy (eval_competitive, pr
 
     python tools/league.py --num-worlds 1024 --num-steps 2400 --ckpt-path ckpts/run0/100 ckpts/run0/200 ckpts/run1/200 --bf16
 
-Every --ckpt-path is a file tools/train.py saved (evaluate.load_policy: its "params" and "normaliser").  With P files the
+Every --ckpt-path is a file tools/train.py saved (evaluate.load_policy: its "params" and "normaliser").  Of a population's
+checkpoint (tools/train.py --pbt-ensemble-size) --member i takes that policy and --all-members every one.  With P policies the
 number of worlds must be a multiple of P^2: world w plays pair w mod P^2, policy q // P as the hiders against policy
 q % P as the seekers, for the whole run.  The simulator runs with num_pbt_policies = P and UseFixedWorld |
 ZeroAgentVelocity, as the reference's script does; --num-hiders is the size of both teams.
 It prints the Elo table before and after (four to a line, as the reference's print_elos does), the P x P matrix of the
 hiders' win rate (row: the hiders' policy, column: the seekers'), and one JSON line of League.read().
-Not here: PBT training, drawn or rating-based matchmaking, several GPUs.
+Training several policies at once is tools/train.py --pbt-ensemble-size.  Not here: drawn or rating-based matchmaking,
+several GPUs.
 """
 import argparse
 import json
@@ -28,6 +30,8 @@ def parse(argv=None):
     ap.add_argument("--num-worlds", type=int, required=True)
     ap.add_argument("--num-steps", type=int, default=2400)
     ap.add_argument("--ckpt-path", type=str, nargs="+", required=True)
+    ap.add_argument("--member", type=int, help="of every population checkpoint given, this policy")
+    ap.add_argument("--all-members", action="store_true", help="of every population checkpoint given, all its policies")
     ap.add_argument("--record-log", type=str)
     ap.add_argument("--num-hiders", type=int, default=3, help="the size of both teams")
     ap.add_argument("--fp16", action="store_true")
@@ -39,10 +43,30 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
+    if args.member is not None and args.all_members:
+        ap.error("--member and --all-members exclude each other")
     P = len(args.ckpt_path)
-    if P > league.MAX_POLICIES or args.num_worlds % (P * P):
+    if not args.all_members and (P > league.MAX_POLICIES or args.num_worlds % (P * P)):       # with --all-members: once the files are read
         ap.error(f"--num-worlds must be a multiple of {P * P} for {P} policies (at most {league.MAX_POLICIES})")
     return args
+
+
+def load_policies(args, dtype, dev):
+    """[(net, normaliser)] of every --ckpt-path in order, a population checkpoint giving --member or, with --all-members,
+    all its members."""
+    policies = []
+    for path in args.ckpt_path:
+        d = torch.load(path, map_location=dev, weights_only=False)
+        states = evaluate.members(d)
+        if "members" in d and not args.all_members:
+            if args.member is None or not 0 <= args.member < len(states):
+                raise SystemExit(f"{path} is a population checkpoint of {len(states)} members: give --member i or --all-members")
+            states = [states[args.member]]
+        policies += [evaluate.load_policy(st, dtype, dev) for st in states]
+    P = len(policies)
+    if P > league.MAX_POLICIES or args.num_worlds % (P * P):
+        raise SystemExit(f"--num-worlds must be a multiple of {P * P} for {P} policies (at most {league.MAX_POLICIES})")
+    return policies
 
 
 def matrix(counts):
@@ -60,7 +84,7 @@ def main(argv=None):
     F = gpu_hideseek.SimFlags
     dtype = torch.float16 if args.fp16 else torch.bfloat16 if args.bf16 else torch.float32
     dev = torch.device("cuda", args.gpu_id)
-    policies = [evaluate.load_policy(path, dtype, dev) for path in args.ckpt_path]
+    policies = load_policies(args, dtype, dev)
     sim = gpu_hideseek.HideAndSeekSimulator(
         exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
         sim_flags=F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders, max_hiders=args.num_hiders,

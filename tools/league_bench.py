@@ -15,8 +15,9 @@ once, over the same 245 steps from the same start.
 League.run and Evaluator.run: random bfloat16 policies, mode "draw", --run-steps steps timed by the wall clock between two
 waits for the device, after 10 steps of warm-up, each on a fresh simulator; the runners alternate inside each of --rounds
 rounds and the median is reported with the spread of the runs.  The Evaluator runs the actor and the critic
-over all rows; the League runs P actors over R / P rows each, after one routed pack and one gather (tools/pack_routed_bench.py has the
-P packs and P + 1 gathers it made before).  --evaluator-only with
+over all rows; the League runs P actors over R / P rows each, between one routed pack and one routed sampler
+(tools/pack_routed_bench.py has the P packs and P gathers it made before, tools/sample_routed_bench.py the logits gather
+and the plain sampler, and League.run as it stands now).  --evaluator-only with
 --package measures the Evaluator of another checkout (the parent commit's) in a process of its own.
 """
 import argparse

@@ -19,7 +19,13 @@ the mean and standard deviation of the return, the mean discounted return and le
 rates.  On a fresh simulator the episodes are tracked from their start; after --restore the tracker waits for every row's
 next episode, because the simulator's state is not restored.  tools/infer.py runs a saved policy without learning.
 Saved checkpoints play each other, with Elo ratings (the reference's eval_competitive), in tools/league.py.
-Not here: PBT, tensorboard / wandb, several GPUs.
+--pbt-ensemble-size P trains P policies at once on the one simulator (gpu_hideseek.population: the league's fixed
+schedule, so --num-worlds must be a multiple of P^2 and both teams have --num-hiders agents), with live Elo ratings from the
+games the rollouts play; --pbt-interval N copies the best policies over the worst and explores lr and the entropy
+coefficient after every N-th update (0, the default: never).  The `Update:` print then has one metrics line per policy and
+the Elo table, four ratings to a line as the reference prints it, and the checkpoint is the population's (tools/infer.py
+and tools/league.py read it with --member).
+Not here: pools of past policies (--pbt-past-policies), tensorboard / wandb, several GPUs.
 """
 import argparse
 import json
@@ -31,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import episodes, trainer  # noqa: E402
+from gpu_hideseek import episodes, league, population, trainer  # noqa: E402
 
 PRINT_EVERY = 10
 
@@ -62,7 +68,13 @@ def parse(argv=None):
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--episode-stats", action="store_true", help="track finished episodes on the device and print them with the metrics")
     ap.add_argument("--out", type=str, help="with --phases: write the table here too")
+    ap.add_argument("--pbt-ensemble-size", type=int, default=0, help="train this many policies at once (gpu_hideseek.population); 0: the plain trainer")
+    ap.add_argument("--pbt-interval", type=int, default=0, help="with --pbt-ensemble-size: exploit / explore after every N-th update; 0: never")
     args = ap.parse_args(argv)
+    if args.pbt_ensemble_size and args.num_hiders != args.num_seekers:
+        ap.error("--pbt-ensemble-size needs equal teams: --num-hiders == --num-seekers")
+    if args.pbt_interval and not args.pbt_ensemble_size:
+        ap.error("--pbt-interval needs --pbt-ensemble-size")
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
     if (args.ckpt_dir is None) != (args.run_name is None):
@@ -74,6 +86,11 @@ def parse(argv=None):
 
 def config(args):
     dtype = torch.float16 if args.fp16 else torch.bfloat16 if args.bf16 else torch.float32
+    if args.pbt_ensemble_size:
+        return population.PopulationConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
+                                           num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
+                                           value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed, num_policies=args.pbt_ensemble_size,
+                                           team_size=args.num_hiders, pbt_interval=args.pbt_interval)
     return trainer.TrainConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
                                num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
                                value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed)
@@ -101,9 +118,9 @@ def main(argv=None):
     sim = gpu_hideseek.HideAndSeekSimulator(
         exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
         sim_flags=F.RandomFlipTeams | F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders,
-        max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=1)
+        max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=max(1, args.pbt_ensemble_size))
     sim.init()
-    tr = trainer.Trainer(sim, config(args), fused=not args.eager)
+    tr = (population.Population if args.pbt_ensemble_size else trainer.Trainer)(sim, config(args), fused=not args.eager)
     run_dir = None if args.ckpt_dir is None else os.path.join(args.ckpt_dir, args.run_name)
     if args.restore is not None:
         tr.load_state_dict(torch.load(os.path.join(run_dir, str(args.restore)), map_location=tr.device, weights_only=False))
@@ -117,6 +134,17 @@ def main(argv=None):
             os.makedirs(run_dir, exist_ok=True)
             torch.save(tr.state_dict(), os.path.join(run_dir, str(tr.update_index)))
 
+    def show(metrics):
+        """The metrics of the last update: one JSON line, or with a population one per policy and the Elo table."""
+        plain = lambda m: {k: v for k, v in m.items() if not isinstance(v, list)}       # noqa: E731
+        if "policies" not in metrics:
+            print("  " + json.dumps(plain(metrics)))
+            return
+        for p, m in enumerate(metrics["policies"]):
+            print(f"  policy {p}: " + json.dumps(plain(m)))
+        print("  " + json.dumps({k: metrics[k] for k in ("games", "bad", "exploit") if k in metrics}))
+        league.print_elos(metrics["elo"])
+
     totals, wall_ms, timed = {k: 0.0 for k in trainer.PHASES}, 0.0, 0
     last_time, last_update, metrics = 0.0, tr.update_index, {}
     for i in range(args.num_updates):
@@ -125,7 +153,7 @@ def main(argv=None):
             print(f"Update: {tr.update_index}")
             if last_time != 0:
                 print("  FPS:", args.num_worlds * args.steps_per_update * (tr.update_index - last_update) / (now - last_time))
-                print("  " + json.dumps({k: v for k, v in metrics.items() if not isinstance(v, list)}))
+                show(metrics)
                 if tr.episodes is not None:
                     print("  " + json.dumps(tr.episodes.read()))
             last_time, last_update = now, tr.update_index
@@ -142,7 +170,7 @@ def main(argv=None):
         if args.ckpt_frequency > 0 and tr.update_index % args.ckpt_frequency == 0:
             save()
     print(f"Update: {tr.update_index}")
-    print("  " + json.dumps({k: v for k, v in metrics.items() if not isinstance(v, list)}))
+    show(metrics)
     if tr.episodes is not None:
         print("  " + json.dumps(tr.episodes.read()))
     save()
@@ -155,7 +183,7 @@ def main(argv=None):
             with open(args.out, "w") as f:
                 f.write(json.dumps({"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "updates": timed, "wall_ms_per_update": wall_ms / timed,
                                     "fps_world_steps": fps, "phases_ms_per_update": {k: v / timed for k, v in totals.items()},
-                                    "last_metrics": {k: v for k, v in metrics.items() if not isinstance(v, list)}}) + "\n\n")
+                                    "last_metrics": {k: v for k, v in metrics.items() if not isinstance(v, list) or k == "elo"}}) + "\n\n")
                 f.write("\n".join(lines) + "\n")
     sim.close()
 
