@@ -1121,6 +1121,76 @@ typedef struct hs_gae_grouped_request {
 int32_t hs_compute_gae_grouped(hs_sim *sim, const hs_gae_grouped_request *req);
 int32_t hs_compute_gae_grouped_async(hs_sim *sim, void *hip_stream, const hs_gae_grouped_request *req);
 
+/* The attention core of the entity self-attention encoder: what sits between the QKV GEMM and the output GEMM of the
+ * reference's other network, EntitySelfAttentionNet(num_embed_channels=128, num_out_channels=256, num_heads=4)
+ * (scripts/jax_policy.py), in one kernel each way (csrc/hs_k_attend.h).  madrona_learn is not part of the reference's
+ * tree: the network around this call (gpu_hideseek.entity_attention) and the arithmetic below are the project's own and
+ * are not pinned by it.
+ * A row is S = HS_ATTEND_TOKENS = 17 tokens, the entities of a packed row in the order self, agents 0..4, boxes 0..8,
+ * ramps 0..1, of E = embed_dim channels in H = HS_ATTEND_HEADS = 4 heads of D = E / 4 (E 64 or 128, D 16 or 32).
+ * qkv [n][S][3][H][D] is the QKV GEMM's result viewed: q_i, k_i, v_i of token i and head h are the D elements from
+ * ((i * 3 + {0, 1, 2}) * H + h) * D on.  key_mask [n][S] u8 (nonzero = the key counts) or null = every key counts; key 0
+ * (self) counts whatever its byte says, so no softmax is empty.  out is [n][S][E], head h in the channels h D .. h D + D - 1.
+ * The arithmetic is the contract.  Narrow inputs are widened to f32 exactly; everything is IEEE f32, unfused, in exactly
+ * this order; expf is the device library's accurate function and is not pinned bit for bit.  For a row, head h, query i:
+ *   dot(a, b) over a head's D channels: with P = D / 4, part g in 0..3 adds a_c * b_c for c = P g, ..., P g + P - 1 in
+ *             ascending order (the first product is the start), then the parts add as a butterfly: every part t_g
+ *             becomes t_g + t_{g xor 1}, then t_g + t_{g xor 2}, i.e. (t0 + t1) + (t2 + t3) up to commuted operands
+ *   scale = 1.0f / sqrtf((float)D)                                  (correctly rounded; 0.25 at D = 16)
+ *   s_j = dot(q_i, k_j) * scale                                     for the valid keys j
+ *   m = the maximum of s_j over the valid keys, from s_0 on in ascending order (fmaxf)
+ *   e_j = expf(s_j - m);   l = e_0, then l = l + e_j for the valid j >= 1 in ascending order
+ *   p_j = e_j / l                                                   (division correctly rounded)
+ *   out[i][h D + c] = ((+0 + p_j0 * v_j0[c]) + p_j1 * v_j1[c]) + ...   over the valid keys in ascending order
+ * (rounded to out_dtype to nearest even).  A masked key is left out BY A SELECT, not by a multiplication with 0: its k and
+ * v may hold NaN or Inf and every output keeps its bits.  A masked QUERY is computed like any other (the caller's pool
+ * drops it).  No atomics, no workspace: a row's bits do not depend on n, on its position or on its neighbours, and the
+ * same inputs give the same bits on every call.
+ * hs_entity_attend_backward recomputes p from q, k and the mask exactly as above (the forward saves nothing) and takes
+ * grad_out [n][S][E] of grad_dtype; grad_qkv has the shape of qkv and grad_dtype:
+ *   dp_ij = dot(dout_i, v_j)                                        for the valid keys j (dout_i: head h's D channels)
+ *   t_i = ((+0 + p_ij0 * dp_ij0) + p_ij1 * dp_ij1) + ...            over the valid keys in ascending order
+ *   ds_ij = p_ij * (dp_ij - t_i)
+ *   dq_i[c] = (((+0 + ds_ij0 * k_j0[c]) + ds_ij1 * k_j1[c]) + ...) * scale     over the valid keys in ascending order
+ *   dv_j[c] = ((+0 + p_0j * dout_0[c]) + p_1j * dout_1[c]) + ... + p_16j * dout_16[c]       every query, ascending
+ *   dk_j[c] = (((+0 + ds_0j * q_0[c]) + ds_1j * q_1[c]) + ... + ds_16j * q_16[c]) * scale
+ *   dk_j and dv_j of a masked key are exactly +0 (a select).
+ * There are no parameters, hence no sum over rows.  An all-zero grad_out gives grad_qkv all +0.  q, the valid keys' k and
+ * v, and grad_out must be finite: nothing checks that on the device.
+ * A lane reads and writes pieces of 4 adjacent elements (up to 16 bytes), so qkv, out, grad_out and grad_qkv must be
+ * 16-byte aligned, as for hs_dense_norm_act.  Elements are indexed in 64 bits, so n * S * 3 * E may pass 2^31; n itself stays
+ * below HS_ATTEND_MAX_ROWS.
+ * Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a
+ * null request, null qkv or out (backward: null grad_out or grad_qkv); an unknown dtype; embed_dim not 64 or 128; n < 1
+ * or n >= 2^24; a pointer not 16-byte aligned (key_mask: any); an output range that overlaps an input range; a call before
+ * hs_init or inside an open step.  The calls read no export and write no simulator state, and any number of them may
+ * overlap on one handle.  The blocking forms are ordered after the device's legacy default stream; the _async forms
+ * enqueue on the caller's hipStream_t without synchronising. */
+enum { HS_ATTEND_TOKENS = 17, HS_ATTEND_HEADS = 4, HS_ATTEND_ROWS_PER_ROUND = 4, HS_ATTEND_MAX_GRID = 2048, HS_ATTEND_MAX_ROWS = 1 << 24 };
+typedef struct hs_entity_attend_request {
+    const void    *qkv;           /* [n][HS_ATTEND_TOKENS][3][HS_ATTEND_HEADS][embed_dim / 4] of qkv_dtype, contiguous, 16-byte aligned */
+    const uint8_t *key_mask;      /* [n][HS_ATTEND_TOKENS] u8, nonzero = valid, or null = all valid */
+    int32_t n;                    /* rows, 1 <= n < HS_ATTEND_MAX_ROWS */
+    int32_t embed_dim;            /* E: 64 or 128 (the reference's) */
+    int32_t qkv_dtype;            /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t out_dtype;            /* of out */
+    void    *out;                 /* [n][HS_ATTEND_TOKENS][embed_dim] of out_dtype, 16-byte aligned */
+} hs_entity_attend_request;       /* 40 bytes */
+typedef struct hs_entity_attend_backward_request {
+    const void    *qkv;           /* as in the forward call */
+    const uint8_t *key_mask;
+    const void    *grad_out;      /* [n][HS_ATTEND_TOKENS][embed_dim] of grad_dtype, 16-byte aligned */
+    int32_t n;
+    int32_t embed_dim;
+    int32_t qkv_dtype;
+    int32_t grad_dtype;           /* of grad_out and grad_qkv */
+    void    *grad_qkv;            /* the shape of qkv, of grad_dtype, 16-byte aligned */
+} hs_entity_attend_backward_request;  /* 48 bytes */
+int32_t hs_entity_attend(hs_sim *sim, const hs_entity_attend_request *req);
+int32_t hs_entity_attend_async(hs_sim *sim, void *hip_stream, const hs_entity_attend_request *req);
+int32_t hs_entity_attend_backward(hs_sim *sim, const hs_entity_attend_backward_request *req);
+int32_t hs_entity_attend_backward_async(hs_sim *sim, void *hip_stream, const hs_entity_attend_backward_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

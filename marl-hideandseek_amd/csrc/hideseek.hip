@@ -37,6 +37,7 @@
 #include "hs_k_league.h"                  // likewise: emitted where launch_league (after launch_episode) names them
 #include "hs_k_pack_routed.h"             // likewise: emitted where launch_pack_routed (after launch_league) names it
 #include "hs_k_sample_routed.h"           // likewise: emitted where launch_sample_routed (after launch_pack_routed) names it
+#include "hs_k_attend.h"                  // likewise: emitted where launch_attend (after launch_gae_grouped) names them
 #include "hs_k_adam.h"
 
 namespace {
@@ -1385,6 +1386,79 @@ int launch_gae_grouped(hs_sim *s, hipStream_t strm, const hs_gae_grouped_request
 }
 }  // namespace
 
+// ---- the attention core of the entity self-attention encoder (hs_k_attend.h) ----
+namespace {
+static_assert(HS_ATTEND_TOKENS == hs::kAttendTokens && HS_ATTEND_HEADS == hs::kAttendHeads && HS_ATTEND_ROWS_PER_ROUND == hs::kRowsWaves &&
+              HS_ATTEND_MAX_GRID == hs::kRowsMaxGrid, "hs_entity_attend_request and k_attend agree");
+static_assert(sizeof(hs_entity_attend_request) == 40 && offsetof(hs_entity_attend_request, key_mask) == 8 && offsetof(hs_entity_attend_request, n) == 16 &&
+              offsetof(hs_entity_attend_request, out_dtype) == 28 && offsetof(hs_entity_attend_request, out) == 32,
+              "hs_entity_attend_request layout (gpu_hideseek/entity_attention.py mirrors it)");
+static_assert(sizeof(hs_entity_attend_backward_request) == 48 && offsetof(hs_entity_attend_backward_request, grad_out) == 16 &&
+              offsetof(hs_entity_attend_backward_request, n) == 24 && offsetof(hs_entity_attend_backward_request, grad_dtype) == 36 &&
+              offsetof(hs_entity_attend_backward_request, grad_qkv) == 40,
+              "hs_entity_attend_backward_request layout (gpu_hideseek/entity_attention.py mirrors it)");
+
+// What the two calls share.
+int check_attend_common(const Check &c, const void *qkv, int32_t n, int32_t E, int32_t qkv_dtype) {
+    if (!qkv) return c.bad("null qkv");
+    HS_TRY(c.dtype(qkv_dtype, "qkv"));
+    if (E != 64 && E != 128) return c.bad("embed_dim must be 64 or 128");
+    if (n < 1 || n >= HS_ATTEND_MAX_ROWS) return c.bad("n must be at least 1 and below HS_ATTEND_MAX_ROWS");
+    if (!aligned(16, {qkv})) return c.bad("qkv must be 16-byte aligned");
+    return HS_OK;
+}
+
+int check_attend(hs_sim *s, const hs_entity_attend_request *r) {
+    const Check c{"hs_entity_attend"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_attend_common(c, r->qkv, r->n, r->embed_dim, r->qkv_dtype));
+    if (!r->out) return c.bad("null out");
+    HS_TRY(c.dtype(r->out_dtype, "out"));
+    if (!aligned(16, {r->out})) return c.bad("out must be 16-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n, SE = (uintptr_t)HS_ATTEND_TOKENS * r->embed_dim;
+    HS_TRY(c.disjoint({range("qkv", r->qkv, n * 3 * SE * elem_size(r->qkv_dtype)), range("key_mask", r->key_mask, n * HS_ATTEND_TOKENS)},
+                      {range("out", r->out, n * SE * elem_size(r->out_dtype))}));
+    return c.handle_ready(s);
+}
+
+int check_attend_bwd(hs_sim *s, const hs_entity_attend_backward_request *r) {
+    const Check c{"hs_entity_attend_backward"};
+    if (!r) return c.bad("null request");
+    HS_TRY(check_attend_common(c, r->qkv, r->n, r->embed_dim, r->qkv_dtype));
+    if (!r->grad_out) return c.bad("null grad_out");
+    if (!r->grad_qkv) return c.bad("null grad_qkv");
+    HS_TRY(c.dtype(r->grad_dtype, "grad"));
+    if (!aligned(16, {r->grad_out, r->grad_qkv})) return c.bad("grad_out and grad_qkv must be 16-byte aligned");
+    const uintptr_t n = (uintptr_t)r->n, SE = (uintptr_t)HS_ATTEND_TOKENS * r->embed_dim, gsize = elem_size(r->grad_dtype);
+    HS_TRY(c.disjoint({range("qkv", r->qkv, n * 3 * SE * elem_size(r->qkv_dtype)), range("key_mask", r->key_mask, n * HS_ATTEND_TOKENS),
+                       range("grad_out", r->grad_out, n * SE * gsize)},
+                      {range("grad_qkv", r->grad_qkv, n * 3 * SE * gsize)}));
+    return c.handle_ready(s);
+}
+
+// One k_attend_fwd over the rows (the request has passed check_attend).
+int launch_attend(hs_sim *, hipStream_t strm, const hs_entity_attend_request *r) {
+    hs::AttendArgs a = {};
+    a.qkv = r->qkv; a.mask = r->key_mask; a.out = r->out;
+    a.n = r->n; a.qkvType = elem_code(r->qkv_dtype); a.outType = elem_code(r->out_dtype);
+    const dim3 grid(hs::rows_grid(a.n, hs::kRowsWaves, hs::kRowsMaxGrid)), blk(hs::kRowsThreads);
+    with_constant<64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_attend_fwd<decltype(e)::value>), grid, blk, 0, strm, a); });
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+// One k_attend_bwd over the rows (the request has passed check_attend_bwd): no parameters, so no slices and no sum.
+int launch_attend_bwd(hs_sim *, hipStream_t strm, const hs_entity_attend_backward_request *r) {
+    hs::AttendBwdArgs a = {};
+    a.qkv = r->qkv; a.mask = r->key_mask; a.gradOut = r->grad_out; a.gradQkv = r->grad_qkv;
+    a.n = r->n; a.qkvType = elem_code(r->qkv_dtype); a.gradType = elem_code(r->grad_dtype);
+    const dim3 grid(hs::rows_grid(a.n, hs::kRowsWaves, hs::kRowsMaxGrid)), blk(hs::kRowsThreads);
+    with_constant<64, 128>(r->embed_dim, [&](auto e) { hipLaunchKernelGGL((hs::k_attend_bwd<decltype(e)::value>), grid, blk, 0, strm, a); });
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1880,6 +1954,10 @@ int32_t hs_sample_actions_routed(hs_sim *s, const hs_sample_routed_request *req)
 int32_t hs_sample_actions_routed_async(hs_sim *s, void *hip_stream, const hs_sample_routed_request *req) { return call_async(s, hip_stream, check_sample_routed, launch_sample_routed, req); }
 int32_t hs_compute_gae_grouped(hs_sim *s, const hs_gae_grouped_request *req) { return call_blocking(s, check_gae_grouped, launch_gae_grouped, req); }
 int32_t hs_compute_gae_grouped_async(hs_sim *s, void *hip_stream, const hs_gae_grouped_request *req) { return call_async(s, hip_stream, check_gae_grouped, launch_gae_grouped, req); }
+int32_t hs_entity_attend(hs_sim *s, const hs_entity_attend_request *req) { return call_blocking(s, check_attend, launch_attend, req); }
+int32_t hs_entity_attend_async(hs_sim *s, void *hip_stream, const hs_entity_attend_request *req) { return call_async(s, hip_stream, check_attend, launch_attend, req); }
+int32_t hs_entity_attend_backward(hs_sim *s, const hs_entity_attend_backward_request *req) { return call_blocking(s, check_attend_bwd, launch_attend_bwd, req); }
+int32_t hs_entity_attend_backward_async(hs_sim *s, void *hip_stream, const hs_entity_attend_backward_request *req) { return call_async(s, hip_stream, check_attend_bwd, launch_attend_bwd, req); }
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {

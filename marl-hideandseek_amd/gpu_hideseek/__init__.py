@@ -330,6 +330,23 @@ class HideAndSeekSimulator:
         return _mlp.compute_backward(self, z, params, grad_y, stream, channels=channels, eps=eps, slope=slope, grad_z=grad_z,
                                      grad_params=grad_params)
 
+    def attend_entities(self, qkv, key_mask=None, *, out=True, out_dtype=None, stream=None):
+        """The attention core of the entity self-attention encoder in one kernel (gpu_hideseek.entity_attention;
+        hs_entity_attend, whose header comment states the arithmetic: IEEE f32 in a fixed order).  `qkv`
+        [n, 17, 3, 4, D] (float32, bfloat16 or float16, contiguous, 16-byte aligned; D 16 or 32) is the QKV GEMM's
+        result viewed, `key_mask` [n, 17] uint8 (nonzero = the key counts; token 0 always does) or None.  out [n, 17, 4 D]
+        in `out_dtype` (by default qkv's) is True (allocated) or a preallocated tensor.  stream=None blocks; a
+        torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {"out": tensor}."""
+        from . import entity_attention as _att
+        return _att.compute(self, qkv, key_mask, stream, out=out, out_dtype=out_dtype)
+
+    def attend_entities_backward(self, qkv, key_mask, grad_out, *, grad_qkv=True, stream=None):
+        """The gradient of attend_entities in one kernel (hs_entity_attend_backward): recomputed from the forward's qkv
+        and key_mask, with the upstream `grad_out` [n, 17, 4 D].  grad_qkv has qkv's shape and grad_out's dtype; a masked
+        key's dk and dv are +0.  The same inputs give the same bits on every call.  Returns {"grad_qkv": tensor}."""
+        from . import entity_attention as _att
+        return _att.compute_backward(self, qkv, key_mask, grad_out, stream, grad_qkv=grad_qkv)
+
     def adam_step(self, params, grads, m, v, state, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=5.0, grad_scale=1.0,
                   zero_grad=True, stats=True, stream=None):
         """The clip by the global gradient norm and one Adam step over flat buffers in two kernels (gpu_hideseek.optim;

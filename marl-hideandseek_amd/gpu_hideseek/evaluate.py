@@ -27,10 +27,11 @@ def members(d):
     return list(d["members"]) if "members" in d else [d]
 
 
-def load_policy(path_or_dict, dtype=None, device=None, member=None):
+def load_policy(path_or_dict, dtype=None, device=None, member=None, encoder=None):
     """(net, normaliser or None) from a trainer state_dict (a file torch.save wrote, or the dict): a policy.make_policy
     of `dtype` whose parameters are the state's flat "params" buffer, laid out as the state's optimiser says, and an
-    ObsNormaliser with the state's moments where the trainer had one.  Of a population's checkpoint, `member` i."""
+    ObsNormaliser with the state's moments where the trainer had one.  Of a population's checkpoint, `member` i.
+    `encoder` is one of policy.ENCODERS, or None for the kind whose flat parameter length is the state's."""
     import torch
     from . import optim, policy
     from .policy_inputs import ObsNormaliser
@@ -42,10 +43,20 @@ def load_policy(path_or_dict, dtype=None, device=None, member=None):
         d = d["members"][member]
     elif member not in (None, 0):
         raise ValueError(f"a trainer checkpoint has one policy: member must be None or 0, got {member!r}")
-    net = policy.make_policy(dtype).to(device)
-    flat = optim.flatten(net.named_parameters(), device)
+    if encoder is not None and encoder not in policy.ENCODERS:
+        raise ValueError(f"encoder must be None or one of {policy.ENCODERS}, got {encoder!r}")
     theirs = {k: (int(lo), int(hi), tuple(shape)) for k, (lo, hi, shape) in d["optimizer"]["layout"].items()}
-    if theirs != flat.layout() or tuple(d["params"].shape) != tuple(flat.params.shape):
+    net = flat = None
+    for kind in policy.ENCODERS if encoder is None else (encoder,):
+        cand = policy.make_policy(dtype, encoder=kind)
+        length = 0                                                 # the padded flat length, as optim.flatten lays it out
+        for p in cand.parameters():
+            length = -(-(length + p.numel()) // optim.PAD) * optim.PAD
+        if tuple(d["params"].shape) == (length,):
+            net = cand.to(device)
+            flat = optim.flatten(net.named_parameters(), device)
+            break
+    if net is None or theirs != flat.layout():
         raise ValueError("the state's parameters are not laid out as policy.make_policy's")
     with torch.no_grad():
         flat.params.copy_(d["params"])

@@ -20,27 +20,41 @@ Composition only: this file contains no kernel call of its own.  Every piece run
 In a chunk the encoder and the MLP do not depend on time: sequence() runs them once over the T * n flattened rows and
 only the LSTM step by step.
 """
-from . import entity_encoder, mlp, recurrent
+from . import entity_attention, entity_encoder, mlp, recurrent
 from ._request import _module_base
 
+ENCODERS = ("simple", "attention")      # the reference's SimpleNet and its EntitySelfAttentionNet
 BUCKETS = (5, 5, 5, 2, 2)     # the reference's action heads: move amount, move angle, rotate, grab, lock
 BINS = 255                    # the two-hot critic's bins (value_head)
 
 
 class Backbone(_module_base()):
     """EntityEncoder(embed) -> MLP(4 * embed, channels, layers) -> LSTMCore(channels, hidden) over k_pack's rows.  The
-    compute dtype is the one the state's h carries: the encoder writes its features in it, and the GEMMs run in it."""
+    compute dtype is the one the state's h carries: the encoder writes its features in it, and the GEMMs run in it.
+    With encoder="attention" the backbone is entity_attention.AttentionEncoder(embed, channels) -> LSTMCore(channels,
+    hidden) with no MLP in between: the reference's EntitySelfAttentionNet stands in place of all of SimpleNet, and its
+    output channels feed the LSTM.  `masked` says whether the rows' entity tables carry their visibility masks (the
+    actor's do, the critic's do not): the attention encoder leaves the masked-out entities out."""
 
-    def __init__(self, embed=64, channels=256, layers=3, hidden=256, fused=True, generator=None):
+    def __init__(self, embed=64, channels=256, layers=3, hidden=256, fused=True, generator=None, encoder="simple", masked=False):
         super().__init__()
-        self.fused = bool(fused)
-        self.encoder = entity_encoder.EntityEncoder(embed, generator=generator)
-        self.mlp = mlp.MLP(4 * embed, channels, layers, fused=fused, generator=generator)
+        if encoder not in ENCODERS:
+            raise ValueError(f"encoder must be one of {ENCODERS}, got {encoder!r}")
+        self.fused, self.kind, self.masked = bool(fused), encoder, bool(masked)
+        if encoder == "attention":
+            self.encoder = entity_attention.AttentionEncoder(embed, channels, fused=fused, generator=generator)
+        else:
+            self.encoder = entity_encoder.EntityEncoder(embed, generator=generator)
+            self.mlp = mlp.MLP(4 * embed, channels, layers, fused=fused, generator=generator)
         self.core = recurrent.LSTMCore(channels, hidden, generator=generator)
 
     def set_fused(self, fused):
         """Switch every piece between its kernels and its eager() on the same parameters."""
-        self.fused = self.mlp.fused = bool(fused)
+        self.fused = bool(fused)
+        if self.kind == "attention":
+            self.encoder.fused = self.fused
+        else:
+            self.mlp.fused = self.fused
         return self
 
     def init_state(self, n, device, dtype=None):
@@ -49,6 +63,8 @@ class Backbone(_module_base()):
 
     def features(self, sim, rows, dtype):
         """The encoder and the MLP over rows [n, W]: [n, channels] in `dtype`.  They carry no state."""
+        if self.kind == "attention":
+            return self.encoder(sim, rows, dtype, self.masked)
         if self.fused:
             feats = self.encoder(sim, rows, dtype)
         else:
@@ -90,8 +106,9 @@ class ActorCritic(_module_base()):
         super().__init__()
         self.buckets, self.bins = tuple(int(b) for b in buckets), int(bins)
         self.dtype = torch.float32 if dtype is None else dtype
-        self.actor = Backbone(generator=generator, **backbone_kw)
-        self.critic = Backbone(generator=generator, **backbone_kw)
+        self.actor = Backbone(generator=generator, masked=True, **backbone_kw)
+        self.critic = Backbone(generator=generator, masked=False, **backbone_kw)
+        self.encoder = self.actor.kind
         hidden = self.actor.core.hidden
         self.actor_head = torch.nn.Linear(hidden, sum(self.buckets))
         self.critic_head = torch.nn.Linear(hidden, self.bins)
@@ -131,7 +148,11 @@ class ActorCritic(_module_base()):
         return (*self._heads(ya, yc), (sa, sc))
 
 
-def make_policy(dtype=None, fused=True, generator=None):
+def make_policy(dtype=None, fused=True, generator=None, encoder="simple"):
     """An ActorCritic of the reference's sizes: embed 64, three layers of 256 channels, 256 hidden channels, heads of
-    5 + 5 + 5 + 2 + 2 logits and 255 bins.  `dtype` (float32 by default) is the compute dtype the state's h carries."""
+    5 + 5 + 5 + 2 + 2 logits and 255 bins.  `dtype` (float32 by default) is the compute dtype the state's h carries.
+    encoder="attention" builds the reference's other network instead, EntitySelfAttentionNet(num_embed_channels=128,
+    num_out_channels=256, num_heads=4), in front of the same LSTM and heads."""
+    if encoder == "attention":
+        return ActorCritic(BUCKETS, BINS, dtype=dtype, generator=generator, embed=128, channels=256, hidden=256, fused=fused, encoder="attention")
     return ActorCritic(BUCKETS, BINS, dtype=dtype, generator=generator, embed=64, channels=256, layers=3, hidden=256, fused=fused)

@@ -245,6 +245,17 @@ class ShardedSimulator:
         return _mlp.compute_backward_sharded(self, z, params, grad_y, stream, grad_z=grad_z, grad_params=grad_params, channels=channels,
                                              eps=eps, slope=slope)
 
+    def attend_entities(self, qkv, key_mask=None, *, out=True, out_dtype=None, stream=None):
+        """HideAndSeekSimulator.attend_entities per shard: `qkv` has one tensor per shard, on the shard's device; `key_mask`
+        is None for all shards or a list; a list of the shards' results (entity_attention.compute_sharded)."""
+        from . import entity_attention as _att
+        return _att.compute_sharded(self, qkv, key_mask, stream, out=out, out_dtype=out_dtype)
+
+    def attend_entities_backward(self, qkv, key_mask, grad_out, *, grad_qkv=True, stream=None):
+        """HideAndSeekSimulator.attend_entities_backward per shard (entity_attention.compute_backward_sharded)."""
+        from . import entity_attention as _att
+        return _att.compute_backward_sharded(self, qkv, key_mask, grad_out, stream, grad_qkv=grad_qkv)
+
     def device_status(self):
         out = {}
         for s in self.shards:

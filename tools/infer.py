@@ -41,6 +41,7 @@ def parse(argv=None):
     ap.add_argument("--gpu-id", type=int, default=0)
     ap.add_argument("--greedy", action="store_true", help="every head's most likely action instead of a draw")
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--encoder", choices=("simple", "attention"), help="the policy's network (tools/train.py --encoder); by default read from the checkpoint")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
@@ -62,7 +63,7 @@ def main(argv=None):
     args = parse(argv)
     F = gpu_hideseek.SimFlags
     dtype = torch.float16 if args.fp16 else torch.bfloat16 if args.bf16 else torch.float32
-    net, normaliser = evaluate.load_policy(args.ckpt_path, dtype, torch.device("cuda", args.gpu_id), member=args.member)
+    net, normaliser = evaluate.load_policy(args.ckpt_path, dtype, torch.device("cuda", args.gpu_id), member=args.member, encoder=args.encoder)
     sim = gpu_hideseek.HideAndSeekSimulator(
         exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
         sim_flags=F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders, max_hiders=args.num_hiders,

@@ -40,6 +40,7 @@ def parse(argv=None):
     ap.add_argument("--greedy", action="store_true", help="every head's most likely action instead of a draw")
     ap.add_argument("--k-factor", type=float, default=league.DEFAULT_K_FACTOR)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--encoder", choices=("simple", "attention"), help="every policy's network (tools/train.py --encoder); by default read from each checkpoint")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
@@ -62,7 +63,7 @@ def load_policies(args, dtype, dev):
             if args.member is None or not 0 <= args.member < len(states):
                 raise SystemExit(f"{path} is a population checkpoint of {len(states)} members: give --member i or --all-members")
             states = [states[args.member]]
-        policies += [evaluate.load_policy(st, dtype, dev) for st in states]
+        policies += [evaluate.load_policy(st, dtype, dev, encoder=args.encoder) for st in states]
     P = len(policies)
     if P > league.MAX_POLICIES or args.num_worlds % (P * P):
         raise SystemExit(f"--num-worlds must be a multiple of {P * P} for {P} policies (at most {league.MAX_POLICIES})")

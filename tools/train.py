@@ -25,6 +25,8 @@ games the rollouts play; --pbt-interval N copies the best policies over the wors
 coefficient after every N-th update (0, the default: never).  The `Update:` print then has one metrics line per policy and
 the Elo table, four ratings to a line as the reference prints it, and the checkpoint is the population's (tools/infer.py
 and tools/league.py read it with --member).
+--encoder attention trains the reference's other network, EntitySelfAttentionNet (gpu_hideseek.entity_attention), in
+place of SimpleNet; the checkpoint's layout says which it was, and tools/infer.py and tools/league.py read it from there.
 Not here: pools of past policies (--pbt-past-policies), tensorboard / wandb, several GPUs.
 """
 import argparse
@@ -37,7 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import episodes, league, population, trainer  # noqa: E402
+from gpu_hideseek import episodes, league, policy, population, trainer  # noqa: E402
 
 PRINT_EVERY = 10
 
@@ -65,6 +67,7 @@ def parse(argv=None):
     ap.add_argument("--num-seekers", type=int, default=3)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--eager", action="store_true", help="the policy's eager pieces and the gather by torch indexing (Trainer(fused=False))")
+    ap.add_argument("--encoder", choices=policy.ENCODERS, default="simple", help="the policy's network in front of the LSTM (policy.make_policy)")
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--episode-stats", action="store_true", help="track finished episodes on the device and print them with the metrics")
     ap.add_argument("--out", type=str, help="with --phases: write the table here too")
@@ -120,7 +123,16 @@ def main(argv=None):
         sim_flags=F.RandomFlipTeams | F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders,
         max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=max(1, args.pbt_ensemble_size))
     sim.init()
-    tr = (population.Population if args.pbt_ensemble_size else trainer.Trainer)(sim, config(args), fused=not args.eager)
+    cfg = config(args)
+
+    def fresh(index):                                                  # the trainers' own seeding, with the encoder asked for
+        return policy.make_policy(cfg.dtype, generator=torch.Generator().manual_seed(cfg.seed + index), encoder=args.encoder)
+    if args.encoder == "simple":
+        tr = (population.Population if args.pbt_ensemble_size else trainer.Trainer)(sim, cfg, fused=not args.eager)
+    elif args.pbt_ensemble_size:
+        tr = population.Population(sim, cfg, nets=[fresh(p) for p in range(args.pbt_ensemble_size)], fused=not args.eager)
+    else:
+        tr = trainer.Trainer(sim, cfg, net=fresh(0), fused=not args.eager)
     run_dir = None if args.ckpt_dir is None else os.path.join(args.ckpt_dir, args.run_name)
     if args.restore is not None:
         tr.load_state_dict(torch.load(os.path.join(run_dir, str(args.restore)), map_location=tr.device, weights_only=False))
@@ -176,7 +188,7 @@ def main(argv=None):
     save()
     if args.phases and timed:
         fps = args.num_worlds * args.steps_per_update * timed / (wall_ms * 1e-3)
-        lines = phase_table(totals, wall_ms, timed, args, fps)
+        lines = ["encoder: " + args.encoder] + phase_table(totals, wall_ms, timed, args, fps)
         print("\n".join(lines))
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
