@@ -1034,6 +1034,37 @@ typedef struct hs_league_request {
 int32_t hs_league_step(hs_sim *sim, const hs_league_request *req);
 int32_t hs_league_step_async(hs_sim *sim, void *hip_stream, const hs_league_request *req);
 
+/* The league on a schedule read from a table: what a pool of past policies needs (gpu_hideseek.population), where the
+ * learners play frozen earlier policies and no world is past against past, which the all-pairs form cannot say.
+ * A schedule is `pairs`, G = group pairs (hider policy, seeker policy) over N = num_policies policies, pairs_host
+ * [G][2] i32 in HOST memory.  World w plays pairs[w mod G]; g = w / G is its group.  It is valid iff, checked in this
+ * order: 1 <= N <= HS_LEAGUE_MAX_POLICIES; 1 <= G <= HS_LEAGUE_MAX_GROUP; every entry is in [0, N); it is REGULAR: every
+ * policy holds the same number c = 2 G / N of sides per group, a pair (i, i) giving i two.  Regularity is exactly what
+ * makes the routing a permutation with equal blocks of R / N slots, so hs_pack_policy_inputs_routed,
+ * hs_sample_actions_routed and hs_compute_gae_grouped run on it as they are.
+ * hs_league_set_schedule validates (HS_ERR_INVALID_ARG, nothing of the handle changed, hs_last_error says which rule),
+ * builds the table the kernel reads (per pair the two policies and the sides each holds in the pairs before it, 16
+ * bytes), uploads it into memory the handle owns and returns when it is there; pairs_host may be freed then.  group == 0
+ * drops the schedule (pairs_host and num_policies are not looked at).  It is refused before hs_init and inside an open
+ * step, and it must not overlap a league step in flight on this handle: the step reads the table, as it reads the step
+ * table above.
+ * hs_league_step_scheduled is hs_league_step with that schedule; the request is the same struct.  What differs:
+ *   num_policies must equal the schedule's N, and the handle's number of worlds must be a multiple of G (not of N^2);
+ *   with i, j = pairs[q], q = w mod G, and held[q][p] the sides p holds in pairs[0 .. q-1]: a hider row goes to policy
+ *   i and a seeker row to j, and
+ *     slot = p R / N + g c k + k held[q][p] + (the number of earlier rows of the world with the same policy);
+ *   counts is [N][N][HS_LEAGUE_OUTCOMES], a game books into counts[i][j], and a pair that occurs more than once in the
+ *   table books into the one cell; cells of pairs the table does not hold are never written.
+ * Sides, malformed worlds, the latching, the outcomes, the Elo arithmetic (over all N policies, i == j moving nothing),
+ * every other validation, the ordering and the stream rules are hs_league_step's, word for word; with the table
+ * [(q / P, q % P) for q < P^2] every output has hs_league_step's bits.  Without a schedule set the call is refused with
+ * HS_ERR_INVALID_ARG.  The set of slots a world owns does not change when its teams flip here either.  Setting a schedule
+ * changes nothing for hs_league_step. */
+#define HS_LEAGUE_MAX_GROUP 256   /* the pairs of a schedule table: HS_LEAGUE_MAX_POLICIES squared */
+int32_t hs_league_set_schedule(hs_sim *sim, const int32_t *pairs_host, int32_t group, int32_t num_policies);
+int32_t hs_league_step_scheduled(hs_sim *sim, const hs_league_request *req);
+int32_t hs_league_step_scheduled_async(hs_sim *sim, void *hip_stream, const hs_league_request *req);
+
 /* The routed pack: hs_pack_policy_inputs_normalized for a league or a population (one kernel, csrc/hs_k_pack_routed.h).
  * One launch packs every agent row into SLOT order, each row normalised with the table of the policy that owns the slot,
  * and collects the moments per policy.  With R = worlds * A rows and N = num_policies (R % N == 0), policy p owns slots

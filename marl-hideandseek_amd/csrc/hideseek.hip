@@ -109,6 +109,8 @@ struct hs_sim {
     double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]
     double *episode_partials = nullptr;    // hs_episode_stats: the sums of each workgroup, [episode_grid][HS_EPISODE_STATS]
     int32_t *league_step = nullptr;        // hs_league_step: the counts of the step and its malformed worlds, [kLeagueMaxBins + 1], zero between calls
+    int4 *league_table = nullptr;          // hs_league_set_schedule: (hiders, seekers, the sides each holds before the pair), [kLeagueMaxGroup]
+    int league_group = 0, league_sides = 0, league_policies = 0;       // the table's G (0: none set), c = 2 G / N, and N
 
     template <typename T> int dalloc(T **p, size_t n, int fill_byte = 0) {
         void *d = nullptr;
@@ -1182,6 +1184,7 @@ static_assert(kExports[HS_EXPORT_AGENT_POLICY].dtype == HS_DTYPE_I32 && kExports
               kExports[HS_EXPORT_DONE].tail[0] == 1 && kExports[HS_EXPORT_SELF_MASK].dtype == HS_DTYPE_F32 && kExports[HS_EXPORT_SELF_MASK].tail[0] == 1 &&
               kExports[HS_EXPORT_EPISODE_RESULT].dtype == HS_DTYPE_F32 && kExports[HS_EXPORT_EPISODE_RESULT].tail[0] == 2,
               "k_league reads the done, self_type, self_mask and episode_result exports and writes policy_assignments");
+static_assert(HS_LEAGUE_MAX_GROUP == hs::kLeagueMaxGroup, "a schedule table holds every ordered pair");
 static_assert(hs::kLeagueThreads >= hs::kMaxAgents && hs::kLeagueMaxPolicies * hs::kLeagueMaxPolicies <= 1024, "a workgroup of k_league holds a world, k_league_fold is one workgroup");
 
 // The request with every null input, and a null policy_assignments, replaced by the handle's own.
@@ -1193,8 +1196,8 @@ hs::LeagueArgs league_args(const hs_sim *s, const hs_league_request *r) {
             s->league_step, S.N, s->A, r->num_policies, r->team_size};
 }
 
-int check_league(hs_sim *s, const hs_league_request *r) {
-    const Check c{"hs_league_step"};
+// hs_league_step and, with `scheduled`, hs_league_step_scheduled: one set of rules, of which only the schedule's differ.
+int check_league_as(const Check &c, hs_sim *s, const hs_league_request *r, bool scheduled) {
     if (!r) return c.bad("null request");
     if (!r->world_hider_team || !r->world_phase) return c.bad("null state pointer");
     if (!r->counts) return c.bad("null counts");
@@ -1202,7 +1205,13 @@ int check_league(hs_sim *s, const hs_league_request *r) {
     if (r->num_policies < 1 || r->num_policies > HS_LEAGUE_MAX_POLICIES) return c.bad("num_policies must be in [1, HS_LEAGUE_MAX_POLICIES]");
     if (r->team_size < 1 || s->A != 2 * r->team_size) return c.bad("team_size must be at least 1 and the handle's agents per world 2 * team_size");
     const int64_t P = r->num_policies;
-    if ((int64_t)s->S.N % (P * P)) return c.bad("the number of worlds must be a multiple of num_policies^2");
+    if (scheduled) {
+        if (s->league_group == 0) return c.bad("no schedule is set (hs_league_set_schedule)");
+        if (r->num_policies != s->league_policies) return c.bad("num_policies must equal the schedule's");
+        if ((int64_t)s->S.N % s->league_group) return c.bad("the number of worlds must be a multiple of the schedule's group");
+    } else if ((int64_t)s->S.N % (P * P)) {
+        return c.bad("the number of worlds must be a multiple of num_policies^2");
+    }
     if ((int64_t)s->S.N * s->A >= (int64_t)1 << 31) return c.bad("worlds * agents must stay below 2^31");
     if (!std::isfinite(r->k_factor) || !(r->k_factor > 0.0)) return c.bad("k_factor must be finite and above 0");
     if (!aligned(4, {r->done, r->self_type, r->self_mask, r->episode_result, r->hider_team, r->policy_assignments, r->slot, r->row_of_slot, r->clear_slot,
@@ -1221,13 +1230,51 @@ int check_league(hs_sim *s, const hs_league_request *r) {
                        range("counts", r->counts, (uintptr_t)(P * P) * HS_LEAGUE_OUTCOMES * sizeof(int64_t)), range("elo", r->elo, (uintptr_t)P * sizeof(double))}));
     return c.handle_ready(s);
 }
-// One k_league over every agent row (the request has passed check_league), then the fold of the step's counts and ratings.
+int check_league(hs_sim *s, const hs_league_request *r) { return check_league_as(Check{"hs_league_step"}, s, r, false); }
+int check_league_scheduled(hs_sim *s, const hs_league_request *r) { return check_league_as(Check{"hs_league_step_scheduled"}, s, r, true); }
+// The fold of the step's counts and ratings, after either kernel over the rows.
+int launch_league_fold(hs_sim *s, hipStream_t strm, const hs_league_request *r) {
+    hipLaunchKernelGGL(hs::k_league_fold<>, dim3(1), dim3(hs::kLeagueMaxPolicies * hs::kLeagueMaxPolicies), 0, strm, s->league_step, r->num_policies, r->k_factor,
+                       (long long *)r->counts, r->elo, r->bad);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+// One k_league over every agent row (the request has passed check_league), then the fold.
 int launch_league(hs_sim *s, hipStream_t strm, const hs_league_request *r) {
     const hs::LeagueArgs a = league_args(s, r);
     hipLaunchKernelGGL(hs::k_league<>, dim3(hs::league_grid(a.worlds, a.A)), dim3(hs::kLeagueThreads), 0, strm, a);
-    hipLaunchKernelGGL(hs::k_league_fold<>, dim3(1), dim3(hs::kLeagueMaxPolicies * hs::kLeagueMaxPolicies), 0, strm, s->league_step, a.P, r->k_factor,
-                       (long long *)r->counts, r->elo, r->bad);
-    HS_HIP(hipGetLastError());
+    return launch_league_fold(s, strm, r);
+}
+// The same with the handle's schedule table (the request has passed check_league_scheduled).
+int launch_league_scheduled(hs_sim *s, hipStream_t strm, const hs_league_request *r) {
+    const hs::LeagueArgs a = league_args(s, r);
+    hipLaunchKernelGGL(hs::k_league_scheduled<>, dim3(hs::league_grid(a.worlds, a.A)), dim3(hs::kLeagueThreads), 0, strm, a, (const int4 *)s->league_table,
+                       s->league_group, s->league_sides);
+    return launch_league_fold(s, strm, r);
+}
+
+// hs_league_set_schedule: the rules of a table, then its device form.  Nothing of the handle changes before every rule has passed.
+int set_league_schedule(hs_sim *s, const int32_t *pairs, int32_t group, int32_t num_policies) {
+    const Check c{"hs_league_set_schedule"};
+    HS_TRY(c.handle_ready(s));
+    if (group == 0) { s->league_group = s->league_sides = s->league_policies = 0; return HS_OK; }
+    if (num_policies < 1 || num_policies > HS_LEAGUE_MAX_POLICIES) return c.bad("num_policies must be in [1, HS_LEAGUE_MAX_POLICIES]");
+    if (group < 0 || group > HS_LEAGUE_MAX_GROUP) return c.bad("group must be 0 (no schedule) or in [1, HS_LEAGUE_MAX_GROUP]");
+    if (!pairs) return c.bad("null pairs");
+    const int N = num_policies, G = group;
+    int sides[HS_LEAGUE_MAX_POLICIES] = {};
+    std::vector<int4> table((size_t)G);
+    for (int q = 0; q < G; ++q) {
+        const int32_t i = pairs[2 * q], j = pairs[2 * q + 1];
+        if (i < 0 || i >= N || j < 0 || j >= N) return c.bad("pairs[" + std::to_string(q) + "] is out of range: every entry must be in [0, num_policies)");
+        table[(size_t)q] = make_int4(i, j, sides[i], sides[j]);
+        ++sides[i]; ++sides[j];
+    }
+    for (int p = 0; p < N; ++p)
+        if (sides[p] * N != 2 * G) return c.bad("the schedule is not regular: every policy must hold the same number 2 group / num_policies of sides");
+    HS_HIP(hipMemcpy(s->league_table, table.data(), table.size() * sizeof(int4), hipMemcpyHostToDevice));
+    HS_HIP(hipDeviceSynchronize());       // the table is in place, whatever stream the next step is enqueued on
+    s->league_group = G; s->league_sides = 2 * G / N; s->league_policies = N;
     return HS_OK;
 }
 }  // namespace
@@ -1610,6 +1657,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->adam_workspace, hs::kAdamWorkspace);
     HS_ALLOC(s->episode_partials, (size_t)hs::episode_grid((int)N, A) * hs::kEpiStats);
     HS_ALLOC(s->league_step, hs::kLeagueMaxBins + 1);
+    HS_ALLOC(s->league_table, hs::kLeagueMaxGroup);
 #undef HS_ALLOC
     // Sim::Sim (sim.cpp:1346-1408): resetLevel = 1 for every world, no grab joints
     {
@@ -1948,6 +1996,14 @@ int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call
 int32_t hs_episode_stats_async(hs_sim *s, void *hip_stream, const hs_episode_request *req) { return call_async(s, hip_stream, check_episode, launch_episode, req); }
 int32_t hs_league_step(hs_sim *s, const hs_league_request *req) { return call_blocking(s, check_league, launch_league, req); }
 int32_t hs_league_step_async(hs_sim *s, void *hip_stream, const hs_league_request *req) { return call_async(s, hip_stream, check_league, launch_league, req); }
+int32_t hs_league_set_schedule(hs_sim *s, const int32_t *pairs_host, int32_t group, int32_t num_policies) {
+    HS_ENTER(s, "null sim");
+    return set_league_schedule(s, pairs_host, group, num_policies);
+}
+int32_t hs_league_step_scheduled(hs_sim *s, const hs_league_request *req) { return call_blocking(s, check_league_scheduled, launch_league_scheduled, req); }
+int32_t hs_league_step_scheduled_async(hs_sim *s, void *hip_stream, const hs_league_request *req) {
+    return call_async(s, hip_stream, check_league_scheduled, launch_league_scheduled, req);
+}
 int32_t hs_pack_policy_inputs_routed(hs_sim *s, const hs_pack_routed_request *req) { return call_blocking(s, check_pack_routed, launch_pack_routed, req); }
 int32_t hs_pack_policy_inputs_routed_async(hs_sim *s, void *hip_stream, const hs_pack_routed_request *req) { return call_async(s, hip_stream, check_pack_routed, launch_pack_routed, req); }
 int32_t hs_sample_actions_routed(hs_sim *s, const hs_sample_routed_request *req) { return call_blocking(s, check_sample_routed, launch_sample_routed, req); }

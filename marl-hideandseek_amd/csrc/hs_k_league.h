@@ -3,6 +3,8 @@
 // pair q = w mod P^2: policy q / P the hiders, policy q % P the seekers) and ranks it in the stable sort of all rows by
 // (policy, row) by the closed form stated there: no scan across worlds and no sort.  The lane of a world's first row books
 // the game that ended with the step under the hider team latched at its start, and latches the next.
+// hs_league_step_scheduled is the same kernel body with the schedule read from a table of the handle (LeagueTable below):
+// the two differ only in how a world finds its pair and the sides held before it.
 //
 // The shape is k_episode's: a workgroup takes whole worlds, kLeagueThreads / A of them, its rows are contiguous (a wave's
 // access to an input is one 256-byte range), and what a world needs of its rows (how many are hiders, is one masked, the
@@ -21,6 +23,7 @@
 namespace hs {
 
 constexpr int kLeagueThreads = 256, kLeagueMaxPolicies = 16, kLeagueOutcomes = 4;
+constexpr int kLeagueMaxGroup = kLeagueMaxPolicies * kLeagueMaxPolicies;                      // the pairs of a schedule table
 constexpr int kLeagueMaxBins = kLeagueMaxPolicies * kLeagueMaxPolicies * kLeagueOutcomes;     // + 1: the malformed worlds
 constexpr int kLeagueHidersWin = 0, kLeagueSeekersWin = 1, kLeagueDraw = 2, kLeagueNoOutcome = 3;
 
@@ -40,8 +43,45 @@ __host__ __device__ constexpr int league_grid(int worlds, int A) {
     return (worlds + league_worlds_per_group(A) - 1) / league_worlds_per_group(A);
 }
 
-template <int kThreads = kLeagueThreads>
-__global__ __launch_bounds__(kThreads) void k_league(LeagueArgs a) {
+// How a world finds its game.  Both forms answer the same questions for world w's pair q = w mod group(): the two
+// policies, the sides a policy holds in the pairs of the group before q, and the game's cell of the N x N table; a group
+// gives every policy sides() sides, and a policy owns block() slots in all.
+// The fixed schedule of hs_league_step, in closed form: pair q is (q / P, q % P).
+struct LeagueAllPairs {
+    int P;
+    struct Game {
+        int q, i, j, P;
+        // as hiders in the pairs p P .. p P + P - 1, as seekers in every P-th
+        __device__ int held(int p, bool) const {
+            const int asHiders = q - p * P < 0 ? 0 : q - p * P > P ? P : q - p * P;
+            const int asSeekers = i + (j > p ? 1 : 0);
+            return asHiders + asSeekers;
+        }
+        __device__ int cell() const { return q; }
+    };
+    __device__ int group() const { return P * P; }
+    __device__ int sides() const { return 2 * P; }
+    __device__ int block(int worlds, int A) const { return worlds / P * A; }      // R / P: worlds is a multiple of P^2
+    __device__ Game game(int q) const { const int i = q / P; return {q, i, q - i * P, P}; }
+};
+// A table (hs_league_set_schedule): entry q is (hider policy, seeker policy, the sides each holds in the pairs before q),
+// 16 bytes, so the lanes of a world read one broadcast int4.  Indexed per world: a workgroup's worlds span groups.
+struct LeagueTable {
+    const int4 *pairs;
+    int G, c, N;
+    struct Game {
+        int i, j, heldI, heldJ, N;
+        __device__ int held(int, bool hider) const { return hider ? heldI : heldJ; }
+        __device__ int cell() const { return i * N + j; }
+    };
+    __device__ int group() const { return G; }
+    __device__ int sides() const { return c; }
+    __device__ int block(int worlds, int A) const { return worlds / G * c * (A / 2); }    // R / N: worlds is a multiple of G
+    __device__ Game game(int q) const { const int4 e = pairs[q]; return {e.x, e.y, e.z, e.w, N}; }
+};
+
+template <int kThreads, typename Schedule>
+__device__ __forceinline__ void league_rows(const LeagueArgs &a, const Schedule sched) {
     __shared__ int32_t flags[kThreads];                   // bit 0: the row's self_type is nonzero, bit 1: its self_mask is 0
     __shared__ int32_t hist[kLeagueMaxBins + 1];
     const int tid = threadIdx.x;
@@ -73,15 +113,14 @@ __global__ __launch_bounds__(kThreads) void k_league(LeagueArgs a) {
         const bool malformed = hiders != k || masked != 0;
         const bool hider = malformed ? r < k : (f & 1) != 0;
         if (malformed) hidersBefore = r < k ? r : k;
-        const int g = w / PP, q = w - g * PP;
-        const int i = q / P, j = q - i * P;               // the hiders' policy, the seekers'
+        const int group = sched.group();
+        const int g = w / group, q = w - g * group;
+        const auto game = sched.game(q);
+        const int i = game.i, j = game.j;                 // the hiders' policy, the seekers'
         const int p = hider ? i : j;
-        // the sides p holds in the worlds before q of the group: as hiders in the pairs p P .. p P + P - 1, as seekers in every P-th
-        const int asHiders = q - p * P < 0 ? 0 : q - p * P > P ? P : q - p * P;
-        const int asSeekers = i + (j > p ? 1 : 0);
+        const int held = game.held(p, hider);             // the sides p holds in the worlds before q of the group
         const int rank = i == j ? r : hider ? hidersBefore : r - hidersBefore;
-        const int perPolicy = a.worlds / P * A;           // R / P: worlds is a multiple of P^2
-        const int s = p * perPolicy + g * (2 * P * k) + k * (asHiders + asSeekers) + rank;
+        const int s = p * sched.block(a.worlds, A) + g * (sched.sides() * k) + k * held + rank;
         a.policy[row] = p;
         if (a.slot) a.slot[row] = s;
         if (a.rowOfSlot) a.rowOfSlot[s] = (int32_t)row;
@@ -96,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_league(LeagueArgs a) {
                     const float x = a.episodeResult[(size_t)w * 2 + h];
                     o = x == 1.f ? kLeagueHidersWin : x == 0.f ? kLeagueSeekersWin : x == 0.5f ? kLeagueDraw : kLeagueNoOutcome;
                 }
-                atomicAdd(&hist[q * kLeagueOutcomes + o], 1);
+                atomicAdd(&hist[game.cell() * kLeagueOutcomes + o], 1);
                 booked = 1;
             }
             if (done != 0 || phase == 0) {
@@ -110,6 +149,17 @@ __global__ __launch_bounds__(kThreads) void k_league(LeagueArgs a) {
         const int32_t v = hist[b];
         if (v != 0) atomicAdd(&a.step[b], v);
     }
+}
+
+template <int kThreads = kLeagueThreads>
+__global__ __launch_bounds__(kThreads) void k_league(LeagueArgs a) {
+    league_rows<kThreads>(a, LeagueAllPairs{a.P});
+}
+
+// hs_league_step_scheduled: `a.P` is the table's N.
+template <int kThreads = kLeagueThreads>
+__global__ __launch_bounds__(kThreads) void k_league_scheduled(LeagueArgs a, const int4 *__restrict__ pairs, int G, int c) {
+    league_rows<kThreads>(a, LeagueTable{pairs, G, c, a.P});
 }
 
 // counts += the step table; elo moved by the step's games, all rated against elo as it stood; *bad = the step's malformed

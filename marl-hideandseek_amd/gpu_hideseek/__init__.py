@@ -404,6 +404,26 @@ class HideAndSeekSimulator:
                                slot=slot, row_of_slot=row_of_slot, clear_slot=clear_slot, bad=bad, done=done, self_type=self_type,
                                self_mask=self_mask, episode_result=episode_result, hider_team=hider_team)
 
+    def set_league_schedule(self, pairs, num_policies):
+        """Give the handle the league schedule `pairs`, a list of (hider_policy, seeker_policy) over `num_policies`
+        policies that league_step_scheduled then plays: world w plays pairs[w % len(pairs)] (hs_league_set_schedule, whose
+        header comment is the contract; league.check_schedule states what makes a table valid, league.all_pairs_schedule
+        and league.past_play_schedule build two).  pairs None drops the schedule.  After init(), outside an open step, and
+        not while a league step of this handle is in flight; returns when the table is on the device.  Raises ValueError
+        for a table that breaks a rule, before the library is involved.  league_step is not affected."""
+        from . import league as _league
+        return _league.set_schedule(self, pairs, num_policies)
+
+    def league_step_scheduled(self, num_policies, team_size, state, counts, elo, *, k_factor=32.0, policy_assignments=None, slot=None, row_of_slot=None,
+                              clear_slot=None, bad=None, done=None, self_type=None, self_mask=None, episode_result=None, hider_team=None, stream=None):
+        """league_step under the schedule set_league_schedule gave the handle (hs_league_step_scheduled): `num_policies` is
+        the schedule's, the number of worlds a multiple of its length, `counts` [N, N, 4] and `elo` [N]; everything else,
+        the result included, is league_step's."""
+        from . import league as _league
+        return _league.compute_scheduled(self, num_policies, team_size, state, counts, elo, stream, k_factor=k_factor, policy_assignments=policy_assignments,
+                                         slot=slot, row_of_slot=row_of_slot, clear_slot=clear_slot, bad=bad, done=done, self_type=self_type,
+                                         self_mask=self_mask, episode_result=episode_result, hider_team=hider_team)
+
     def step_begin(self):
         """Enqueue one step on this handle's own stream and return (hs_step_begin); pair with step_end()."""
         _check(self._L.hs_step_begin(self._h))

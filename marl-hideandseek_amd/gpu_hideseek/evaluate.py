@@ -27,17 +27,23 @@ def members(d):
     return list(d["members"]) if "members" in d else [d]
 
 
-def load_policy(path_or_dict, dtype=None, device=None, member=None, encoder=None):
+def load_policy(path_or_dict, dtype=None, device=None, member=None, encoder=None, past=None):
     """(net, normaliser or None) from a trainer state_dict (a file torch.save wrote, or the dict): a policy.make_policy
     of `dtype` whose parameters are the state's flat "params" buffer, laid out as the state's optimiser says, and an
-    ObsNormaliser with the state's moments where the trainer had one.  Of a population's checkpoint, `member` i.
+    ObsNormaliser with the state's moments where the trainer had one.  Of a population's checkpoint, `member` i, or
+    `past` i: member i of its pool of past policies.
     `encoder` is one of policy.ENCODERS, or None for the kind whose flat parameter length is the state's."""
     import torch
     from . import optim, policy
     from .policy_inputs import ObsNormaliser
     device = torch.device("cuda", 0) if device is None else torch.device(device)
     d = torch.load(path_or_dict, map_location=device, weights_only=False) if not isinstance(path_or_dict, dict) else path_or_dict
-    if "members" in d:
+    if past is not None:
+        pool = d.get("past", ()) if "members" in d else ()
+        if member is not None or isinstance(past, bool) or not isinstance(past, int) or not 0 <= past < len(pool):
+            raise ValueError(f"a checkpoint with a pool of {len(pool)} past policies: past must be in [0, {len(pool)}) and member None, got past {past!r}, member {member!r}")
+        d = pool[past]
+    elif "members" in d:
         if member is None or not 0 <= member < len(d["members"]):
             raise ValueError(f"a population checkpoint of {len(d['members'])} members: member must be in [0, {len(d['members'])}), got {member!r}")
         d = d["members"][member]

@@ -18,7 +18,16 @@ rated against the ratings before it.
 host_step is the contract in plain numpy (int64 counts, float64 ratings, the same pair order): the tests' reference, and
 it needs no GPU.  Single device: there is no ShardedSimulator form, because the ratings would have to cross the shards.
 Training several policies at once on this schedule (several train states, live ratings, hyper-parameter exploration) is
-gpu_hideseek.population; pools of past policies are not implemented.
+gpu_hideseek.population.
+
+A schedule can also be a TABLE (hs_league_set_schedule, hs_league_step_scheduled): `pairs`, a list of G (hider_policy,
+seeker_policy) over N policies; world w plays pairs[w mod G] and g = w // G is its group.  check_schedule states what makes
+a table valid; the rule that matters is that it is REGULAR, every policy holding the same number c = 2 G / N of sides per
+group, because that is exactly what gives every policy R / N rows at every step: the routing stays a permutation with
+equal blocks, and the routed pack, the routed sampler and the grouped advantages run on it unchanged.
+all_pairs_schedule(P) is the fixed schedule as a table; past_play_schedule(T, Q) is the population's pool of past
+policies (the reference's --pbt-past-policies with past_play_portion = 1): learners 0 .. T-1 play the frozen policies
+T .. T+Q-1 on both sides, never past against past.  The League evaluator itself plays the fixed schedule only.
 """
 import ctypes as C
 import math
@@ -27,6 +36,8 @@ from . import policy_inputs, replay, rollout
 from ._request import _disjoint, _run, _tensor, on_current_stream
 
 MAX_POLICIES = 16         # HS_LEAGUE_MAX_POLICIES
+MAX_GROUP = 256           # HS_LEAGUE_MAX_GROUP
+FILLS = ("cross", "self")
 OUTCOMES = 4              # HS_LEAGUE_OUTCOMES
 HIDERS_WIN, SEEKERS_WIN, DRAW, NO_OUTCOME = 0, 1, 2, 3
 DEFAULT_K_FACTOR = 32.0
@@ -45,7 +56,7 @@ class HsLeagueRequest(C.Structure):
                 ("world_hider_team", C.c_void_p), ("world_phase", C.c_void_p), ("bad", C.c_void_p), ("counts", C.c_void_p), ("elo", C.c_void_p)]
 
 
-def _league_shape(num_worlds, agents, num_policies, team_size):
+def _league_shape(num_worlds, agents, num_policies, team_size, group=None):
     for name, v in (("num_policies", num_policies), ("team_size", team_size)):
         if isinstance(v, bool) or not isinstance(v, int):
             raise ValueError(f"{name} must be an integer, got {v!r}")
@@ -53,8 +64,14 @@ def _league_shape(num_worlds, agents, num_policies, team_size):
         raise ValueError(f"num_policies must be in [1, {MAX_POLICIES}], got {num_policies}")
     if team_size < 1 or agents != 2 * team_size:
         raise ValueError(f"team_size must be at least 1 and the simulator's agents per world 2 * team_size: team_size {team_size}, {agents} agents")
-    if num_worlds < 1 or num_worlds % (num_policies * num_policies):
-        raise ValueError(f"num_worlds must be a multiple of num_policies^2 = {num_policies * num_policies}, got {num_worlds}")
+    if group is None:
+        if num_worlds < 1 or num_worlds % (num_policies * num_policies):
+            raise ValueError(f"num_worlds must be a multiple of num_policies^2 = {num_policies * num_policies}, got {num_worlds}")
+    else:
+        if isinstance(group, bool) or not isinstance(group, int) or not 1 <= group <= MAX_GROUP:
+            raise ValueError(f"group must be an integer in [1, {MAX_GROUP}], got {group!r}")
+        if num_worlds < 1 or num_worlds % group:
+            raise ValueError(f"num_worlds must be a multiple of the schedule's group = {group}, got {num_worlds}")
     if num_worlds * agents >= 2 ** 31:
         raise ValueError("num_worlds * agents must stay below 2^31")
 
@@ -74,6 +91,69 @@ def schedule(num_worlds, num_policies):
     return [(w % (P * P)) // P for w in range(num_worlds)], [(w % (P * P)) % P for w in range(num_worlds)]
 
 
+def check_schedule(pairs, num_policies):
+    """The table `pairs` over `num_policies` policies as a list of (int, int), or ValueError naming the first rule it breaks,
+    in this order: 1 <= N <= 16; 1 <= G <= 256; every entry in [0, N); regular, every policy holding the same number
+    c = 2 G / N of sides per group (a pair (i, i) gives i two)."""
+    N = num_policies
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= MAX_POLICIES:
+        raise ValueError(f"num_policies must be an integer in [1, {MAX_POLICIES}], got {N!r}")
+    try:
+        table = [(int(i), int(j)) for i, j in pairs]
+    except (TypeError, ValueError):
+        raise ValueError("pairs must be a list of (hider_policy, seeker_policy)") from None
+    G = len(table)
+    if not 1 <= G <= MAX_GROUP:
+        raise ValueError(f"the group, len(pairs), must be in [1, {MAX_GROUP}], got {G}")
+    for q, (i, j) in enumerate(table):
+        if not (0 <= i < N and 0 <= j < N):
+            raise ValueError(f"pairs[{q}] = ({i}, {j}) is out of range: every entry must be in [0, {N})")
+    sides = [0] * N
+    for i, j in table:
+        sides[i] += 1
+        sides[j] += 1
+    if any(n * N != 2 * G for n in sides):
+        raise ValueError(f"the schedule is not regular: every policy must hold 2 G / N = {2 * G}/{N} sides per group, they hold {sides}")
+    return table
+
+
+def all_pairs_schedule(num_policies):
+    """The fixed schedule as a table: pair q is (q // P, q % P)."""
+    P = int(num_policies)
+    return [(q // P, q % P) for q in range(P * P)]
+
+
+def past_play_schedule(num_train, num_past, fill="cross"):
+    """The table of T = num_train learners (policies 0 .. T-1) and a pool of Q = num_past frozen ones (T .. T+Q-1), with
+    1 <= Q <= T and T + Q <= 16: for t in 0..T-1, for u in 0..Q-1: (t, T+u) then (T+u, t); then, for r in 1..T-Q, for t in
+    0..T-1: (t, (t+r) % T) with fill "cross", (t, t) with fill "self".  G = T (T + Q), every policy holds 2 T sides, and
+    no pair is past against past.  Q > T is refused: the pool would hold fewer sides than the learners, and only games
+    between past policies, which nobody learns from, could fill the gap."""
+    T, Q = num_train, num_past
+    for name, v in (("num_train", T), ("num_past", Q)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if fill not in FILLS:
+        raise ValueError(f"fill must be one of {FILLS}, got {fill!r}")
+    if not 1 <= Q <= T:
+        raise ValueError(f"num_past must be in [1, num_train]: num_train {T}, num_past {Q}")
+    if T + Q > MAX_POLICIES:
+        raise ValueError(f"num_train + num_past must be at most {MAX_POLICIES}, got {T} + {Q}")
+    pairs = [x for t in range(T) for u in range(Q) for x in ((t, T + u), (T + u, t))]
+    pairs += [(t, (t + r) % T if fill == "cross" else t) for r in range(1, T - Q + 1) for t in range(T)]
+    return pairs
+
+
+def _held(pairs, num_policies):
+    """held[q][p]: the sides policy p holds in the pairs before q."""
+    held, row = [], [0] * num_policies
+    for i, j in pairs:
+        held.append(list(row))
+        row[i] += 1
+        row[j] += 1
+    return held
+
+
 def new_state(num_worlds, device):
     """The per-world state, {name: tensor}: no world's team order latched."""
     import torch
@@ -87,11 +167,12 @@ def print_elos(elos, file=None):
         print("".join(f"{idx:>3}: {elo:>8.2f}       " for idx, elo in enumerate(vals[lo:lo + 4], lo)), file=file)
 
 
-def host_step(state, counts, elo, num_policies, team_size, done, self_type, self_mask, episode_result, hider_team, k_factor=DEFAULT_K_FACTOR):
+def host_step(state, counts, elo, num_policies, team_size, done, self_type, self_mask, episode_result, hider_team, k_factor=DEFAULT_K_FACTOR, pairs=None):
     """The contract of hs_league_step in plain numpy, one world at a time.  `state` {"world_hider_team", "world_phase"}
     (int32 [worlds]), `counts` (int64 [P, P, 4]) and `elo` (float64 [P]) are updated in place; done, self_type, self_mask
     are [R], episode_result [worlds, 2], hider_team [worlds].  Returns {"policy_assignments", "slot", "row_of_slot",
-    "clear_slot": int32 [R], "bad": int}."""
+    "clear_slot": int32 [R], "bad": int}.  With `pairs` (a table that passes check_schedule for num_policies) it is the
+    contract of hs_league_step_scheduled: world w plays pairs[w mod G], and only the pair and the slot are found otherwise."""
     import numpy as np
     P, k = int(num_policies), int(team_size)
     A = 2 * k
@@ -102,21 +183,26 @@ def host_step(state, counts, elo, num_policies, team_size, done, self_type, self
     policy, slot = np.zeros(R, np.int32), np.zeros(R, np.int32)
     delta = np.zeros((P, P, OUTCOMES), np.int64)
     bad = 0
-    held = [[sum((qq // P == p) + (qq % P == p) for qq in range(q)) for p in range(P)] for q in range(P * P)]
+    if pairs is None:
+        G, c = P * P, 2 * P
+        held = [[sum((qq // P == p) + (qq % P == p) for qq in range(q)) for p in range(P)] for q in range(P * P)]
+    else:
+        G, c = len(pairs), 2 * len(pairs) // P
+        held = _held(pairs, P)
     for w in range(worlds):
         rows = slice(w * A, (w + 1) * A)
         hider = self_type[rows] != 0
         if int(hider.sum()) != k or bool((self_mask[rows] == 0).any()):
             bad += 1
             hider = np.arange(A) < k
-        g, q = divmod(w, P * P)
-        i, j = divmod(q, P)
+        g, q = divmod(w, G)
+        i, j = divmod(q, P) if pairs is None else pairs[q]
         for r in range(A):
             p = i if hider[r] else j
             sides = held[q][p]                  # the sides p holds in the worlds of the group before q
             rank = sum(1 for b in range(r) if (i if hider[b] else j) == p)
             policy[w * A + r] = p
-            slot[w * A + r] = p * (R // P) + g * 2 * P * k + k * sides + rank
+            slot[w * A + r] = p * (R // P) + g * c * k + k * sides + rank
         ended = done[w * A] != 0
         if ended and state["world_phase"][w] == 1:
             h = int(state["world_hider_team"][w])
@@ -148,16 +234,18 @@ def host_step(state, counts, elo, num_policies, team_size, done, self_type, self
 
 
 def request(num_worlds, agents, gpu_id, num_policies, team_size, state, counts, elo, k_factor=DEFAULT_K_FACTOR, policy_assignments=None, slot=None,
-            row_of_slot=None, clear_slot=None, bad=None, done=None, self_type=None, self_mask=None, episode_result=None, hider_team=None):
+            row_of_slot=None, clear_slot=None, bad=None, done=None, self_type=None, self_mask=None, episode_result=None, hider_team=None, group=None):
     """Validate a call over num_worlds x agents agent rows on GPU `gpu_id` for a league of `num_policies` with teams of
     `team_size`: `state` as new_state() makes it, `counts` [P, P, 4] int64, `elo` [P] float64; the routing outputs
     policy_assignments, slot, row_of_slot, clear_slot (int32 [rows], [rows, 1] or [num_worlds, agents]) and bad (int32 [1])
     are each None or a tensor (policy_assignments None: the simulator's own export is written); the inputs given
     explicitly as in episodes.request, None meaning the simulator's own.  Returns ({"counts", "elo", "state" and the
-    outputs given}, HsLeagueRequest).  Raises ValueError before the library is involved."""
+    outputs given}, HsLeagueRequest).  With `group` (the G of a schedule table) the request is one for
+    hs_league_step_scheduled: num_worlds must be a multiple of group, not of num_policies^2.  Raises ValueError before the
+    library is involved."""
     import torch
     dev = torch.device("cuda", gpu_id)
-    _league_shape(num_worlds, agents, num_policies, team_size)
+    _league_shape(num_worlds, agents, num_policies, team_size, group)
     k_factor = _k_factor(k_factor)
     P, rows = num_policies, num_worlds * agents
     if not isinstance(state, dict) or set(state) != {k for k, _ in WORLD_STATE}:
@@ -207,6 +295,32 @@ def compute(sim, num_policies, team_size, state, counts, elo, stream=None, **kw)
     """HideAndSeekSimulator.league_step."""
     res, req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, num_policies, team_size, state, counts, elo, **kw)
     _run(sim, "hs_league_step", req, stream)
+    return res
+
+
+def set_schedule(sim, pairs, num_policies):
+    """HideAndSeekSimulator.set_league_schedule."""
+    from ._native import check
+    if pairs is None:
+        check(sim._L.hs_league_set_schedule(sim._h, None, 0, 0))
+        sim._league_schedule = None
+        return None
+    table = check_schedule(pairs, num_policies)
+    flat = (C.c_int32 * (2 * len(table)))(*(x for pair in table for x in pair))
+    check(sim._L.hs_league_set_schedule(sim._h, flat, len(table), num_policies))
+    sim._league_schedule = (len(table), num_policies)
+    return table
+
+
+def compute_scheduled(sim, num_policies, team_size, state, counts, elo, stream=None, **kw):
+    """HideAndSeekSimulator.league_step_scheduled."""
+    sched = getattr(sim, "_league_schedule", None)
+    if sched is None:
+        raise ValueError("no schedule is set: call set_league_schedule(pairs, num_policies) first")
+    if num_policies != sched[1]:
+        raise ValueError(f"num_policies must equal the schedule's {sched[1]}, got {num_policies!r}")
+    res, req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, num_policies, team_size, state, counts, elo, group=sched[0], **kw)
+    _run(sim, "hs_league_step_scheduled", req, stream)
     return res
 
 

@@ -25,9 +25,15 @@ games the rollouts play; --pbt-interval N copies the best policies over the wors
 coefficient after every N-th update (0, the default: never).  The `Update:` print then has one metrics line per policy and
 the Elo table, four ratings to a line as the reference prints it, and the checkpoint is the population's (tools/infer.py
 and tools/league.py read it with --member).
+--pbt-past-policies Q adds a pool of Q frozen past policies to the population (the reference's flag, which it runs with
+past_play_portion = 1): the learners play the pool's members on both sides, never past against past
+(league.past_play_schedule; 1 <= Q <= P, --num-worlds a multiple of P (P + Q)), and --pbt-snapshot-interval N copies the
+best-rated learner into the pool's next slot after every N-th update, before that update's exploit step (0, the default:
+the pool stays a copy of the first learners).  The Elo table then covers all P + Q policies, the learners first, and a
+line names the update each pool slot's snapshot was taken at.
 --encoder attention trains the reference's other network, EntitySelfAttentionNet (gpu_hideseek.entity_attention), in
 place of SimpleNet; the checkpoint's layout says which it was, and tools/infer.py and tools/league.py read it from there.
-Not here: pools of past policies (--pbt-past-policies), tensorboard / wandb, several GPUs.
+Not here: tensorboard / wandb, several GPUs.
 """
 import argparse
 import json
@@ -73,7 +79,13 @@ def parse(argv=None):
     ap.add_argument("--out", type=str, help="with --phases: write the table here too")
     ap.add_argument("--pbt-ensemble-size", type=int, default=0, help="train this many policies at once (gpu_hideseek.population); 0: the plain trainer")
     ap.add_argument("--pbt-interval", type=int, default=0, help="with --pbt-ensemble-size: exploit / explore after every N-th update; 0: never")
+    ap.add_argument("--pbt-past-policies", type=int, default=0, help="with --pbt-ensemble-size: a pool of this many frozen past policies; 0: none")
+    ap.add_argument("--pbt-snapshot-interval", type=int, default=0, help="with --pbt-past-policies: a snapshot into the pool after every N-th update; 0: never")
     args = ap.parse_args(argv)
+    if args.pbt_past_policies and not args.pbt_ensemble_size:
+        ap.error("--pbt-past-policies needs --pbt-ensemble-size")
+    if args.pbt_snapshot_interval and not args.pbt_past_policies:
+        ap.error("--pbt-snapshot-interval needs --pbt-past-policies")
     if args.pbt_ensemble_size and args.num_hiders != args.num_seekers:
         ap.error("--pbt-ensemble-size needs equal teams: --num-hiders == --num-seekers")
     if args.pbt_interval and not args.pbt_ensemble_size:
@@ -93,7 +105,8 @@ def config(args):
         return population.PopulationConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
                                            num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
                                            value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed, num_policies=args.pbt_ensemble_size,
-                                           team_size=args.num_hiders, pbt_interval=args.pbt_interval)
+                                           team_size=args.num_hiders, pbt_interval=args.pbt_interval, num_past_policies=args.pbt_past_policies,
+                                           snapshot_interval=args.pbt_snapshot_interval)
     return trainer.TrainConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
                                num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
                                value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed)
@@ -121,7 +134,7 @@ def main(argv=None):
     sim = gpu_hideseek.HideAndSeekSimulator(
         exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
         sim_flags=F.RandomFlipTeams | F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders,
-        max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=max(1, args.pbt_ensemble_size))
+        max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=max(1, args.pbt_ensemble_size + args.pbt_past_policies))
     sim.init()
     cfg = config(args)
 
@@ -154,8 +167,11 @@ def main(argv=None):
             return
         for p, m in enumerate(metrics["policies"]):
             print(f"  policy {p}: " + json.dumps(plain(m)))
-        print("  " + json.dumps({k: metrics[k] for k in ("games", "bad", "exploit") if k in metrics}))
+        print("  " + json.dumps({k: metrics[k] for k in ("games", "bad", "snapshot", "exploit") if k in metrics}))
         league.print_elos(metrics["elo"])
+        if "past" in metrics:
+            T = len(metrics["policies"])
+            print("  past policies: " + ", ".join(f"{T + u} from update {n}" for u, n in enumerate(metrics["past"])))
 
     totals, wall_ms, timed = {k: 0.0 for k in trainer.PHASES}, 0.0, 0
     last_time, last_update, metrics = 0.0, tr.update_index, {}
