@@ -956,6 +956,105 @@ typedef struct hs_episode_request {
 int32_t hs_episode_stats(hs_sim *sim, const hs_episode_request *req);
 int32_t hs_episode_stats_async(hs_sim *sim, void *hip_stream, const hs_episode_request *req);
 
+/* Behaviour statistics: what the agents do with the level.  One call after a step advances a tracker per world (how far
+ * the boxes and ramps have been moved in the preparation phase and in the main phase, which of them each side has locked
+ * when the seekers are released and at the end, how far each side travels and how often it grabs) and folds every episode
+ * that ended with that step into a table of f64 sums (csrc/hs_k_behaviour.h: one kernel, one lane per world, then the
+ * fixed-order add of the workgroups' partial sums onto the table).
+ * Inputs, device memory of the handle's GPU; a null pointer means the handle's own:
+ *   positions [worlds][17][2] f32: the global_positions export; entries 0-8 are the boxes, 9-10 the ramps, 11-16 the
+ *     agents, the hiders first and then the seekers, as globalPositionsDebugSystem writes them;
+ *   locks [worlds][11] i32, per box and then per ramp: 0 free, 1 locked by the hiders, 2 locked by the seekers; null = the
+ *     handle's body metadata, which is what columns 15 / 16 of box_data and 12 / 13 of ramp_data export (an object the
+ *     world's `counts` do not hold is 0);
+ *   counts [worlds][4] i32: boxes, ramps, hiders and seekers of the world's CURRENT episode, null = the handle's own; a
+ *     value is used clamped: boxes to [0, 9], ramps to [0, 2], hiders to [0, 6], seekers to [0, 6 - hiders];
+ *   prep_counter, done, self_type i32 and self_mask f32, each [rows] (row = world * A + slot): the exports after the step;
+ *   grabbing f32, row r at grabbing[r * grab_stride]: null = column 12 (isGrabbing) of the self_data export, stride 13;
+ *   move_eps f32, finite and >= 0: an object counts as moved if its displacement is above it.
+ * What belongs to which episode.  A step resets before it observes, so positions, locks, counts, prep_counter, self_type,
+ * self_mask and grabbing of one call all describe the same moment, and when they come with done != 0 that moment is the
+ * FIRST of the next episode.  done alone looks back.  A row that left keeps a stale done: a world ENDED only if some row
+ * has done != 0 AND was active in the previous call.  was_active [rows] i32 is state for that: after a call it is this
+ * call's self_mask != 0.
+ * State, caller-owned device memory, read and written in place.  Per world: phase i32 (HS_BEHAVIOUR_UNARMED = 0: the next
+ * observation starts an episode; HS_BEHAVIOUR_PREP = 1; HS_BEHAVIOUR_MAIN = 2; HS_BEHAVIOUR_WAITING = 3: waiting for a
+ * done, so that no episode is booked of which a part was not seen); n_obj [2] i32 (boxes, ramps) and n_side [2] i32
+ * (seekers, hiders), latched at the episode's start; start_pos [11][2], prep_pos [11][2], last_pos [17][2] f32;
+ * prep_locks [11], last_locks [11] i32; travel [2] f32, grab [2] i32, agent_steps [2] i32: side 0 is the seekers, side 1
+ * the hiders.  Per row: was_active i32.
+ * The arithmetic is the contract: IEEE f32, unfused, in exactly this order.  d(a, b) = sqrtf((ax - bx) * (ax - bx) +
+ * (ay - by) * (ay - by)): two differences, two products, one sum and a correctly rounded square root, each one f32
+ * operation.  Per world and call:
+ *   1. ended as above.  p = prep_counter of the world's lowest row with self_mask != 0.  If there is no such row, bad
+ *      gains 1 and the call does nothing more for this world but step 2 and step 6.
+ *   2. If ended and phase is 1 or 2, the episode is booked from the state as the previous call left it.  For each kind,
+ *      boxes j < n_obj[0] (entries j) and ramps j < n_obj[1] (entries 9 + j):
+ *        move_prep_j = d(prep_pos_j, start_pos_j), move_main_j = d(last_pos_j, prep_pos_j); if the episode never reached the
+ *        main phase (phase == 1): move_prep_j = d(last_pos_j, start_pos_j), move_main_j = +0, and last_locks stand for
+ *        prep_locks.
+ *      The kind gains: max_j move_prep, max_j move_main (+0 with no object), the number of j with move_prep_j > move_eps
+ *      and with move_main_j > move_eps, the numbers of j locked by the hiders and by the seekers in prep_locks and in
+ *      last_locks, and n_obj.  Each side gains travel, grab and agent_steps.  world_episodes gains 1, reached_main gains
+ *      phase == 2.
+ *   3. If ended, or phase == 0, or (phase != 3 and the world RESTARTED: a row with self_mask != 0 that was not active
+ *      in the previous call and has done == 0, hs_episode_stats's rule; with changing team sizes this is the only sign),
+ *      this observation starts an episode: n_obj and n_side are latched from counts; start_pos = prep_pos =
+ *      positions[0..10], last_pos = positions, prep_locks = last_locks = locks; travel = +0, grab = agent_steps = 0;
+ *      phase = p > 0 ? 1 : 2.
+ *   4. Otherwise, if phase is 1 or 2, the episode goes on: for the hiders i < n_side[1] at entries 11 + i in ascending
+ *      order travel[1] = travel[1] + d(positions_i, last_pos_i), for the seekers i < n_side[0] at entries
+ *      11 + n_side[1] + i likewise onto travel[0]; last_pos = positions, last_locks = locks; if phase == 1 and p == 0:
+ *      prep_pos = positions[0..10], prep_locks = locks, phase = 2.
+ *   5. After 3 or 4, per row with self_mask != 0 and side = self_type != 0: agent_steps[side] += 1 and
+ *      grab[side] += grabbing != 0.
+ *   6. was_active = self_mask != 0, per row.
+ * table [HS_BEHAVIOUR_STATS] f64: [0] world_episodes, [1] reached_main, [2] bad; for the boxes from HS_BEHAVIOUR_BOXES and
+ * the ramps from HS_BEHAVIOUR_RAMPS the nine sums of step 2 in the order of the HS_BEHAVIOUR_KIND_* offsets; for the
+ * seekers from HS_BEHAVIOUR_SEEKERS and the hiders from HS_BEHAVIOUR_HIDERS sum travel, sum grab, sum agent_steps.  A call
+ * ADDS this step's sums (each term the f64 of the f32 / i32 value) to the table: zeroing it is the caller's business.
+ * They are added without atomics, in an order that depends on the handle's worlds alone, starting from +0.0, and then
+ * added to the table once: the same inputs give the same bits on every call.  The partial sums go through a workspace of
+ * the handle, so two calls on one handle must not overlap.
+ * A reset the host requests in mid-episode sets no done and is not covered: the episode it cuts short runs on into the
+ * next one.  Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says
+ * which): a null request; a null state pointer or table; move_eps not finite or negative; grab_stride < 1 with grabbing
+ * given; a pointer not aligned to its element size (table: 8 bytes); a state array or the table overlapping an input,
+ * another state array or the table; a call before hs_init or inside an open step.  Under HS_FLAG_EXT_SKIP_OBSERVATIONS a
+ * null positions, prep_counter, self_type, self_mask or grabbing is refused with HS_ERR_UNSUPPORTED (the observation
+ * stage writes them, and it does not run); with all of them given the call works there.  Writes no simulator state.
+ * hs_behaviour_stats is ordered after the device's legacy default stream and blocking; hs_behaviour_stats_async enqueues
+ * on the caller's hipStream_t without synchronising (the caller orders it after the step that wrote the exports). */
+enum { HS_BEHAVIOUR_STATS = 27, HS_BEHAVIOUR_KIND_STATS = 9, HS_BEHAVIOUR_SIDE_STATS = 3 };
+enum { HS_BEHAVIOUR_UNARMED = 0, HS_BEHAVIOUR_PREP = 1, HS_BEHAVIOUR_MAIN = 2, HS_BEHAVIOUR_WAITING = 3 };
+enum { HS_BEHAVIOUR_WORLD_EPISODES = 0, HS_BEHAVIOUR_REACHED_MAIN = 1, HS_BEHAVIOUR_BAD = 2, HS_BEHAVIOUR_BOXES = 3, HS_BEHAVIOUR_RAMPS = 12,
+       HS_BEHAVIOUR_SEEKERS = 21, HS_BEHAVIOUR_HIDERS = 24 };
+enum { HS_BEHAVIOUR_KIND_MAX_PREP = 0, HS_BEHAVIOUR_KIND_MAX_MAIN = 1, HS_BEHAVIOUR_KIND_MOVED_PREP = 2, HS_BEHAVIOUR_KIND_MOVED_MAIN = 3,
+       HS_BEHAVIOUR_KIND_HIDER_LOCKED_PREP = 4, HS_BEHAVIOUR_KIND_SEEKER_LOCKED_PREP = 5, HS_BEHAVIOUR_KIND_HIDER_LOCKED_END = 6,
+       HS_BEHAVIOUR_KIND_SEEKER_LOCKED_END = 7, HS_BEHAVIOUR_KIND_OBJECTS = 8 };
+enum { HS_BEHAVIOUR_SIDE_TRAVEL = 0, HS_BEHAVIOUR_SIDE_GRAB = 1, HS_BEHAVIOUR_SIDE_AGENT_STEPS = 2 };
+typedef struct hs_behaviour_request {
+    const float   *positions;     /* [worlds][17][2] f32 or null = the global_positions export */
+    const int32_t *locks;         /* [worlds][11] i32 or null = the handle's body metadata */
+    const int32_t *counts;        /* [worlds][4] i32 or null = the handle's own */
+    const int32_t *prep_counter;  /* [rows] i32 or null = the prep_counter export */
+    const int32_t *done;          /* [rows] i32 or null = the done export */
+    const int32_t *self_type;     /* [rows] i32 or null = the self_type export */
+    const float   *self_mask;     /* [rows] f32 or null = the self_mask export */
+    const float   *grabbing;      /* [rows] f32 at stride grab_stride, or null = column 12 of the self_data export */
+    int32_t grab_stride;          /* in elements, >= 1 where grabbing is given */
+    float move_eps;               /* finite, >= 0 */
+    int32_t *phase, *n_obj, *n_side;              /* [worlds], [worlds][2], [worlds][2] i32, read and written */
+    float   *start_pos, *prep_pos, *last_pos;     /* [worlds][11][2], [worlds][11][2], [worlds][17][2] f32 */
+    int32_t *prep_locks, *last_locks;             /* [worlds][11] i32 each */
+    float   *travel;              /* [worlds][2] f32 */
+    int32_t *grab, *agent_steps;  /* [worlds][2] i32 each */
+    int32_t *was_active;          /* [rows] i32 */
+    double  *table;               /* [HS_BEHAVIOUR_STATS] f64, added to */
+} hs_behaviour_request;           /* 176 bytes */
+int32_t hs_behaviour_stats(hs_sim *sim, const hs_behaviour_request *req);
+int32_t hs_behaviour_stats_async(hs_sim *sim, void *hip_stream, const hs_behaviour_request *req);
+
 /* The league: P policies play each other on one simulator, and are rated.  One call after a step routes every agent row
  * (row = world * A + slot) to a policy, ranks it among that policy's rows, books the games that ended with the step in a
  * P x P table and moves the Elo ratings (csrc/hs_k_league.h: one kernel over the rows, one lane per row, then a

@@ -34,6 +34,7 @@
 #include "hs_k_dense.h"
 #include "hs_k_gather.h"                  // ahead of hs_k_adam.h: its one kernel is a template, emitted where launch_gather (the last stage) names it
 #include "hs_k_episode.h"                 // likewise: its two kernels are templates, emitted where launch_episode (after launch_gather) names them
+#include "hs_k_behaviour.h"               // likewise: emitted where launch_behaviour (after launch_attend) names them
 #include "hs_k_league.h"                  // likewise: emitted where launch_league (after launch_episode) names them
 #include "hs_k_pack_routed.h"             // likewise: emitted where launch_pack_routed (after launch_league) names it
 #include "hs_k_sample_routed.h"           // likewise: emitted where launch_sample_routed (after launch_pack_routed) names it
@@ -108,6 +109,7 @@ struct hs_sim {
     float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
     double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]
     double *episode_partials = nullptr;    // hs_episode_stats: the sums of each workgroup, [episode_grid][HS_EPISODE_STATS]
+    double *behaviour_partials = nullptr;  // hs_behaviour_stats: the sums of each workgroup, [behaviour_grid][HS_BEHAVIOUR_STATS]
     int32_t *league_step = nullptr;        // hs_league_step: the counts of the step and its malformed worlds, [kLeagueMaxBins + 1], zero between calls
     int4 *league_table = nullptr;          // hs_league_set_schedule: (hiders, seekers, the sides each holds before the pair), [kLeagueMaxGroup]
     int league_group = 0, league_sides = 0, league_policies = 0;       // the table's G (0: none set), c = 2 G / N, and N
@@ -1506,6 +1508,76 @@ int launch_attend_bwd(hs_sim *, hipStream_t strm, const hs_entity_attend_backwar
 }
 }  // namespace
 
+// ---- behaviour statistics (hs_k_behaviour.h) ----
+namespace {
+static_assert(HS_BEHAVIOUR_STATS == hs::kBehStats && HS_BEHAVIOUR_KIND_STATS == hs::kBehKind && HS_BEHAVIOUR_SIDE_STATS == hs::kBehSide &&
+              HS_BEHAVIOUR_UNARMED == hs::kBehUnarmed && HS_BEHAVIOUR_PREP == hs::kBehPrep && HS_BEHAVIOUR_MAIN == hs::kBehMain &&
+              HS_BEHAVIOUR_WAITING == hs::kBehWaiting && HS_BEHAVIOUR_WORLD_EPISODES == hs::kBehWorldEpisodes &&
+              HS_BEHAVIOUR_REACHED_MAIN == hs::kBehReachedMain && HS_BEHAVIOUR_BAD == hs::kBehBad && HS_BEHAVIOUR_BOXES == hs::kBehBoxes &&
+              HS_BEHAVIOUR_RAMPS == hs::kBehRamps && HS_BEHAVIOUR_SEEKERS == hs::kBehSeekers && HS_BEHAVIOUR_HIDERS == hs::kBehHiders &&
+              HS_BEHAVIOUR_RAMPS == HS_BEHAVIOUR_BOXES + HS_BEHAVIOUR_KIND_STATS && HS_BEHAVIOUR_SEEKERS == HS_BEHAVIOUR_RAMPS + HS_BEHAVIOUR_KIND_STATS &&
+              HS_BEHAVIOUR_HIDERS == HS_BEHAVIOUR_SEEKERS + HS_BEHAVIOUR_SIDE_STATS && HS_BEHAVIOUR_STATS == HS_BEHAVIOUR_HIDERS + HS_BEHAVIOUR_SIDE_STATS,
+              "hs_behaviour_request and k_behaviour agree");
+static_assert(sizeof(hs_behaviour_request) == 176 && offsetof(hs_behaviour_request, grabbing) == 56 && offsetof(hs_behaviour_request, grab_stride) == 64 &&
+              offsetof(hs_behaviour_request, move_eps) == 68 && offsetof(hs_behaviour_request, phase) == 72 && offsetof(hs_behaviour_request, start_pos) == 96 &&
+              offsetof(hs_behaviour_request, travel) == 136 && offsetof(hs_behaviour_request, was_active) == 160 && offsetof(hs_behaviour_request, table) == 168,
+              "hs_behaviour_request layout (gpu_hideseek/behaviour.py mirrors it)");
+static_assert(kExports[HS_EXPORT_GLOBAL_DEBUG_POSITIONS].dtype == HS_DTYPE_F32 && !kExports[HS_EXPORT_GLOBAL_DEBUG_POSITIONS].per_agent &&
+              kExports[HS_EXPORT_GLOBAL_DEBUG_POSITIONS].tail[0] == hs::kNumDSlots && kExports[HS_EXPORT_GLOBAL_DEBUG_POSITIONS].tail[1] == 2 &&
+              kExports[HS_EXPORT_PREP_COUNTER].dtype == HS_DTYPE_I32 && kExports[HS_EXPORT_PREP_COUNTER].per_agent && kExports[HS_EXPORT_PREP_COUNTER].tail[0] == 1 &&
+              kExports[HS_EXPORT_SELF_OBS].dtype == HS_DTYPE_F32 && kExports[HS_EXPORT_SELF_OBS].per_agent && kExports[HS_EXPORT_SELF_OBS].tail[0] == 13 &&
+              hs::kMaxBoxes == 9 && hs::kMaxRamps == 2 && hs::kMaxAgents == 6 && hs::kBoxSlot0 == 0 && hs::kRampSlot0 == hs::kMaxBoxes,
+              "k_behaviour reads the global_positions, prep_counter and self_data exports and the box and ramp slots");
+static_assert(hs::kBehStats * hs::kBehSumSegs <= 1024, "k_behaviour_fold is one workgroup");
+
+// The request with every null input replaced by the handle's own (the state and the table are left as given).
+hs::BehaviourArgs behaviour_args(const hs_sim *s, const hs_behaviour_request *r) {
+    const hs::SimState &S = s->S;
+    return {r->positions ? r->positions : S.xGlobalPos, r->locks, r->counts, r->prep_counter ? r->prep_counter : S.xPrep, r->done ? r->done : S.xDone,
+            r->self_type ? r->self_type : S.xSelfType, r->self_mask ? r->self_mask : S.xSelfMask, r->grabbing ? r->grabbing : S.xSelfObs + 12,
+            r->grabbing ? r->grab_stride : 13, r->move_eps, S.counts, S.slotOfWorld, S.bmeta, r->phase, r->n_obj, r->n_side, r->start_pos, r->prep_pos,
+            r->last_pos, r->prep_locks, r->last_locks, r->travel, r->grab, r->agent_steps, r->was_active, s->behaviour_partials, S.N, s->A};
+}
+
+int check_behaviour(hs_sim *s, const hs_behaviour_request *r) {
+    const Check c{"hs_behaviour_stats"};
+    if (!r) return c.bad("null request");
+    if (!r->phase || !r->n_obj || !r->n_side || !r->start_pos || !r->prep_pos || !r->last_pos || !r->prep_locks || !r->last_locks || !r->travel || !r->grab ||
+        !r->agent_steps || !r->was_active)
+        return c.bad("null state pointer");
+    if (!r->table) return c.bad("null table");
+    if (!(std::isfinite(r->move_eps) && r->move_eps >= 0.f)) return c.bad("move_eps must be finite and at least 0");
+    if (r->grabbing && r->grab_stride < 1) return c.bad("grab_stride must be at least 1 where grabbing is given");
+    if (!aligned(4, {r->positions, r->locks, r->counts, r->prep_counter, r->done, r->self_type, r->self_mask, r->grabbing, r->phase, r->n_obj, r->n_side,
+                     r->start_pos, r->prep_pos, r->last_pos, r->prep_locks, r->last_locks, r->travel, r->grab, r->agent_steps, r->was_active}))
+        return c.bad("every input and state pointer must be 4-byte aligned");
+    if (!aligned(8, {r->table})) return c.bad("table must be 8-byte aligned");
+    if ((s->S.flags & hs::FLAG_EXT_SKIP_OBSERVATIONS) && (!r->positions || !r->prep_counter || !r->self_type || !r->self_mask || !r->grabbing))
+        return c.bad("a null positions, prep_counter, self_type, self_mask or grabbing needs the exports that HS_FLAG_EXT_SKIP_OBSERVATIONS leaves unwritten",
+                     HS_ERR_UNSUPPORTED);
+    const hs::BehaviourArgs a = behaviour_args(s, r);
+    const uintptr_t worlds = (uintptr_t)s->S.N, rows = worlds * (uintptr_t)s->A;
+    HS_TRY(c.disjoint({range("positions", a.positions, worlds * 136), range("locks", a.locks, worlds * 44), range("counts", a.counts4, worlds * 16),
+                       range("prep_counter", a.prep, rows * 4), range("done", a.done, rows * 4), range("self_type", a.selfType, rows * 4),
+                       range("self_mask", a.selfMask, rows * 4), range("grabbing", a.grabbing, ((rows - 1) * (uintptr_t)a.grabStride + 1) * 4)},
+                      {range("phase", r->phase, worlds * 4), range("n_obj", r->n_obj, worlds * 8), range("n_side", r->n_side, worlds * 8),
+                       range("start_pos", r->start_pos, worlds * 88), range("prep_pos", r->prep_pos, worlds * 88), range("last_pos", r->last_pos, worlds * 136),
+                       range("prep_locks", r->prep_locks, worlds * 44), range("last_locks", r->last_locks, worlds * 44), range("travel", r->travel, worlds * 8),
+                       range("grab", r->grab, worlds * 8), range("agent_steps", r->agent_steps, worlds * 8), range("was_active", r->was_active, rows * 4),
+                       range("table", r->table, HS_BEHAVIOUR_STATS * sizeof(double))}));
+    return c.handle_ready(s);
+}
+// One k_behaviour over every world (the request has passed check_behaviour), then the fixed-order add onto the table.
+int launch_behaviour(hs_sim *s, hipStream_t strm, const hs_behaviour_request *r) {
+    const hs::BehaviourArgs a = behaviour_args(s, r);
+    const int grid = hs::behaviour_grid(a.worlds);
+    hipLaunchKernelGGL(hs::k_behaviour<>, dim3(grid), dim3(hs::kBehThreads), 0, strm, a);
+    hipLaunchKernelGGL(hs::k_behaviour_fold<>, dim3(1), dim3(hs::kBehStats * hs::kBehSumSegs), 0, strm, (const double *)s->behaviour_partials, grid, r->table);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1656,6 +1728,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
     HS_ALLOC(s->adam_workspace, hs::kAdamWorkspace);
     HS_ALLOC(s->episode_partials, (size_t)hs::episode_grid((int)N, A) * hs::kEpiStats);
+    HS_ALLOC(s->behaviour_partials, (size_t)hs::behaviour_grid((int)N) * hs::kBehStats);
     HS_ALLOC(s->league_step, hs::kLeagueMaxBins + 1);
     HS_ALLOC(s->league_table, hs::kLeagueMaxGroup);
 #undef HS_ALLOC
@@ -1994,6 +2067,10 @@ int32_t hs_gather_sequences(hs_sim *s, const hs_gather_request *req) { return ca
 int32_t hs_gather_sequences_async(hs_sim *s, void *hip_stream, const hs_gather_request *req) { return call_async(s, hip_stream, check_gather, launch_gather, req); }
 int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call_blocking(s, check_episode, launch_episode, req); }
 int32_t hs_episode_stats_async(hs_sim *s, void *hip_stream, const hs_episode_request *req) { return call_async(s, hip_stream, check_episode, launch_episode, req); }
+int32_t hs_behaviour_stats(hs_sim *s, const hs_behaviour_request *req) { return call_blocking(s, check_behaviour, launch_behaviour, req); }
+int32_t hs_behaviour_stats_async(hs_sim *s, void *hip_stream, const hs_behaviour_request *req) {
+    return call_async(s, hip_stream, check_behaviour, launch_behaviour, req);
+}
 int32_t hs_league_step(hs_sim *s, const hs_league_request *req) { return call_blocking(s, check_league, launch_league, req); }
 int32_t hs_league_step_async(hs_sim *s, void *hip_stream, const hs_league_request *req) { return call_async(s, hip_stream, check_league, launch_league, req); }
 int32_t hs_league_set_schedule(hs_sim *s, const int32_t *pairs_host, int32_t group, int32_t num_policies) {

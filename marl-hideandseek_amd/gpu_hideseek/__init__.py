@@ -388,6 +388,21 @@ class HideAndSeekSimulator:
         return _episodes.compute(self, state, table, stream, gamma=gamma, reward=reward, done=done, self_type=self_type, self_mask=self_mask,
                                  episode_result=episode_result, hider_team=hider_team)
 
+    def behaviour_stats(self, state, table, *, move_eps=0.5, positions=None, locks=None, counts=None, prep_counter=None, done=None, self_type=None,
+                        self_mask=None, grabbing=None, stream=None):
+        """After a step: advance the per-world behaviour trackers `state` (behaviour.new_state) and add every episode
+        that ended with the step to `table` ([27] float64), in one kernel (gpu_hideseek.behaviour; hs_behaviour_stats,
+        whose header comment states the arithmetic and the table): how far the boxes and ramps were moved in the
+        preparation phase and after it, who had locked them when the seekers were released and at the end, how far each
+        side travelled and how often it grabbed.  An input left None is the simulator's own (positions: the
+        global_positions export; locks: the body metadata the lock columns of box_data / ramp_data export; counts: the
+        world's boxes, ramps, hiders and seekers; grabbing: column 12 of self_data); an explicit one is a tensor on the
+        device.  stream=None blocks; a torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns
+        {"table": table, "state": state}.  behaviour.BehaviourStats is the tracker built on this call."""
+        from . import behaviour as _behaviour
+        return _behaviour.compute(self, state, table, stream, move_eps=move_eps, positions=positions, locks=locks, counts=counts,
+                                  prep_counter=prep_counter, done=done, self_type=self_type, self_mask=self_mask, grabbing=grabbing)
+
     def league_step(self, num_policies, team_size, state, counts, elo, *, k_factor=32.0, policy_assignments=None, slot=None, row_of_slot=None,
                     clear_slot=None, bad=None, done=None, self_type=None, self_mask=None, episode_result=None, hider_team=None, stream=None):
         """After a step, for a league of `num_policies` policies with `team_size` hiders and seekers per world: route every

@@ -94,6 +94,7 @@ class Evaluator:
         self.mask_before = None
         self.counter = 0
         self.episodes = episodes.EpisodeStats(sim, gamma=gamma).arm(from_start=from_start)
+        self.behaviour = None             # a behaviour.BehaviourStats, or None: run() calls its step() after every sim.step()
 
     def _export(self, name):
         return getattr(self.sim, name + "_tensor")().to_torch().reshape(self.rows, -1)
@@ -121,6 +122,8 @@ class Evaluator:
             self.act()
             self.sim.step()
             self.episodes.step()
+            if self.behaviour is not None:
+                self.behaviour.step()
             self.clear.copy_(self._export("done")[:, 0])
             if record_log is not None:
                 replay.record_step(self.sim, record_log)

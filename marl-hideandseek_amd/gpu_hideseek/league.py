@@ -331,7 +331,8 @@ class League:
     and comes right from sim.init().  mode "draw" samples the actions with the uniforms keyed by (seed, step, global agent
     row), as the Evaluator's are; "greedy" takes every head's first maximum.  Nothing in a run changes a policy or a
     normaliser.  Single device: there is no ShardedSimulator form, because the ratings would have to cross the shards.
-    `episodes`, None by default: an episodes.EpisodeStats of the same simulator whose step() run() calls after every step."""
+    `episodes` and `behaviour`, None by default: an episodes.EpisodeStats and a behaviour.BehaviourStats of the same
+    simulator whose step() run() calls after every step."""
 
     def __init__(self, sim, policies, team_size, mode="draw", seed=0, k_factor=DEFAULT_K_FACTOR):
         import torch
@@ -375,6 +376,7 @@ class League:
         self.state = [net.actor.init_state(m, dev, net.dtype) for net in nets]
         self.counter = 0
         self.episodes = None
+        self.behaviour = None
         # the tensors above stay where they are: the request is checked and built once
         self._req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, P, self.team_size, self.world, self.counts, self.elo, self.k_factor,
                             slot=self.slot, row_of_slot=self.row_of_slot, clear_slot=self.clear_slot, bad=self.bad)[1]
@@ -456,6 +458,8 @@ class League:
             self._league_step()
             if self.episodes is not None:
                 self.episodes.step()
+            if self.behaviour is not None:
+                self.behaviour.step()
             if record_log is not None:
                 replay.record_step(self.sim, record_log)
             if on_step is not None:

@@ -270,7 +270,8 @@ class Population:
     cfg.team_size and a number of worlds that is a multiple of num_policies^2; with cfg.num_past_policies = Q > 0, a pool of
     Q frozen policies as well (`past`), the schedule league.past_play_schedule set on the simulator, and a number of worlds
     that is a multiple of num_policies (num_policies + Q).  The module docstring states the loop.
-    `phases` (a trainer.PhaseTimer) and `episodes` (an episodes.EpisodeStats) work as on Trainer."""
+    `phases` (a trainer.PhaseTimer), `episodes` (an episodes.EpisodeStats) and `behaviour` (a behaviour.BehaviourStats)
+    work as on Trainer."""
 
     def __init__(self, sim, cfg=None, nets=None, fused=True):
         import numpy as np
@@ -329,7 +330,7 @@ class Population:
         self.rng = np.random.Generator(np.random.PCG64(cfg.seed))
         self.update_index, self.counter = 0, 0
         self.stepped = False
-        self.phases, self.episodes = None, None
+        self.phases, self.episodes, self.behaviour = None, None, None
         self.league_step()                                # routes the rows as they stand and latches the team orders; books no game
 
     # ---- what the policies hold ----
@@ -372,6 +373,8 @@ class Population:
         """What follows every sim.step(): the tracker, the close of slot `t` (None: there is none), the league step."""
         if self.episodes is not None:
             self.episodes.step()
+        if self.behaviour is not None:
+            self.behaviour.step()
         if t is not None:
             self._close_slot(t)
         self.league_step()

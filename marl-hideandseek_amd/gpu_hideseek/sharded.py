@@ -179,6 +179,16 @@ class ShardedSimulator:
         return _episodes.compute_sharded(self, state, table, stream, gamma=gamma, reward=reward, done=done, self_type=self_type,
                                          self_mask=self_mask, episode_result=episode_result, hider_team=hider_team)
 
+    def behaviour_stats(self, state, table, *, move_eps=0.5, positions=None, locks=None, counts=None, prep_counter=None, done=None, self_type=None,
+                        self_mask=None, grabbing=None, stream=None):
+        """HideAndSeekSimulator.behaviour_stats per shard: `state` and `table` have one entry per shard, on the shard's
+        device; every explicit input and `stream` is None for all shards or a list with one entry per shard.  A list of
+        the shards' results.  A world's statistics depend on that world alone: the shards' tables add up to the counts
+        and sums of the unsharded run (the sums in another order of addition)."""
+        from . import behaviour as _behaviour
+        return _behaviour.compute_sharded(self, state, table, stream, move_eps=move_eps, positions=positions, locks=locks, counts=counts,
+                                          prep_counter=prep_counter, done=done, self_type=self_type, self_mask=self_mask, grabbing=grabbing)
+
     def ppo_loss(self, logits, action, old_log_prob, advantage, *, buckets=(5, 5, 5, 2, 2), adv_moments=None, mask=None, value=None,
                  returns=None, old_value=None, clip_coef=0.2, value_loss_coef=0.5, entropy_coef=0.01, grad_scale=1.0,
                  grad_logits=True, grad_value=None, stats=True, grad_dtype=None, stream=None):

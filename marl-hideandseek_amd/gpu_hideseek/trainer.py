@@ -26,7 +26,8 @@ updated since, and runs the full forward with the policy as updated since, so lo
 policy that update() starts from, and every observation adds its moments once.  Then compute_advantages (moments=True)
 over the buffers, then ObsNormaliser.update with the T moments.  With trainer.episodes set to an episodes.EpisodeStats
 (None by default), collect() calls its step() after every sim.step() it makes, the closing one included, so every step
-reaches the tracker once across rollouts; metrics() and state_dict() do not know about it.
+reaches the tracker once across rollouts; metrics() and state_dict() do not know about it.  trainer.behaviour, a
+behaviour.BehaviourStats, works the same way.
 
 update() runs num_epochs epochs: a fresh torch.randperm(K n) on the device from a seeded generator, cut into
 num_minibatches equal parts; per part Rollout.minibatch (one launch), sequence_logits (net.sequence from the gathered
@@ -159,6 +160,7 @@ class Trainer:
         self._mb = None
         self.phases = None                # a PhaseTimer, or None: no events
         self.episodes = None              # an episodes.EpisodeStats, or None: collect() calls its step() after every sim.step()
+        self.behaviour = None             # a behaviour.BehaviourStats, or None: likewise
         E = cfg.num_epochs
         self.ppo_stats = torch.zeros(E, PPO_STATS, dtype=torch.float64, device=dev)
         self.value_stats = torch.zeros(E, VALUE_STATS, dtype=torch.float64, device=dev)
@@ -198,6 +200,8 @@ class Trainer:
                         sim.step()
                     if self.episodes is not None:
                         self.episodes.step()
+                    if self.behaviour is not None:
+                        self.behaviour.step()
                     if t > 0:
                         self._close_slot(t - 1)
                     buf.clear[t].copy_(self._export("done")[:, 0])
@@ -224,6 +228,8 @@ class Trainer:
                 sim.step()
             if self.episodes is not None:
                 self.episodes.step()
+            if self.behaviour is not None:
+                self.behaviour.step()
             self.stepped = True
             self._close_slot(T - 1)
             self.clear.copy_(buf.done[T - 1])

@@ -10,7 +10,8 @@ optimiser's state is not needed; of a population's checkpoint (tools/train.py --
 policy.  The simulator runs with UseFixedWorld | ZeroAgentVelocity, as the reference's script
 does.  --record-log appends a checkpoint of every world after every step.  --print-rewards prints every step's reward
 tensor.  At the end it prints the per-side table of the episodes that finished (240 steps each) and one JSON line.
-Several checkpoints playing each other, with Elo ratings (the reference's eval_competitive), is tools/league.py.
+--behaviour-stats also tracks what the agents do with the level (gpu_hideseek.behaviour) and prints it as a JSON line
+before that one.  Several checkpoints playing each other, with Elo ratings (the reference's eval_competitive), is tools/league.py.
 Training several policies at once is tools/train.py --pbt-ensemble-size.  Not here: --single-policy, --print-obs and
 --print-action-probs.
 """
@@ -23,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import evaluate  # noqa: E402
+from gpu_hideseek import behaviour, evaluate  # noqa: E402
 
 
 def parse(argv=None):
@@ -41,6 +42,7 @@ def parse(argv=None):
     ap.add_argument("--gpu-id", type=int, default=0)
     ap.add_argument("--greedy", action="store_true", help="every head's most likely action instead of a draw")
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--behaviour-stats", action="store_true", help="track object movement, locks, travel and grabs on the device and print them")
     ap.add_argument("--encoder", choices=("simple", "attention"), help="the policy's network (tools/train.py --encoder); by default read from the checkpoint")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
@@ -70,6 +72,8 @@ def main(argv=None):
         min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=1)
     sim.init()
     ev = evaluate.Evaluator(sim, net, normaliser, mode="greedy" if args.greedy else "draw", seed=args.seed)
+    if args.behaviour_stats:
+        ev.behaviour = behaviour.BehaviourStats(sim).arm(from_start=True)
     log = open(args.record_log, "wb") if args.record_log else None
 
     def on_step(i, ev):
@@ -81,6 +85,8 @@ def main(argv=None):
         if log is not None:
             log.close()
     print("\n".join(table(stats)))
+    if ev.behaviour is not None:
+        print("behaviour: " + json.dumps(ev.behaviour.read()))
     print(json.dumps(stats))
     sim.close()
     return stats

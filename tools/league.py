@@ -10,6 +10,8 @@ q % P as the seekers, for the whole run.  The simulator runs with num_pbt_polici
 ZeroAgentVelocity, as the reference's script does; --num-hiders is the size of both teams.
 It prints the Elo table before and after (four to a line, as the reference's print_elos does), the P x P matrix of the
 hiders' win rate (row: the hiders' policy, column: the seekers'), and one JSON line of League.read().
+--behaviour-stats also tracks what the agents do with the level, over all policies together (gpu_hideseek.behaviour), and
+prints it as a JSON line before that one.
 Training several policies at once is tools/train.py --pbt-ensemble-size.  Not here: drawn or rating-based matchmaking,
 several GPUs.
 """
@@ -22,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import evaluate, league  # noqa: E402
+from gpu_hideseek import behaviour, evaluate, league  # noqa: E402
 
 
 def parse(argv=None):
@@ -40,6 +42,7 @@ def parse(argv=None):
     ap.add_argument("--greedy", action="store_true", help="every head's most likely action instead of a draw")
     ap.add_argument("--k-factor", type=float, default=league.DEFAULT_K_FACTOR)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--behaviour-stats", action="store_true", help="track object movement, locks, travel and grabs on the device and print them")
     ap.add_argument("--encoder", choices=("simple", "attention"), help="every policy's network (tools/train.py --encoder); by default read from each checkpoint")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
@@ -92,6 +95,8 @@ def main(argv=None):
         min_seekers=args.num_hiders, max_seekers=args.num_hiders, num_pbt_policies=len(policies))
     sim.init()
     lg = league.League(sim, policies, args.num_hiders, mode="greedy" if args.greedy else "draw", seed=args.seed, k_factor=args.k_factor)
+    if args.behaviour_stats:
+        lg.behaviour = behaviour.BehaviourStats(sim).arm(from_start=True)
     print("Elo before:")
     league.print_elos(lg.read()["elo"])
     log = open(args.record_log, "wb") if args.record_log else None
@@ -103,6 +108,8 @@ def main(argv=None):
     print(f"Elo after {out['games']} games:")
     league.print_elos(out["elo"])
     print("\n".join(matrix(out["counts"])))
+    if lg.behaviour is not None:
+        print("behaviour: " + json.dumps(lg.behaviour.read()))
     print(json.dumps(out))
     sim.close()
     return out

@@ -18,6 +18,10 @@ and prints, as a second JSON line at each `Update:` print, what has finished sin
 the mean and standard deviation of the return, the mean discounted return and length, and the hiders' and seekers' win
 rates.  On a fresh simulator the episodes are tracked from their start; after --restore the tracker waits for every row's
 next episode, because the simulator's state is not restored.  tools/infer.py runs a saved policy without learning.
+--behaviour-stats tracks what the agents do with the level (gpu_hideseek.behaviour: one more launch after every simulator
+step) and prints it the same way, as a JSON line of its own: per episode how far the boxes and ramps were moved in the
+preparation phase and after it, how many of them each side had locked when the seekers were released and at the end, and
+each side's travel per agent-step and grab rate.
 Saved checkpoints play each other, with Elo ratings (the reference's eval_competitive), in tools/league.py.
 --pbt-ensemble-size P trains P policies at once on the one simulator (gpu_hideseek.population: the league's fixed
 schedule, so --num-worlds must be a multiple of P^2 and both teams have --num-hiders agents), with live Elo ratings from the
@@ -45,7 +49,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import episodes, league, policy, population, trainer  # noqa: E402
+from gpu_hideseek import behaviour, episodes, league, policy, population, trainer  # noqa: E402
 
 PRINT_EVERY = 10
 
@@ -76,6 +80,7 @@ def parse(argv=None):
     ap.add_argument("--encoder", choices=policy.ENCODERS, default="simple", help="the policy's network in front of the LSTM (policy.make_policy)")
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--episode-stats", action="store_true", help="track finished episodes on the device and print them with the metrics")
+    ap.add_argument("--behaviour-stats", action="store_true", help="track object movement, locks, travel and grabs on the device and print them with the metrics")
     ap.add_argument("--out", type=str, help="with --phases: write the table here too")
     ap.add_argument("--pbt-ensemble-size", type=int, default=0, help="train this many policies at once (gpu_hideseek.population); 0: the plain trainer")
     ap.add_argument("--pbt-interval", type=int, default=0, help="with --pbt-ensemble-size: exploit / explore after every N-th update; 0: never")
@@ -153,6 +158,8 @@ def main(argv=None):
         tr.phases = trainer.PhaseTimer()
     if args.episode_stats:
         tr.episodes = episodes.EpisodeStats(sim, gamma=args.gamma).arm(from_start=args.restore is None)
+    if args.behaviour_stats:
+        tr.behaviour = behaviour.BehaviourStats(sim).arm(from_start=args.restore is None)
 
     def save():
         if run_dir is not None:
@@ -184,6 +191,8 @@ def main(argv=None):
                 show(metrics)
                 if tr.episodes is not None:
                     print("  " + json.dumps(tr.episodes.read()))
+                if tr.behaviour is not None:
+                    print("  " + json.dumps(tr.behaviour.read()))
             last_time, last_update = now, tr.update_index
         t0 = time.perf_counter()
         metrics = tr.update_iter()
@@ -201,6 +210,8 @@ def main(argv=None):
     show(metrics)
     if tr.episodes is not None:
         print("  " + json.dumps(tr.episodes.read()))
+    if tr.behaviour is not None:
+        print("  " + json.dumps(tr.behaviour.read()))
     save()
     if args.phases and timed:
         fps = args.num_worlds * args.steps_per_update * timed / (wall_ms * 1e-3)
