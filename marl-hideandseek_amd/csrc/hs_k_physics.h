@@ -27,6 +27,7 @@
 #include "hs_rays.h"
 #include "hs_collide.h"
 #include "hs_solver.h"
+#include "hs_broadphase.h"
 #include "hs_k_reset.h"
 
 namespace hs {
@@ -71,6 +72,7 @@ struct alignas(16) OctRes {
         struct {
             float lo[3][kNumDSlots][kTile], hi[3][kNumDSlots][kTile];   // hull AABBs: integrate -> detect
             float wall[4][kLdsWalls][kTile];                            // cx, cy, hx, hy: staged by detect
+            unsigned xch[kNumDSlots][kTile];                            // detect: bit b = slot b (above this one) found this slot
         } det;
         struct {
             float clip[kClipWords];                                     // polygon clipping of the convex tests
@@ -113,6 +115,7 @@ struct alignas(16) OctRes {
 constexpr int kSeenDeferred = 2;
 static_assert(sizeof(OctRes) <= 20 * 1024, "8 waves of 8 worlds share the CU's 160 KiB of LDS");
 static_assert(offsetof(OctRes, u.sat.items) >= offsetof(OctRes, u.det.wall), "items must not overlap the AABBs");
+static_assert(sizeof(decltype(OctRes::u.det)) <= sizeof(decltype(OctRes::u.sat)), "the broadphase scratch adds nothing to the octet's LDS");
 static_assert(sizeof(ManDD) / 4 * OctRes::kSlots <= OctRes::kVelOffsetWords, "manifold slots lie below the velocities");
 static_assert(2 * 3 * kNumDSlots * 8 <= OctRes::kVelOffsetWords, "the hull AABBs lie below the velocities");
 
@@ -301,29 +304,67 @@ HSD void integrate_body(OctRes &R, BodyReg &b, int slot, int g, int meta, const 
 }
 
 // ------------------------------------------------------------------------------------------
-// All-pairs AABB candidates (<= 17 bodies, <= 36 walls per world: no BVH), 8 lanes per world: lane l of a world
-// owns body slots l, l + 8, l + 16.  Also builds the octet's work list of convex tests.  Returns the number of
-// box-only items in .x and of items that involve a ramp (wedge hull) in .y; the ramp items start at the next
-// multiple of 32 so that most rounds of the convex test run the box code only.
+// The broadphase.  Its helpers first: the octet's walls -> LDS, 16 bytes per lane and component (rows beyond a world's
+// count hold whatever the column does).  In two halves, so that other work can stand between the loads from global
+// memory and their use.
+typedef float WallPiece __attribute__((ext_vector_type(4)));
+struct WallPieces { WallPiece cx, cy, hx, hy; };
+static_assert(kLdsWalls * (kTile / 4) == kPhysThreads, "one 16-byte piece per lane and component");
+HSD WallPieces stage_walls_load(const SimState &S) {
+    const int L = hs_lane();
+    const float *src = S.walls.octet(S.wbeg >> 3) + 4 * L;      // piece L of a component: row L / 2, half L % 2
+    return {*(const WallPiece *)(src + 0 * kMaxWalls * kTile), *(const WallPiece *)(src + 1 * kMaxWalls * kTile),
+            *(const WallPiece *)(src + 2 * kMaxWalls * kTile), *(const WallPiece *)(src + 3 * kMaxWalls * kTile)};
+}
+HSD void stage_walls_store(OctRes &R, const WallPieces &p) {
+    const int L = hs_lane();
+    *(WallPiece *)(&R.u.det.wall[0][0][0] + 4 * L) = p.cx; *(WallPiece *)(&R.u.det.wall[1][0][0] + 4 * L) = p.cy;
+    *(WallPiece *)(&R.u.det.wall[2][0][0] + 4 * L) = p.hx; *(WallPiece *)(&R.u.det.wall[3][0][0] + 4 * L) = p.hy;
+}
+// (a fence for the compiler's scheduler: the LDS reads issued above it are all in flight before the first use below it)
+HSD void issue_fence() { __builtin_amdgcn_sched_barrier(0); }
+// value of lane s (0..7) of the caller's world; lane0 = world_lane0()
+HSD int world_lane0() { return (hs_lane() & ~(kWorldLanes - 1)) * 4; }
+HSD unsigned world_lane(unsigned x, int lane0, int s) { return (unsigned)__builtin_amdgcn_ds_bpermute(lane0 + s * 4, (int)x); }
+// The strip masks of the staged walls (hs_broadphase.h), once per step: lane l of a world gets the walls that touch
+// strip l in x (xm) and in y (ym), a bit per staged wall.  Each lane finds the strips of walls l, l + 8, l + 16, l + 24;
+// the eight lanes then exchange them.  Walls do not move during a step.
+HSD void wall_strip_masks(const OctRes &R, unsigned &xm, unsigned &ym) {
+    static_assert(kLdsWalls == 4 * kWorldLanes && kStrips == kWorldLanes, "a byte of strips per wall, four walls per lane");
+    const int L = hs_lane(), g = L / kWorldLanes, l = L % kWorldLanes;
+    const int nw = R.numWalls[g];
+    unsigned wx = 0u, wy = 0u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int k = l + r * kWorldLanes;
+        const unsigned b = wall_strips(R.u.det.wall[0][k][g], R.u.det.wall[1][k][g], R.u.det.wall[2][k][g], R.u.det.wall[3][k][g]);
+        wx |= k < nw ? (b & 0xffu) << (8 * r) : 0u;
+        wy |= k < nw ? (b >> 8) << (8 * r) : 0u;
+    }
+    xm = 0u; ym = 0u;
+    const int lane0 = world_lane0();
+    unsigned fx[kWorldLanes], fy[kWorldLanes];
+#pragma unroll
+    for (int j = 0; j < kWorldLanes; ++j) { fx[j] = world_lane(wx, lane0, j); fy[j] = world_lane(wy, lane0, j); }
+    issue_fence();
+#pragma unroll
+    for (int j = 0; j < kWorldLanes; ++j) { xm |= strip_mask_part(fx[j], l, j); ym |= strip_mask_part(fy[j], l, j); }
+}
+// AABB candidates (<= 17 bodies, <= 36 walls per world: no BVH), 8 lanes per world: lane l of a world owns body
+// slots l, l + 8, l + 16.  Every pair of slots is tested once, and a body only against the walls that share a strip
+// with it (hs_broadphase.h): the candidate masks are those of the loops over all pairs and all walls.  Also builds
+// the octet's work list of convex tests.  Returns the number of box-only items in .nbox and of items that involve a
+// ramp (wedge hull) in .nwedge; the ramp items start at the next multiple of 32 so that most rounds of the convex
+// test run the box code only.
 struct ItemCounts { int nbox, nwedge; bool anySpill; };
 template <int JB>   // JB body slots per lane: 2 cover 16 slots (<= 5 agents), 3 all 17
-HSD ItemCounts phase_detect(const SimState &S, OctRes &R, int NS) {
+HSD ItemCounts phase_detect(const SimState &S, OctRes &R, int NS, unsigned xm, unsigned ym) {
     constexpr int G = kWorldLanes;
     const int L = hs_lane(), g = L / G, l = L % G;
-    // the octet's walls -> LDS, 16 bytes per lane and component (rows beyond a world's count are never read)
-    {
-        constexpr int PR = kTile / 4;                               // 16-byte pieces per row of the octet
-        static_assert(kLdsWalls * PR <= 64, "one piece per lane per component");
-        const float *src = S.walls.octet(S.wbeg >> 3);
-        float4 v[4];
-        const bool on = L < kLdsWalls * PR;
-        const int row = L / PR, part = L % PR;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (on) v[c] = *(const float4 *)(src + (c * kMaxWalls + row) * kTile + 4 * part);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (on) *(float4 *)(&R.u.det.wall[c][row][4 * part]) = v[c];
-    }
+    const WallPieces wp = stage_walls_load(S);          // (stored after the body pairs, which need no wall)
     if (l == 0) { R.scAcc[g] = 0u; R.ddAcc[g] = 0u; }
+#pragma unroll
+    for (int jb = 0; jb < JB; ++jb) if (l + jb * G < kNumDSlots) R.u.det.xch[l + jb * G][g] = 0u;
     wave_sync();
     const int nwl = R.numWalls[g], npl = R.numPlanes[g];
     int tot_items = 0;
@@ -339,38 +380,115 @@ HSD ItemCounts phase_detect(const SimState &S, OctRes &R, int NS) {
         lo[jb] = {0.f, 0.f, 0.f}; hi[jb] = {0.f, 0.f, 0.f};
         if (have[jb]) { lo[jb] = rld3(R.u.det.lo, slot, g); hi[jb] = rld3(R.u.det.hi, slot, g); }
     }
-    // The loops run over the OTHER body / the wall, each read from LDS once and tested against all of the lane's slots.
+    // Body pairs, each unordered pair once (hs_broadphase.h): a slot is tested against the next NS / 2 slots, cyclically.
+    // A hit on a partner ABOVE the slot is the slot's own candidate; a hit on a partner below it (the wrapped part of
+    // the walk) belongs to the partner's list, and goes there through the partner's exchange word.
     // (no branch on the other body's presence: the loads of several trips are in flight together)
-#pragma unroll 4
-    for (int j = 1; j < NS; ++j) {
-        const int mj = R.meta[j][g];
-        const bool dynj = meta_resp(mj) == RESP_DYNAMIC;
-        const V3 loj = rld3(R.u.det.lo, j, g), hij = rld3(R.u.det.hi, j, g);
+    {
+        int pj[JB]; unsigned hm[JB];
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb) { pj[jb] = have[jb] ? l + jb * G : 0; hm[jb] = 0u; }
+        const int nd = pair_steps(NS);
+        // two distances per trip: the partners' words are all requested before the first comparison
+        for (int d = 1; d <= nd; d += 2) {
+            int pjs[2][JB], mj[2][JB]; V3 loj[2][JB], hij[2][JB];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int jb = 0; jb < JB; ++jb) {
+                    const int j = pair_next(pj[jb], NS);
+                    pj[jb] = j; pjs[u][jb] = j;
+                    mj[u][jb] = R.meta[j][g];
+                    loj[u][jb] = rld3(R.u.det.lo, j, g); hij[u][jb] = rld3(R.u.det.hi, j, g);
+                }
+            issue_fence();
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int jb = 0; jb < JB; ++jb) {
+                    const bool dynj = meta_resp(mj[u][jb]) == RESP_DYNAMIC;
+                    const bool hit = (d + u <= nd) & (mj[u][jb] != 0) & have[jb] & pair_mine(l + jb * G, d + u, NS) & (dynamic[jb] | dynj) &
+                        aabb_hit(lo[jb], hi[jb], loj[u][jb], hij[u][jb]);
+                    hm[jb] |= hit ? 1u << pjs[u][jb] : 0u;
+                }
+        }
 #pragma unroll
         for (int jb = 0; jb < JB; ++jb) {
-            const bool hit = (mj != 0) & have[jb] & (l + jb * G < j) & (dynamic[jb] | dynj) &
-                (lo[jb].x <= hij.x) & (loj.x <= hi[jb].x) & (lo[jb].y <= hij.y) & (loj.y <= hi[jb].y) &
-                (lo[jb].z <= hij.z) & (loj.z <= hi[jb].z);
-            dd_mask[jb] |= hit ? 1u << j : 0u;
+            const int slot = l + jb * G;
+            unsigned below = hm[jb] & ((1u << slot) - 1u);
+            while (below) {                             // (few: most lanes have none)
+                const int j = __ffs(below) - 1; below &= below - 1;
+                atomicOr(&R.u.det.xch[j][g], 1u << slot);
+            }
+        }
+        stage_walls_store(R, wp);
+        wave_sync();
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb) {
+            const int slot = l + jb * G;
+            dd_mask[jb] = (hm[jb] & ~((2u << slot) - 1u)) | (slot < kNumDSlots ? R.u.det.xch[slot][g] : 0u);
         }
     }
+    // Walls: the exact test on the staged walls that share a strip with the body in x and in y (hs_broadphase.h: that
+    // set holds every wall the test accepts), lowest index first.
     bool zin[JB];                                       // the walls all span z in [0, 2.5]
+    unsigned wcand[JB], whit[JB];
 #pragma unroll
     for (int jb = 0; jb < JB; ++jb) zin[jb] = dynamic[jb] & (lo[jb].z <= 2.5f) & (0.f <= hi[jb].z);
-    auto wall_test = [&](int k, float cx, float cy, float hx, float hy) {
-        const float wx0 = cx - hx, wx1 = cx + hx, wy0 = cy - hy, wy1 = cy + hy;
+    {
+        unsigned sx[JB], sy[JB], ax[JB], ay[JB];
 #pragma unroll
         for (int jb = 0; jb < JB; ++jb) {
-            const bool hit = zin[jb] & (lo[jb].x <= wx1) & (wx0 <= hi[jb].x) & (lo[jb].y <= wy1) & (wy0 <= hi[jb].y);
-            s_mask[jb] |= hit ? 1ull << k : 0ull;
+            sx[jb] = extent_strips(lo[jb].x, hi[jb].x); sy[jb] = extent_strips(lo[jb].y, hi[jb].y);
+            ax[jb] = 0u; ay[jb] = 0u;
         }
-    };
-    const int nwLds = nwl < kLdsWalls ? nwl : kLdsWalls;
-#pragma unroll 4
-    for (int k = 0; k < nwLds; ++k) wall_test(k, R.u.det.wall[0][k][g], R.u.det.wall[1][k][g], R.u.det.wall[2][k][g], R.u.det.wall[3][k][g]);
+        const int lane0 = world_lane0();
+        unsigned mx[kStrips], my[kStrips];
+#pragma unroll
+        for (int s = 0; s < kStrips; ++s) { mx[s] = world_lane(xm, lane0, s); my[s] = world_lane(ym, lane0, s); }
+        issue_fence();
+#pragma unroll
+        for (int s = 0; s < kStrips; ++s)
+#pragma unroll
+            for (int jb = 0; jb < JB; ++jb) { ax[jb] |= (sx[jb] >> s & 1u) ? mx[s] : 0u; ay[jb] |= (sy[jb] >> s & 1u) ? my[s] : 0u; }
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb) { wcand[jb] = zin[jb] ? ax[jb] & ay[jb] : 0u; whit[jb] = 0u; }
+    }
+    for (;;) {                                          // two walls per slot and trip, requested together
+        unsigned left = 0u;
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb) left |= wcand[jb];
+        if (left == 0u) break;
+        int wk[2][JB]; bool won[2][JB]; float wv[2][JB][4];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int jb = 0; jb < JB; ++jb) {
+                const unsigned m = wcand[jb];
+                const int k = (__ffs(m) - 1) & (kLdsWalls - 1);      // (no candidate left: any staged row, the result is dropped)
+                wcand[jb] = m & (m - 1u);
+                wk[u][jb] = k; won[u][jb] = m != 0u;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) wv[u][jb][c] = R.u.det.wall[c][k][g];
+            }
+        issue_fence();
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int jb = 0; jb < JB; ++jb) {
+                const WallBox wb = wall_box(wv[u][jb][0], wv[u][jb][1], wv[u][jb][2], wv[u][jb][3]);
+                const bool hit = won[u][jb] & wall_hit(zin[jb], lo[jb].x, hi[jb].x, lo[jb].y, hi[jb].y, wb);
+                whit[jb] |= hit ? 1u << wk[u][jb] : 0u;
+            }
+    }
+#pragma unroll
+    for (int jb = 0; jb < JB; ++jb) s_mask[jb] = whit[jb];
     for (int k = kLdsWalls; k < nwl; ++k) {             // (the few walls beyond the staged ones, from global memory)
         const int w = S.wbeg + g;
-        wall_test(k, S.walls(0 * kMaxWalls + k, w), S.walls(1 * kMaxWalls + k, w), S.walls(2 * kMaxWalls + k, w), S.walls(3 * kMaxWalls + k, w));
+        const WallBox wb = wall_box(S.walls(0 * kMaxWalls + k, w), S.walls(1 * kMaxWalls + k, w), S.walls(2 * kMaxWalls + k, w), S.walls(3 * kMaxWalls + k, w));
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb)
+            s_mask[jb] |= wall_hit(zin[jb], lo[jb].x, hi[jb].x, lo[jb].y, hi[jb].y, wb) ? 1ull << k : 0ull;
     }
     // candidate slots in the world's lists: prefix sums in body-slot order (slots l of all lanes, then l + 8, ...),
     // i.e. the oracle's candidate order — a pair's place in it is where its record lives in the workspace
@@ -1561,6 +1679,12 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
     }
     wave_sync();
     HS_TICK(1)
+    // The walls' strip masks for the step's four broadphases, from the walls staged as a broadphase stages them
+    // (the velocities whose memory the staged walls take are dead from the integration on: OctRes::u).
+    unsigned wallsX, wallsY;
+    stage_walls_store(R, stage_walls_load(S));
+    wave_sync();
+    wall_strip_masks(R, wallsX, wallsY);
     // The substeps.  (The spill path — pairs beyond the LDS capacities, a handful in millions of world-steps — sits behind
     // wave-uniform branches on ic.anySpill inside the phases.  While the kernel kept its lane constants alive across all
     // phases it sat at its 256-register budget and this code cost the hot path 12 spilled registers whichever way it was
@@ -1569,7 +1693,7 @@ HSD void physics_step(SimState &S, OctRes &R, GenScratch *gen) {
     // registers and the plain form spills nothing.)
 #pragma unroll 1
     for (int sub = 0; sub < kNumSubsteps; ++sub) {
-        const ItemCounts ic = phase_detect<ROUNDS>(S, R, NS);
+        const ItemCounts ic = phase_detect<ROUNDS>(S, R, NS, wallsX, wallsY);
         HS_TICK(2)
         substep_rest<ROUNDS>(S, R, br, nbodies, NS, ic, sub + 1 < kNumSubsteps, aforce HS_TICK_ARGS);
     }
