@@ -28,6 +28,7 @@
 #include "hs_collide.h"
 #include "hs_solver.h"
 #include "hs_broadphase.h"
+#include "hs_solve_order.h"
 #include "hs_k_reset.h"
 
 namespace hs {
@@ -98,7 +99,6 @@ struct alignas(16) OctRes {
     unsigned short scInfo[kNumDSlots][kTile];   // per body: first static candidate | count << 8
     unsigned int scAcc[kTile];                  // bit k: static candidate k of the world has a manifold (set by the convex test)
     unsigned int ddAcc[kTile];                  // bit k: body-body candidate k has a manifold
-    unsigned int ddOrd[2][kTile];               // the accepted body-body candidates in solve order, 4 bits each (phase_dd)
     float plane0[4][kTile];                     // the ground plane nx, ny, nz, d of every world
     unsigned char bodies[kNumDSlots * kTile];   // compact list of existing bodies: slot << 3 | world
     union {
@@ -133,13 +133,41 @@ HSD int pair_pack(int a, int b) { return a | (b << 5) | (kLocGlobal << 11); }
 static_assert(kNumDSlots <= 32 && kMaxWalls + kMaxPlanes <= 64, "pair encoding");
 static_assert(sizeof(ManDD) % 16 == 0 && sizeof(ManS) % 16 == 0, "manifold records move 16 bytes at a time");
 constexpr int kManWords = sizeof(ManDD) / 4;          // slot stride (a ManS record uses the first 28 words)
-template <typename M> HSD void man_lds_load(const float *clip, int slot, M &m) {
-    m = *reinterpret_cast<const M *>(clip + slot * kManWords);          // 16-byte reads
+// A body-body record is read and written 16 bytes at a time through pointers that NAME their memory: an LDS slot with
+// ds_read_b128 / ds_write_b128, a workspace record with global_load_dwordx4 / global_store_dwordx4.  (With plain pointers
+// the compiler folds "slot or workspace" into one generic pointer and the record moves through flat_ instructions, which
+// take the vector-memory address path and count on both wait counters even when the record is in LDS — nearly always.)
+typedef float Piece __attribute__((ext_vector_type(4)));
+#define HS_LDS __attribute__((address_space(3)))
+#define HS_GLOBAL __attribute__((address_space(1)))
+HSD Piece lds_piece(const float *p) { return *(const HS_LDS Piece *)p; }
+HSD Piece glb_piece(const float *p) { return *(const HS_GLOBAL Piece *)p; }
+HSD void lds_put_piece(float *p, Piece v) { *(HS_LDS Piece *)p = v; }
+HSD void glb_put_piece(float *p, Piece v) { *(HS_GLOBAL Piece *)p = v; }
+HSD float glb_word(const float *p) { return *(const HS_GLOBAL float *)p; }
+// the pieces `at` (word offsets) of a record: slot `loc` of the clip buffers, or `rec` in the workspace where loc is kLocGlobal
+template <int N> struct Pieces { Piece p[N]; };
+template <int N> HSD void man_load(const float *clip, int loc, const float *rec, const int (&at)[N], Pieces<N> &out) {
+    // The LDS reads are straight-line code that the scheduler may start early (a record in the workspace reads the last
+    // slot for nothing); the workspace arm is a branch that more than nine substeps in ten skip.
+    const float *s = clip + min(loc, OctRes::kSlots - 1) * kManWords;
+#pragma unroll
+    for (int i = 0; i < N; ++i) out.p[i] = lds_piece(s + at[i]);
+    if (loc == kLocGlobal) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) out.p[i] = glb_piece(rec + at[i]);
+    }
 }
-// accumulated normal multipliers of a manifold in LDS: the last 4 words of either record
-template <typename M> HSD void man_lds_set_lam(float *clip, int slot, int j, float v) {
+// accumulated normal multipliers of a manifold: the last 4 words of either record, one store per manifold
+template <typename M> HSD void man_put_lam(float *clip, int loc, M *rec, Piece lam) {
     static_assert(offsetof(M, lam) == sizeof(M) - 16, "lam is the record's tail");
-    clip[slot * kManWords + (sizeof(M) / 4 - 4 + j)] = v;
+    if (loc != kLocGlobal) lds_put_piece(clip + loc * kManWords + (sizeof(M) / 4 - 4), lam);
+    else glb_put_piece(rec->lam, lam);
+}
+// A static manifold (wall_round, last_round) keeps the folded generic pointer: read through man_load, in either form, the
+// static velocity passes measured 1.0 us per wave and step slower (profiles/solver_bookkeeping_bench.txt).
+HSD void man_static_load(const float *clip, int loc, const ManS *rec, ManS &m) {
+    if (loc != kLocGlobal) m = *reinterpret_cast<const ManS *>(clip + loc * kManWords); else m = *rec;
 }
 
 // ---- accessors of the resident columns ----
@@ -606,6 +634,7 @@ struct SpillCtx {
     int wbeg;
 };
 HSD SpillCtx spill_ctx(const SimState &S) { return {S.walls.p, S.planes.p, (ManDD *)S.wsDD, (ManS *)S.wsSC, S.spPair, S.spInfo, S.wbeg}; }
+HSD HullSrc sat_hull_b(const Col<float, 4 * kMaxWalls> &walls, const OctRes &R, int g, int w, bool isdd, int bsel);   // (with the convex tests below)
 
 // Convex tests of the spilled pairs: world by world, body-body then body-static, 32 pairs per trip, two lanes per pair
 // for the axis search (sat_axes) and the pair's first lane for the contact generation right away (no compaction: this
@@ -648,9 +677,7 @@ HS_COLD void spill_sat(SpillCtx c, OctRes *Rp) {
                         if (!hi && !collide_hull_plane(hull_ref_body(oa, pa, qa), pn, planes(3 * kMaxPlanes + p, w), raw)) raw.np = 0;
                     } else {
                         const HullSrc ha = hull_src_body(oa, pa, qa);
-                        const HullSrc hb = isdd ? hull_src_body(meta_obj(R.meta[bsel][g]), rld3(R.pos, bsel, g), rld4(R.rot, bsel, g))
-                                                : hull_src_wall(walls(0 * kMaxWalls + bsel, w), walls(1 * kMaxWalls + bsel, w),
-                                                                walls(2 * kMaxWalls + bsel, w), walls(3 * kMaxWalls + bsel, w));
+                        const HullSrc hb = sat_hull_b(walls, R, g, w, isdd, bsel);
                         const AxisResult res = sat_axes(ha, hb, hi);
                         const ClipBuf cb = {R.u.sat.clip, lane >> 1, OctRes::kClip};
                         if (!hi && res.code != 0 && !sat_contact(ha, hb, res, cb, raw)) raw.np = 0;
@@ -759,11 +786,19 @@ HS_COLD void spill_static(SpillCtx c, OctRes *Rp, int NS) {
 // to a pending list.  Stage 2 — contact generation, the long part: polygon clipping on one lane — runs on the pending
 // pairs only, compacted, 32 per round: about a third of the candidates collide, so one round serves the whole octet.
 HSD HullSrc sat_hull_a(const OctRes &R, int g, int a) { return hull_src_body(meta_obj(R.meta[a][g]), rld3(R.pos, a, g), rld4(R.rot, a, g)); }
-HSD HullSrc sat_hull_b(const SimState &S, const OctRes &R, int g, int w, bool isdd, int bsel) {
-    if (isdd) return hull_src_body(meta_obj(R.meta[bsel][g]), rld3(R.pos, bsel, g), rld4(R.rot, bsel, g));
-    // (the staged walls share their LDS with the clip buffers: from global memory here)
-    return hull_src_wall(S.walls(0 * kMaxWalls + bsel, w), S.walls(1 * kMaxWalls + bsel, w),
-                         S.walls(2 * kMaxWalls + bsel, w), S.walls(3 * kMaxWalls + bsel, w));
+// The second hull is a body (LDS) or a wall (global memory: the staged walls share their LDS with the clip buffers).  The
+// wall's four words are requested first, as global loads of their own and whichever kind the item is — a body slot is a
+// valid wall row, the words are dropped — so they are in flight while the bodies are read and the first hull is built,
+// and the wait stands where the hull needs them.  (Written as "body ? LDS : global" the two sources fold into generic
+// pointers: flat loads, each waited for at once.)
+HSD HullSrc sat_hull_b(const Col<float, 4 * kMaxWalls> &walls, const OctRes &R, int g, int w, bool isdd, int bsel) {
+    static_assert(kNumDSlots <= kMaxWalls, "a body slot is a valid wall row");
+    const float *const wp = &walls(min(bsel, kMaxWalls - 1), w);
+    const float cx = glb_word(wp), cy = glb_word(wp + kMaxWalls * kTile);
+    const float hx = glb_word(wp + 2 * kMaxWalls * kTile), hy = glb_word(wp + 3 * kMaxWalls * kTile);
+    const int slot = isdd ? bsel : 0;
+    const HullSrc body = hull_src_body(meta_obj(R.meta[slot][g]), rld3(R.pos, slot, g), rld4(R.rot, slot, g));
+    return hull_src_sel(isdd, body, hull_src_wall(cx, cy, hx, hy));
 }
 // stage 2 for the first `npend` pending pairs: lane i < 32 takes pair i.  `last`: this is the substep's last round,
 // whose manifolds stay in LDS (in the lane's own clip column); returns whether a manifold went to global memory.
@@ -792,7 +827,7 @@ HSD bool sat_flush(const SimState &S, OctRes &R, int npend, bool last) {
             const V3 pn = {S.planes(0 * kMaxPlanes + p, w), S.planes(1 * kMaxPlanes + p, w), S.planes(2 * kMaxPlanes + p, w)};
             have = collide_hull_plane(hull_ref_body(meta_obj(R.meta[a][g]), rld3(R.pos, a, g), rld4(R.rot, a, g)), pn, S.planes(3 * kMaxPlanes + p, w), raw);
         } else {
-            have = sat_contact(sat_hull_a(R, g, a), sat_hull_b(S, R, g, w, isdd, bsel), res, cb, raw);
+            have = sat_contact(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), res, cb, raw);
         }
         if (have) {
             const int oa = meta_obj(R.meta[a][g]);
@@ -892,9 +927,9 @@ HSD bool phase_sat(const SimState &S, OctRes &R, ItemCounts ic) {
                 // extra planes (debug levels only): no axis search — the contact round tests the hull against the plane
                 if (lead) res.code = 3;
             } else if (wide) {
-                res = sat_axes_wide(sat_hull_a(R, g, a), sat_hull_b(S, R, g, w, isdd, bsel), lane & 15);
+                res = sat_axes_wide(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), lane & 15);
             } else {
-                res = sat_axes(sat_hull_a(R, g, a), sat_hull_b(S, R, g, w, isdd, bsel), hi);
+                res = sat_axes(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), hi);
             }
         }
         // the colliding pairs of this round join the pending list (their lead lanes file the results)
@@ -1042,17 +1077,36 @@ HSD void pair_point_velocity(BodyS &me, bool isA, V3 n, V3 rl, float lamN, float
     else { me.lin = nmadd(me.lin, p, me.invM); me.ang = me.ang - da; }
 }
 
+// This lane's side of a body-body manifold: the header, the contact points in ITS body's frame (rA on the first lane
+// of the pair, rB on the second) and the multipliers — six of the record's nine pieces.
+struct ManSide { int np; float muS, muD; V3 n; V3 r[4]; Piece lam; };
+HSD void man_side_load(const float *clip, int loc, const ManDD *rec, bool isA, ManSide &m) {
+    static_assert(offsetof(ManDD, rA) == 32 && offsetof(ManDD, rB) == 80 && offsetof(ManDD, lam) == 128, "pieces of a ManDD");
+    const int r0 = isA ? 8 : 20;
+    const int at[6] = {0, 4, r0, r0 + 4, r0 + 8, 32};
+    Pieces<6> q;
+    man_load(clip, loc, reinterpret_cast<const float *>(rec), at, q);
+    m.np = __float_as_int(q.p[0].z); m.muS = q.p[0].w; m.muD = q.p[1].x;
+    m.n = {q.p[1].y, q.p[1].z, q.p[1].w};
+    m.r[0] = {q.p[2].x, q.p[2].y, q.p[2].z}; m.r[1] = {q.p[2].w, q.p[3].x, q.p[3].y};
+    m.r[2] = {q.p[3].z, q.p[3].w, q.p[4].x}; m.r[3] = {q.p[4].y, q.p[4].z, q.p[4].w};
+    m.lam = q.p[5];
+}
+
+// Returns (POS) / takes (!POS) the lane's order word of the substep (hs_solve_order.h ord_pack): the velocity pass
+// solves the manifolds the position pass solved, in the same batches with the same dependencies.
 template <bool POS>
-HSD void phase_dd(const SimState &S, OctRes &R, bool anySpill) {
+HSD unsigned phase_dd(const SimState &S, OctRes &R, bool anySpill, unsigned ordIn) {
     constexpr int GL = kWorldLanes, PAIRS = GL / 2;               // lanes per world; manifolds of a world in flight at once
+    static_assert(PAIRS == kOrdBatch && kMaxDDCand <= kOrdBatch * kOrdBatches, "the order word holds every batch");
     const int L = hs_lane(), g = L / GL, q = L % GL;
     const int h = q >> 1;                                         // this lane's pair within the world's lanes
     const bool isA = (q & 1) == 0;
     const int gbit0 = g * GL;                                     // first lane of this group in the wave
     const int w = S.wbeg + g;                                     // the world's slot in the tiled columns
-    const int ndd = R.ndd[g];
     const bool grab = R.hasGrab[g] != 0;
-    if (!anySpill && __ballot(R.ddAcc[g] != 0u || (POS && grab)) == 0ull) return;        // nothing to do in the whole octet
+    const unsigned acc = R.ddAcc[g];
+    if (!anySpill && __ballot(acc != 0u || (POS && grab)) == 0ull) return 0u;            // nothing to do in the whole octet
     if (POS && grab && q == 0) {
         const int teams = S.teams[R.wid[g]];
         for (int a = 0; a < kMaxAgents; ++a) {
@@ -1070,71 +1124,51 @@ HSD void phase_dd(const SimState &S, OctRes &R, bool anySpill) {
         }
     }
     ManDD *const wsDD = (ManDD *)S.wsDD + (size_t)w * kAllDD;
-    const unsigned acc = R.ddAcc[g];
     const int nacc = __popc(acc);
-    if (POS) {
-        // The solve order, once per substep (the velocity pass reuses it): kMaxDDCand = 16 candidates, lane q ranks the
-        // keys of the accepted ones among q and q+8 (keys are unique: distinct pairs) and enters them at their rank.
-        if (q < 2) R.ddOrd[q][g] = 0u;
-        int key0 = 0x7fffffff, key1 = 0x7fffffff;
-        if (q < ndd && ((acc >> q) & 1u)) { const int p = R.ddPair[q][g]; key0 = (pair_a(p) << 8) | pair_b(p); }
-        if (q + GL < ndd && ((acc >> (q + GL)) & 1u)) { const int p = R.ddPair[q + GL][g]; key1 = (pair_a(p) << 8) | pair_b(p); }
-        int rank0 = 0, rank1 = 0;
-#pragma unroll
-        for (int p = 0; p < GL; ++p) {
-            const int k0 = __shfl(key0, gbit0 + p), k1 = __shfl(key1, gbit0 + p);
-            rank0 += (k0 < key0) + (k1 < key0); rank1 += (k0 < key1) + (k1 < key1);
-        }
-        wave_sync();
-        if (key0 != 0x7fffffff) atomicOr(&R.ddOrd[rank0 >> 3][g], (unsigned)q << ((rank0 & 7) * 4));
-        if (key1 != 0x7fffffff) atomicOr(&R.ddOrd[rank1 >> 3][g], (unsigned)(q + GL) << ((rank1 & 7) * 4));
-    }
+    unsigned ord = POS ? 0u : ordIn;
     wave_sync();
-    for (int base = 0; base < kMaxDDCand; base += PAIRS) {
+    for (int base = 0, batch = 0; base < kMaxDDCand; base += PAIRS, ++batch) {
         if (__ballot(base < nacc) == 0ull) break;
-        // the h-th pair of lanes takes the manifold of rank base + h
+        // The h-th pair of lanes takes the accepted candidate of rank base + h: the candidates are filed in pair order
+        // (hs_solve_order.h), so that is the (base + h)-th set bit of the accepted mask.
         const int rk = base + h;
-        const int mine = rk < nacc ? (int)((R.ddOrd[rk >> 3][g] >> ((rk & 7) * 4)) & 15u) : -1;
-        int ma = -1, mb = -1, loc = kLocGlobal;
-        ManDD m;
+        const int mine = POS ? (rk < nacc ? kth_set_bit(acc, rk) : -1) : ord_cand(ord, batch);
+        int code = -1, loc = kLocGlobal;
+        ManSide m;
         if (mine >= 0) {
             const int pr = R.ddPair[mine][g];
-            ma = pair_a(pr); mb = pair_b(pr); loc = pair_loc(pr);
-            if (loc != kLocGlobal) man_lds_load(R.u.sat.clip, loc, m); else m = wsDD[mine];
+            code = pr & 0x7ff; loc = pair_loc(pr);
+            man_side_load(R.u.sat.clip, loc, wsDD + mine, isA, m);
         }
-        // the earlier pairs of this batch that touch one of its bodies
-        unsigned dep = 0u;
-#pragma unroll
-        for (int p = 0; p < PAIRS - 1; ++p) {
-            const int pa = __shfl(ma, gbit0 + 2 * p), pb = __shfl(mb, gbit0 + 2 * p);
-            if (p < h && pa >= 0 && (pa == ma || pa == mb || pb == ma || pb == mb)) dep |= 1u << p;
+        // The earlier pairs of this batch that touch one of its bodies: their codes come from the lanes 2, 4 and 6 below
+        // (both lanes of a pair hold the pair's code), one DPP move each, no LDS.
+        unsigned dep;
+        if (POS) {
+            dep = batch_dep_mask(h, code, dpp_row_shr<2>(code), dpp_row_shr<4>(code), dpp_row_shr<6>(code));
+            if (mine >= 0) ord |= ord_pack(batch, mine, dep);
+        } else {
+            dep = ord_dep(ord, batch);
         }
+        const unsigned depBits = dep_spread(dep);                 // (bit 2p: pair p, as the ballot below has them)
         bool pending = mine >= 0;
         BodyS me;
-        const int myBody = isA ? ma : mb;
-        const V3 n = ld3(m.n);
+        const int myBody = isA ? pair_a(code) : pair_b(code);
         while (true) {
             const unsigned long long pend_mask = __ballot(pending && isA);
             if (pend_mask == 0ull) break;
-            // (bit 2p of the world's 8 bits: pair p is pending)
-            const unsigned wp = (unsigned)(pend_mask >> gbit0);
-            unsigned pendPairs = 0u;
-#pragma unroll
-            for (int p = 0; p < PAIRS; ++p) pendPairs |= ((wp >> (2 * p)) & 1u) << p;
-            if (pending && (dep & pendPairs) == 0u) {
+            if (pending && (depBits & (unsigned)(pend_mask >> gbit0)) == 0u) {
                 rbody_load(R, g, myBody, me);
                 if (POS) {
+                    Piece lam = m.lam;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (j < m.np) {
-                            const float lam = pair_point_position(me, isA, n, isA ? ld3(m.rA[j]) : ld3(m.rB[j]), m.muS);
-                            if (isA) { if (loc != kLocGlobal) man_lds_set_lam<ManDD>(R.u.sat.clip, loc, j, m.lam[j] + lam); else wsDD[mine].lam[j] = m.lam[j] + lam; }
-                        }
+                        if (j < m.np) lam[j] = lam[j] + pair_point_position(me, isA, m.n, m.r[j], m.muS);
+                    if (isA) man_put_lam(R.u.sat.clip, loc, wsDD + mine, lam);
                     rbody_store_pose(R, g, myBody, me);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (j < m.np) pair_point_velocity(me, isA, n, isA ? ld3(m.rA[j]) : ld3(m.rB[j]), m.lam[j], m.muD);
+                        if (j < m.np) pair_point_velocity(me, isA, m.n, m.r[j], m.lam[j], m.muD);
                     rbody_store_vel(R, g, myBody, me);
                 }
                 pending = false;
@@ -1145,6 +1179,7 @@ HSD void phase_dd(const SimState &S, OctRes &R, bool anySpill) {
     wave_sync();
     // (the world's SPILLED body-body pairs come after every pair above in pair order)
     if (__builtin_expect(anySpill, 0)) { spill_dd<POS>(spill_ctx(S), &R); wave_sync(); }
+    return ord;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1226,10 +1261,10 @@ HSD void wall_round(const SimState &S, OctRes &R, int first, int nwb) {
             todo &= todo - 1u;
             const int loc = pair_loc(R.scPair[k][g]);
             ManS m;
-            if (loc != kLocGlobal) man_lds_load(R.u.sat.clip, loc, m); else m = wsSC[k];
-            static_manifold<POS, 4>(me, m, [&](int j, float v) {
-                if (loc != kLocGlobal) man_lds_set_lam<ManS>(R.u.sat.clip, loc, j, v); else wsSC[k].lam[j] = v;
-            });
+            man_static_load(R.u.sat.clip, loc, wsSC + k, m);
+            Piece lam = {m.lam[0], m.lam[1], m.lam[2], m.lam[3]};
+            static_manifold<POS, 4>(me, m, [&](int j, float v) { lam[j] = v; });
+            if (POS) man_put_lam(R.u.sat.clip, loc, wsSC + k, lam);
         }
         if (POS) rbody_store_pose(R, g, slot, me); else rbody_store_vel(R, g, slot, me);
     }
@@ -1268,7 +1303,7 @@ HSD void last_round(const SimState &S, OctRes &R, BodyReg &b, bool valid, int sl
         ManS m;
         if (walls) {
             loc = pair_loc(R.scPair[k][g]);
-            if (loc != kLocGlobal) man_lds_load(R.u.sat.clip, loc, m); else m = wsSC[k];
+            man_static_load(R.u.sat.clip, loc, wsSC + k, m);
             n = ld3(m.n); mu = POS ? m.muS : m.muD; np = m.np;
         } else {
             n = -V3{R.plane0[0][g], R.plane0[1][g], R.plane0[2][g]};
@@ -1287,15 +1322,14 @@ HSD void last_round(const SimState &S, OctRes &R, BodyReg &b, bool valid, int sl
             const float lamj = walls ? m.lam[j] : b.lam[j];                                                                \
             if (POS) {                                                                                                     \
                 const float nl = lamj + solve_point_position_ground(me, n, rAj, walls ? m.offB[j] : kGroundOff, mu, yaw, dj[j], share); \
-                if (!walls) b.lam[j] = nl;                                                                                 \
-                else if (loc != kLocGlobal) man_lds_set_lam<ManS>(R.u.sat.clip, loc, (j), nl);                             \
-                else wsSC[k].lam[j] = nl;                                                                                  \
+                if (!walls) b.lam[j] = nl; else m.lam[j] = nl;                                                             \
             } else {                                                                                                       \
                 solve_point_velocity<false>(me, none, n, rAj, V3{0.f, 0.f, 0.f}, lamj, mu);                                \
             }                                                                                                              \
         }
         HS_LAST_POINT(0) HS_LAST_POINT(1) HS_LAST_POINT(2) HS_LAST_POINT(3)
 #undef HS_LAST_POINT
+        if (POS && walls) man_put_lam(R.u.sat.clip, loc, wsSC + k, Piece{m.lam[0], m.lam[1], m.lam[2], m.lam[3]});
     }
     if (POS) rbody_store_pose(R, g, slot, me); else rbody_store_vel(R, g, slot, me);
 }
@@ -1536,7 +1570,7 @@ HSD void substep_rest(const SimState &S, OctRes &R, BodyReg (&br)[ROUNDS], int n
     const int L = hs_lane();
     const bool manGlobal = phase_sat(S, R, ic);
     HS_TICK(3)
-    phase_dd<true>(S, R, ic.anySpill);
+    const unsigned ddOrder = phase_dd<true>(S, R, ic.anySpill, 0u);
     HS_TICK(4)
     // (with 6 agents a third round exists for up to 136 bodies, but an octet rarely holds more than 128: then round 1 is
     // the last one that holds bodies, and the passes are two, not three)
@@ -1554,7 +1588,7 @@ HSD void substep_rest(const SimState &S, OctRes &R, BodyReg (&br)[ROUNDS], int n
     for (int r = 0; r < ROUNDS; ++r) { HS_BODY(r) if (valid) derive_body_velocity(R, slot, g, meta); }
     if (manGlobal) mem_sync(); else wave_sync();   // (the multipliers of manifolds in the global workspace, for the velocity pass)
     HS_TICK(5)
-    phase_dd<false>(S, R, ic.anySpill);
+    phase_dd<false>(S, R, ic.anySpill, ddOrder);
     HS_TICK(6)
     if (shortLast) static_passes<ROUNDS, kShortLastR, false>(S, R, br, nbodies, nLast, nMerged);
     else static_passes<ROUNDS, ROUNDS - 1, false>(S, R, br, nbodies, nLast, nMerged);
