@@ -163,24 +163,29 @@ def test_headless_cpp_driver_runs():
     assert bad.returncode != 0 and "CPU" in bad.stderr
 
 
-def test_physics_only_65536_worlds():
+def test_physics_only_65536_worlds(oracle):
     """BASELINE.json configs[2] (65 536 worlds, observations skipped): runs, stays finite, and a sampled world
-    range matches a small simulator with the same global world ids bit for bit."""
+    range matches a small simulator with the same global world ids bit for bit, and the oracle of that range (the
+    same six steps of actions; every exported tensor, bodies and walls)."""
     import torch
+    import lockstep
     N, steps, lo, n = 65536, 6, 40000, 32
     big = _sim(N, sim_flags=1 << 16)
     small = _sim(n, sim_flags=1 << 16, world_offset=lo)
-    big.init(); small.init()
+    ref = lockstep.make_ref(n, flags=1 << 16, world_offset=lo)
+    big.init(); small.init(); ref.init()
     ab, asm = big.action_tensor().to_torch(), small.action_tensor().to_torch()
     for s in range(steps):
         g = torch.arange(N * 4, device=ab.device)
         ab[:, 0] = ((g * 7 + s) % 10 - 5).int(); ab[:, 1] = ((g * 3 + 2 * s) % 10 - 5).int()
         asm[:, 0:2] = ab[lo * 4:(lo + n) * 4, 0:2]
-        big.step(); small.step()
+        ref.tensor("action")[:, 0:2] = ab[lo * 4:(lo + n) * 4, 0:2].cpu().numpy()
+        big.step(); small.step(); ref.step()
     bb, bm = big.debug_bodies()
     sb, sm_ = small.debug_bodies()
     assert np.isfinite(bb).all()
     assert np.array_equal(bb[lo:lo + n].view(np.int32), sb.view(np.int32)) and np.array_equal(bm[lo:lo + n], sm_)
+    lockstep.check(lockstep.GpuSide(big, lo, n), ref, f"worlds {lo}..{lo + n} of {N} after {steps} steps")
 
 
 def test_importing_the_package_before_torch_keeps_torch_working():

@@ -40,6 +40,13 @@ def test_across_a_balance_deal(oracle):
     p.drive(40, "full", seed=5)
 
 
+def test_across_a_deal_with_a_partial_last_octet(oracle):
+    """19 worlds, 2+2, 70 steps: two full octets, which the deals after steps 32 and 64 shuffle, and three worlds in a
+    partial last octet, which must stay in their slots (k_balance_move_all and k_balance_commit with nfull < N)."""
+    p = Pair(19, seed=32)
+    p.drive(70, "full", seed=5)
+
+
 def test_world_with_the_most_walls(oracle):
     """Among 32 generated levels the one with the most walls, its first agent moved to the spot farthest from every
     wall (scenes.open_spot) so that its lidar rays reach walls on all sides; the same in every other world.  4 steps."""
