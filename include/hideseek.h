@@ -848,6 +848,53 @@ typedef struct hs_adam_request {
 int32_t hs_adam_step(hs_sim *sim, const hs_adam_request *req);
 int32_t hs_adam_step_async(hs_sim *sim, void *hip_stream, const hs_adam_request *req);
 
+/* The dynamic loss scale of float16 training: a scale S on the device that hs_ppo_loss_scaled and hs_twohot_value_scaled
+ * multiply their gradients by, and that hs_adam_step_scaled divides out again, halves when the gradient norm overflows
+ * and doubles after a run of good steps (csrc/hs_k_loss_scale.h).  No call reads the device from the host.  The rule is
+ * the published one of torch.cuda.amp.GradScaler and flax's DynamicScale (start 2^16, halve on overflow, double after
+ * 2000 good steps); madrona_learn is not part of the reference's tree, so it is this project's statement and not pinned
+ * by the reference.  The arithmetic is the contract.
+ * The state, f64 [HS_LOSS_SCALE_STATE] on the device, = {S, the good steps since S last changed, the backoffs so far,
+ * the growths so far}; a fresh one is {the initial scale, 0, 0, 0}.
+ * The loss calls.  S = (float)state[0], one load;   w = (grad_scale * S) / (float)cnt   with the product in f32;
+ * everything else is hs_ppo_loss's and hs_twohot_value's arithmetic word for word.  The statistics hold no S: they are
+ * the unscaled loss's.  The state is read, never written.  With grad_scale * S a power of two every output has the bits
+ * of the unscaled call whose grad_scale is that product.
+ * The optimiser.  The norm is hs_adam_step's, the same order and the same partials.  With S the state's value when the
+ * call began, in f64:
+ *   e = grad_scale / S;   gnorm = e * sqrt(sum);   skipped = gnorm is not finite
+ *   clip as hs_adam_step has it;   s = (float)(e * clip)
+ * and the update, the Adam state and stats are hs_adam_step's with e where it has grad_scale: stats[0] is the norm of the
+ * unscaled gradients.  Then, in f64:
+ *   skipped:   S' = max(S * backoff, min_scale);   good' = 0;   backoffs' = backoffs + 1
+ *   else:      good' = good + 1;   if good' >= growth_interval:   S' = min(S * growth, max_scale), good' = 0,
+ *              growths' = growths + 1;   otherwise S' = S
+ * All factors and bounds are powers of two, so S stays one and every product above is exact: gradients multiplied by 2^k
+ * with S = 2^k give the bits of hs_adam_step on the original gradients.
+ * The first kernel copies the loss-scale state into the handle's workspace next to the Adam state; the second reads only
+ * the copies and writes only the caller's states.  A later loss call on the same stream reads the new S.  No atomics.
+ * Validation (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): everything the unscaled entry point
+ * refuses; a null state or one not 8-byte aligned; growth, backoff, min_scale or max_scale not a power of two (frexp
+ * mantissa 0.5) or outside growth >= 1, 0 < backoff <= 1, 0 < min_scale <= max_scale <= 2^126;
+ * growth_interval < 1; reserved != 0; a state that overlaps any other array of the request; a call before hs_init or
+ * inside an open step.  Blocking and _async forms as for every other entry point.
+ * Not part of these calls: overflow in the forward pass (f16 activations that reach infinity give NaN logits, which no
+ * gradient scale repairs), a narrow shadow copy of the weights, several devices, a scale per parameter group. */
+enum { HS_LOSS_SCALE_STATE = 4 };
+typedef struct hs_loss_scale {
+    double *state;                /* [HS_LOSS_SCALE_STATE] f64 on the device, 8-byte aligned */
+    double growth, backoff;       /* powers of two; growth >= 1, 0 < backoff <= 1; 2, 0.5 */
+    double min_scale, max_scale;  /* powers of two, 0 < min_scale <= max_scale <= 2^126; 1, 2^24 */
+    int32_t growth_interval;      /* >= 1; 2000 */
+    int32_t reserved;             /* must be 0 */
+} hs_loss_scale;                  /* 48 bytes */
+int32_t hs_ppo_loss_scaled(hs_sim *sim, const hs_ppo_request *req, const double *loss_scale_state);
+int32_t hs_ppo_loss_scaled_async(hs_sim *sim, void *hip_stream, const hs_ppo_request *req, const double *loss_scale_state);
+int32_t hs_twohot_value_scaled(hs_sim *sim, const hs_twohot_request *req, const double *loss_scale_state);
+int32_t hs_twohot_value_scaled_async(hs_sim *sim, void *hip_stream, const hs_twohot_request *req, const double *loss_scale_state);
+int32_t hs_adam_step_scaled(hs_sim *sim, const hs_adam_request *req, const hs_loss_scale *scale);
+int32_t hs_adam_step_scaled_async(hs_sim *sim, void *hip_stream, const hs_adam_request *req, const hs_loss_scale *scale);
+
 /* The minibatch gather: cutting shuffled sequences out of a rollout for one minibatch of the update, every field of the
  * rollout in one kernel (csrc/hs_k_gather.h).  The reference trains on back-propagation-through-time chunks
  * (scripts/jax_train.py: steps_per_update = 40, num_bptt_chunks = 8, num_mini_batches = 2); madrona_learn's own gather is

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <limits>
 #include <memory>
 #include <type_traits>
 
@@ -39,6 +40,7 @@
 #include "hs_k_pack_routed.h"             // likewise: emitted where launch_pack_routed (after launch_league) names it
 #include "hs_k_sample_routed.h"           // likewise: emitted where launch_sample_routed (after launch_pack_routed) names it
 #include "hs_k_attend.h"                  // likewise: emitted where launch_attend (after launch_gae_grouped) names them
+#include "hs_k_loss_scale.h"              // likewise: emitted where launch_adam_scaled (after launch_behaviour) names them; it includes hs_k_adam.h itself
 #include "hs_k_adam.h"
 
 namespace {
@@ -107,7 +109,7 @@ struct hs_sim {
     float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
     float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
     float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
-    double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]
+    double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]; hs_adam_step_scaled: then the snapshot of the loss-scale state, [kLossScaleWorkspace]
     double *episode_partials = nullptr;    // hs_episode_stats: the sums of each workgroup, [episode_grid][HS_EPISODE_STATS]
     double *behaviour_partials = nullptr;  // hs_behaviour_stats: the sums of each workgroup, [behaviour_grid][HS_BEHAVIOUR_STATS]
     int32_t *league_step = nullptr;        // hs_league_step: the counts of the step and its malformed worlds, [kLeagueMaxBins + 1], zero between calls
@@ -348,13 +350,24 @@ struct Check {
         return dtype_ok(d) ? HS_OK : bad(std::string(what) + " dtype must be HS_DTYPE_F32, HS_DTYPE_BF16 or HS_DTYPE_F16");
     }
     // no output overlaps an input or an earlier output
-    int disjoint(std::initializer_list<ByteRange> in, std::initializer_list<ByteRange> out) const {
-        for (const ByteRange *o = out.begin(); o != out.end(); ++o) {
-            for (const ByteRange &x : in)
-                if (overlap(*o, x)) return bad(std::string(o->name) + " overlaps " + x.name);
-            for (const ByteRange *e = out.begin(); e != o; ++e)
+    int disjoint(const ByteRange *in, size_t nin, const ByteRange *out, size_t nout) const {
+        for (const ByteRange *o = out; o != out + nout; ++o) {
+            for (const ByteRange *x = in; x != in + nin; ++x)
+                if (overlap(*o, *x)) return bad(std::string(o->name) + " overlaps " + x->name);
+            for (const ByteRange *e = out; e != o; ++e)
                 if (overlap(*o, *e)) return bad(std::string(o->name) + " overlaps " + e->name);
         }
+        return HS_OK;
+    }
+    int disjoint(std::initializer_list<ByteRange> in, std::initializer_list<ByteRange> out) const {
+        return disjoint(in.begin(), in.size(), out.begin(), out.size());
+    }
+    // the same over a request's ranges as one list, the first `nin` of them its inputs
+    int disjoint(const std::vector<ByteRange> &v, size_t nin) const { return disjoint(v.data(), nin, v.data() + nin, v.size() - nin); }
+    // `x`, a trailing argument, overlaps none of them
+    int apart(const ByteRange &x, const std::vector<ByteRange> &v) const {
+        for (const ByteRange &y : v)
+            if (overlap(x, y)) return bad(std::string(x.name) + " overlaps " + y.name);
         return HS_OK;
     }
     // the learner calls read what a finished hs_init / step left
@@ -563,6 +576,18 @@ static_assert(sizeof(hs_ppo_request) == 160 && offsetof(hs_ppo_request, n) == 72
               offsetof(hs_ppo_request, clip_coef) == 116 && offsetof(hs_ppo_request, grad_logits) == 136 && offsetof(hs_ppo_request, stats) == 152,
               "hs_ppo_request layout (gpu_hideseek/ppo_loss.py mirrors it)");
 
+// The bytes a request whose counts, strides and dtypes have passed reads (the first *nin ranges) and writes.
+std::vector<ByteRange> ppo_ranges(const hs_ppo_request *r, int L, size_t *nin) {
+    const uintptr_t lsize = elem_size(r->logits_dtype), gsize = elem_size(r->grad_dtype), vsize = elem_size(r->value_dtype), n = (uintptr_t)r->n;
+    *nin = 9;
+    return {range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + L) * lsize), range("action", r->action, n * HS_SAMPLE_HEADS * 4),
+            range("old_log_prob", r->old_log_prob, n * 4), range("advantage", r->advantage, n * 4),
+            range("adv_moments", r->adv_moments, HS_GAE_MOMENTS * sizeof(double)), range("mask", r->mask, n * 4),
+            range("value", r->value, n * vsize), range("returns", r->returns, n * 4), range("old_value", r->old_value, n * 4),
+            range("grad_logits", r->grad_logits, ((n - 1) * (uintptr_t)r->grad_stride + L) * gsize),
+            range("grad_value", r->grad_value, n * vsize), range("stats", r->stats, HS_PPO_STATS * sizeof(double))};
+}
+
 int check_ppo(hs_sim *s, const hs_ppo_request *r) {
     const Check c{"hs_ppo_loss"};
     if (!r) return c.bad("null request");
@@ -591,19 +616,15 @@ int check_ppo(hs_sim *s, const hs_ppo_request *r) {
     if (!aligned(lsize, {r->logits}) || !aligned(gsize, {r->grad_logits}) || !aligned(vsize, {r->value, r->grad_value}))
         return c.bad("logits, grad_logits, value and grad_value must be aligned to their element size");
     if (!aligned(8, {r->adv_moments, r->stats})) return c.bad("adv_moments and stats must be 8-byte aligned");
-    const uintptr_t n = (uintptr_t)r->n;
-    HS_TRY(c.disjoint({range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + L) * lsize), range("action", r->action, n * HS_SAMPLE_HEADS * 4),
-                       range("old_log_prob", r->old_log_prob, n * 4), range("advantage", r->advantage, n * 4),
-                       range("adv_moments", r->adv_moments, HS_GAE_MOMENTS * sizeof(double)), range("mask", r->mask, n * 4),
-                       range("value", r->value, n * vsize), range("returns", r->returns, n * 4), range("old_value", r->old_value, n * 4)},
-                      {range("grad_logits", r->grad_logits, ((n - 1) * (uintptr_t)r->grad_stride + L) * gsize),
-                       range("grad_value", r->grad_value, n * vsize), range("stats", r->stats, HS_PPO_STATS * sizeof(double))}));
+    size_t nin;
+    const std::vector<ByteRange> v = ppo_ranges(r, L, &nin);
+    HS_TRY(c.disjoint(v, nin));
     return c.handle_ready(s);
 }
 
 // With a mask the count of the active samples, then one k_ppo over the samples (the request has passed check_ppo), then
 // the fixed-order sum of the statistics.
-int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
+hs::PpoArgs ppo_args(hs_sim *s, const hs_ppo_request *r) {
     hs::PpoArgs a = {};
     a.logits = r->logits; a.action = r->action; a.oldLogProb = r->old_log_prob; a.advantage = r->advantage;
     a.advMoments = r->adv_moments; a.mask = r->mask; a.value = r->value; a.returns = r->returns; a.oldValue = r->old_value;
@@ -612,6 +633,10 @@ int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
     a.L = pack_buckets(r->buckets, &a.bucketK, &a.bucketOff);
     a.n = r->n; a.stride = r->logits_stride; a.gradStride = r->grad_stride; a.countParts = hs::ppo_count_grid(a.n);
     a.clip = r->clip_coef; a.valueCoef = r->value_loss_coef; a.entropyCoef = r->entropy_coef; a.gradScale = r->grad_scale;
+    return a;
+}
+int launch_ppo(hs_sim *s, hipStream_t strm, const hs_ppo_request *r) {
+    const hs::PpoArgs a = ppo_args(s, r);
     const dim3 grid(hs::ppo_grid(a.n)), blk(hs::kPpoThreads);
     if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), blk, 0, strm, r->mask, a.n, s->ppo_counts);
     with_elem(r->logits_dtype, [&](auto tl) {
@@ -690,6 +715,17 @@ static_assert(sizeof(hs_twohot_request) == 96 && offsetof(hs_twohot_request, n) 
               offsetof(hs_twohot_request, lo) == 40 && offsetof(hs_twohot_request, value_dtype) == 56 && offsetof(hs_twohot_request, value) == 72 &&
               offsetof(hs_twohot_request, stats) == 88, "hs_twohot_request layout (gpu_hideseek/value_head.py mirrors it)");
 
+// The bytes a request whose counts, strides and dtypes have passed reads (the first *nin ranges) and writes.
+std::vector<ByteRange> twohot_ranges(const hs_twohot_request *r, size_t *nin) {
+    const uintptr_t lsize = elem_size(r->logits_dtype), gsize = elem_size(r->grad_dtype), vsize = elem_size(r->value_dtype);
+    const uintptr_t n = (uintptr_t)r->n, B = (uintptr_t)r->bins;
+    *nin = 3;
+    return {range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + B) * lsize), range("returns", r->returns, n * 4),
+            range("mask", r->mask, n * 4),
+            range("value", r->value, n * vsize), range("grad_logits", r->grad_logits, ((n - 1) * (uintptr_t)r->grad_stride + B) * gsize),
+            range("stats", r->stats, HS_TWOHOT_STATS * sizeof(double))};
+}
+
 int check_twohot(hs_sim *s, const hs_twohot_request *r) {
     const Check c{"hs_twohot_value"};
     if (!r) return c.bad("null request");
@@ -711,22 +747,24 @@ int check_twohot(hs_sim *s, const hs_twohot_request *r) {
     if (!aligned(lsize, {r->logits}) || !aligned(gsize, {r->grad_logits}) || !aligned(vsize, {r->value}))
         return c.bad("logits, grad_logits and value must be aligned to their element size");
     if (!aligned(8, {r->stats})) return c.bad("stats must be 8-byte aligned");
-    const uintptr_t n = (uintptr_t)r->n;
-    HS_TRY(c.disjoint({range("logits", r->logits, ((n - 1) * (uintptr_t)r->logits_stride + B) * lsize), range("returns", r->returns, n * 4),
-                       range("mask", r->mask, n * 4)},
-                      {range("value", r->value, n * vsize), range("grad_logits", r->grad_logits, ((n - 1) * (uintptr_t)r->grad_stride + B) * gsize),
-                       range("stats", r->stats, HS_TWOHOT_STATS * sizeof(double))}));
+    size_t nin;
+    const std::vector<ByteRange> v = twohot_ranges(r, &nin);
+    HS_TRY(c.disjoint(v, nin));
     return c.handle_ready(s);
 }
 
 // With a mask the count of the active samples, then one k_twohot over the samples (the request has passed
 // check_twohot), then the fixed-order sum of the statistics.
-int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
+hs::TwohotArgs twohot_args(hs_sim *s, const hs_twohot_request *r) {
     hs::TwohotArgs a = {};
     a.logits = r->logits; a.returns = r->returns; a.mask = r->mask; a.value = r->value; a.gradLogits = r->grad_logits;
     a.partials = r->stats ? s->twohot_partials : nullptr; a.counts = s->twohot_counts;
     a.n = r->n; a.stride = r->logits_stride; a.gradStride = r->grad_stride; a.B = r->bins; a.countParts = hs::ppo_count_grid(a.n);
     a.lo = r->lo; a.hi = r->hi; a.lossCoef = r->loss_coef; a.gradScale = r->grad_scale;
+    return a;
+}
+int launch_twohot(hs_sim *s, hipStream_t strm, const hs_twohot_request *r) {
+    const hs::TwohotArgs a = twohot_args(s, r);
     const dim3 grid(hs::twohot_grid(a.n)), blk(hs::kTwThreads);
     if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), dim3(hs::kPpoThreads), 0, strm, r->mask, a.n, s->twohot_counts);
     with_elem(r->logits_dtype, [&](auto tl) {
@@ -1004,6 +1042,13 @@ static_assert(sizeof(hs_adam_request) == 104 && offsetof(hs_adam_request, grads)
               offsetof(hs_adam_request, stats) == 96,
               "hs_adam_request layout (gpu_hideseek/optim.py mirrors it)");
 
+// The bytes a request with an accepted n reads and writes: all of them outputs.
+std::vector<ByteRange> adam_ranges(const hs_adam_request *r) {
+    const uintptr_t bytes = (uintptr_t)r->n * 4;
+    return {range("params", r->params, bytes), range("grads", r->grads, bytes), range("m", r->m, bytes), range("v", r->v, bytes),
+            range("state", r->state, HS_ADAM_STATE * sizeof(double)), range("stats", r->stats, HS_ADAM_STATS * sizeof(double))};
+}
+
 int check_adam(hs_sim *s, const hs_adam_request *r) {
     const Check c{"hs_adam_step"};
     if (!r) return c.bad("null request");
@@ -1022,21 +1067,23 @@ int check_adam(hs_sim *s, const hs_adam_request *r) {
     if (r->weight_decay < 0.f) return c.bad("weight_decay must be at least 0");
     if (!(r->grad_scale > 0.0)) return c.bad("grad_scale must be above 0");
     if (!(r->beta1 >= 0.f && r->beta1 < 1.f) || !(r->beta2 >= 0.f && r->beta2 < 1.f)) return c.bad("beta1 and beta2 must be in [0, 1)");
-    const uintptr_t bytes = (uintptr_t)r->n * 4;
-    HS_TRY(c.disjoint({}, {range("params", r->params, bytes), range("grads", r->grads, bytes), range("m", r->m, bytes), range("v", r->v, bytes),
-                           range("state", r->state, HS_ADAM_STATE * sizeof(double)), range("stats", r->stats, HS_ADAM_STATS * sizeof(double))}));
+    HS_TRY(c.disjoint(adam_ranges(r), 0));
     return c.handle_ready(s);
 }
 
 // k_adam_norm, its partial sums of squares and the snapshot of the state into the workspace, then one k_adam_step over the
 // elements (the request has passed check_adam).
-int launch_adam(hs_sim *s, hipStream_t strm, const hs_adam_request *r) {
+hs::AdamArgs adam_args(hs_sim *s, const hs_adam_request *r) {
     hs::AdamArgs a = {};
     a.p = r->params; a.g = r->grads; a.m = r->m; a.v = r->v; a.ws = s->adam_workspace; a.state = r->state; a.stats = r->stats;
     a.n = (int)r->n; a.nparts = hs::adam_grid(a.n, hs::kAdamMaxGrid); a.zeroGrad = r->zero_grad != 0;
     a.lr = r->lr; a.b1 = r->beta1; a.b2 = r->beta2; a.eps = r->eps; a.wd = r->weight_decay;
     a.omb1 = (float)(1.0 - (double)r->beta1); a.omb2 = (float)(1.0 - (double)r->beta2);
     a.gradScale = r->grad_scale; a.maxNorm = r->max_grad_norm;
+    return a;
+}
+int launch_adam(hs_sim *s, hipStream_t strm, const hs_adam_request *r) {
+    const hs::AdamArgs a = adam_args(s, r);
     const dim3 blk(hs::kAdamThreads);
     hipLaunchKernelGGL(hs::k_adam_norm<>, dim3(a.nparts), blk, 0, strm, (const float *)r->grads, a.n, (const double *)r->state, s->adam_workspace);
     hipLaunchKernelGGL(hs::k_adam_step<>, dim3(hs::adam_grid(a.n, hs::kAdamStepMaxGrid)), blk, 0, strm, a);
@@ -1578,6 +1625,97 @@ int launch_behaviour(hs_sim *s, hipStream_t strm, const hs_behaviour_request *r)
 }
 }  // namespace
 
+// ---- the dynamic loss scale (hs_k_loss_scale.h) ----
+namespace {
+static_assert(HS_LOSS_SCALE_STATE == hs::kLossScaleState, "hs_loss_scale and k_adam_step_scaled agree");
+static_assert(sizeof(hs_loss_scale) == 48 && offsetof(hs_loss_scale, growth) == 8 && offsetof(hs_loss_scale, min_scale) == 24 &&
+              offsetof(hs_loss_scale, growth_interval) == 40 && offsetof(hs_loss_scale, reserved) == 44,
+              "hs_loss_scale layout (gpu_hideseek/optim.py mirrors it)");
+
+// x = 2^k exactly, lo <= x <= hi
+bool power_of_two_in(double x, double lo, double hi) {
+    int k;
+    return std::isfinite(x) && x >= lo && x <= hi && std::frexp(x, &k) == 0.5;
+}
+// The state pointer of a scaled call whose request has passed its own check: the ranges are the request's.
+int check_loss_scale_state(const Check &c, const double *state, const std::vector<ByteRange> &ranges) {
+    if (!state) return c.bad("null loss_scale_state");
+    if (!aligned(8, {state})) return c.bad("loss_scale_state must be 8-byte aligned");
+    return c.apart(range("loss_scale_state", state, HS_LOSS_SCALE_STATE * sizeof(double)), ranges);
+}
+int check_ppo_scaled(hs_sim *s, const hs_ppo_request *r, const double *state) {
+    const Check c{"hs_ppo_loss_scaled"};
+    HS_TRY(check_ppo(s, r));
+    int L;
+    size_t nin;
+    HS_TRY(c.buckets(r->buckets, &L));
+    return check_loss_scale_state(c, state, ppo_ranges(r, L, &nin));
+}
+int check_twohot_scaled(hs_sim *s, const hs_twohot_request *r, const double *state) {
+    const Check c{"hs_twohot_value_scaled"};
+    HS_TRY(check_twohot(s, r));
+    size_t nin;
+    return check_loss_scale_state(c, state, twohot_ranges(r, &nin));
+}
+int check_adam_scaled(hs_sim *s, const hs_adam_request *r, const hs_loss_scale *ls) {
+    const Check c{"hs_adam_step_scaled"};
+    HS_TRY(check_adam(s, r));
+    if (!ls) return c.bad("null loss scale");
+    const double top = std::ldexp(1.0, 126), tiny = std::numeric_limits<double>::denorm_min();
+    if (!power_of_two_in(ls->growth, 1.0, top)) return c.bad("growth must be a power of two, at least 1");
+    if (!power_of_two_in(ls->backoff, tiny, 1.0)) return c.bad("backoff must be a power of two in (0, 1]");
+    if (!power_of_two_in(ls->min_scale, tiny, top) || !power_of_two_in(ls->max_scale, ls->min_scale, top))
+        return c.bad("min_scale and max_scale must be powers of two, 0 < min_scale <= max_scale <= 2^126");
+    if (ls->growth_interval < 1) return c.bad("growth_interval must be at least 1");
+    if (ls->reserved != 0) return c.bad("reserved must be 0");
+    return check_loss_scale_state(c, ls->state, adam_ranges(r));
+}
+
+// launch_ppo with k_ppo_scaled (the request and the state have passed check_ppo_scaled).
+int launch_ppo_scaled(hs_sim *s, hipStream_t strm, const hs_ppo_request *r, const double *state) {
+    const hs::PpoArgs a = ppo_args(s, r);
+    const dim3 grid(hs::ppo_grid(a.n)), blk(hs::kPpoThreads);
+    if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), blk, 0, strm, r->mask, a.n, s->ppo_counts);
+    with_elem(r->logits_dtype, [&](auto tl) {
+        with_optional_elem(r->grad_logits, r->grad_dtype, [&](auto tg) {
+            with_optional_elem(r->value, r->value_dtype, [&](auto tv) {
+                hipLaunchKernelGGL((hs::k_ppo_scaled<decltype(tl), decltype(tg), decltype(tv)>), grid, blk, 0, strm, a, state);
+            });
+        });
+    });
+    if (r->stats) launch_partials_sum<double, hs::kPpoStats, hs::kPpoSumSegs>(strm, s->ppo_partials, hs::ppo_grid(a.n), hs::kPpoStats, r->stats);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+// launch_twohot with k_twohot_scaled.
+int launch_twohot_scaled(hs_sim *s, hipStream_t strm, const hs_twohot_request *r, const double *state) {
+    const hs::TwohotArgs a = twohot_args(s, r);
+    const dim3 grid(hs::twohot_grid(a.n)), blk(hs::kTwThreads);
+    if (r->mask) hipLaunchKernelGGL(hs::k_ppo_count<>, dim3(a.countParts), dim3(hs::kPpoThreads), 0, strm, r->mask, a.n, s->twohot_counts);
+    with_elem(r->logits_dtype, [&](auto tl) {
+        with_optional_elem(r->grad_logits, r->grad_dtype, [&](auto tg) {
+            with_optional_elem(r->value, r->value_dtype, [&](auto tv) {
+                hipLaunchKernelGGL((hs::k_twohot_scaled<decltype(tl), decltype(tg), decltype(tv)>), grid, blk, 0, strm, a, state);
+            });
+        });
+    });
+    if (r->stats) launch_partials_sum<double, hs::kTwStats, hs::kTwSumSegs>(strm, s->twohot_partials, hs::twohot_grid(a.n), hs::kTwStats, r->stats);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+// launch_adam with the two scaled kernels: the norm launch also snapshots the loss-scale state, the step launch updates it.
+int launch_adam_scaled(hs_sim *s, hipStream_t strm, const hs_adam_request *r, const hs_loss_scale *ls) {
+    const hs::AdamArgs a = adam_args(s, r);
+    const hs::LossScaleArgs l = {ls->state, ls->growth, ls->backoff, ls->min_scale, ls->max_scale, (double)ls->growth_interval};
+    const dim3 blk(hs::kAdamThreads);
+    hipLaunchKernelGGL(hs::k_adam_norm_scaled<>, dim3(a.nparts), blk, 0, strm, (const float *)r->grads, a.n, (const double *)r->state,
+                       (const double *)ls->state, s->adam_workspace);
+    hipLaunchKernelGGL(hs::k_adam_step_scaled<>, dim3(hs::adam_grid(a.n, hs::kAdamStepMaxGrid)), blk, 0, strm, a, l);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1726,7 +1864,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->embed_partials, (size_t)hs::kRowsMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
     HS_ALLOC(s->lstm_partials, (size_t)hs::kRowsMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
     HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
-    HS_ALLOC(s->adam_workspace, hs::kAdamWorkspace);
+    HS_ALLOC(s->adam_workspace, hs::kLossScaleWorkspace);
     HS_ALLOC(s->episode_partials, (size_t)hs::episode_grid((int)N, A) * hs::kEpiStats);
     HS_ALLOC(s->behaviour_partials, (size_t)hs::behaviour_grid((int)N) * hs::kBehStats);
     HS_ALLOC(s->league_step, hs::kLeagueMaxBins + 1);
@@ -2049,6 +2187,18 @@ int32_t hs_ppo_loss(hs_sim *s, const hs_ppo_request *req) { return call_blocking
 int32_t hs_ppo_loss_async(hs_sim *s, void *hip_stream, const hs_ppo_request *req) { return call_async(s, hip_stream, check_ppo, launch_ppo, req); }
 int32_t hs_twohot_value(hs_sim *s, const hs_twohot_request *req) { return call_blocking(s, check_twohot, launch_twohot, req); }
 int32_t hs_twohot_value_async(hs_sim *s, void *hip_stream, const hs_twohot_request *req) { return call_async(s, hip_stream, check_twohot, launch_twohot, req); }
+int32_t hs_ppo_loss_scaled(hs_sim *s, const hs_ppo_request *req, const double *loss_scale_state) {
+    return call_blocking(s, check_ppo_scaled, launch_ppo_scaled, req, loss_scale_state);
+}
+int32_t hs_ppo_loss_scaled_async(hs_sim *s, void *hip_stream, const hs_ppo_request *req, const double *loss_scale_state) {
+    return call_async(s, hip_stream, check_ppo_scaled, launch_ppo_scaled, req, loss_scale_state);
+}
+int32_t hs_twohot_value_scaled(hs_sim *s, const hs_twohot_request *req, const double *loss_scale_state) {
+    return call_blocking(s, check_twohot_scaled, launch_twohot_scaled, req, loss_scale_state);
+}
+int32_t hs_twohot_value_scaled_async(hs_sim *s, void *hip_stream, const hs_twohot_request *req, const double *loss_scale_state) {
+    return call_async(s, hip_stream, check_twohot_scaled, launch_twohot_scaled, req, loss_scale_state);
+}
 int32_t hs_entity_encode(hs_sim *s, const hs_entity_encode_request *req) { return call_blocking(s, check_embed, launch_embed, req); }
 int32_t hs_entity_encode_async(hs_sim *s, void *hip_stream, const hs_entity_encode_request *req) { return call_async(s, hip_stream, check_embed, launch_embed, req); }
 int32_t hs_entity_encode_backward(hs_sim *s, const hs_entity_encode_backward_request *req) { return call_blocking(s, check_embed_bwd, launch_embed_bwd, req); }
@@ -2063,6 +2213,12 @@ int32_t hs_dense_norm_act_backward(hs_sim *s, const hs_dense_norm_act_backward_r
 int32_t hs_dense_norm_act_backward_async(hs_sim *s, void *hip_stream, const hs_dense_norm_act_backward_request *req) { return call_async(s, hip_stream, check_dense_bwd, launch_dense_bwd, req); }
 int32_t hs_adam_step(hs_sim *s, const hs_adam_request *req) { return call_blocking(s, check_adam, launch_adam, req); }
 int32_t hs_adam_step_async(hs_sim *s, void *hip_stream, const hs_adam_request *req) { return call_async(s, hip_stream, check_adam, launch_adam, req); }
+int32_t hs_adam_step_scaled(hs_sim *s, const hs_adam_request *req, const hs_loss_scale *ls) {
+    return call_blocking(s, check_adam_scaled, launch_adam_scaled, req, ls);
+}
+int32_t hs_adam_step_scaled_async(hs_sim *s, void *hip_stream, const hs_adam_request *req, const hs_loss_scale *ls) {
+    return call_async(s, hip_stream, check_adam_scaled, launch_adam_scaled, req, ls);
+}
 int32_t hs_gather_sequences(hs_sim *s, const hs_gather_request *req) { return call_blocking(s, check_gather, launch_gather, req); }
 int32_t hs_gather_sequences_async(hs_sim *s, void *hip_stream, const hs_gather_request *req) { return call_async(s, hip_stream, check_gather, launch_gather, req); }
 int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call_blocking(s, check_episode, launch_episode, req); }

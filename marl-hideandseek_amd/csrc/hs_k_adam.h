@@ -73,8 +73,10 @@ HSD void adam_store(float *p, int64_t i, int n, const float (&x)[kAdamVec]) {
     }
 }
 
-template <int kThreads = kAdamThreads>
-__global__ __launch_bounds__(kThreads) void k_adam_norm(const float *__restrict__ g, int n, const double *__restrict__ state, double *__restrict__ ws) {
+// k_adam_norm's work: the workgroup's partial into ws[blockIdx.x], then snapshot(lane) in workgroup 0.  (A function of its
+// own so that the loss-scaled step, hs_k_loss_scale.h, takes a second snapshot beside the same sum.)
+template <int kThreads, typename Snapshot>
+HSD void adam_norm(const float *g, int n, double *ws, const Snapshot snapshot) {
     __shared__ double red[kThreads];
     const int tid = threadIdx.x;
     const int64_t quads = ((int64_t)n + kAdamVec - 1) / kAdamVec, stride = (int64_t)gridDim.x * kThreads;
@@ -92,11 +94,19 @@ __global__ __launch_bounds__(kThreads) void k_adam_norm(const float *__restrict_
         for (int l = 1; l < kThreads; ++l) s = s + red[l];
         ws[blockIdx.x] = s;
     }
-    if (blockIdx.x == 0 && tid < kAdamState) ws[kAdamMaxGrid + tid] = state[tid];
+    if (blockIdx.x == 0) snapshot(tid);
 }
 
 template <int kThreads = kAdamThreads>
-__global__ __launch_bounds__(kThreads) void k_adam_step(AdamArgs a) {
+__global__ __launch_bounds__(kThreads) void k_adam_norm(const float *__restrict__ g, int n, const double *__restrict__ state, double *__restrict__ ws) {
+    adam_norm<kThreads>(g, n, ws, [=](int tid) { if (tid < kAdamState) ws[kAdamMaxGrid + tid] = state[tid]; });
+}
+
+// k_adam_step's work with scale() where the header has grad_scale: the norm from the partials, the update of the
+// workgroup's elements, and by lane 0 of workgroup 0 the new state, the statistics and then after(skipped).  (The
+// loss-scaled step, hs_k_loss_scale.h, gives grad_scale / S and the update of the loss-scale state.)
+template <int kThreads, typename Scale, typename After>
+HSD void adam_update(const AdamArgs &a, const Scale scale, const After after) {
     __shared__ double part[kAdamMaxGrid];
     const int tid = threadIdx.x;
     if (tid < a.nparts) part[tid] = a.ws[tid];
@@ -104,10 +114,11 @@ __global__ __launch_bounds__(kThreads) void k_adam_step(AdamArgs a) {
     double sum = part[0];                                                      // every lane reads the same word: a broadcast
     for (int k = 1; k < a.nparts; ++k) sum = sum + part[k];
     const double p1 = a.ws[kAdamMaxGrid], p2 = a.ws[kAdamMaxGrid + 1], t = a.ws[kAdamMaxGrid + 2], skips = a.ws[kAdamMaxGrid + 3];
-    const double gnorm = a.gradScale * sqrt(sum);
+    const double gradScale = scale();
+    const double gnorm = gradScale * sqrt(sum);
     const bool skipped = !__builtin_isfinite(gnorm);
     const double clip = skipped ? 0.0 : (a.maxNorm > 0.0 && gnorm > a.maxNorm) ? a.maxNorm / gnorm : 1.0;
-    const float s = (float)(a.gradScale * clip);
+    const float s = (float)(gradScale * clip);
     const double p1n = p1 * (double)a.b1, p2n = p2 * (double)a.b2;
     const float bc1 = (float)(1.0 - p1n), bc2 = (float)(1.0 - p2n);
     const bool decay = a.wd != 0.f;
@@ -137,7 +148,13 @@ __global__ __launch_bounds__(kThreads) void k_adam_step(AdamArgs a) {
         if (skipped) a.state[3] = skips + 1.0;
         else { a.state[0] = p1n; a.state[1] = p2n; a.state[2] = t + 1.0; }
         if (a.stats) { a.stats[0] = gnorm; a.stats[1] = clip; a.stats[2] = skipped ? 1.0 : 0.0; a.stats[3] = skipped ? t : t + 1.0; }
+        after(skipped);
     }
+}
+
+template <int kThreads = kAdamThreads>
+__global__ __launch_bounds__(kThreads) void k_adam_step(AdamArgs a) {
+    adam_update<kThreads>(a, [&] { return a.gradScale; }, [](bool) {});
 }
 
 }  // namespace hs

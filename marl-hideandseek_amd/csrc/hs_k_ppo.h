@@ -108,8 +108,9 @@ HSD float ppo_stored(bool on, float y) { return on && y != 0.f ? y : 0.f; }
 // TL, TG, TV: the element types of logits, grad_logits (PpoAbsent: none) and value / grad_value (PpoAbsent: no value term):
 // what changes the instructions of a block of samples is decided at compile time.  The mask, old_value, adv_moments and
 // the statistics are each a wave-uniform branch around one load or a handful of additions.
-template <typename TL, typename TG, typename TV>
-__global__ __launch_bounds__(kPpoThreads) void k_ppo(PpoArgs a) {
+// (The kernel's work with scale() where the header has grad_scale: k_ppo_scaled, hs_k_loss_scale.h, gives grad_scale * S.)
+template <typename TL, typename TG, typename TV, typename Scale>
+HSD void ppo_samples(const PpoArgs &a, const Scale scale) {
     __shared__ PpoImage im;
     constexpr bool kGrad = !std::is_same<TG, PpoAbsent>::value, kValue = !std::is_same<TV, PpoAbsent>::value;
     const TL *logits = (const TL *)a.logits;
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo(PpoArgs a) {
         }
         cnt = im.count[0];
     }
-    const float w = a.gradScale / (float)cnt;
+    const float w = scale() / (float)cnt;
     float mean = 0.f, stdEps = 1.f;
     if (a.advMoments) ppo_normaliser(a.advMoments, mean, stdEps);
     const float lo = 1.f - a.clip, hi = 1.f + a.clip;
@@ -243,6 +244,11 @@ __global__ __launch_bounds__(kPpoThreads) void k_ppo(PpoArgs a) {
             a.partials[(size_t)blockIdx.x * kPpoStats + tid] = s;
         }
     }
+}
+
+template <typename TL, typename TG, typename TV>
+__global__ __launch_bounds__(kPpoThreads) void k_ppo(PpoArgs a) {
+    ppo_samples<TL, TG, TV>(a, [&] { return a.gradScale; });
 }
 
 }  // namespace hs

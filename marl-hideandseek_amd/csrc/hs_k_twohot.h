@@ -68,8 +68,9 @@ HSD float tw_add_xor(float a, int k) { return a + __shfl_xor(a, k, kTwLanesPerRo
 
 // TL, TG, TV: the element types of logits, grad_logits (PpoAbsent: none) and value (PpoAbsent: none).  returns, mask and
 // the statistics are wave-uniform branches.
-template <typename TL, typename TG, typename TV>
-__global__ __launch_bounds__(kTwThreads) void k_twohot(TwohotArgs a) {
+// (The kernel's work with scale() where the header has grad_scale: k_twohot_scaled, hs_k_loss_scale.h, gives grad_scale * S.)
+template <typename TL, typename TG, typename TV, typename Scale>
+HSD void twohot_samples(const TwohotArgs &a, const Scale scale) {
     __shared__ TwImage im;
     constexpr bool kGrad = !std::is_same<TG, PpoAbsent>::value, kValue = !std::is_same<TV, PpoAbsent>::value;
     constexpr int kPerL = 16 / (int)sizeof(TL);
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(kTwThreads) void k_twohot(TwohotArgs a) {
         }
         cnt = im.count[0];
     }
-    const float w = a.gradScale / (float)cnt;
+    const float w = scale() / (float)cnt;
     const float lo = a.lo, hi = a.hi, step = (hi - lo) / (float)(B - 1);
     double sCe = 0.0, sSq = 0.0, sV = 0.0, sR = 0.0, sR2 = 0.0, sN = 0.0;
 
@@ -225,6 +226,11 @@ __global__ __launch_bounds__(kTwThreads) void k_twohot(TwohotArgs a) {
             a.partials[(size_t)blockIdx.x * kTwStats + tid] = s;
         }
     }
+}
+
+template <typename TL, typename TG, typename TV>
+__global__ __launch_bounds__(kTwThreads) void k_twohot(TwohotArgs a) {
+    twohot_samples<TL, TG, TV>(a, [&] { return a.gradScale; });
 }
 
 }  // namespace hs

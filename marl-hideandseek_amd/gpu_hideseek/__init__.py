@@ -225,7 +225,7 @@ class HideAndSeekSimulator:
 
     def ppo_loss(self, logits, action, old_log_prob, advantage, *, buckets=(5, 5, 5, 2, 2), adv_moments=None, mask=None, value=None,
                  returns=None, old_value=None, clip_coef=0.2, value_loss_coef=0.5, entropy_coef=0.01, grad_scale=1.0,
-                 grad_logits=True, grad_value=None, stats=True, grad_dtype=None, stream=None):
+                 grad_logits=True, grad_value=None, stats=True, grad_dtype=None, loss_scale=None, stream=None):
         """The PPO loss of a minibatch and its gradients in one kernel (gpu_hideseek.ppo_loss; hs_ppo_loss, whose header
         comment states the arithmetic: IEEE f32 in a fixed order).  Over the n = logits.shape[0] samples: `logits`
         [n, W >= sum(buckets)] (float32, bfloat16 or float16, contiguous in the last dimension: pass logits.detach()),
@@ -234,17 +234,19 @@ class HideAndSeekSimulator:
         `returns` [n] float32 and, for the clipped value loss, `old_value` [n] float32.  `grad_logits`, `grad_value` and
         `stats` are each True (a new tensor: grad_logits shaped like `logits` in `grad_dtype`, by default the logits'
         dtype; grad_value like `value`; stats [7] float64), a preallocated tensor or None; grad_value=None means True
-        with a value.  A bucket masked with -inf and an inactive sample get gradients of exactly 0.  stream=None blocks;
+        with a value.  A bucket masked with -inf and an inactive sample get gradients of exactly 0.  With `loss_scale`,
+        the float64 [4] state of an optim.LossScale, the gradients (not the stats) are multiplied by its scale, read on
+        the device (hs_ppo_loss_scaled).  stream=None blocks;
         a torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {name: tensor} of what was
         written, plus "coefficients" for ppo_loss.attach / stats_to_metrics."""
         from . import ppo_loss as _ppo_loss
         return _ppo_loss.compute(self, logits, action, old_log_prob, advantage, stream, buckets=buckets, adv_moments=adv_moments,
                                  mask=mask, value=value, returns=returns, old_value=old_value, clip_coef=clip_coef,
                                  value_loss_coef=value_loss_coef, entropy_coef=entropy_coef, grad_scale=grad_scale,
-                                 grad_logits=grad_logits, grad_value=grad_value, stats=stats, grad_dtype=grad_dtype)
+                                 grad_logits=grad_logits, grad_value=grad_value, stats=stats, grad_dtype=grad_dtype, loss_scale=loss_scale)
 
     def value_head(self, logits, returns=None, *, bins=255, lo=-20.0, hi=20.0, mask=None, value=True, grad_logits=None, stats=None,
-                   loss_coef=1.0, grad_scale=1.0, grad_dtype=None, value_dtype=None, stream=None):
+                   loss_coef=1.0, grad_scale=1.0, grad_dtype=None, value_dtype=None, loss_scale=None, stream=None):
         """The two-hot symlog critic head in one kernel (gpu_hideseek.value_head; hs_twohot_value, whose header comment
         states the arithmetic: IEEE f32 in a fixed order).  Over the n = logits.shape[0] samples: `logits`
         [n, W >= bins] (float32, bfloat16 or float16, contiguous in the last dimension: pass logits.detach()) are the
@@ -256,13 +258,14 @@ class HideAndSeekSimulator:
         ppo_loss divides by, so the two gradients add.  Each output is True (allocated: value in `value_dtype` and
         grad_logits in `grad_dtype`, by default the logits' dtype), a preallocated tensor (for value a slot buf[t] of a
         [T, rows] buffer will do) or None; value defaults to True, grad_logits and stats to True exactly when returns
-        are given.  Active samples must hold finite logits and returns that are not NaN.  stream=None blocks; a
+        are given.  Active samples must hold finite logits and returns that are not NaN.  With `loss_scale`, the float64
+        [4] state of an optim.LossScale, grad_logits is multiplied by its scale (hs_twohot_value_scaled).  stream=None blocks; a
         torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns {name: tensor} of what was
         written, plus "coefficients" for value_head.attach."""
         from . import value_head as _value_head
         return _value_head.compute(self, logits, returns, stream, bins=bins, lo=lo, hi=hi, mask=mask, value=value,
                                    grad_logits=grad_logits, stats=stats, loss_coef=loss_coef, grad_scale=grad_scale,
-                                   grad_dtype=grad_dtype, value_dtype=value_dtype)
+                                   grad_dtype=grad_dtype, value_dtype=value_dtype, loss_scale=loss_scale)
 
     def encode_entities(self, rows, params, *, embed_dim=64, eps=1e-6, slope=0.01, features=True, argmax=None, dtype=None, stream=None):
         """The entity encoder in one kernel (gpu_hideseek.entity_encoder; hs_entity_encode, whose header comment states
@@ -348,19 +351,21 @@ class HideAndSeekSimulator:
         return _att.compute_backward(self, qkv, key_mask, grad_out, stream, grad_qkv=grad_qkv)
 
     def adam_step(self, params, grads, m, v, state, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=5.0, grad_scale=1.0,
-                  zero_grad=True, stats=True, stream=None):
+                  zero_grad=True, stats=True, loss_scale=None, stream=None):
         """The clip by the global gradient norm and one Adam step over flat buffers in two kernels (gpu_hideseek.optim;
         hs_adam_step, whose header comment states the arithmetic: the norm in float64 and the update in IEEE f32, both in a
         fixed order).  `params`, `grads`, `m` and `v` are float32 [n], contiguous, 16-byte aligned and disjoint, updated in
         place; `state` is float64 [4] = beta1^t, beta2^t, t, skipped steps (optim.fresh_state()).  The gradients are taken as
         grads * grad_scale and scaled by max_grad_norm / norm when their norm exceeds max_grad_norm (<= 0 or None: no
         clip); a step whose norm is not finite changes nothing but the skip count.  With zero_grad the gradients are +0
-        afterwards.  stats [4] float64 = norm, clip factor, skipped, t is True (allocated), a tensor or None.  stream=None
+        afterwards.  stats [4] float64 = norm, clip factor, skipped, t is True (allocated), a tensor or None.  With
+        `loss_scale`, an optim.LossScale, the gradients are also divided by its scale, an overflow is skipped and the
+        scale adjusted on the device (hs_adam_step_scaled).  stream=None
         blocks; a torch.cuda.Stream or raw handle enqueues there without synchronising.  The same inputs give the same
         bits on every call.  Returns {"stats": tensor} or {}.  optim.Adam is the torch optimiser built on this call."""
         from . import optim as _optim
         return _optim.compute(self, params, grads, m, v, state, stream, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                              max_grad_norm=max_grad_norm, grad_scale=grad_scale, zero_grad=zero_grad, stats=stats)
+                              max_grad_norm=max_grad_norm, grad_scale=grad_scale, zero_grad=zero_grad, stats=stats, loss_scale=loss_scale)
 
     def gather_sequences(self, index, fields, *, chunks, chunk_steps, rows, bad=None, stream=None):
         """Cut the m sequences `index` (int32 [m] on the device; id = chunk * rows + row) out of a rollout of `chunks` x

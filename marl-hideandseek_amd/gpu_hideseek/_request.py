@@ -149,6 +149,18 @@ def _vector(name, t, n, dev, dtypes, kind="a torch tensor"):
     _tensor(name, t, [(n,), (n, 1)], dtypes, dev, kind)
 
 
+LOSS_SCALE_STATE = 4      # HS_LOSS_SCALE_STATE: S, good steps since S last changed, backoffs, growths
+
+
+def _loss_scale_input(loss_scale, dev):
+    """[("loss_scale", tensor)] for the inputs of a request, or [] without one: the state of optim.LossScale, float64
+    [LOSS_SCALE_STATE], contiguous (8-byte aligned with that)."""
+    if loss_scale is None:
+        return []
+    _tensor("loss_scale", loss_scale, (LOSS_SCALE_STATE,), ("float64",), dev, "None or a torch tensor", align=8)
+    return [("loss_scale", loss_scale)]
+
+
 def _overlap(a, b):
     """Whether the storage ranges of two tensors intersect."""
     def span(t):

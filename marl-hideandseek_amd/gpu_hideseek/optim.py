@@ -23,14 +23,20 @@ moved by its momentum (and its moments decay), where torch skips a parameter who
 norm is not finite is skipped as a whole (nothing but the skip count changes; the gradients are still zeroed); the clip
 is optax's (g * max_norm / norm when norm > max_norm), not clip_grad_norm_'s max_norm / (norm + 1e-6).
 
+The dynamic loss scale of float16 training (LossScale; hs_adam_step_scaled, csrc/hs_k_loss_scale.h): a scale S on the
+device that the two loss kernels multiply their gradients by (ppo_loss and value_head take LossScale.state as
+loss_scale=) and that Adam(..., loss_scale=LossScale(device)) divides out again; a step whose norm overflows is skipped
+and halves S, growth_interval good steps in a row double it.  Nothing of it reads the device from the host.  The rule is
+torch.cuda.amp.GradScaler's and flax's DynamicScale's, the project's statement of it.
+
 Not part of this module: parameters spread over several devices, the reduction of gradients between shards (there is no
-ShardedSimulator form), and a bfloat16 / float16 shadow copy of the weights (the modules cast their weights inside the
-autograd graph).
+ShardedSimulator form), a bfloat16 / float16 shadow copy of the weights (the modules cast their weights inside the
+autograd graph), and a loss scale per parameter group.
 """
 import ctypes as C
 import math
 
-from ._request import _OUTPUT, _above_zero, _disjoint, _finite, _run, _tensor
+from ._request import LOSS_SCALE_STATE, _OUTPUT, _above_zero, _disjoint, _finite, _loss_scale_input, _run, _tensor
 
 ALIGN = 16                # bytes: params, grads, m and v
 PAD = 64                  # elements: every parameter of a flat buffer starts at a multiple of it
@@ -47,6 +53,92 @@ class HsAdamRequest(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("lr", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("max_grad_norm", C.c_double),
                 ("grad_scale", C.c_double), ("zero_grad", C.c_int32), ("state", C.c_void_p), ("stats", C.c_void_p)]
+
+
+class HsLossScale(C.Structure):
+    """hs_loss_scale (include/hideseek.h)."""
+    _fields_ = [("state", C.c_void_p), ("growth", C.c_double), ("backoff", C.c_double), ("min_scale", C.c_double), ("max_scale", C.c_double),
+                ("growth_interval", C.c_int32), ("reserved", C.c_int32)]
+
+
+def _power_of_two(name, x, lo, hi, bounds):
+    """x as a float: 2^k exactly and in [lo, hi]; `bounds` is how the message names the range."""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(float(x)) or not lo <= float(x) <= hi or math.frexp(float(x))[0] != 0.5:
+        raise ValueError(f"{name} must be a power of two, {bounds}, got {x!r}")
+    return float(x)
+
+
+LOSS_SCALE_DEFAULTS = dict(init_scale=2.0 ** 16, growth=2.0, backoff=0.5, growth_interval=2000, min_scale=1.0, max_scale=2.0 ** 24)
+LOSS_SCALE_TOP = 2.0 ** 126           # the largest factor and bound hs_loss_scale takes
+
+
+def loss_scale_settings(**kw):
+    """LossScale's keywords, the missing ones from LOSS_SCALE_DEFAULTS, as checked floats (growth_interval an int):
+    powers of two in their ranges.  Raises ValueError; nothing of the device is touched."""
+    unknown = sorted(set(kw) - set(LOSS_SCALE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"unknown loss scale settings {unknown}: expected some of {sorted(LOSS_SCALE_DEFAULTS)}")
+    s = dict(LOSS_SCALE_DEFAULTS, **kw)
+    tiny, top = 5e-324, LOSS_SCALE_TOP
+    out = {"growth": _power_of_two("growth", s["growth"], 1.0, top, "at least 1 and at most 2^126"),
+           "backoff": _power_of_two("backoff", s["backoff"], tiny, 1.0, "above 0 and at most 1"),
+           "min_scale": _power_of_two("min_scale", s["min_scale"], tiny, top, "above 0 and at most 2^126")}
+    out["max_scale"] = _power_of_two("max_scale", s["max_scale"], out["min_scale"], top, "at least min_scale and at most 2^126")
+    out["init_scale"] = _power_of_two("init_scale", s["init_scale"], out["min_scale"], out["max_scale"], "in [min_scale, max_scale]")
+    n = s["growth_interval"]
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n < 2 ** 31:
+        raise ValueError(f"growth_interval must be an integer in [1, 2^31), got {n!r}")
+    out["growth_interval"] = n
+    return out
+
+
+class LossScale:
+    """The dynamic loss scale: `state`, float64 [4] on `device` = [S, good steps since S last changed, backoffs so far,
+    growths so far], starting at [init_scale, 0, 0, 0], and the rule's settings.  A step of an Adam that was given this
+    object multiplies S by `backoff` (not below min_scale) when the gradient norm is not finite, and by `growth` (not
+    above max_scale) after `growth_interval` good steps in a row; all of them powers of two, so that scaling is exact.
+    The bounds are settings, not measurements.  Only read() copies to the host."""
+
+    def __init__(self, device, init_scale=2.0 ** 16, growth=2.0, backoff=0.5, growth_interval=2000, min_scale=1.0, max_scale=2.0 ** 24):
+        s = loss_scale_settings(init_scale=init_scale, growth=growth, backoff=backoff, growth_interval=growth_interval, min_scale=min_scale,
+                                max_scale=max_scale)
+        init = s.pop("init_scale")
+        for k, v in s.items():
+            setattr(self, k, v)
+        import torch
+        self.state = torch.tensor([init, 0.0, 0.0, 0.0], dtype=torch.float64, device=device)
+
+    def request(self):
+        """The HsLossScale of a call."""
+        return HsLossScale(self.state.data_ptr(), self.growth, self.backoff, self.min_scale, self.max_scale, self.growth_interval, 0)
+
+    def settings(self):
+        return {k: getattr(self, k) for k in ("growth", "backoff", "growth_interval", "min_scale", "max_scale")}
+
+    def state_dict(self):
+        """{"state": a clone of the state, and the settings}."""
+        return dict(self.settings(), state=self.state.clone())
+
+    def load_state_dict(self, state_dict):
+        """Load what state_dict() returned: the state and the settings."""
+        t = state_dict["state"]
+        if tuple(t.shape) != (LOSS_SCALE_STATE,) or t.dtype != self.state.dtype:
+            raise ValueError(f"the loss scale's state has shape {tuple(t.shape)} and dtype {t.dtype}: expected ({LOSS_SCALE_STATE},), {self.state.dtype}")
+        s = loss_scale_settings(init_scale=state_dict["min_scale"], **{k: state_dict[k] for k in self.settings()})
+        for k in self.settings():
+            setattr(self, k, s[k])
+        self.state.copy_(t)
+
+    def read(self):
+        """{"scale", "good_steps", "backoffs", "growths"} as Python numbers (this copies to the host and so waits)."""
+        s, good, backoffs, growths = self.state.detach().cpu().tolist()
+        return {"scale": s, "good_steps": int(good), "backoffs": int(backoffs), "growths": int(growths)}
+
+
+def _scaler(loss_scale):
+    if loss_scale is not None and not isinstance(loss_scale, LossScale):
+        raise ValueError(f"loss_scale must be None or an optim.LossScale, got {loss_scale!r}")
+    return loss_scale
 
 
 def fresh_state(device=None):
@@ -92,14 +184,16 @@ def _hyper(lr, betas, eps, weight_decay, max_grad_norm, grad_scale):
 
 def request(gpu_id, params, grads, m, v, state, lr=DEFAULTS["lr"], betas=DEFAULTS["betas"], eps=DEFAULTS["eps"],
             weight_decay=DEFAULTS["weight_decay"], max_grad_norm=DEFAULTS["max_grad_norm"], grad_scale=DEFAULTS["grad_scale"], zero_grad=True,
-            stats=True):
+            stats=True, loss_scale=None):
     """Validate one optimiser step on GPU `gpu_id` over the flat float32 tensors params, grads, m and v [n] (contiguous,
     16-byte aligned, no two overlapping) and the float64 state [4] (fresh_state()), allocate stats [4] float64 when given
     as True (None: no statistics), and return ({"stats": tensor} or {}, HsAdamRequest).  max_grad_norm <= 0 or None
-    switches the clip off.  Raises ValueError before the library is involved."""
+    switches the clip off.  `loss_scale` is None or a LossScale, whose state may overlap none of the others (compute then
+    runs hs_adam_step_scaled).  Raises ValueError before the library is involved."""
     import torch
     dev = torch.device("cuda", gpu_id)
     hyper = _hyper(lr, betas, eps, weight_decay, max_grad_norm, grad_scale)
+    _scaler(loss_scale)
     if not isinstance(params, torch.Tensor):
         raise ValueError("params must be a torch tensor")
     if params.dim() != 1 or not 1 <= params.shape[0] < 2 ** 31:
@@ -116,6 +210,7 @@ def request(gpu_id, params, grads, m, v, state, lr=DEFAULTS["lr"], betas=DEFAULT
             arrays.append(("stats", stats))
     else:
         stats = None
+    arrays += _loss_scale_input(None if loss_scale is None else loss_scale.state, dev)
     _disjoint(arrays, [], dev)
     if stats is True:
         stats = torch.empty(STATS, dtype=torch.float64, device=dev)
@@ -127,8 +222,15 @@ def request(gpu_id, params, grads, m, v, state, lr=DEFAULTS["lr"], betas=DEFAULT
 def compute(sim, params, grads, m, v, state, stream=None, **kw):
     """HideAndSeekSimulator.adam_step."""
     res, req = request(sim.gpu_id, params, grads, m, v, state, **kw)
-    _run(sim, "hs_adam_step", req, stream)
+    _step(sim, req, kw.get("loss_scale"), stream)
     return res
+
+
+def _step(sim, req, loss_scale, stream):
+    if loss_scale is None:
+        _run(sim, "hs_adam_step", req, stream)
+    else:
+        _run(sim, "hs_adam_step_scaled", req, stream, C.byref(loss_scale.request()))
 
 
 def stats_to_metrics(stats):
@@ -227,20 +329,23 @@ class Adam(_optimizer_base()):
     hs_adam_step call (sim.adam_step's entry point) with zero_grad=True, reading lr, betas, eps, weight_decay, max_grad_norm and grad_scale from
     param_groups[0] on every call (LR schedulers and PBT's exploration of lr change them there), and returns the device
     tensor of the statistics without synchronising: the optimiser's own tensor, overwritten by the next step (clone it to
-    keep it; stats_to_metrics reads it).  The module docstring says where this differs from torch.optim.Adam."""
+    keep it; stats_to_metrics reads it).  With loss_scale, a LossScale on the same device, step() makes the
+    hs_adam_step_scaled call instead: the gradients are divided by the scale, a step that overflowed is skipped and the
+    scale adjusted, all on the device.  The module docstring says where this differs from torch.optim.Adam."""
 
     def __init__(self, sim, parameters, lr=DEFAULTS["lr"], betas=DEFAULTS["betas"], eps=DEFAULTS["eps"], weight_decay=DEFAULTS["weight_decay"],
-                 max_grad_norm=DEFAULTS["max_grad_norm"], grad_scale=DEFAULTS["grad_scale"]):
+                 max_grad_norm=DEFAULTS["max_grad_norm"], grad_scale=DEFAULTS["grad_scale"], loss_scale=None):
         import torch
         named = _named(parameters)
         _hyper(lr, betas, eps, weight_decay, max_grad_norm, grad_scale)
-        self.sim = sim
+        self.sim, self.loss_scale = sim, _scaler(loss_scale)
         device = torch.device("cuda", sim.gpu_id)
         self.flat = flatten(named, device)
         self.m, self.v = torch.zeros_like(self.flat.params), torch.zeros_like(self.flat.params)
         self.adam_state = fresh_state(device)
         self.stats = torch.zeros(STATS, dtype=torch.float64, device=device)
-        request(sim.gpu_id, self.flat.params, self.flat.grads, self.m, self.v, self.adam_state, stats=self.stats)      # the buffers, checked once
+        request(sim.gpu_id, self.flat.params, self.flat.grads, self.m, self.v, self.adam_state, stats=self.stats,
+                loss_scale=self.loss_scale)                                                                               # the buffers, checked once
         super().__init__([p for _, p in named], dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
                                                      max_grad_norm=max_grad_norm, grad_scale=grad_scale))
 
@@ -262,7 +367,7 @@ class Adam(_optimizer_base()):
         # the buffers are the optimiser's own and passed request() when it was built: only the hyper-parameters are new
         req = HsAdamRequest(self.flat.params.data_ptr(), self.flat.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.flat.params.numel(),
                             *hyper, 1, self.adam_state.data_ptr(), self.stats.data_ptr())
-        _run(self.sim, "hs_adam_step", req, stream)
+        _step(self.sim, req, self.loss_scale, stream)
         return self.stats
 
     def zero_grad(self, set_to_none=False):
@@ -273,13 +378,19 @@ class Adam(_optimizer_base()):
 
     def state_dict(self):
         """{"m", "v": the flat moments, "state": the 4-element state, "layout": {name: (first, last, shape)},
-        "param_groups": the hyper-parameters}: clones."""
+        "param_groups": the hyper-parameters}: clones.  With a loss scale also "loss_scale": its state_dict()."""
         hyper = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
-        return {"m": self.m.clone(), "v": self.v.clone(), "state": self.adam_state.clone(),
-                "layout": {k: (lo, hi, tuple(shape)) for k, (lo, hi, shape) in self.layout().items()}, "param_groups": hyper}
+        out = {"m": self.m.clone(), "v": self.v.clone(), "state": self.adam_state.clone(),
+               "layout": {k: (lo, hi, tuple(shape)) for k, (lo, hi, shape) in self.layout().items()}, "param_groups": hyper}
+        if self.loss_scale is not None:
+            out["loss_scale"] = self.loss_scale.state_dict()
+        return out
 
     def load_state_dict(self, state_dict):
-        """Load what state_dict() returned.  Raises ValueError if its layout is not this optimiser's."""
+        """Load what state_dict() returned.  Raises ValueError if its layout is not this optimiser's, or if only one of
+        the two has a loss scale."""
+        if ("loss_scale" in state_dict) != (self.loss_scale is not None):
+            raise ValueError("the state %s a loss scale and this optimiser %s" % (("has", "has none") if "loss_scale" in state_dict else ("has no", "has one")))
         theirs = {k: (int(lo), int(hi), tuple(shape)) for k, (lo, hi, shape) in state_dict["layout"].items()}
         if theirs != self.layout() or list(theirs) != list(self.layout()):
             raise ValueError("the state's layout differs from this optimiser's: other parameters, shapes or order")
@@ -288,6 +399,8 @@ class Adam(_optimizer_base()):
                 raise ValueError(f"the state's {k} has shape {tuple(state_dict[k].shape)} and dtype {state_dict[k].dtype}: expected {tuple(t.shape)}, {t.dtype}")
         for k, t in (("m", self.m), ("v", self.v), ("state", self.adam_state)):
             t.copy_(state_dict[k])
+        if self.loss_scale is not None:
+            self.loss_scale.load_state_dict(state_dict["loss_scale"])
         for g, saved in zip(self.param_groups, state_dict.get("param_groups", [])):
             g.update({k: v for k, v in saved.items() if k != "params"})
 

@@ -186,7 +186,8 @@ class _Member(trainer.Trainer):
         if net is None:
             net = policy.make_policy(self.dtype, generator=torch.Generator().manual_seed(cfg.seed + index))
         self.net = net.to(dev).set_fused(self.fused)
-        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm)
+        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm,
+                              loss_scale=trainer.make_loss_scale(cfg, dev))
         self.normaliser = ObsNormaliser(sim.gpu_id, table=table) if cfg.normalise_obs else None
         self.rollout = pop.rollout
         self.state = self.net.init_state(self.rows, dev, self.dtype)
@@ -519,7 +520,7 @@ class Population:
         return pairs
 
     def apply_exploit(self, dst, src):
-        """Policy `dst` takes policy `src`'s parameters, optimiser state, normaliser and rating, and explored lr and
+        """Policy `dst` takes policy `src`'s parameters, optimiser state (its loss scale included), normaliser and rating, and explored lr and
         entropy_coef.  Device-to-device copies: nothing waits."""
         import torch
         cfg, a, b = self.cfg, self.members[dst], self.members[src]
@@ -530,6 +531,8 @@ class Population:
             a.opt.m.copy_(b.opt.m)
             a.opt.v.copy_(b.opt.v)
             a.opt.adam_state.copy_(b.opt.adam_state)
+            if a.opt.loss_scale is not None:
+                a.opt.loss_scale.state.copy_(b.opt.loss_scale.state)
             if a.normaliser is not None:
                 a.normaliser.state.copy_(b.normaliser.state)
                 a.normaliser.table.copy_(b.normaliser.table)

@@ -21,7 +21,8 @@ import ctypes as C
 
 from .action_sampling import DEFAULT_BUCKETS, HEADS, MAX_BUCKETS, MAX_LOGITS
 from .advantages import MOMENTS
-from ._request import _DTYPES, _OUTPUT, _above_zero, _dtype_arg, _finite, _name, _outputs, _rows, _run, _shard_calls, _stride, _tensor, _vector, _wanted
+from ._request import (_DTYPES, _OUTPUT, _above_zero, _dtype_arg, _finite, _loss_scale_input, _name, _outputs, _rows, _run, _shard_calls, _stride, _tensor,
+                       _vector, _wanted)
 
 STATS = 7             # HS_PPO_STATS: sum pg, sum vl, sum ent, sum kl, policy-clipped, value-clipped, count
 ROWS_PER_BLOCK = 32   # kPpoRows: samples a workgroup takes at a time
@@ -45,10 +46,12 @@ class HsPpoRequest(C.Structure):
 def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUCKETS, adv_moments=None, mask=None,
             value=None, returns=None, old_value=None, clip_coef=DEFAULT_CLIP, value_loss_coef=DEFAULT_VALUE_LOSS_COEF,
             entropy_coef=DEFAULT_ENTROPY_COEF, grad_scale=1.0, grad_logits=True, grad_value=None, stats=True,
-            grad_dtype=None):
+            grad_dtype=None, loss_scale=None):
     """Validate a call over the n = logits.shape[0] samples of a minibatch on GPU `gpu_id`, allocate the outputs given as
     True (grad_logits in `grad_dtype`, by default the dtype of the logits; grad_value=None means True with a value and
-    nothing without), and return ({name: tensor}, HsPpoRequest).  Raises ValueError before the library is involved."""
+    nothing without), and return ({name: tensor}, HsPpoRequest).  `loss_scale` is None or the float64 [4] state of an
+    optim.LossScale on the device, which no output may overlap (compute then runs hs_ppo_loss_scaled: the gradients are
+    multiplied by state[0], the statistics are not).  Raises ValueError before the library is involved."""
     import torch
     dev = torch.device("cuda", gpu_id)
     buckets = tuple(int(b) for b in buckets)
@@ -86,7 +89,7 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
             _vector("old_value", old_value, n, dev, ("float32",))
     inputs = [(k, t) for k, t in (("logits", logits), ("action", action), ("old_log_prob", old_log_prob), ("advantage", advantage),
                                   ("adv_moments", adv_moments), ("mask", mask), ("value", value), ("returns", returns),
-                                  ("old_value", old_value)) if t is not None]
+                                  ("old_value", old_value)) if t is not None] + _loss_scale_input(loss_scale, dev)
     gdt = logits.dtype if grad_dtype is None else grad_dtype
     if outputs.get("grad_logits") is True:
         _dtype_arg("grad_dtype", gdt)
@@ -114,7 +117,11 @@ def request(gpu_id, logits, action, old_log_prob, advantage, buckets=DEFAULT_BUC
 def compute(sim, logits, action, old_log_prob, advantage, stream=None, **kw):
     """HideAndSeekSimulator.ppo_loss."""
     res, req = request(sim.gpu_id, logits, action, old_log_prob, advantage, **kw)
-    _run(sim, "hs_ppo_loss", req, stream)
+    scale = kw.get("loss_scale")
+    if scale is None:
+        _run(sim, "hs_ppo_loss", req, stream)
+    else:
+        _run(sim, "hs_ppo_loss_scaled", req, stream, C.c_void_p(scale.data_ptr()))
     return res
 
 

@@ -70,10 +70,24 @@ class TrainConfig:
     dtype: object = None
     seed: int = 5
     normalise_obs: bool = True
+    loss_scale: object = None             # None, "dynamic" (optim.LossScale's defaults) or a dict of LossScale's keywords
+
+
+def loss_scale_settings(setting):
+    """None for TrainConfig.loss_scale None, else optim.LossScale's checked keywords.  Raises ValueError."""
+    if setting is None:
+        return None
+    if isinstance(setting, str) and setting == "dynamic":
+        return optim.loss_scale_settings()
+    if isinstance(setting, dict):
+        return optim.loss_scale_settings(**setting)
+    raise ValueError(f"loss_scale must be None, \"dynamic\" or a dict of optim.LossScale's keywords, got {setting!r}")
 
 
 def check_config(cfg, rows):
-    """Raise ValueError for a config that does not fit `rows` agent rows: T % K, K n % num_minibatches, counts below 1."""
+    """Raise ValueError for a config that does not fit `rows` agent rows: T % K, K n % num_minibatches, counts below 1;
+    or for a loss_scale that optim.LossScale would refuse."""
+    loss_scale_settings(cfg.loss_scale)
     for k in ("steps_per_update", "num_bptt_chunks", "num_minibatches", "num_epochs"):
         v = getattr(cfg, k)
         if isinstance(v, bool) or not isinstance(v, int) or v < 1:
@@ -131,6 +145,12 @@ class PhaseTimer:
         return out
 
 
+def make_loss_scale(cfg, device):
+    """The optim.LossScale of cfg.loss_scale on `device`, or None."""
+    s = loss_scale_settings(cfg.loss_scale)
+    return None if s is None else optim.LossScale(device, **s)
+
+
 class Trainer:
     """The policy (policy.make_policy, seeded with cfg.seed, unless `net` is given), optim.Adam over its parameters, an
     ObsNormaliser, the Rollout, the carried LSTM state and the sampling counter of one simulator (after sim.init())."""
@@ -146,7 +166,7 @@ class Trainer:
         if net is None:
             net = policy.make_policy(self.dtype, generator=torch.Generator().manual_seed(cfg.seed))
         self.net = net.to(dev).set_fused(self.fused)
-        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm)
+        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm, loss_scale=make_loss_scale(cfg, dev))
         self.normaliser = ObsNormaliser(sim.gpu_id) if cfg.normalise_obs else None
         self.rollout = rollout.Rollout(sim, cfg.steps_per_update, cfg.num_bptt_chunks, self.dtype, hidden=self.net.actor.core.hidden)
         self.state = self.net.init_state(n, dev, self.dtype)
@@ -286,10 +306,12 @@ class Trainer:
             logits, critic_logits = self.sequence_logits(mb)
             logits, critic_logits = logits.reshape(S, -1), critic_logits.reshape(S, -1)
             mask = mb["mask"].reshape(S)
+            scale = None if self.opt.loss_scale is None else self.opt.loss_scale.state     # the gradients carry the scale that opt.step() divides out
             pol = sim.ppo_loss(logits.detach(), mb["action"].reshape(S, -1), mb["log_prob"].reshape(S), mb["advantage"].reshape(S), buckets=net.buckets,
-                               adv_moments=self.adv_moments, mask=mask, clip_coef=cfg.clip_coef, entropy_coef=cfg.entropy_coef, stats=self._ppo_out)
+                               adv_moments=self.adv_moments, mask=mask, clip_coef=cfg.clip_coef, entropy_coef=cfg.entropy_coef, stats=self._ppo_out,
+                               loss_scale=scale)
             val = sim.value_head(critic_logits.detach(), mb["returns"].reshape(S), bins=net.bins, mask=mask, value=None, loss_coef=cfg.value_loss_coef,
-                                 stats=self._value_out)
+                                 stats=self._value_out, loss_scale=scale)
             torch.autograd.backward([logits, critic_logits], [pol["grad_logits"], val["grad_logits"]])
             self.ppo_stats[epoch] += self._ppo_out
             self.value_stats[epoch] += self._value_out
@@ -328,7 +350,7 @@ class Trainer:
 
     def metric_tensors(self):
         """The statistics of the last update as float64 scalars on the device, without synchronising: METRIC_NAMES, then
-        the value loss of every epoch."""
+        the value loss of every epoch, then with a loss scale its value after the update."""
         import torch
         cfg = self.cfg
         steps = cfg.num_epochs * cfg.num_minibatches
@@ -338,14 +360,17 @@ class Trainer:
         per_epoch = [value_head.stats_to_metrics(self.value_stats[e])["value_loss"] for e in range(cfg.num_epochs)]
         vals = [pol["policy_loss"], pol["entropy"], pol["approx_kl"], pol["clip_fraction"], val["value_loss"], val["explained_variance"], val["mean_value"],
                 adv["advantages"][0], adv["advantages"][1], adv["returns"][0], adv["returns"][1], self.adam_stats[0] / steps, self.adam_stats[1], self.adam_stats[2]]
-        return [v.to(torch.float64) for v in vals + per_epoch]
+        scale = [] if self.opt.loss_scale is None else [self.opt.loss_scale.state[0]]
+        return [v.to(torch.float64) for v in vals + per_epoch + scale]
 
     def metrics_from(self, host):
         """The metrics dict from the values of metric_tensors() as Python numbers."""
         cfg, names = self.cfg, self.METRIC_NAMES
         out = dict(zip(names, host))
         out["skipped"], out["adam_step"] = int(out["skipped"]), int(out["adam_step"])
-        out["value_loss_epochs"] = host[len(names):]
+        out["value_loss_epochs"] = host[len(names):len(names) + cfg.num_epochs]
+        if self.opt.loss_scale is not None:
+            out["loss_scale"] = host[len(names) + cfg.num_epochs]
         out["loss"] = out["policy_loss"] - cfg.entropy_coef * out["entropy"] + cfg.value_loss_coef * out["value_loss"]
         out["update"] = self.update_index
         return out

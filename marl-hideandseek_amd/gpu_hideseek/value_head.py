@@ -22,7 +22,7 @@ symlog(), symexp() and twohot() are the eager composition in plain torch, for re
 """
 import ctypes as C
 
-from ._request import _DTYPES, _OUTPUT, _dtype_arg, _finite, _name, _outputs, _rows, _run, _shard_calls, _stride, _vector, _wanted
+from ._request import _DTYPES, _OUTPUT, _dtype_arg, _finite, _loss_scale_input, _name, _outputs, _rows, _run, _shard_calls, _stride, _vector, _wanted
 
 STATS = 6             # HS_TWOHOT_STATS: sum ce, sum (v - R)^2, sum v, sum R, sum R^2, count
 MAX_BINS = 256        # HS_TWOHOT_MAX_BINS
@@ -89,10 +89,12 @@ def eager_loss(logits, returns, mask=None, B=DEFAULT_BINS, lo=DEFAULT_LO, hi=DEF
 
 # ---- the fused call ----
 def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=DEFAULT_HI, mask=None, value=True,
-            grad_logits=None, stats=None, loss_coef=1.0, grad_scale=1.0, grad_dtype=None, value_dtype=None):
+            grad_logits=None, stats=None, loss_coef=1.0, grad_scale=1.0, grad_dtype=None, value_dtype=None, loss_scale=None):
     """Validate a call over the n = logits.shape[0] samples on GPU `gpu_id`, allocate the outputs given as True (value in
     `value_dtype` and grad_logits in `grad_dtype`, by default the dtype of the logits; grad_logits=None and stats=None
-    mean True exactly when returns are given), and return ({name: tensor}, HsTwohotRequest).  Raises ValueError before
+    mean True exactly when returns are given), and return ({name: tensor}, HsTwohotRequest).  `loss_scale` is None or
+    the float64 [4] state of an optim.LossScale on the device, which no output may overlap (compute then runs
+    hs_twohot_value_scaled: grad_logits is multiplied by state[0], value and stats are not).  Raises ValueError before
     the library is involved."""
     import torch
     dev = torch.device("cuda", gpu_id)
@@ -116,7 +118,7 @@ def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=D
         _vector("returns", returns, n, dev, ("float32",))
     if mask is not None:
         _vector("mask", mask, n, dev, ("float32",))
-    inputs = [(k, t) for k, t in (("logits", logits), ("returns", returns), ("mask", mask)) if t is not None]
+    inputs = [(k, t) for k, t in (("logits", logits), ("returns", returns), ("mask", mask)) if t is not None] + _loss_scale_input(loss_scale, dev)
     _dtype_arg("value_dtype", value_dtype)
     _dtype_arg("grad_dtype", grad_dtype)
     W = int(logits.shape[1])
@@ -141,7 +143,11 @@ def request(gpu_id, logits, returns=None, bins=DEFAULT_BINS, lo=DEFAULT_LO, hi=D
 def compute(sim, logits, returns=None, stream=None, **kw):
     """HideAndSeekSimulator.value_head."""
     res, req = request(sim.gpu_id, logits, returns, **kw)
-    _run(sim, "hs_twohot_value", req, stream)
+    scale = kw.get("loss_scale")
+    if scale is None:
+        _run(sim, "hs_twohot_value", req, stream)
+    else:
+        _run(sim, "hs_twohot_value_scaled", req, stream, C.c_void_p(scale.data_ptr()))
     return res
 
 

@@ -37,6 +37,10 @@ the pool stays a copy of the first learners).  The Elo table then covers all P +
 line names the update each pool slot's snapshot was taken at.
 --encoder attention trains the reference's other network, EntitySelfAttentionNet (gpu_hideseek.entity_attention), in
 place of SimpleNet; the checkpoint's layout says which it was, and tools/infer.py and tools/league.py read it from there.
+--fp16 trains with the dynamic loss scale (gpu_hideseek.optim.LossScale: the gradients of a minibatch of about 10^6 samples
+lie below float16's normal range without it): the metrics line then carries "loss_scale", the scale after the update, next
+to "skipped", the steps that overflowed and halved it, and --phases prints both per update.  --loss-scale-init X sets the
+start (a power of two; 2^16 by default), --no-loss-scale trains float16 with no scale.
 Not here: tensorboard / wandb, several GPUs.
 """
 import argparse
@@ -73,6 +77,8 @@ def parse(argv=None):
     ap.add_argument("--value-loss-coef", type=float, default=1.0)
     ap.add_argument("--fp16", action="store_true")
     ap.add_argument("--bf16", action="store_true")
+    ap.add_argument("--no-loss-scale", action="store_true", help="with --fp16: no dynamic loss scale (TrainConfig.loss_scale None); most of the gradient then underflows")
+    ap.add_argument("--loss-scale-init", type=float, help="with --fp16: the loss scale's start, a power of two (default 2^16)")
     ap.add_argument("--num-hiders", type=int, default=3)
     ap.add_argument("--num-seekers", type=int, default=3)
     ap.add_argument("--seed", type=int, default=5)
@@ -97,6 +103,10 @@ def parse(argv=None):
         ap.error("--pbt-interval needs --pbt-ensemble-size")
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
+    if (args.no_loss_scale or args.loss_scale_init is not None) and not args.fp16:
+        ap.error("--no-loss-scale and --loss-scale-init need --fp16")
+    if args.no_loss_scale and args.loss_scale_init is not None:
+        ap.error("--no-loss-scale and --loss-scale-init exclude each other")
     if (args.ckpt_dir is None) != (args.run_name is None):
         ap.error("--ckpt-dir and --run-name go together")
     if args.restore is not None and args.ckpt_dir is None:
@@ -106,15 +116,17 @@ def parse(argv=None):
 
 def config(args):
     dtype = torch.float16 if args.fp16 else torch.bfloat16 if args.bf16 else torch.float32
+    # float16 gradients are about 1 / (samples of a minibatch) and underflow without a scale: --fp16 turns the dynamic one on
+    scale = None if not args.fp16 or args.no_loss_scale else "dynamic" if args.loss_scale_init is None else {"init_scale": args.loss_scale_init}
     if args.pbt_ensemble_size:
         return population.PopulationConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
                                            num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
                                            value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed, num_policies=args.pbt_ensemble_size,
                                            team_size=args.num_hiders, pbt_interval=args.pbt_interval, num_past_policies=args.pbt_past_policies,
-                                           snapshot_interval=args.pbt_snapshot_interval)
+                                           snapshot_interval=args.pbt_snapshot_interval, loss_scale=scale)
     return trainer.TrainConfig(steps_per_update=args.steps_per_update, num_bptt_chunks=args.num_bptt_chunks, num_minibatches=args.num_minibatches,
                                num_epochs=args.num_epochs, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy_loss_coef,
-                               value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed)
+                               value_loss_coef=args.value_loss_coef, dtype=dtype, seed=args.seed, loss_scale=scale)
 
 
 def phase_table(totals, wall_ms, updates, args, fps):
@@ -198,7 +210,8 @@ def main(argv=None):
         metrics = tr.update_iter()
         if args.phases:
             spans = tr.phases.totals()
-            print("  update %d: %.1f ms" % (tr.update_index, 1e3 * (time.perf_counter() - t0)), flush=True)
+            scaled = "" if "loss_scale" not in metrics else ", loss scale %g, %d skipped steps" % (metrics["loss_scale"], metrics["skipped"])
+            print("  update %d: %.1f ms%s" % (tr.update_index, 1e3 * (time.perf_counter() - t0), scaled), flush=True)
             if i > 0:                                                  # the first update warms up
                 wall_ms += 1e3 * (time.perf_counter() - t0)
                 timed += 1
