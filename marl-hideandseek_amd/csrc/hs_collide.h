@@ -148,6 +148,12 @@ HSD HullRef hull_from(const HullSrc &s) {
     h.kind = s.kind; h.c = s.c; h.ax = m.c0; h.ay = m.c1; h.az = m.c2; h.e = s.e;
     return h;
 }
+HSD HullRef hull_ref_sel(bool c, const HullRef &a, const HullRef &b) {
+    HullRef r;
+    r.kind = c ? a.kind : b.kind; r.c = vsel(c, a.c, b.c); r.e = vsel(c, a.e, b.e);
+    r.ax = vsel(c, a.ax, b.ax); r.ay = vsel(c, a.ay, b.ay); r.az = vsel(c, a.az, b.az);
+    return r;
+}
 HSD HullRef hull_ref_wall(float cx, float cy, float hx, float hy) {
     HullRef h;
     h.kind = HULL_BOX;
@@ -293,6 +299,9 @@ HSD V3 cb_get(const ClipBuf &b, int w, int i) {
     const float *p = b.base + ((w * 8 + i) * 3) * b.stride + b.lane;
     return {p[0], p[b.stride], p[2 * b.stride]};
 }
+// the x word of a vertex alone
+HSD float cb_get_x(const ClipBuf &b, int w, int i) { return b.base[((w * 8 + i) * 3) * b.stride + b.lane]; }
+HSD void cb_set_x(const ClipBuf &b, int w, int i, float x) { b.base[((w * 8 + i) * 3) * b.stride + b.lane] = x; }
 HSD void cb_set(const ClipBuf &b, int w, int i, V3 v) {
     float *p = b.base + ((w * 8 + i) * 3) * b.stride + b.lane;
     p[0] = v.x; p[b.stride] = v.y; p[2 * b.stride] = v.z;
@@ -309,9 +318,16 @@ HSD int clip_face_contact(const HullRef &R, int fr, V3 nr, const HullRef &I, con
     int cur_buf = 0;
     for (int k = 0; k < n; ++k) cb_set(cb, 0, k, hull_v(I, hull_fidx(I, fi, k)));
     const int rc = hull_fcnt(R, fr);
+    // every vertex of the reference face is built once: an edge's end is the next edge's start, and the closing edge ends
+    // at the first vertex
+    const V3 vfirst = hull_v(R, hull_fidx(R, fr, 0));
+    V3 vnext = vfirst;
     for (int k = 0; k < rc && n > 0; ++k) {
         const int k1 = (k + 1 == rc) ? 0 : k + 1;
-        V3 v0 = hull_v(R, hull_fidx(R, fr, k)), v1 = hull_v(R, hull_fidx(R, fr, k1));
+        const V3 v0 = vnext;
+        V3 v1 = vfirst;
+        if (k1 != 0) v1 = hull_v(R, hull_fidx(R, fr, k1));
+        vnext = v1;
         V3 s = cross(v1 - v0, nr);
         int m = 0;
         const int src = cur_buf, dst = cur_buf ^ 1;
@@ -329,16 +345,17 @@ HSD int clip_face_contact(const HullRef &R, int fr, V3 nr, const HullRef &I, con
         n = m;
         cur_buf = dst;
     }
-    // compact points on or below the reference plane into the other buffer
+    // compact points on or below the reference plane into the other buffer.  A kept point's distance goes with it: into
+    // the x word of vertex c of the SOURCE polygon, which is dead by then (c <= i, and vertex i has just been read).
     const int src = cur_buf, pts = cur_buf ^ 1;
     int c = 0;
     for (int i = 0; i < n; ++i) {
         V3 p = cb_get(cb, src, i);
         float d = dot(nr, p) - dr;
-        if (d <= 0.f) { cb_set(cb, pts, c, p); c++; }
+        if (d <= 0.f) { cb_set(cb, pts, c, p); cb_set_x(cb, src, c, d); c++; }
     }
 #define HS_PT(i) cb_get(cb, pts, (i))
-#define HS_DIST(i) (dot(nr, HS_PT(i)) - dr)
+#define HS_DIST(i) cb_get_x(cb, src, (i))
     if (c <= 4) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) if (i < c) { pInc[i] = HS_PT(i); dist_out[i] = HS_DIST(i); }
@@ -350,20 +367,24 @@ HSD int clip_face_contact(const HullRef &R, int fr, V3 nr, const HullRef &I, con
     int i1 = -1; float bd = -1.f;
     for (int i = 0; i < c; ++i) { if (i == i0) continue; float d2 = len2(HS_PT(i) - p0); if (d2 > bd) { bd = d2; i1 = i; } }
     const V3 p1 = HS_PT(i1);
-    int i2 = -1, i3 = -1; float amax = 0.f, amin = 0.f;
+    // i2: the first strict maximum of the signed area over S = {i != i0, i1};  i3: the first strict minimum over S \ {i2}.
+    // One walk over S with one area per point: it tracks i2, the first minimum m1 of S and the first minimum m2 of
+    // S \ {m1}.  If m1 != i2, m1 is the answer — it lies in S \ {i2}, nothing there is smaller, and an equal value at a
+    // lower index would have been the first minimum of S as well.  If m1 == i2 the answer is m2 by definition.  The update
+    // keeps both "first" rules: a strictly smaller value takes m1 and hands the old m1 (earlier, and the first minimum of
+    // what was seen) down to m2; any other value, ties with a1 included, can only take m2, and only strictly.  c >= 5
+    // leaves at least three points in S, so m2 always exists (c = 5: two candidates remain after i2, m1 or m2 as above).
+    int i2 = -1, m1 = -1, m2 = -1; float amax = 0.f, a1 = 0.f, a2 = 0.f;
     for (int i = 0; i < c; ++i) {
         if (i == i0 || i == i1) continue;
         V3 p = HS_PT(i);
         float ar = dot(cross(p0 - p, p1 - p), nr);
         if (i2 < 0 || ar > amax) { amax = ar; i2 = i; }
+        if (m1 < 0 || ar < a1) { a2 = a1; m2 = m1; a1 = ar; m1 = i; }
+        else if (m2 < 0 || ar < a2) { a2 = ar; m2 = i; }
     }
-    for (int i = 0; i < c; ++i) {
-        if (i == i0 || i == i1 || i == i2) continue;
-        V3 p = HS_PT(i);
-        float ar = dot(cross(p0 - p, p1 - p), nr);
-        if (i3 < 0 || ar < amin) { amin = ar; i3 = i; }
-    }
-    pInc[0] = p0; dist_out[0] = HS_DIST(i0);
+    const int i3 = m1 != i2 ? m1 : m2;
+    pInc[0] = p0; dist_out[0] = d0;
     pInc[1] = p1; dist_out[1] = HS_DIST(i1);
     pInc[2] = HS_PT(i2); dist_out[2] = HS_DIST(i2);
     pInc[3] = HS_PT(i3); dist_out[3] = HS_DIST(i3);
@@ -389,8 +410,9 @@ HSD AxisResult sat_axes(const HullSrc &sa, const HullSrc &sb, const bool hi) {
     AxisResult res = {0, {0.f, 0.f, 0.f}};
     // ---- face normals: this lane takes the faces of X against the vertices of Y (X = A on the low lane, B on its partner)
     float bestA, bestB; int fa, fb;
+    // (X and Y outlive the face part: A and B of the edge part are the same two hulls, told apart by the lane's role)
+    const HullRef X = hull_from(hull_src_sel(hi, sb, sa)), Y = hull_from(hull_src_sel(hi, sa, sb));
     {
-        const HullRef X = hull_from(hull_src_sel(hi, sb, sa)), Y = hull_from(hull_src_sel(hi, sa, sb));
         WedgeVerts wx = {}, wy = {};
         if (X.kind == HULL_WEDGE) wedge_verts(X, wx);
         if (Y.kind == HULL_WEDGE) wedge_verts(Y, wy);
@@ -407,7 +429,7 @@ HSD AxisResult sat_axes(const HullSrc &sa, const HullSrc &sb, const bool hi) {
         bestA = hi ? best_o : best; fa = hi ? fx_o : fx;
         bestB = hi ? best : best_o; fb = hi ? fx : fx_o;
     }
-    const HullRef A = hull_from(sa), B = hull_from(sb);
+    const HullRef A = hull_ref_sel(hi, Y, X), B = hull_ref_sel(hi, X, Y);
     WedgeVerts wa = {}, wb = {};
     if (A.kind == HULL_WEDGE) wedge_verts(A, wa);
     if (B.kind == HULL_WEDGE) wedge_verts(B, wb);

@@ -634,7 +634,7 @@ struct SpillCtx {
     int wbeg;
 };
 HSD SpillCtx spill_ctx(const SimState &S) { return {S.walls.p, S.planes.p, (ManDD *)S.wsDD, (ManS *)S.wsSC, S.spPair, S.spInfo, S.wbeg}; }
-HSD HullSrc sat_hull_b(const Col<float, 4 * kMaxWalls> &walls, const OctRes &R, int g, int w, bool isdd, int bsel);   // (with the convex tests below)
+HSD HullSrc sat_hull_b(const Col<float, 4 * kMaxWalls> &walls, const OctRes &R, int g, int w, bool isdd, int bsel, int *objB = nullptr);   // (with the convex tests below)
 
 // Convex tests of the spilled pairs: world by world, body-body then body-static, 32 pairs per trip, two lanes per pair
 // for the axis search (sat_axes) and the pair's first lane for the contact generation right away (no compaction: this
@@ -791,13 +791,16 @@ HSD HullSrc sat_hull_a(const OctRes &R, int g, int a) { return hull_src_body(met
 // valid wall row, the words are dropped — so they are in flight while the bodies are read and the first hull is built,
 // and the wait stands where the hull needs them.  (Written as "body ? LDS : global" the two sources fold into generic
 // pointers: flat loads, each waited for at once.)
-HSD HullSrc sat_hull_b(const Col<float, 4 * kMaxWalls> &walls, const OctRes &R, int g, int w, bool isdd, int bsel) {
+// `objB`: where to leave the object type of the body read (sat_flush needs it for the record).
+HSD HullSrc sat_hull_b(const Col<float, 4 * kMaxWalls> &walls, const OctRes &R, int g, int w, bool isdd, int bsel, int *objB) {
     static_assert(kNumDSlots <= kMaxWalls, "a body slot is a valid wall row");
     const float *const wp = &walls(min(bsel, kMaxWalls - 1), w);
     const float cx = glb_word(wp), cy = glb_word(wp + kMaxWalls * kTile);
     const float hx = glb_word(wp + 2 * kMaxWalls * kTile), hy = glb_word(wp + 3 * kMaxWalls * kTile);
     const int slot = isdd ? bsel : 0;
-    const HullSrc body = hull_src_body(meta_obj(R.meta[slot][g]), rld3(R.pos, slot, g), rld4(R.rot, slot, g));
+    const int obj = meta_obj(R.meta[slot][g]);
+    if (objB) *objB = obj;
+    const HullSrc body = hull_src_body(obj, rld3(R.pos, slot, g), rld4(R.rot, slot, g));
     return hull_src_sel(isdd, body, hull_src_wall(cx, cy, hx, hy));
 }
 // stage 2 for the first `npend` pending pairs: lane i < 32 takes pair i.  `last`: this is the substep's last round,
@@ -822,25 +825,31 @@ HSD bool sat_flush(const SimState &S, OctRes &R, int npend, bool last) {
         RawManifold raw;
         const bool plane = res.code == 3;                 // an extra plane of a debug level (static candidate kMaxWalls + p)
         bool have;
+        // the poses and object types are read once, for the hulls and for the record: the contact generation in between
+        // writes clip-scratch words only
+        const int oa = meta_obj(R.meta[a][g]);
+        const V3 pa = rld3(R.pos, a, g);
+        const Q qa = rld4(R.rot, a, g);
+        int obB = OBJ_NONE;
+        HullSrc hb = hull_src_body(oa, pa, qa);           // (a placeholder until the second hull is read; a plane has none)
         if (plane) {
             const int p = bsel - kMaxWalls;
             const V3 pn = {S.planes(0 * kMaxPlanes + p, w), S.planes(1 * kMaxPlanes + p, w), S.planes(2 * kMaxPlanes + p, w)};
-            have = collide_hull_plane(hull_ref_body(meta_obj(R.meta[a][g]), rld3(R.pos, a, g), rld4(R.rot, a, g)), pn, S.planes(3 * kMaxPlanes + p, w), raw);
+            have = collide_hull_plane(hull_ref_body(oa, pa, qa), pn, S.planes(3 * kMaxPlanes + p, w), raw);
         } else {
-            have = sat_contact(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), res, cb, raw);
+            hb = sat_hull_b(S.walls, R, g, w, isdd, bsel, &obB);
+            have = sat_contact(hull_src_body(oa, pa, qa), hb, res, cb, raw);
         }
         if (have) {
-            const int oa = meta_obj(R.meta[a][g]);
-            const int ob = isdd ? meta_obj(R.meta[bsel][g]) : plane ? OBJ_PLANE : OBJ_WALL;
-            const V3 pa = rld3(R.pos, a, g);
-            const Q qai = qinv(rld4(R.rot, a, g));
+            const int ob = isdd ? obB : plane ? OBJ_PLANE : OBJ_WALL;
+            const Q qai = qinv(qa);
             const float muS = 0.5f * (obj_mu_s(oa) + obj_mu_s(ob)), muD = 0.5f * (obj_mu_d(oa) + obj_mu_d(ob));
             if (isdd) {
                 ManDD m;
                 m.a = a; m.b = bsel; m.np = raw.np; m.muS = muS; m.muD = muD;
                 st3(m.n, raw.n);
-                const V3 pb = rld3(R.pos, bsel, g);
-                const Q qbi = qinv(rld4(R.rot, bsel, g));
+                const V3 pb = hb.c;                       // (a body-body pair: the second hull's source is body bsel's pose)
+                const Q qbi = qinv(hb.q);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const bool on = j < raw.np;
@@ -1218,12 +1227,19 @@ HSD void ground_pos(OctRes &R, BodyReg &b, int slot, int g, int meta) {
     // agents are yaw-only bodies (obj_inv_inertia): their floor contacts share the manifold's normal multiplier
     const bool yaw = slot >= kAgentSlot0;
     float dj[4] = {0.f, 0.f, 0.f, 0.f}, share = 0.f;
-    if (yaw) share = yaw_ground_prepass(me, gn, b.np, hull_local_vertex(obj, b.vidx & 7), hull_local_vertex(obj, (b.vidx >> 3) & 7),
-                                        hull_local_vertex(obj, (b.vidx >> 6) & 7), hull_local_vertex(obj, (b.vidx >> 9) & 7), kGroundOff, dj);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j < b.np) b.lam[j] += solve_point_position_ground(me, gn, hull_local_vertex(obj, (b.vidx >> (3 * j)) & 7), kGroundOff, gmuS,
-                                                              yaw, dj[j], share);
+    // the points at the substep's start, once for the prepass and the point solves (every lane of the round together)
+    const V3 r0 = hull_local_vertex(obj, b.vidx & 7), r1 = hull_local_vertex(obj, (b.vidx >> 3) & 7);
+    const V3 r2 = hull_local_vertex(obj, (b.vidx >> 6) & 7), r3 = hull_local_vertex(obj, (b.vidx >> 9) & 7);
+    V3 q0 = {0.f, 0.f, 0.f}, q1 = q0, q2 = q0, q3 = q0;
+    q0 = prev_point(me, r0);
+    if (b.np > 1) q1 = prev_point(me, r1);
+    if (b.np > 2) q2 = prev_point(me, r2);
+    if (b.np > 3) q3 = prev_point(me, r3);
+    if (yaw) share = yaw_ground_prepass(me, gn, b.np, r0, r1, r2, r3, q0, q1, q2, q3, kGroundOff, dj);
+    b.lam[0] += solve_point_position_ground(me, gn, r0, q0, kGroundOff, gmuS, yaw, dj[0], share);
+    if (b.np > 1) b.lam[1] += solve_point_position_ground(me, gn, r1, q1, kGroundOff, gmuS, yaw, dj[1], share);
+    if (b.np > 2) b.lam[2] += solve_point_position_ground(me, gn, r2, q2, kGroundOff, gmuS, yaw, dj[2], share);
+    if (b.np > 3) b.lam[3] += solve_point_position_ground(me, gn, r3, q3, kGroundOff, gmuS, yaw, dj[3], share);
     rbody_store_pose(R, g, slot, me);
 }
 HSD void ground_vel(OctRes &R, const BodyReg &b, int slot, int g, int meta) {
@@ -1314,17 +1330,27 @@ HSD void last_round(const SimState &S, OctRes &R, BodyReg &b, bool valid, int sl
         // the ground manifold of an agent (a yaw-only body): manifold-level normal part first (hs_solver.h)
         const bool yaw = POS && !walls && slot >= kAgentSlot0;
         float dj[4] = {0.f, 0.f, 0.f, 0.f}, share = 0.f;
-        if (yaw) share = yaw_ground_prepass(me, n, np, hull_local_vertex(obj, b.vidx & 7), hull_local_vertex(obj, (b.vidx >> 3) & 7),
-                                            hull_local_vertex(obj, (b.vidx >> 6) & 7), hull_local_vertex(obj, (b.vidx >> 9) & 7), kGroundOff, dj);
+        // the manifold's points in the body frame and, for the position pass, at the substep's start: once for the prepass
+        // and the point solves, wall and ground manifolds alike (named per point: no arrays indexed by the contact number)
+#define HS_LAST_ARM(j) (walls ? ld3(m.rA[j]) : hull_local_vertex(obj, (b.vidx >> (3 * (j))) & 7))
+        const V3 rA0 = HS_LAST_ARM(0), rA1 = HS_LAST_ARM(1), rA2 = HS_LAST_ARM(2), rA3 = HS_LAST_ARM(3);
+#undef HS_LAST_ARM
+        V3 pv0 = {0.f, 0.f, 0.f}, pv1 = pv0, pv2 = pv0, pv3 = pv0;
+        if (POS) {
+            if (0 < np) pv0 = prev_point(me, rA0);
+            if (1 < np) pv1 = prev_point(me, rA1);
+            if (2 < np) pv2 = prev_point(me, rA2);
+            if (3 < np) pv3 = prev_point(me, rA3);
+        }
+        if (yaw) share = yaw_ground_prepass(me, n, np, rA0, rA1, rA2, rA3, pv0, pv1, pv2, pv3, kGroundOff, dj);
 #define HS_LAST_POINT(j)                                                                                                   \
         if ((j) < np) {                                                                                                    \
-            const V3 rAj = walls ? ld3(m.rA[j]) : hull_local_vertex(obj, (b.vidx >> (3 * (j))) & 7);                       \
             const float lamj = walls ? m.lam[j] : b.lam[j];                                                                \
             if (POS) {                                                                                                     \
-                const float nl = lamj + solve_point_position_ground(me, n, rAj, walls ? m.offB[j] : kGroundOff, mu, yaw, dj[j], share); \
+                const float nl = lamj + solve_point_position_ground(me, n, rA##j, pv##j, walls ? m.offB[j] : kGroundOff, mu, yaw, dj[j], share); \
                 if (!walls) b.lam[j] = nl; else m.lam[j] = nl;                                                             \
             } else {                                                                                                       \
-                solve_point_velocity<false>(me, none, n, rAj, V3{0.f, 0.f, 0.f}, lamj, mu);                                \
+                solve_point_velocity<false>(me, none, n, rA##j, V3{0.f, 0.f, 0.f}, lamj, mu);                              \
             }                                                                                                              \
         }
         HS_LAST_POINT(0) HS_LAST_POINT(1) HS_LAST_POINT(2) HS_LAST_POINT(3)

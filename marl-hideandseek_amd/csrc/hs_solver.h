@@ -109,11 +109,14 @@ HSD float solve_point_position(BodyS &A, BodyS &B, V3 n, V3 rAl, V3 rBl, float o
 // src/mgr.cpp:577-584) the normal part has been done for the whole manifold by yaw_ground_prepass (below): `dj` is
 // the point's penetration before any correction and `share` its equal share of the manifold's normal multiplier; what
 // remains per point is the static-friction correction, the same expressions for both kinds of body.
-HSD float solve_point_position_ground(BodyS &A, V3 n, V3 rAl, float offB, float muS, bool yaw, float dj, float share) {
+// `pAprev`: the point at the substep's start, prev_point(A, rAl) — A.ppos / A.prot do not change within a substep, so the
+// caller forms it once per manifold for the prepass and the point solves alike.  (The point's present arm qrot(A.rot,
+// rAl) is NOT shared in the same way: the friction correction of an earlier point yaws the agent.)
+HSD V3 prev_point(const BodyS &A, V3 rAl) { return A.ppos + qrot(A.prot, rAl); }
+HSD float solve_point_position_ground(BodyS &A, V3 n, V3 rAl, V3 pAprev, float offB, float muS, bool yaw, float dj, float share) {
     BodyS none;
     V3 rAw = qrot(A.rot, rAl);
     V3 pA = A.pos + rAw;
-    const V3 pAprev = A.ppos + qrot(A.prot, rAl);
     float lam;
     if (!yaw) {
         float d = dot_add(pA, n, -offB);
@@ -149,8 +152,9 @@ HSD float solve_point_position_ground(BodyS &A, V3 n, V3 rAl, float offB, float 
 // with it the whole friction budget of the substep, at a lever arm (a straight push spun the agent up).  The
 // penetrations of all points are evaluated before any correction, the body is lifted once by the deepest of them along
 // the normal (translation only), and the multiplier dmax / invM is shared equally by the touching points.  Returns the
-// share (0: nothing touches); r0..r3 are the contact points in the body frame.
-HSD float yaw_ground_prepass(BodyS &A, V3 n, int np, V3 r0, V3 r1, V3 r2, V3 r3, float off, float (&dj)[4]) {
+// share (0: nothing touches); r0..r3 are the contact points in the body frame, q0..q3 the same points at the substep's
+// start (prev_point).
+HSD float yaw_ground_prepass(BodyS &A, V3 n, int np, V3 r0, V3 r1, V3 r2, V3 r3, V3 q0, V3 q1, V3 q2, V3 q3, float off, float (&dj)[4]) {
     int k = 0; float dmax = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -159,7 +163,7 @@ HSD float yaw_ground_prepass(BodyS &A, V3 n, int np, V3 r0, V3 r1, V3 r2, V3 r3,
             const V3 r = j == 0 ? r0 : j == 1 ? r1 : j == 2 ? r2 : r3;
             float d = dot_add(A.pos + qrot(A.rot, r), n, -off);
             if (d > 0.f) {
-                const float excess = dot_add(A.ppos + qrot(A.prot, r), n, -off) - kMaxDepenVel * kSubstepH;
+                const float excess = dot_add(j == 0 ? q0 : j == 1 ? q1 : j == 2 ? q2 : q3, n, -off) - kMaxDepenVel * kSubstepH;
                 if (excess > 0.f) d = d - excess;
             }
             dj[j] = d;
