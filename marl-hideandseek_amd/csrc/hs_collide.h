@@ -9,6 +9,7 @@
 // are bit-packed immediates instead of lookup tables.
 #pragma once
 #include "hs_dev.h"
+#include "hs_sat_box.h"
 
 namespace hs {
 
@@ -401,8 +402,8 @@ HSD int clip_face_contact(const HullRef &R, int fr, V3 nr, const HullRef &I, con
 // pairs, its partner B's face normals and the second half; they exchange results with cross-lane shuffles and
 // combine them exactly as the sequential loop would (strictly-greater updates, earlier axis wins ties).  The result
 // is valid on the low lane:  code 0 = separated;  1 | ea << 4 | eb << 8 = edge contact along `ax`;
-// 2 | face << 4 | refB << 8 = face contact with reference face `face` of B (refB) or A.
-struct AxisResult { int code; V3 ax; };
+// 2 | face << 4 | refB << 8 = face contact with reference face `face` of B (refB) or A  (AxisResult: hs_sat_box.h).
+// This form takes any hull kind with rolled loops; it serves the spill path.  The box rounds run sat_axes_box below.
 // the partner lane of a pair is its neighbour (lanes 2k, 2k + 1): one DPP move instead of a trip through the LDS crossbar
 HSD int pair_swap(int x) { return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false); }
 HSD float pair_swap(float x) { return __int_as_float(pair_swap(__float_as_int(x))); }
@@ -463,6 +464,23 @@ HSD AxisResult sat_axes(const HullSrc &sa, const HullSrc &sb, const bool hi) {
     const bool refB = bestB > 0.98f * bestA + 0.00125f;
     res.code = 2 | ((refB ? fb : fa) << 4) | ((refB ? 1 : 0) << 8);
     return res;
+}
+
+// Stage 1 for two BOXES — every pair of a box round (hs_k_physics.h phase_sat): the lane split and the result of sat_axes,
+// bit for bit, with the search itself straight-line (hs_sat_box.h: the two halves and their combination are plain
+// functions of the lane's own hull X, the other hull Y and the role; here only the exchange between the two lanes).
+HSD AxisResult sat_axes_box(const HullSrc &sa, const HullSrc &sb, const bool hi) {
+    const AxisResult none = {0, {0.f, 0.f, 0.f}};
+    const HullSrc sx = hull_src_sel(hi, sb, sa), sy = hull_src_sel(hi, sa, sb);
+    const BoxRef X = box_ref(sx.c, sx.q, sx.e), Y = box_ref(sy.c, sy.q, sy.e);
+    const BoxFaceHalf f = sat_box_faces(X, Y);
+    const BoxFaceHalf f_o = {pair_swap(f.best), pair_swap(f.f), pair_swap(f.sep)};
+    if (f.sep | f_o.sep) return none;
+    const BoxEdgeHalf e = sat_box_edges(X, Y, hi);
+    const BoxEdgeHalf e_o = {pair_swap(e.best), pair_swap(e.ea), pair_swap(e.eb), {pair_swap(e.ax.x), pair_swap(e.ax.y), pair_swap(e.ax.z)}, pair_swap(e.sep)};
+    if (e.sep | e_o.sep) return none;
+    if (hi) return none;                      // the low lane holds the result: its own halves are A's faces and pairs 0 .. 3
+    return sat_box_combine(f, f_o, e, e_o);
 }
 
 // Stage 1 for the few pairs that involve the ramp's wedge (a couple per octet and substep, yet a round of their own:

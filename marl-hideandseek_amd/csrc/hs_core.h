@@ -66,6 +66,7 @@ HSD V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 HSD V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
 HSD V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 HSD V3 mulc(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+HSD V3 vsel(bool c, V3 a, V3 b) { return {c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z}; }
 // (fused multiply-adds, written out one by one: the kernels and the CPU oracle read the same ones in the same places)
 HSD float hs_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 HSD float dot(V3 a, V3 b) { return hs_fma(a.z, b.z, hs_fma(a.y, b.y, a.x * b.x)); }

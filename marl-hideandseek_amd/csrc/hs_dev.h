@@ -32,8 +32,6 @@ HSD int meta_obj(int m) { return (m & 0xff) - 1; }
 HSD int meta_resp(int m) { return (m >> 8) & 0xff; }
 HSD int meta_owner(int m) { return (m >> 16) & 0xff; }
 
-HSD V3 vsel(bool c, V3 a, V3 b) { return {c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z}; }
-
 // 1 / inverse inertia per axis (0 where the inverse is 0): the same IEEE quotients integrate would compute, folded
 // at compile time
 HSD V3 obj_inertia(int o) {

@@ -538,7 +538,9 @@ HSD ItemCounts phase_detect(const SimState &S, OctRes &R, int NS, unsigned xm, u
     const bool anySpill = __ballot(spillDD || spillSC) != 0ull;
     unsigned short *const spPair = S.spPair + (size_t)(S.wbeg + g) * (kAllDD + kAllSC);
     int *const spInfo = S.spInfo + (size_t)(S.wbeg + g) * kSpInfoWords;
-    // ---- the octet's work list: box-only items from the front, items with a ramp behind them (from a multiple of 32)
+    // ---- the octet's work list: box-only items from the front, items with a ramp behind them (from a multiple of 32).
+    // INVARIANT: an item in front of wedge0 has two boxes (bodies other than ramps, walls) — phase_sat's box rounds
+    // run the box-only axis search (sat_axes_box) on them without looking at the hull kind.
     int n_wedge = 0;
 #pragma unroll
     for (int jb = 0; jb < JB; ++jb) {
@@ -938,7 +940,8 @@ HSD bool phase_sat(const SimState &S, OctRes &R, ItemCounts ic) {
             } else if (wide) {
                 res = sat_axes_wide(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), lane & 15);
             } else {
-                res = sat_axes(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), hi);
+                // a box round holds no ramp item: phase_detect files every item that involves a ramp behind wedge0
+                res = sat_axes_box(sat_hull_a(R, g, a), sat_hull_b(S.walls, R, g, w, isdd, bsel), hi);
             }
         }
         // the colliding pairs of this round join the pending list (their lead lanes file the results)
