@@ -1486,6 +1486,12 @@ int32_t hs_debug_dump_hull(int32_t obj, float *verts, int32_t *faces, int32_t *c
  * inertia axes of the agents to tests/golden/object_table.json (src/mgr.cpp:441-588). */
 int32_t hs_debug_object_params(int32_t obj, float *out);
 
+/* The DEVICE's reading of the scalar core's probe table (csrc/hs_core_probe.h, which lists the ops and their operands): `n`
+ * cases of 16 words in host memory `in`, 16 words each to host memory `out`, one case per lane.  Integer operands and results
+ * travel as bit patterns.  HS_ERR_INVALID_ARG, and nothing written, for a null pointer, n <= 0, n > 1 << 20 or an unknown op.
+ * tests/test_gpu_core_probe.py compares it bit for bit with the CPU oracle's reading of the same text (hsref_core_eval). */
+int32_t hs_debug_core_eval(int32_t op, int32_t n, const float *in, float *out);
+
 /* Profiling aid: one dword-per-lane coalesced copy of `bytes` bytes (read + write), used to calibrate the
  * rocprofv3 FETCH_SIZE / WRITE_SIZE counters for the simulator's access pattern. */
 int32_t hs_debug_calibrate(int64_t bytes);

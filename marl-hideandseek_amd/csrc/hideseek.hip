@@ -42,6 +42,7 @@
 #include "hs_k_attend.h"                  // likewise: emitted where launch_attend (after launch_gae_grouped) names them
 #include "hs_k_loss_scale.h"              // likewise: emitted where launch_adam_scaled (after launch_behaviour) names them; it includes hs_k_adam.h itself
 #include "hs_k_adam.h"
+#include "hs_core_probe.h"                // after every kernel header: the scalar core's probe table, read by k_core_eval alone
 
 namespace {
 
@@ -2414,6 +2415,34 @@ int32_t hs_debug_object_params(int32_t obj, float *out) {
     hipLaunchKernelGGL(k_object_params, dim3(1), dim3(64), 0, nullptr, (int)obj, d);
     HS_HIP(hipDeviceSynchronize());
     HS_HIP(hipMemcpy(out, d, 6 * sizeof(float), hipMemcpyDeviceToHost));
+    HS_HIP(hipFree(d));
+    return HS_OK;
+}
+
+// hs_debug_core_eval: the scalar core's probe table (hs_core_probe.h) as the device compiler reads it, one case per lane.
+// A template (like the kernels of hs_k_norm.h), so that the compiler emits it after the kernels there were before it and
+// numbers their functions, and with them their branch labels, as before.
+extern "C++" {
+template <int kThreads>
+__global__ void __launch_bounds__(kThreads) k_core_eval(int op, int n, const float *in, float *out) {
+    using namespace hs;
+    const int i = (int)(blockIdx.x * (unsigned)kThreads + threadIdx.x);
+    if (i >= n) return;
+    float x[kCoreWords], y[kCoreWords];
+    for (int k = 0; k < kCoreWords; ++k) x[k] = in[(size_t)i * kCoreWords + k];
+    core_eval(op, x, y);
+    for (int k = 0; k < kCoreWords; ++k) out[(size_t)i * kCoreWords + k] = y[k];
+}
+}  // extern "C++"
+int32_t hs_debug_core_eval(int32_t op, int32_t n, const float *in, float *out) {
+    if (!in || !out || n <= 0 || n > (1 << 20) || op < 0 || op >= hs::CORE_NUM_OPS) return fail(HS_ERR_INVALID_ARG, "bad argument");
+    const size_t nb = (size_t)n * hs::kCoreWords * sizeof(float);
+    float *d = nullptr;
+    HS_HIP(hipMalloc((void **)&d, 2 * nb));
+    HS_HIP(hipMemcpy(d, in, nb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_core_eval<256>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (int)op, (int)n, (const float *)d, d + (size_t)n * hs::kCoreWords);
+    HS_HIP(hipDeviceSynchronize());
+    HS_HIP(hipMemcpy(out, d + (size_t)n * hs::kCoreWords, nb, hipMemcpyDeviceToHost));
     HS_HIP(hipFree(d));
     return HS_OK;
 }

@@ -3,7 +3,13 @@
 // includes this file; nothing here includes anything of the oracle's).  Plain C++17: pure scalar functions and constants that
 // know nothing of lanes, LDS or memory layout.  Everything above this layer is written twice, separately, and the parity
 // tests compare the two; this layer is pinned from first principles (tests/test_oracle_rng_math.py,
-// tests/test_oracle_first_principles.py, tests/golden/object_table.json, tests/golden/ray_hull_cases.npz).
+// tests/test_oracle_first_principles.py, tests/golden/object_table.json, tests/golden/ray_hull_cases.npz), function by
+// function through the probe table hs_core_probe.h: tests/test_core_float64.py holds the host compile to plain float64
+// restatements (rounding-count bounds for the products and sums, exact known answers for the fused multiply-adds, the RNG
+// and aabb_overlaps, the trigonometry on its callers' domain and at every range switch, both branches of
+// quat_add_rotation, the rays against half-space clipping), tests/host/core_check.cpp runs the same table under the
+// address and undefined-behaviour sanitizers, and tests/test_gpu_core_probe.py compares the device compile with the host
+// compile word for word — the assumption that the two compilers make the same bits of this text.
 //
 // Float discipline: both sides compile this with -ffp-contract=off and without fast-math.  Every expression here is
 // written in a fixed association order with its fused multiply-adds spelled out (hs_fma: one rounding, the same on both

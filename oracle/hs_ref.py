@@ -16,7 +16,8 @@ _LIB_PATH = os.path.join(_HERE, "_build", "libhs_ref.so")
 
 def build(force=False):
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".hpp", ".cpp"))]
-    srcs.append(os.path.join(_HERE, "..", "marl-hideandseek_amd", "csrc", "hs_core.h"))   # the scalar core shared with the kernels
+    for h in ("hs_core.h", "hs_core_probe.h"):                # the scalar core shared with the kernels, and its probe table
+        srcs.append(os.path.join(_HERE, "..", "marl-hideandseek_amd", "csrc", h))
     if (not force and os.path.exists(_LIB_PATH)
             and os.path.getmtime(_LIB_PATH) >= max(os.path.getmtime(s) for s in srcs)):
         return _LIB_PATH
@@ -72,6 +73,8 @@ def lib():
         L.hsref_hull_tables.restype = None
         L.hsref_object_params.argtypes = [C.c_int32, C.c_void_p]
         L.hsref_object_params.restype = None
+        L.hsref_core_eval.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.hsref_core_eval.restype = None
         _lib = L
     return _lib
 
@@ -80,6 +83,17 @@ def object_params(obj):
     """(inv_mass, mu_s, mu_d, inv_inertia xyz) of SimObject `obj` as the oracle's solver uses them."""
     out = np.zeros(6, np.float32)
     lib().hsref_object_params(int(obj), out.ctypes.data)
+    return out
+
+
+def core_eval(op, inputs):
+    """The scalar core's probe table (csrc/hs_core_probe.h) as the host compiler reads it: `inputs` [n, 16] 32-bit words
+    (float32, or uint32 / int32 bit patterns) -> [n, 16] float32."""
+    x = np.ascontiguousarray(inputs)
+    assert x.ndim == 2 and x.shape[1] == 16 and x.dtype.itemsize == 4, (x.shape, x.dtype)
+    out = np.zeros(x.shape, np.float32)
+    if len(x):
+        lib().hsref_core_eval(int(op), len(x), x.ctypes.data, out.ctypes.data)
     return out
 
 

@@ -4,6 +4,7 @@
 #include "hs_ref_sim.hpp"
 #include "hs_ref_ckpt.hpp"
 #include "hs_ref_render.hpp"
+#include "../marl-hideandseek_amd/csrc/hs_core_probe.h"
 
 using namespace hsref;
 
@@ -155,6 +156,12 @@ void hsref_hull_tables(int32_t obj, float *verts, int32_t *faces, int32_t *count
 void hsref_object_params(int32_t obj, float *out) {
     V3 i = obj_inv_inertia(obj);
     out[0] = obj_inv_mass(obj); out[1] = obj_mu_s(obj); out[2] = obj_mu_d(obj); out[3] = i.x; out[4] = i.y; out[5] = i.z;
+}
+
+// The scalar core's probe table (csrc/hs_core_probe.h), this compiler's reading of it: n cases of 16 words in, 16 words out.
+// tests/test_core_float64.py pins it to float64, tests/test_gpu_core_probe.py compares the device's reading with it.
+void hsref_core_eval(int32_t op, int32_t n, const float *in, float *out) {
+    for (int32_t i = 0; i < n; ++i) core_eval(op, in + (size_t)i * kCoreWords, out + (size_t)i * kCoreWords);
 }
 
 }  // extern "C"

@@ -302,7 +302,9 @@ def test_header_states_the_struct_and_the_entry_points(hideseek_lib):
     assert "HS_LOSS_SCALE_STATE == hs::kLossScaleState" in host and "atomic" not in kernel
     assert len(re.findall(r"__global__", kernel)) == 4 and "for (" not in kernel      # the element loops are hs_k_adam.h's, hs_k_ppo.h's and hs_k_twohot.h's
     includes = re.findall(r'#include "(hs_\w+\.h)"', host)
-    assert includes.index("hs_k_loss_scale.h") == len(includes) - 2
+    # the last two kernel headers, in this order; behind them only the scalar core's probe table, which holds no kernel
+    assert includes[-3:] == ["hs_k_loss_scale.h", "hs_k_adam.h", "hs_core_probe.h"]
+    assert "__global__" not in open(os.path.join(csrc, "hs_core_probe.h")).read()
     entry = open(os.path.join(root, "__graft_entry__.py")).read()
     for fn in ("hs_ppo_loss_scaled", "hs_twohot_value_scaled", "hs_adam_step_scaled"):
         assert f'"{fn}"' in entry and f'"{fn}_async"' in entry

@@ -485,4 +485,5 @@ def test_header_states_the_request(hideseek_lib):
     # every kernel of the file is a template, and the file is included after the other kernel headers
     assert len(re.findall(r"__global__", kernel)) == len(re.findall(r"template <int kThreads = kAdamThreads>\n__global__", kernel)) == 2
     includes = re.findall(r'#include "(hs_\w+\.h)"', host)
-    assert includes[-1] == "hs_k_adam.h"
+    assert includes[-2:] == ["hs_k_adam.h", "hs_core_probe.h"]        # behind it only the scalar core's probe table, which holds no kernel
+    assert "__global__" not in open(os.path.join(csrc, "hs_core_probe.h")).read()
