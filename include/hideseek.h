@@ -826,8 +826,9 @@ int32_t hs_dense_norm_act_backward_async(hs_sim *sim, void *hip_stream, const hs
  * beta outside [0, 1); two of the arrays overlapping; a call before hs_init or inside an open step.  The call reads no
  * export and writes no simulator state.  hs_adam_step is ordered after the device's legacy default stream and blocking;
  * hs_adam_step_async enqueues on the caller's hipStream_t without synchronising.
- * Not part of this call: parameters spread over several devices and the reduction of gradients between shards, and a
- * bf16 / f16 shadow copy of the weights (the modules cast their weights inside the autograd graph). */
+ * Not part of this call: a bf16 / f16 shadow copy of the weights (the modules cast their weights inside the autograd
+ * graph), and parameters spread over several devices: data-parallel training keeps one replica per shard, reduces the
+ * replicas' gradients with hs_reduce_gradients (below) and makes this call on every replica. */
 enum { HS_ADAM_MAX_GRID = 256, HS_ADAM_STATE = 4, HS_ADAM_STATS = 4 };
 typedef struct hs_adam_request {
     float   *params;              /* [n] f32, 16-byte aligned: updated in place */
@@ -847,6 +848,48 @@ typedef struct hs_adam_request {
 } hs_adam_request;                /* 104 bytes */
 int32_t hs_adam_step(hs_sim *sim, const hs_adam_request *req);
 int32_t hs_adam_step_async(hs_sim *sim, void *hip_stream, const hs_adam_request *req);
+
+/* The gradient reduction of data-parallel training: every shard's replica has the gradient of the mean loss over its own
+ * active samples in a flat f32 buffer of n elements, and dst receives the gradient of the mean over ALL shards' active
+ * samples, the buffers weighted by the shards' counts, in one kernel (csrc/hs_k_reduce.h).  Every replica makes the same
+ * call on copies of the same buffers and so holds the same bits: there is no broadcast and no collective library.
+ * madrona_learn is not part of the reference's tree; the rule is this project's.  The arithmetic is the contract.
+ * With c_g = count[g], g < shards:
+ *   C = c_0 + c_1 + ...        in f64, in index order, over the shards with c_g != 0
+ *   w_g = (float)(c_g / C)     the division correctly rounded, rounded to f32 once
+ * A shard with c_g == 0 is left out by a uniform branch: its buffer is not read and not multiplied by 0, so an infinity or
+ * a NaN in it does not reach dst.  Per element, in IEEE f32, unfused, over the remaining shards a < ... < g in index order:
+ *   acc = w_a * x_a;   acc = acc + w_g * x_g;   dst = acc
+ * If every count is 0, dst is +0.  The counts are taken as they are: a NaN count is not 0, so C and every weight are NaN
+ * and so is dst, which hs_adam_step then skips; a NaN or an infinity in a counted buffer propagates likewise.  With one
+ * shard and c_0 > 0 the weight is exactly 1 and dst is src[0] bit for bit.  An element's result depends on nothing but
+ * its `shards` inputs and the counts: not on its position, on n or on the grid.  No atomics: the same inputs give the same
+ * bits on every call.  total, f64 [1] or null, receives C.
+ * dst may be exactly one src[g], the same address: a lane reads its quad from every source before it writes it.
+ * Otherwise dst must be disjoint from every source; a partial overlap is refused.  The sources may overlap each other.
+ * A lane reads and writes a quad of 4 floats as one piece of 16 bytes, so every src[g] and dst must be 16-byte aligned;
+ * the short last quad goes by element and nothing past n is read or written.  (shards + 1) * 4 n bytes are moved.
+ * Everything is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a
+ * null request; shards outside [1, HS_REDUCE_MAX_SHARDS]; n < 1 or n >= 2^31; a null dst, count or src[g < shards]; dst or
+ * a src[g] not 16-byte aligned, count or total not 8-byte aligned; dst overlapping a src[g] without being it, or being
+ * more than one of them; count overlapping dst; total overlapping dst, count or a src[g]; a call before hs_init or inside
+ * an open step.  src[g >= shards] is not looked at.  Every pointer is on the handle's device.  The call reads no export
+ * and writes no simulator state.  hs_reduce_gradients is ordered after the device's legacy default stream and blocking;
+ * hs_reduce_gradients_async enqueues on the caller's hipStream_t without synchronising.
+ * Not part of this call: moving the buffers between devices (the caller copies them next to each other first;
+ * gpu_hideseek.trainer.ShardedTrainer does), one process per device, RCCL, overlapping the reduction with the backward
+ * pass, and a reduce-scatter form for many shards. */
+enum { HS_REDUCE_MAX_SHARDS = 16 };
+typedef struct hs_grad_reduce_request {
+    const float *src[HS_REDUCE_MAX_SHARDS];   /* each [n] f32, 16-byte aligned; the first `shards` are read */
+    const double *count;          /* [shards] f64 on the device: each shard's number of active samples */
+    float   *dst;                 /* [n] f32, 16-byte aligned; may be one src[g] */
+    int64_t n;                    /* elements, 1 <= n < 2^31 */
+    int32_t shards;               /* 1 <= shards <= HS_REDUCE_MAX_SHARDS */
+    double *total;                /* [1] f64 on the device, or null: receives C */
+} hs_grad_reduce_request;         /* 168 bytes */
+int32_t hs_reduce_gradients(hs_sim *sim, const hs_grad_reduce_request *req);
+int32_t hs_reduce_gradients_async(hs_sim *sim, void *hip_stream, const hs_grad_reduce_request *req);
 
 /* The dynamic loss scale of float16 training: a scale S on the device that hs_ppo_loss_scaled and hs_twohot_value_scaled
  * multiply their gradients by, and that hs_adam_step_scaled divides out again, halves when the gradient norm overflows

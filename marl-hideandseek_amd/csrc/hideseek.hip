@@ -40,6 +40,7 @@
 #include "hs_k_pack_routed.h"             // likewise: emitted where launch_pack_routed (after launch_league) names it
 #include "hs_k_sample_routed.h"           // likewise: emitted where launch_sample_routed (after launch_pack_routed) names it
 #include "hs_k_attend.h"                  // likewise: emitted where launch_attend (after launch_gae_grouped) names them
+#include "hs_k_reduce.h"                  // likewise: emitted where launch_reduce (at the end of this file) names it; it includes hs_k_adam.h itself
 #include "hs_k_loss_scale.h"              // likewise: emitted where launch_adam_scaled (after launch_behaviour) names them; it includes hs_k_adam.h itself
 #include "hs_k_adam.h"
 #include "hs_core_probe.h"                // after every kernel header: the scalar core's probe table, read by k_core_eval alone
@@ -1717,6 +1718,49 @@ int launch_adam_scaled(hs_sim *s, hipStream_t strm, const hs_adam_request *r, co
 }
 }  // namespace
 
+// ---- the gradient reduction (hs_k_reduce.h) ----
+namespace {
+static_assert(HS_REDUCE_MAX_SHARDS == hs::kReduceMaxShards, "hs_grad_reduce_request and k_reduce agree");
+static_assert(sizeof(hs_grad_reduce_request) == 168 && offsetof(hs_grad_reduce_request, count) == 128 && offsetof(hs_grad_reduce_request, dst) == 136 &&
+              offsetof(hs_grad_reduce_request, n) == 144 && offsetof(hs_grad_reduce_request, shards) == 152 && offsetof(hs_grad_reduce_request, total) == 160,
+              "hs_grad_reduce_request layout (gpu_hideseek/optim.py mirrors it)");
+
+int check_reduce(hs_sim *s, const hs_grad_reduce_request *r) {
+    const Check c{"hs_reduce_gradients"};
+    if (!r) return c.bad("null request");
+    if (r->shards < 1 || r->shards > HS_REDUCE_MAX_SHARDS) return c.bad("shards must be in [1, HS_REDUCE_MAX_SHARDS]");
+    if (r->n < 1 || r->n >= (int64_t)1 << 31) return c.bad("n must be at least 1 and below 2^31");
+    if (!r->dst) return c.bad("null dst");
+    if (!r->count) return c.bad("null count");
+    for (int g = 0; g < r->shards; ++g)
+        if (!r->src[g]) return c.bad("null src[" + std::to_string(g) + "]");
+    for (int g = 0; g < r->shards; ++g)
+        if (!aligned(16, {r->src[g]})) return c.bad("src[" + std::to_string(g) + "] must be 16-byte aligned");
+    if (!aligned(16, {r->dst})) return c.bad("dst must be 16-byte aligned");
+    if (!aligned(8, {r->count, r->total})) return c.bad("count and total must be 8-byte aligned");
+    const uintptr_t bytes = (uintptr_t)r->n * 4;
+    const ByteRange dst = range("dst", r->dst, bytes), count = range("count", r->count, (uintptr_t)r->shards * sizeof(double)),
+                    total = range("total", r->total, sizeof(double));
+    int same = 0;                                                          // dst may be exactly one source, the same address
+    for (int g = 0; g < r->shards; ++g) {
+        const ByteRange src = range("src", r->src[g], bytes);
+        if (r->src[g] == r->dst) ++same;
+        else if (overlap(dst, src)) return c.bad("dst overlaps src[" + std::to_string(g) + "] without being it");
+        if (overlap(total, src)) return c.bad("total overlaps src[" + std::to_string(g) + "]");
+    }
+    if (same > 1) return c.bad("dst is more than one of the sources");
+    if (overlap(count, dst)) return c.bad("count overlaps dst");
+    if (overlap(total, dst)) return c.bad("total overlaps dst");
+    if (overlap(total, count)) return c.bad("total overlaps count");
+    return c.handle_ready(s);
+}
+
+// One k_reduce over the quads (the request has passed check_reduce).  Defined at the end of the file: the kernel is a
+// template, emitted where its launch names it, and behind every kernel that was there before it the compiler numbers
+// their functions, and with them their branch labels, as before.
+int launch_reduce(hs_sim *s, hipStream_t strm, const hs_grad_reduce_request *r);
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -2220,6 +2264,10 @@ int32_t hs_adam_step_scaled(hs_sim *s, const hs_adam_request *req, const hs_loss
 int32_t hs_adam_step_scaled_async(hs_sim *s, void *hip_stream, const hs_adam_request *req, const hs_loss_scale *ls) {
     return call_async(s, hip_stream, check_adam_scaled, launch_adam_scaled, req, ls);
 }
+int32_t hs_reduce_gradients(hs_sim *s, const hs_grad_reduce_request *req) { return call_blocking(s, check_reduce, launch_reduce, req); }
+int32_t hs_reduce_gradients_async(hs_sim *s, void *hip_stream, const hs_grad_reduce_request *req) {
+    return call_async(s, hip_stream, check_reduce, launch_reduce, req);
+}
 int32_t hs_gather_sequences(hs_sim *s, const hs_gather_request *req) { return call_blocking(s, check_gather, launch_gather, req); }
 int32_t hs_gather_sequences_async(hs_sim *s, void *hip_stream, const hs_gather_request *req) { return call_async(s, hip_stream, check_gather, launch_gather, req); }
 int32_t hs_episode_stats(hs_sim *s, const hs_episode_request *req) { return call_blocking(s, check_episode, launch_episode, req); }
@@ -2496,3 +2544,15 @@ int32_t hs_last_step_kernel_ms(hs_sim *s, float out_ms[3]) {
 }
 
 }  // extern "C"
+
+// ---- the gradient reduction (hs_k_reduce.h): its launch, the last kernel the file names ----
+namespace {
+int launch_reduce(hs_sim *, hipStream_t strm, const hs_grad_reduce_request *r) {
+    hs::ReduceArgs a = {};
+    for (int g = 0; g < r->shards; ++g) a.src[g] = r->src[g];
+    a.count = r->count; a.dst = r->dst; a.total = r->total; a.n = (int)r->n; a.shards = r->shards;
+    hipLaunchKernelGGL(hs::k_reduce<>, dim3(hs::adam_grid(a.n, hs::kAdamStepMaxGrid)), dim3(hs::kAdamThreads), 0, strm, a);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace

@@ -367,6 +367,18 @@ class HideAndSeekSimulator:
         return _optim.compute(self, params, grads, m, v, state, stream, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                               max_grad_norm=max_grad_norm, grad_scale=grad_scale, zero_grad=zero_grad, stats=stats, loss_scale=loss_scale)
 
+    def reduce_gradients(self, srcs, counts, out=None, total=None, stream=None):
+        """The gradient of the mean over several shards' active samples from the shards' own flat gradient buffers, in one
+        kernel (gpu_hideseek.optim; hs_reduce_gradients, whose header comment states the arithmetic: the weights
+        counts[g] / sum(counts) in float64, the weighted sum in IEEE f32 in index order, a shard whose count is 0 left
+        out).  `srcs` is a list of 1 to 16 float32 tensors [n], contiguous and 16-byte aligned, all on this handle's device;
+        `counts` is float64 [len(srcs)].  `out` is None (allocated) or a float32 tensor [n] that is one of the sources
+        or overlaps none; `total`, True or a float64 tensor [1], receives the sum of the counts.  stream=None blocks; a
+        torch.cuda.Stream or raw handle enqueues there without synchronising.  The same inputs give the same bits on every
+        call.  Returns {"out": tensor[, "total": tensor]}."""
+        from . import optim as _optim
+        return _optim.reduce_gradients(self, srcs, counts, out, total, stream)
+
     def gather_sequences(self, index, fields, *, chunks, chunk_steps, rows, bad=None, stream=None):
         """Cut the m sequences `index` (int32 [m] on the device; id = chunk * rows + row) out of a rollout of `chunks` x
         `chunk_steps` steps over `rows` rows, every field in one kernel (gpu_hideseek.rollout; hs_gather_sequences, whose

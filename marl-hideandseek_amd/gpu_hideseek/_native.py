@@ -93,7 +93,7 @@ def load():
     for fn, extra in (("hs_pack_policy_inputs", []), ("hs_pack_policy_inputs_normalized", [C.c_void_p]), ("hs_obs_norm_update", []),
                       ("hs_sample_actions", []), ("hs_compute_gae", []), ("hs_ppo_loss", []), ("hs_twohot_value", []),
                       ("hs_entity_encode", []), ("hs_entity_encode_backward", []), ("hs_lstm_cell", []), ("hs_lstm_cell_backward", []),
-                      ("hs_dense_norm_act", []), ("hs_dense_norm_act_backward", []), ("hs_adam_step", []), ("hs_gather_sequences", []),
+                      ("hs_dense_norm_act", []), ("hs_dense_norm_act_backward", []), ("hs_adam_step", []), ("hs_reduce_gradients", []), ("hs_gather_sequences", []),
                       ("hs_episode_stats", []), ("hs_behaviour_stats", []), ("hs_league_step", []), ("hs_league_step_scheduled", []), ("hs_pack_policy_inputs_routed", []),
                       ("hs_sample_actions_routed", []), ("hs_compute_gae_grouped", []), ("hs_entity_attend", []),
                       ("hs_entity_attend_backward", []), ("hs_ppo_loss_scaled", [C.c_void_p]), ("hs_twohot_value_scaled", [C.c_void_p]),

@@ -29,14 +29,20 @@ loss_scale=) and that Adam(..., loss_scale=LossScale(device)) divides out again;
 and halves S, growth_interval good steps in a row double it.  Nothing of it reads the device from the host.  The rule is
 torch.cuda.amp.GradScaler's and flax's DynamicScale's, the project's statement of it.
 
-Not part of this module: parameters spread over several devices, the reduction of gradients between shards (there is no
-ShardedSimulator form), a bfloat16 / float16 shadow copy of the weights (the modules cast their weights inside the
-autograd graph), and a loss scale per parameter group.
+Several devices (reduce_gradients; hs_reduce_gradients, csrc/hs_k_reduce.h): data-parallel training keeps one replica of
+the parameters and one Adam per shard, and before every step each replica replaces its gradient with the mean over all
+shards' active samples, the shards' flat gradient buffers weighted by their counts, in one kernel and in a fixed order.
+Every replica reduces copies of the same buffers and so steps with the same bits: nothing is broadcast.  host_reduce is
+the numpy restatement of that arithmetic; trainer.ShardedTrainer is the loop built on it.
+
+Not part of this module: parameters SPREAD over several devices (every replica holds all of them), one process per device,
+RCCL, overlapping the reduction with the backward pass, a reduce-scatter form for many shards, a bfloat16 / float16 shadow
+copy of the weights (the modules cast their weights inside the autograd graph), and a loss scale per parameter group.
 """
 import ctypes as C
 import math
 
-from ._request import LOSS_SCALE_STATE, _OUTPUT, _above_zero, _disjoint, _finite, _loss_scale_input, _run, _tensor
+from ._request import LOSS_SCALE_STATE, _OUTPUT, _above_zero, _disjoint, _finite, _loss_scale_input, _overlap, _run, _tensor
 
 ALIGN = 16                # bytes: params, grads, m and v
 PAD = 64                  # elements: every parameter of a flat buffer starts at a multiple of it
@@ -59,6 +65,15 @@ class HsLossScale(C.Structure):
     """hs_loss_scale (include/hideseek.h)."""
     _fields_ = [("state", C.c_void_p), ("growth", C.c_double), ("backoff", C.c_double), ("min_scale", C.c_double), ("max_scale", C.c_double),
                 ("growth_interval", C.c_int32), ("reserved", C.c_int32)]
+
+
+REDUCE_MAX_SHARDS = 16    # HS_REDUCE_MAX_SHARDS
+
+
+class HsGradReduceRequest(C.Structure):
+    """hs_grad_reduce_request (include/hideseek.h)."""
+    _fields_ = [("src", C.c_void_p * REDUCE_MAX_SHARDS), ("count", C.c_void_p), ("dst", C.c_void_p), ("n", C.c_int64), ("shards", C.c_int32),
+                ("total", C.c_void_p)]
 
 
 def _power_of_two(name, x, lo, hi, bounds):
@@ -237,6 +252,84 @@ def stats_to_metrics(stats):
     """The statistics of a step as Python numbers (this copies to the host and so waits for the step)."""
     gnorm, clip, skipped, step = stats.detach().cpu().tolist()
     return {"grad_norm": gnorm, "clip": clip, "skipped": bool(skipped), "step": int(step)}
+
+
+# ---- the reduction of gradients between shards ----
+def host_reduce(srcs, counts):
+    """hs_reduce_gradients in numpy, operation by operation as include/hideseek.h states it: (dst float32 [n], C).  The
+    counts, their sum C (in index order, over the counts that are not 0) and the quotients are float64; a weight is the
+    quotient rounded to float32 once; every product and every sum is float32, the first product taken as it is and the
+    others added in index order.  A shard whose count is 0 is left out, whatever it holds; with every count 0 the result
+    is +0."""
+    import numpy as np
+    srcs = [np.asarray(x, np.float32).reshape(-1) for x in srcs]
+    counts = np.asarray(counts, np.float64).reshape(-1)
+    if not 1 <= len(srcs) <= REDUCE_MAX_SHARDS or counts.shape[0] != len(srcs) or any(x.shape != srcs[0].shape for x in srcs):
+        raise ValueError(f"1 to {REDUCE_MAX_SHARDS} arrays of one length and one count for each expected")
+    live = [g for g in range(len(srcs)) if counts[g] != 0.0]
+    total = np.float64(0.0)
+    acc = np.zeros(srcs[0].shape[0], np.float32)
+    with np.errstate(all="ignore"):
+        for g in live:
+            total = total + counts[g]
+        for k, g in enumerate(live):
+            prod = np.float32(counts[g] / total) * srcs[g]
+            acc = prod if k == 0 else acc + prod
+    assert acc.dtype == np.float32
+    return acc, float(total)
+
+
+def reduce_request(gpu_id, srcs, counts, out=None, total=None):
+    """Validate one reduction on GPU `gpu_id`: `srcs`, a list of 1 to REDUCE_MAX_SHARDS float32 tensors [n] (contiguous,
+    16-byte aligned), `counts` float64 [len(srcs)], `out` None or True (allocated) or a float32 tensor [n] that is one of
+    the sources (the same address) or overlaps none, `total` None, True or a float64 tensor [1] that overlaps nothing else.
+    Returns ({"out": tensor[, "total": tensor]}, HsGradReduceRequest).  Raises ValueError before the library is involved."""
+    import torch
+    dev = torch.device("cuda", gpu_id)
+    if isinstance(srcs, torch.Tensor) or not isinstance(srcs, (list, tuple)) or not 1 <= len(srcs) <= REDUCE_MAX_SHARDS:
+        raise ValueError(f"srcs must be a list of 1 to {REDUCE_MAX_SHARDS} torch tensors, one per shard")
+    G = len(srcs)
+    if not isinstance(srcs[0], torch.Tensor):
+        raise ValueError("srcs[0] must be a torch tensor")
+    if srcs[0].dim() != 1 or not 1 <= srcs[0].shape[0] < 2 ** 31:
+        raise ValueError(f"srcs[0] must be a contiguous float32 tensor of shape (n,), 1 <= n < 2^31, on {dev}: its shape is {tuple(srcs[0].shape)}")
+    n = int(srcs[0].shape[0])
+    inputs = [(f"srcs[{g}]", t) for g, t in enumerate(srcs)]
+    for name, t in inputs:
+        _tensor(name, t, (n,), ("float32",), dev, align=ALIGN)
+    _tensor("counts", counts, (G,), ("float64",), dev)
+    inputs.append(("counts", counts))
+    given = []
+    if out is not None and out is not True:
+        _tensor("out", out, (n,), ("float32",), dev, _OUTPUT, align=ALIGN)
+        given.append(("out", out))
+    if total is not None and total is not False and total is not True:
+        _tensor("total", total, (1,), ("float64",), dev, _OUTPUT)
+        given.append(("total", total))
+    for k, (name, t) in enumerate(given):                    # out may be one source itself; total overlaps nothing
+        same = [other for other, x in inputs[:G] if name == "out" and x.data_ptr() == t.data_ptr()]
+        if len(same) > 1:
+            raise ValueError(f"out is more than one of the sources: {', '.join(same)}")
+        for other, x in inputs + given[:k]:
+            if other not in same and _overlap(t, x):
+                raise ValueError(f"{name} overlaps {other}" + (" without being it" if other.startswith("srcs") and name == "out" else ""))
+    _disjoint([], inputs + given, dev)                       # the device, last
+    res = {"out": torch.empty(n, dtype=torch.float32, device=dev) if out is None or out is True else out}
+    if total is not None and total is not False:
+        res["total"] = torch.empty(1, dtype=torch.float64, device=dev) if total is True else total
+    req = HsGradReduceRequest()
+    for g, t in enumerate(srcs):
+        req.src[g] = t.data_ptr()
+    req.count, req.dst, req.n, req.shards = counts.data_ptr(), res["out"].data_ptr(), n, G
+    req.total = res["total"].data_ptr() if "total" in res else None
+    return res, req
+
+
+def reduce_gradients(sim, srcs, counts, out=None, total=None, stream=None):
+    """HideAndSeekSimulator.reduce_gradients."""
+    res, req = reduce_request(sim.gpu_id, srcs, counts, out, total)
+    _run(sim, "hs_reduce_gradients", req, stream)
+    return res
 
 
 # ---- the flat buffer ----

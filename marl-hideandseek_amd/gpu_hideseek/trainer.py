@@ -8,7 +8,8 @@ defaults are jax_train.py's, the order of the calls below is the project's.
         metrics = tr.update_iter()          # collect() then update(); one read of the device at its end
 
 Composition only: every kernel is another module's (policy_inputs, policy, action_sampling, value_head, advantages,
-rollout, ppo_loss, optim).  Single device: there is no ShardedSimulator form (optim states the same limit).
+rollout, ppo_loss, optim).  Trainer is the single-device loop; ShardedTrainer (at the end of this module) is the same loop
+over the shards of a ShardedSimulator, one replica per shard, their gradients reduced by optim.reduce_gradients.
 
 collect() fills the rollout (rollout.py states what slot t holds).  Per slot: sim.step() -> the done and self_mask exports
 into clear[t] and mask[t] -> the carried LSTM states zeroed in the rows whose episode starts with this observation or which
@@ -128,11 +129,13 @@ class _NoSpan:
 
 
 class PhaseTimer:
-    """Device events around the phases of collect() and update() (PHASES), for tools/train.py --phases: set
-    trainer.phases = PhaseTimer(); totals() waits for the device and returns {phase: ms} since the last totals()."""
+    """Device events around the phases of collect() and update() (`names`, by default PHASES), for tools/train.py
+    --phases: set trainer.phases = PhaseTimer(); totals() waits for the device and returns {phase: ms} since the last
+    totals()."""
 
-    def __init__(self):
-        self.events = {k: [] for k in PHASES}
+    def __init__(self, names=PHASES):
+        self.names = tuple(names)
+        self.events = {k: [] for k in self.names}
 
     def __call__(self, name):
         return _Span(self.events[name])
@@ -141,7 +144,7 @@ class PhaseTimer:
         import torch
         torch.cuda.synchronize()
         out = {k: sum(a.elapsed_time(b) for a, b in ev) for k, ev in self.events.items()}
-        self.events = {k: [] for k in PHASES}
+        self.events = {k: [] for k in self.names}
         return out
 
 
@@ -207,60 +210,92 @@ class Trainer:
         for x in (t for s in self.state for t in s):
             x.masked_fill_(zero, 0)
 
+    # collect() in the pieces a slot is made of (ShardedTrainer runs them slot by slot over its members).  All of them are
+    # called under on_current_stream() and torch.no_grad().
+    def _after_step(self, t):
+        """After the sim.step() that leads to slot t: close slot t - 1, take clear[t] and mask[t], zero the carried states."""
+        buf = self.rollout
+        if t > 0:
+            self._close_slot(t - 1)
+        buf.clear[t].copy_(self._export("done")[:, 0])
+        buf.mask[t].copy_(self._export("self_mask")[:, 0])
+        with self._phase("rollout_forward"):
+            self._zero_carried(buf.clear[t], buf.mask[t], buf.mask[t - 1] if t > 0 else buf.mask[t])
+
+    def _resume_slot(self):
+        """Slot 0 without a step: the closing step of the last collect() led here, and zeroed."""
+        buf = self.rollout
+        buf.clear[0].copy_(self.clear)
+        buf.mask[0].copy_(self._export("self_mask")[:, 0])
+
+    def _slot(self, t):
+        """Slot t from the exports: pack, at a chunk's first slot the snapshot of the carried states, forward, value, actions."""
+        sim, buf, net, cfg = self.sim, self.rollout, self.net, self.cfg
+        L = buf.chunk_steps
+        self.stepped = False
+        with self._phase("pack"):
+            sim.pack_policy_inputs(actor=buf.actor[t], critic=buf.critic[t], moments=buf.moments[t], normaliser=self.normaliser)
+        if t % L == 0:
+            k = t // L
+            for dst, src in ((buf.actor_h, self.state[0][0]), (buf.actor_c, self.state[0][1]), (buf.critic_h, self.state[1][0]), (buf.critic_c, self.state[1][1])):
+                dst[k].copy_(src)
+        with self._phase("rollout_forward"):
+            logits, critic_logits, self.state = net(sim, buf.actor[t], buf.critic[t], self.state, None)
+            sim.value_head(critic_logits, value=buf.value[t])
+            out = sim.sample_actions(logits, buckets=net.buckets, seed=(cfg.seed, 0), counter=self.counter, log_prob=buf.log_prob[t])
+            buf.action[t].copy_(out["action"].reshape(self.rows, -1))
+        self.counter += 1
+
+    def _after_closing_step(self):
+        """After the sim.step() past the last slot: close slot T - 1, keep its done as the next clear[0], zero the carried states."""
+        buf = self.rollout
+        T = buf.steps
+        self.stepped = True
+        self._close_slot(T - 1)
+        self.clear.copy_(buf.done[T - 1])
+        with self._phase("rollout_forward"):
+            self._zero_carried(self.clear, self._export("self_mask")[:, 0], buf.mask[T - 1])
+
+    def _gae(self):
+        """The bootstrap value, then advantages, returns and their moments over the rollout."""
+        buf, cfg = self.rollout, self.cfg
+        self.bootstrap_value()
+        self.sim.compute_advantages(buf.reward, buf.done, buf.value, self.bootstrap, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, mask=buf.mask,
+                                    advantages=buf.advantage, returns=buf.returns, moments=self.adv_moments)
+
+    def _fold_moments(self, moments):
+        """One batch of slot moments [K, 593] into the normaliser."""
+        if self.normaliser is not None:
+            self.normaliser.update(self.sim, moments)
+
+    def _step_trackers(self):
+        if self.episodes is not None:
+            self.episodes.step()
+        if self.behaviour is not None:
+            self.behaviour.step()
+
     def collect(self):
         """Fill the rollout with steps_per_update slots, the bootstrap value, the advantages and returns, and fold the
         slots' moments into the normaliser."""
         import torch
-        sim, buf, net, cfg = self.sim, self.rollout, self.net, self.cfg
-        T, L = buf.steps, buf.chunk_steps
+        sim, buf = self.sim, self.rollout
         with on_current_stream(), torch.no_grad():
-            for t in range(T):
+            for t in range(buf.steps):
                 if t > 0 or not self.stepped:
                     with self._phase("sim"):
                         sim.step()
-                    if self.episodes is not None:
-                        self.episodes.step()
-                    if self.behaviour is not None:
-                        self.behaviour.step()
-                    if t > 0:
-                        self._close_slot(t - 1)
-                    buf.clear[t].copy_(self._export("done")[:, 0])
-                    buf.mask[t].copy_(self._export("self_mask")[:, 0])
-                    with self._phase("rollout_forward"):
-                        self._zero_carried(buf.clear[t], buf.mask[t], buf.mask[t - 1] if t > 0 else buf.mask[t])
-                else:                                    # the closing step of the last collect() led here, and zeroed
-                    buf.clear[0].copy_(self.clear)
-                    buf.mask[0].copy_(self._export("self_mask")[:, 0])
-                self.stepped = False
-                with self._phase("pack"):
-                    sim.pack_policy_inputs(actor=buf.actor[t], critic=buf.critic[t], moments=buf.moments[t], normaliser=self.normaliser)
-                if t % L == 0:
-                    k = t // L
-                    for dst, src in ((buf.actor_h, self.state[0][0]), (buf.actor_c, self.state[0][1]), (buf.critic_h, self.state[1][0]), (buf.critic_c, self.state[1][1])):
-                        dst[k].copy_(src)
-                with self._phase("rollout_forward"):
-                    logits, critic_logits, self.state = net(sim, buf.actor[t], buf.critic[t], self.state, None)
-                    sim.value_head(critic_logits, value=buf.value[t])
-                    out = sim.sample_actions(logits, buckets=net.buckets, seed=(cfg.seed, 0), counter=self.counter, log_prob=buf.log_prob[t])
-                    buf.action[t].copy_(out["action"].reshape(self.rows, -1))
-                self.counter += 1
+                    self._step_trackers()
+                    self._after_step(t)
+                else:
+                    self._resume_slot()
+                self._slot(t)
             with self._phase("sim"):
                 sim.step()
-            if self.episodes is not None:
-                self.episodes.step()
-            if self.behaviour is not None:
-                self.behaviour.step()
-            self.stepped = True
-            self._close_slot(T - 1)
-            self.clear.copy_(buf.done[T - 1])
-            with self._phase("rollout_forward"):
-                self._zero_carried(self.clear, self._export("self_mask")[:, 0], buf.mask[T - 1])
+            self._step_trackers()
+            self._after_closing_step()
             with self._phase("gae"):                     # the bootstrap's critic-only forward included
-                self.bootstrap_value()
-                sim.compute_advantages(buf.reward, buf.done, buf.value, self.bootstrap, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, mask=buf.mask,
-                                       advantages=buf.advantage, returns=buf.returns, moments=self.adv_moments)
-                if self.normaliser is not None:
-                    self.normaliser.update(sim, buf.moments)
+                self._gae()
+                self._fold_moments(buf.moments)
 
     def bootstrap_value(self):
         """The critic's value of the observation in the simulator's exports into self.bootstrap, by a critic-only forward
@@ -418,4 +453,239 @@ class Trainer:
             self.normaliser.load_state_dict(d["normaliser"])
         self.generator.set_state(d["generator"].cpu())      # a state loaded with map_location is on the device
         self.update_index, self.counter = int(d["update_index"]), int(d["counter"])
+        self.stepped = False
+
+
+# ---- the same loop over the shards of a ShardedSimulator ----
+SHARDED_PHASES = PHASES + ("reduce",)     # the staging copies between the devices and the reduction, per minibatch
+
+
+class ShardedTrainer:
+    """Data-parallel training over a ShardedSimulator (after ssim.init()): one Trainer ("member") per shard, on the shard's
+    device, in this process and on one host thread, as ShardedSimulator itself.  Every member is built from the same seed
+    (or from a deep copy of `net`), so the flat parameter buffers start bit-equal, and they stay so: every member learns on
+    its own shard's rollout but steps with the same gradient, the mean over ALL shards' active samples, which every member
+    computes for itself from copies of the same buffers in a fixed order (optim.reduce_gradients, hs_reduce_gradients).
+    Nothing is broadcast and there is no collective library.
+
+    collect() goes slot by slot over all shards: ssim.step() (every shard starts before any is waited for), the trackers,
+    then each member's own work for the slot (Trainer's per-slot methods) on its device.  After every member's GAE the
+    members' adv_moments, raw sums, are copied to every device and added in shard order, so hs_ppo_loss normalises the
+    advantages with the mean and std over all shards; every member's normaliser is updated with the [G T, 593] stack of
+    all shards' slot moments, shard-major, one batch.
+    run_epochs(): per epoch every member draws its own permutation (member g's generator is seeded cfg.seed + g); per
+    minibatch part every member runs forward_backward on its own part; then every copy is enqueued before any reduction
+    (for every device d and shard g != d, member g's gradient buffer into row g of d's staging buffer [G, n] and its
+    count of active samples, _ppo_out[6], into d's count vector; torch orders a copy between devices on both devices'
+    current streams, and no host wait is added); then every member reduces in place into its own gradient buffer, its own
+    row read where it lies; then every member's own opt.step().  Both losses divide by a shard's count c_g, so
+    sum (c_g / C) grad_g is the gradient of the mean over all C active samples.  The loss scale is the same S on every
+    replica, because every replica sees the same norm.
+    metrics(): the shards' ppo_stats and value_stats (raw sums) added on shard 0's device, the Adam statistics shard 0's,
+    one read; Trainer's keys plus "shards" and "count" (C of the last minibatch).  `episodes` and `behaviour` take a
+    tracker with a step() method, or a list of them (one episodes.EpisodeStats per shard, say): collect() calls step()
+    after every ssim.step().  `phases`: a PhaseTimer(SHARDED_PHASES) when every shard is on one device.
+    The shards may hold different numbers of worlds; a config that does not fit one of them raises, naming the shard.
+    Not here: Population and League over shards, one process per GPU, RCCL, overlapping the reduction with the backward
+    pass, a reduce-scatter form for many shards."""
+
+    def __init__(self, ssim, cfg=None, net=None, fused=True):
+        import copy
+        import torch
+        self.ssim, self.cfg, self.fused = ssim, TrainConfig() if cfg is None else cfg, bool(fused)
+        cfg = self.cfg
+        if not 1 <= len(ssim.shards) <= optim.REDUCE_MAX_SHARDS:
+            raise ValueError(f"{len(ssim.shards)} shards: 1 to {optim.REDUCE_MAX_SHARDS} expected")
+        self.ranges = [tuple(r) for r in ssim.ranges]
+        self.members = []
+        for g, s in enumerate(ssim.shards):
+            try:
+                m = Trainer(s, cfg, net=None if net is None else copy.deepcopy(net), fused=fused)
+            except ValueError as e:
+                raise ValueError(f"shard {g} ({s.num_worlds} worlds on GPU {s.gpu_id}): {e}") from None
+            m.generator.manual_seed(cfg.seed + g)
+            self.members.append(m)
+        G, first = len(self.members), self.members[0]
+        self.shards, self.device, self.dtype = G, first.device, first.dtype
+        self.rows = sum(m.rows for m in self.members)
+        n = first.opt.flat.params.numel()
+        for g, m in enumerate(self.members):
+            if m.opt.layout() != first.opt.layout() or not torch.equal(m.opt.flat.params.to(self.device), first.opt.flat.params):
+                raise ValueError(f"shard {g}'s parameters differ from shard 0's")
+        # per device: the other shards' gradients (row d itself is not used: the member's own buffer is read where it lies),
+        # the counts, and C
+        self.stage = [torch.zeros(G, n, dtype=torch.float32, device=m.device) for m in self.members]
+        self.counts = [torch.zeros(G, dtype=torch.float64, device=m.device) for m in self.members]
+        self.totals = [torch.zeros(1, dtype=torch.float64, device=m.device) for m in self.members]
+        self.stepped = False
+        self.episodes, self.behaviour = None, None
+        self._phases = None
+
+    # ---- what the members share ----
+    @property
+    def update_index(self):
+        return self.members[0].update_index
+
+    @property
+    def phases(self):
+        return self._phases
+
+    @phases.setter
+    def phases(self, timer):
+        if timer is not None and len({m.device for m in self.members}) != 1:
+            raise ValueError("phases: the events of one PhaseTimer are for one device, and the shards are on several")
+        self._phases = timer
+        for m in self.members:
+            m.phases = timer
+
+    def _phase(self, name):
+        return _NoSpan() if self._phases is None else self._phases(name)
+
+    def _each(self):
+        """(g, member) with the member's device as torch's current one."""
+        import torch
+        for g, m in enumerate(self.members):
+            with torch.cuda.device(m.device):
+                yield g, m
+
+    def _step(self):
+        with self._phase("sim"):
+            self.ssim.step()
+        for hook in (self.episodes, self.behaviour):
+            for tracker in ([] if hook is None else hook if isinstance(hook, (list, tuple)) else [hook]):
+                tracker.step()
+
+    # ---- the rollout ----
+    def collect(self):
+        """Fill every member's rollout, slot by slot over all shards; then the global advantage moments and the
+        normalisers' update with all shards' slot moments."""
+        import torch
+        T = self.members[0].rollout.steps
+        with on_current_stream(), torch.no_grad():
+            for t in range(T):
+                if t > 0 or not self.stepped:
+                    self._step()
+                    for _, m in self._each():
+                        m._after_step(t)
+                else:
+                    for _, m in self._each():
+                        m._resume_slot()
+                for _, m in self._each():
+                    m._slot(t)
+            self._step()
+            self.stepped = True
+            for _, m in self._each():
+                m._after_closing_step()
+            with self._phase("gae"):
+                for _, m in self._each():
+                    m._gae()
+                self._share_moments()
+
+    def _share_moments(self):
+        """Every member's adv_moments becomes the sum of all shards', added in shard order; every member's normaliser is
+        updated with all shards' slot moments, shard-major."""
+        import torch
+        own = [m.adv_moments.clone() for m in self.members]
+        slots = [m.rollout.moments for m in self.members]
+        for _, m in self._each():
+            m.adv_moments.copy_(own[0])                              # between devices where they differ
+            for x in own[1:]:
+                m.adv_moments.add_(x.to(m.device))
+            m._fold_moments(torch.cat([x.to(m.device) for x in slots]))
+
+    # ---- the update ----
+    def exchange_gradients(self):
+        """Enqueue every copy between the devices: for device d and shard g != d, member g's gradients into row g of d's
+        staging buffer; every shard's count of active samples (its last ppo_loss call's) into d's count vector."""
+        for d, md in enumerate(self.members):
+            for g, mg in enumerate(self.members):
+                if g != d:
+                    self.stage[d][g].copy_(mg.opt.flat.grads)
+                self.counts[d][g:g + 1].copy_(mg._ppo_out[6:7])
+
+    def reduce_gradients(self):
+        """Every member's gradient buffer becomes the mean over all shards' active samples (after exchange_gradients())."""
+        with on_current_stream():
+            for d, m in self._each():
+                srcs = [m.opt.flat.grads if g == d else self.stage[d][g] for g in range(self.shards)]
+                m.sim.reduce_gradients(srcs, self.counts[d], out=m.opt.flat.grads, total=self.totals[d])
+
+    def run_epochs(self):
+        """num_epochs epochs of num_minibatches minibatches over the members' rollouts: update() without the read."""
+        cfg = self.cfg
+        for m in self.members:
+            m.ppo_stats.zero_()
+            m.value_stats.zero_()
+            m.adam_stats.zero_()
+        with on_current_stream():
+            for epoch in range(cfg.num_epochs):
+                parts = [rollout.epoch_parts(m.permutation(), cfg.num_minibatches) for _, m in self._each()]
+                for i in range(cfg.num_minibatches):
+                    for g, m in self._each():
+                        m.forward_backward(parts[g][i], epoch)
+                    with self._phase("reduce"):
+                        self.exchange_gradients()
+                        self.reduce_gradients()
+                    for _, m in self._each():
+                        with m._phase("adam"):
+                            stats = m.opt.step()
+                        m.adam_stats[:2] += stats[::2]
+                        m.adam_stats[2] = stats[3]
+        for m in self.members:
+            m.update_index += 1
+
+    def update(self):
+        """run_epochs(), then the metrics (the one read of the device)."""
+        self.run_epochs()
+        return self.metrics()
+
+    def metrics(self):
+        """The statistics of the last update() over all shards as Python numbers: Trainer's keys, "shards" and "count".
+        One copy to the host, from shard 0's device."""
+        import torch
+        first = self.members[0]
+        keep = first.ppo_stats.clone(), first.value_stats.clone()
+        for m in self.members[1:]:                                   # raw sums: they add
+            first.ppo_stats += m.ppo_stats.to(self.device)
+            first.value_stats += m.value_stats.to(self.device)
+        with torch.cuda.device(self.device):
+            host = torch.stack(first.metric_tensors() + [self.totals[0][0]]).cpu().tolist()
+        first.ppo_stats.copy_(keep[0])
+        first.value_stats.copy_(keep[1])
+        out = first.metrics_from(host[:-1])
+        out["shards"], out["count"] = self.shards, host[-1]
+        return out
+
+    def update_iter(self):
+        """collect() then update(): the metrics, with "fps" = all shards' rows * steps_per_update / the wall time."""
+        import torch
+        for m in self.members:
+            torch.cuda.synchronize(m.device)
+        t0 = time.perf_counter()
+        self.collect()
+        out = self.update()
+        for m in self.members[1:]:                                   # the read waited for shard 0's device alone
+            torch.cuda.synchronize(m.device)
+        out["fps"] = self.rows * self.cfg.steps_per_update / (time.perf_counter() - t0)
+        return out
+
+    # ---- checkpoints ----
+    def state_dict(self):
+        """Shard 0's state_dict() (parameters, optimiser, normaliser, generator, counters: the replicas agree on them),
+        with every shard's carried LSTM state, clear and permutation generator, and the shard ranges."""
+        d = self.members[0].state_dict()
+        d["state"] = [[[t.clone() for t in s] for s in m.state] for m in self.members]
+        d["clear"] = [m.clear.clone() for m in self.members]
+        d["generators"] = [m.generator.get_state().clone() for m in self.members]
+        d["ranges"] = [list(r) for r in self.ranges]
+        return d
+
+    def load_state_dict(self, d):
+        """Load what state_dict() returned into a ShardedTrainer of the same policy, config and shard layout.  Raises
+        ValueError if the ranges differ."""
+        theirs = [tuple(int(x) for x in r) for r in d.get("ranges", [])]
+        if theirs != self.ranges:
+            raise ValueError(f"the state's shards hold the worlds {theirs}: this trainer's hold {self.ranges}")
+        for g, m in enumerate(self.members):
+            m.load_state_dict(dict(d, state=d["state"][g], clear=d["clear"][g], generator=d["generators"][g]))
         self.stepped = False

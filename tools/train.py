@@ -41,7 +41,13 @@ place of SimpleNet; the checkpoint's layout says which it was, and tools/infer.p
 lie below float16's normal range without it): the metrics line then carries "loss_scale", the scale after the update, next
 to "skipped", the steps that overflowed and halved it, and --phases prints both per update.  --loss-scale-init X sets the
 start (a power of two; 2^16 by default), --no-loss-scale trains float16 with no scale.
-Not here: tensorboard / wandb, several GPUs.
+--gpu-ids 0,1,... trains data-parallel over the shards of a ShardedSimulator, one per id (an id may repeat: two shards
+on one device), through trainer.ShardedTrainer: one replica of the policy per shard, every replica stepping with the
+gradient of the mean over all shards' samples (optim.reduce_gradients).  --num-worlds is the total, cut into contiguous
+ranges.  --phases then needs all ids to be one device and has one more row, "reduce" (the copies between the shards and
+the reduction); the trackers of --episode-stats and --behaviour-stats run per shard and print one line per shard.  Not
+with --pbt-ensemble-size.  Without --gpu-ids the single-device path runs as before.
+Not here: tensorboard / wandb, one process per GPU.
 """
 import argparse
 import json
@@ -54,13 +60,29 @@ sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
 from gpu_hideseek import behaviour, episodes, league, policy, population, trainer  # noqa: E402
+from gpu_hideseek import sharded as sharded_mod  # noqa: E402
 
 PRINT_EVERY = 10
+
+
+class Trackers:
+    """One tracker per shard behind a tracker's two methods: step() all of them, read() the list of their numbers."""
+
+    def __init__(self, trackers):
+        self.trackers = list(trackers)
+
+    def step(self):
+        for t in self.trackers:
+            t.step()
+
+    def read(self):
+        return [t.read() for t in self.trackers]
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpu-id", type=int, default=0)
+    ap.add_argument("--gpu-ids", type=str, help="comma-separated device ids, one shard each (trainer.ShardedTrainer); an id may repeat")
     ap.add_argument("--ckpt-dir", type=str)
     ap.add_argument("--run-name", type=str)
     ap.add_argument("--restore", type=int)
@@ -101,6 +123,13 @@ def parse(argv=None):
         ap.error("--pbt-ensemble-size needs equal teams: --num-hiders == --num-seekers")
     if args.pbt_interval and not args.pbt_ensemble_size:
         ap.error("--pbt-interval needs --pbt-ensemble-size")
+    if args.gpu_ids is not None:
+        try:
+            args.gpu_ids = [int(x) for x in args.gpu_ids.split(",")]
+        except ValueError:
+            ap.error("--gpu-ids takes comma-separated integers")
+        if args.pbt_ensemble_size:
+            ap.error("--gpu-ids and --pbt-ensemble-size exclude each other: there is no population over shards")
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
     if (args.no_loss_scale or args.loss_scale_init is not None) and not args.fp16:
@@ -137,7 +166,7 @@ def phase_table(totals, wall_ms, updates, args, fps):
         "FPS (world steps per second, as the reference prints it): %.0f;  agent rows per second: %.0f" % (fps, fps * (args.num_hiders + args.num_seekers)),
         "%-26s %14s %8s" % ("phase", "ms per update", "share")]
     rest = wall_ms
-    for k in trainer.PHASES:
+    for k in totals:
         lines.append("%-26s %14.2f %7.1f%%" % (k, totals[k] / updates, 100 * totals[k] / wall_ms))
         rest -= totals[k]
     lines.append("%-26s %14.2f %7.1f%%" % ("other", rest / updates, 100 * rest / wall_ms))
@@ -148,16 +177,19 @@ def phase_table(totals, wall_ms, updates, args, fps):
 def main(argv=None):
     args = parse(argv)
     F = gpu_hideseek.SimFlags
-    sim = gpu_hideseek.HideAndSeekSimulator(
-        exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, gpu_id=args.gpu_id, num_worlds=args.num_worlds,
-        sim_flags=F.RandomFlipTeams | F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders,
-        max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=max(1, args.pbt_ensemble_size + args.pbt_past_policies))
+    kw = dict(exec_mode=gpu_hideseek.madrona.ExecMode.CUDA, num_worlds=args.num_worlds,
+              sim_flags=F.RandomFlipTeams | F.UseFixedWorld | F.ZeroAgentVelocity, rand_seed=args.seed, min_hiders=args.num_hiders,
+              max_hiders=args.num_hiders, min_seekers=args.num_seekers, max_seekers=args.num_seekers, num_pbt_policies=max(1, args.pbt_ensemble_size + args.pbt_past_policies))
+    sharded = args.gpu_ids is not None
+    sim = sharded_mod.ShardedSimulator(args.gpu_ids, **kw) if sharded else gpu_hideseek.HideAndSeekSimulator(gpu_id=args.gpu_id, **kw)
     sim.init()
     cfg = config(args)
 
     def fresh(index):                                                  # the trainers' own seeding, with the encoder asked for
         return policy.make_policy(cfg.dtype, generator=torch.Generator().manual_seed(cfg.seed + index), encoder=args.encoder)
-    if args.encoder == "simple":
+    if sharded:
+        tr = trainer.ShardedTrainer(sim, cfg, net=None if args.encoder == "simple" else fresh(0), fused=not args.eager)
+    elif args.encoder == "simple":
         tr = (population.Population if args.pbt_ensemble_size else trainer.Trainer)(sim, cfg, fused=not args.eager)
     elif args.pbt_ensemble_size:
         tr = population.Population(sim, cfg, nets=[fresh(p) for p in range(args.pbt_ensemble_size)], fused=not args.eager)
@@ -167,11 +199,13 @@ def main(argv=None):
     if args.restore is not None:
         tr.load_state_dict(torch.load(os.path.join(run_dir, str(args.restore)), map_location=tr.device, weights_only=False))
     if args.phases:
-        tr.phases = trainer.PhaseTimer()
+        tr.phases = trainer.PhaseTimer(trainer.SHARDED_PHASES if sharded else trainer.PHASES)
     if args.episode_stats:
-        tr.episodes = episodes.EpisodeStats(sim, gamma=args.gamma).arm(from_start=args.restore is None)
+        tr.episodes = Trackers([episodes.EpisodeStats(s, gamma=args.gamma).arm(from_start=args.restore is None) for s in sim.shards]) if sharded else \
+            episodes.EpisodeStats(sim, gamma=args.gamma).arm(from_start=args.restore is None)
     if args.behaviour_stats:
-        tr.behaviour = behaviour.BehaviourStats(sim).arm(from_start=args.restore is None)
+        tr.behaviour = Trackers([behaviour.BehaviourStats(s).arm(from_start=args.restore is None) for s in sim.shards]) if sharded else \
+            behaviour.BehaviourStats(sim).arm(from_start=args.restore is None)
 
     def save():
         if run_dir is not None:
@@ -192,7 +226,7 @@ def main(argv=None):
             T = len(metrics["policies"])
             print("  past policies: " + ", ".join(f"{T + u} from update {n}" for u, n in enumerate(metrics["past"])))
 
-    totals, wall_ms, timed = {k: 0.0 for k in trainer.PHASES}, 0.0, 0
+    totals, wall_ms, timed = {k: 0.0 for k in (tr.phases.names if args.phases else trainer.PHASES)}, 0.0, 0
     last_time, last_update, metrics = 0.0, tr.update_index, {}
     for i in range(args.num_updates):
         if (tr.update_index - last_update) % PRINT_EVERY == 0 or i == 0:
