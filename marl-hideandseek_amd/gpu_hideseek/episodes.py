@@ -133,6 +133,13 @@ def compute_sharded(ssim, state, table, stream=None, gamma=DEFAULT_GAMMA, **inpu
                         lead=lambda s: (s.num_worlds, s.agents_per_world, s.gpu_id))
 
 
+def step_trackers(*hooks):
+    """After a driver's sim.step(): step() of every tracker, in order.  A hook is None, a tracker or a list of trackers."""
+    for hook in hooks:
+        for tracker in ([] if hook is None else hook if isinstance(hook, (list, tuple)) else [hook]):
+            tracker.step()
+
+
 class EpisodeStats:
     """The tracker of one simulator: it owns the state and the table.  arm() once, step() after every sim.step(), read()
     whenever the numbers are wanted."""

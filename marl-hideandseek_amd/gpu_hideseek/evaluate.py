@@ -105,9 +105,7 @@ class Evaluator:
         sim, net = self.sim, self.net
         with on_current_stream(), torch.no_grad():
             mask = self._export("self_mask")[:, 0]
-            zero = rollout.state_zero_into(self.clear, mask, mask if self.mask_before is None else self.mask_before).unsqueeze(1)
-            for x in (t for s in self.state for t in s):
-                x.masked_fill_(zero, 0)
+            rollout.zero_where(rollout.state_zero_into(self.clear, mask, mask if self.mask_before is None else self.mask_before), *self.state[0], *self.state[1])
             self.mask_before = mask.clone()
             sim.pack_policy_inputs(actor=self.actor, critic=self.critic, normaliser=self.normaliser)
             logits, _, self.state = net(sim, self.actor, self.critic, self.state, None)
@@ -121,9 +119,7 @@ class Evaluator:
         for i in range(int(num_steps)):
             self.act()
             self.sim.step()
-            self.episodes.step()
-            if self.behaviour is not None:
-                self.behaviour.step()
+            episodes.step_trackers(self.episodes, self.behaviour)
             self.clear.copy_(self._export("done")[:, 0])
             if record_log is not None:
                 replay.record_step(self.sim, record_log)

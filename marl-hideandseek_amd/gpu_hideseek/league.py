@@ -15,6 +15,7 @@ shapes, and nothing is read back from the device to size them.  counts[i][j] = (
 without an outcome) of hiders i against seekers j.  Ratings are batched by step: the games that end with one step are all
 rated against the ratings before it.
 
+Table is that state on the device with the step that moves it; League holds one, and so does population.Population.
 host_step is the contract in plain numpy (int64 counts, float64 ratings, the same pair order): the tests' reference, and
 it needs no GPU.  Single device: there is no ShardedSimulator form, because the ratings would have to cross the shards.
 Training several policies at once on this schedule (several train states, live ratings, hyper-parameter exploration) is
@@ -34,6 +35,7 @@ import math
 
 from . import policy_inputs, replay, rollout
 from ._request import _disjoint, _run, _tensor, on_current_stream
+from .episodes import step_trackers
 
 MAX_POLICIES = 16         # HS_LEAGUE_MAX_POLICIES
 MAX_GROUP = 256           # HS_LEAGUE_MAX_GROUP
@@ -324,6 +326,72 @@ def compute_scheduled(sim, num_policies, team_size, state, counts, elo, stream=N
     return res
 
 
+def table_views(table, num_policies):
+    """The three views of a packed league table `table` (int64 [P P 4 + P + 1], on any device) for P = num_policies:
+    (counts [P, P, 4] int64, elo [P] float64, bad_total [1] int64).  They alias `table`."""
+    import torch
+    P, n = num_policies, num_policies * num_policies * OUTCOMES
+    return table[:n].view(P, P, OUTCOMES), table[n:n + P].view(torch.float64), table[n + P:]
+
+
+class Table:
+    """The league's state on the device for `num_policies` policies on `sim`: the routing of the last step (TENSORS[:4]),
+    the per-world state `world`, and counts | elo | bad_total (the malformed worlds of all steps) packed in `_table`, so
+    that read() is one copy.  The tensors are never replaced: the request is checked and built once.  With `schedule`
+    (a table of pairs) it is set on the simulator and step() is hs_league_step_scheduled.  Raises ValueError for the
+    shape, then for k_factor, before anything touches the device."""
+    TENSORS = ("slot", "row_of_slot", "clear_slot", "bad", "world", "_table", "counts", "elo", "bad_total")
+
+    def __init__(self, sim, num_policies, team_size, k_factor=DEFAULT_K_FACTOR, schedule=None):
+        import torch
+        P, group = num_policies, None if schedule is None else len(schedule)
+        _league_shape(sim.num_worlds, sim.agents_per_world, P, team_size, group)
+        self.k_factor = _k_factor(k_factor)
+        self.sim, self.num_policies = sim, P
+        dev = torch.device("cuda", sim.gpu_id)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.slot, self.row_of_slot, self.clear_slot = (torch.zeros(sim.num_worlds * sim.agents_per_world, **i32) for _ in range(3))
+        self.bad = torch.zeros(1, **i32)
+        self.world = new_state(sim.num_worlds, dev)
+        self._table = torch.zeros(P * P * OUTCOMES + P + 1, dtype=torch.int64, device=dev)
+        self.counts, self.elo, self.bad_total = table_views(self._table, P)
+        self.elo.fill_(INITIAL_ELO)
+        if schedule is not None:
+            sim.set_league_schedule(schedule, P)
+        self._fn = "hs_league_step" if schedule is None else "hs_league_step_scheduled"
+        self._req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, P, team_size, self.world, self.counts, self.elo, self.k_factor,
+                            slot=self.slot, row_of_slot=self.row_of_slot, clear_slot=self.clear_slot, bad=self.bad, group=group)[1]
+
+    def bind(self, owner):
+        """Set every tensor of TENSORS as an attribute of `owner` under its name here.  Returns self."""
+        for k in self.TENSORS:
+            setattr(owner, k, getattr(self, k))
+        return self
+
+    def step(self):
+        """The entry point on the simulator's exports as they stand, on torch's current stream, then bad_total += bad."""
+        with on_current_stream():
+            _run(self.sim, self._fn, self._req, None)
+        self.bad_total.add_(self.bad)
+
+    def read(self):
+        """{"counts": [P][P][4] lists (hider wins, seeker wins, draws, played without an outcome, of hiders i against
+        seekers j), "games": their sum, "elo": [P], "bad": the malformed worlds seen} by one copy to the host (which waits
+        for the device).  Nothing is reset."""
+        counts, elo, bad_total = table_views(self._table.cpu(), self.num_policies)
+        return {"counts": counts.tolist(), "games": int(counts.sum()), "elo": elo.tolist(), "bad": int(bad_total[0])}
+
+    def state_dict(self):
+        """{"world": clones of the per-world state, "table": a clone of the packed buffer}."""
+        return {"world": {k: t.clone() for k, t in self.world.items()}, "table": self._table.clone()}
+
+    def load_state_dict(self, d):
+        """Copy what state_dict() returned into the tensors held here."""
+        self._table.copy_(d["table"])
+        for k, t in self.world.items():
+            t.copy_(d["world"][k])
+
+
 class League:
     """`policies`, a list of (net, normaliser or None) with net a policy.ActorCritic on the simulator's device, playing
     each other on `sim` under the fixed schedule: the multi-policy sibling of evaluate.Evaluator.  The simulator has
@@ -342,8 +410,8 @@ class League:
         if not policies or any(len(p) != 2 for p in policies):
             raise ValueError("policies must be a list of (net, normaliser or None)")
         P = len(policies)
-        _league_shape(sim.num_worlds, sim.agents_per_world, P, team_size)
-        self.k_factor = _k_factor(k_factor)
+        self.league_table = Table(sim, P, team_size, k_factor).bind(self)      # refuses the shape, then k_factor, before the nets are looked at
+        self.k_factor = self.league_table.k_factor
         nets = [net for net, _ in policies]
         if any(net.buckets != nets[0].buckets for net in nets):
             raise ValueError("every policy must have the same action heads")
@@ -353,16 +421,6 @@ class League:
         self.block = m = R // P                   # the rows of a policy, and the length of its block of slots
         self.device = dev = torch.device("cuda", sim.gpu_id)
         self.logit_width = L = sum(nets[0].buckets)
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.slot, self.row_of_slot, self.clear_slot = (torch.zeros(R, **i32) for _ in range(3))
-        self.bad = torch.zeros(1, **i32)
-        self.world = new_state(sim.num_worlds, dev)
-        # counts [P, P, 4] i64 | elo [P] f64 | the malformed worlds of all calls, in one buffer: read() is one copy
-        self._table = torch.zeros(P * P * OUTCOMES + P + 1, dtype=torch.int64, device=dev)
-        self.counts = self._table[:P * P * OUTCOMES].view(P, P, OUTCOMES)
-        self.elo = self._table[P * P * OUTCOMES:P * P * OUTCOMES + P].view(torch.float64)
-        self.bad_total = self._table[P * P * OUTCOMES + P:]
-        self.elo.fill_(INITIAL_ELO)
         # With one compute dtype (always, from tools/league.py) one routed pack writes every policy's block of slots under
         # that policy's table (hs_pack_policy_inputs_routed): `tables` holds a copy of each normaliser's table, the identity
         # for a policy without one, refreshed by arm() and at the start of run().  With several dtypes every policy packs
@@ -372,20 +430,12 @@ class League:
         self.gathered = {} if self.routed else {net.dtype: torch.zeros(1, m, rollout.ROW, dtype=net.dtype, device=dev) for net in nets}
         self.tables = torch.zeros(P, policy_inputs.NORM_TABLE, dtype=torch.float32, device=dev)
         self.logits_by_slot = torch.zeros(1, R, L, dtype=torch.float32, device=dev)
-        self._acted_slot = torch.zeros(R, **i32)          # `slot` as the last act() had it: the routing its logits belong to
+        self._acted_slot = torch.zeros(R, dtype=torch.int32, device=dev)      # `slot` as the last act() had it: the routing its logits belong to
         self.state = [net.actor.init_state(m, dev, net.dtype) for net in nets]
         self.counter = 0
         self.episodes = None
         self.behaviour = None
-        # the tensors above stay where they are: the request is checked and built once
-        self._req = request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, P, self.team_size, self.world, self.counts, self.elo, self.k_factor,
-                            slot=self.slot, row_of_slot=self.row_of_slot, clear_slot=self.clear_slot, bad=self.bad)[1]
         self.arm()
-
-    def _league_step(self):
-        with on_current_stream():
-            _run(self.sim, "hs_league_step", self._req, None)
-        self.bad_total.add_(self.bad)
 
     def refresh_tables(self):
         """Copy every normaliser's table as it stands into `tables` (the identity for a policy without normaliser): what
@@ -408,7 +458,7 @@ class League:
         for s in self.state:
             for x in s:
                 x.zero_()
-        self._league_step()
+        self.league_table.step()
         return self
 
     def act(self):
@@ -429,12 +479,9 @@ class League:
                     sim.pack_policy_inputs(actor=packed, normaliser=normaliser)
                     sim.gather_sequences(self.row_of_slot[block], [(packed.view(1, R, -1), gathered, False)], chunks=1, chunk_steps=1, rows=R)
                     mine = gathered[0]
-                zero = (self.clear_slot[block] != 0).unsqueeze(1)
-                for x in self.state[p]:
-                    x.masked_fill_(zero, 0)
-                y, self.state[p] = net.actor(sim, mine, self.state[p], None)
-                head = net.actor_head
-                self.logits_by_slot[0, block] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype)).float()
+                rollout.zero_where(self.clear_slot[block] != 0, *self.state[p])
+                logits, self.state[p] = net.actor_logits(sim, mine, self.state[p], None)
+                self.logits_by_slot[0, block] = logits.float()
             # slot-order logits -> row-order actions in one launch, with the bits sample_actions gives the gathered logits
             sim.sample_actions_routed(self.logits_by_slot[0], self.row_of_slot, buckets=self.policies[0][0].buckets, mode=self.mode, seed=(self.seed, 0),
                                       counter=self.counter)
@@ -455,11 +502,8 @@ class League:
         for i in range(int(num_steps)):
             self.act()
             self.sim.step()
-            self._league_step()
-            if self.episodes is not None:
-                self.episodes.step()
-            if self.behaviour is not None:
-                self.behaviour.step()
+            self.league_table.step()
+            step_trackers(self.episodes, self.behaviour)
             if record_log is not None:
                 replay.record_step(self.sim, record_log)
             if on_step is not None:
@@ -467,15 +511,8 @@ class League:
         return self.read()
 
     def read(self):
-        """{"counts": [P][P][4] lists (hider wins, seeker wins, draws, played without an outcome, of hiders i against
-        seekers j), "games": their sum, "elo": [P], "bad": the malformed worlds seen} by one copy to the host (which waits
-        for the device).  Nothing is reset."""
-        import torch
-        P = self.num_policies
-        host = self._table.cpu()
-        n = P * P * OUTCOMES
-        counts = host[:n].view(P, P, OUTCOMES)
-        return {"counts": counts.tolist(), "games": int(counts.sum()), "elo": host[n:n + P].view(torch.float64).tolist(), "bad": int(host[n + P])}
+        """Table.read(): {"counts", "games", "elo", "bad"} by one copy to the host."""
+        return self.league_table.read()
 
 
 def hider_win_rates(counts):

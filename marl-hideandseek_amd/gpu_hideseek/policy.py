@@ -129,23 +129,33 @@ class ActorCritic(_module_base()):
         dtype = self.dtype if dtype is None else dtype
         return self.actor.init_state(n, device, dtype), self.critic.init_state(n, device, dtype)
 
-    def _heads(self, ya, yc):
+    @staticmethod
+    def _head(head, y):
+        """A head on a backbone's output, in the output's dtype."""
         import torch
-        lin = torch.nn.functional.linear
-        return (lin(ya, self.actor_head.weight.to(ya.dtype), self.actor_head.bias.to(ya.dtype)),
-                lin(yc, self.critic_head.weight.to(yc.dtype), self.critic_head.bias.to(yc.dtype)))
+        return torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype))
+
+    def actor_logits(self, sim, rows, state, clear=None):
+        """One step of the actor alone: rows [n, W], state the actor's (h, c) -> (logits [n, sum(buckets)], the new actor state)."""
+        y, state = self.actor(sim, rows, state, clear)
+        return self._head(self.actor_head, y), state
+
+    def critic_logits(self, sim, rows, state, clear=None):
+        """One step of the critic alone: rows [n, W], state the critic's (h, c) -> (critic_logits [n, bins], the new critic state)."""
+        y, state = self.critic(sim, rows, state, clear)
+        return self._head(self.critic_head, y), state
 
     def forward(self, sim, actor_rows, critic_rows, state, clear=None):
         """One step -> (logits [n, sum(buckets)], critic_logits [n, bins], the new state)."""
         ya, sa = self.actor(sim, actor_rows, state[0], clear)
         yc, sc = self.critic(sim, critic_rows, state[1], clear)
-        return (*self._heads(ya, yc), (sa, sc))
+        return self._head(self.actor_head, ya), self._head(self.critic_head, yc), (sa, sc)
 
     def sequence(self, sim, actor_rows, critic_rows, state, clears=None):
         """A chunk [T, n, W] -> (logits [T, n, sum(buckets)], critic_logits [T, n, bins], the final state)."""
         ya, sa = self.actor.sequence(sim, actor_rows, state[0], clears)
         yc, sc = self.critic.sequence(sim, critic_rows, state[1], clears)
-        return (*self._heads(ya, yc), (sa, sc))
+        return self._head(self.actor_head, ya), self._head(self.critic_head, yc), (sa, sc)
 
 
 def make_policy(dtype=None, fused=True, generator=None, encoder="simple"):

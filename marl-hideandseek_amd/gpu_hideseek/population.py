@@ -1,7 +1,7 @@
 """Population training: P policies learn at once on one simulator under the league's fixed schedule (the function of the
 reference's scripts/jax_train.py --pbt-ensemble-size N): the two sides improve against each other, not against a copy of
-themselves.  Composition only, as gpu_hideseek.trainer is: the league's routing (hs_league_step), the routed pack, the
-routed sampler, grouped advantages, and per policy the trainer's update.  Single device, like Trainer and League.
+themselves.  Composition only, as gpu_hideseek.trainer is: the league's routing (hs_league_step, a league.Table), the routed
+pack, the routed sampler, grouped advantages, and per policy a trainer.Learner's update.  Single device, like Trainer and League.
 
     sim.init()
     pop = population.Population(sim, population.PopulationConfig(num_policies=4, team_size=3, pbt_interval=10))
@@ -29,7 +29,7 @@ booked twice.  After the rollout: the bootstrap (a critic-only routed pack witho
 carried critic states, which stay as they are, one decode), one compute_advantages(groups=P) whose moments [P, 5] are per
 policy, and P normaliser updates from moments[p].
 
-update() runs, per policy in turn, the trainer's epochs (Trainer.run_epochs: the gather with rows = R, net.sequence,
+update() runs, per policy in turn, the learner's epochs (Learner.run_epochs: the gather with rows = R, net.sequence,
 ppo_loss with adv_moments[p] and the policy's entropy_coef, value_head, backward, Adam with the policy's lr), then reads
 every policy's metrics, the ratings and the counts in ONE copy to the host.
 
@@ -63,7 +63,7 @@ and replaces learners only.  With snapshot_interval = 0 the pool stays what it w
 load_state_dict).  Q > T is refused (league.past_play_schedule says why).
 
 state_dict() is {"members": [...], "league", "hyper", "update_index", "counter"}; a member has Trainer.state_dict()'s
-keys, so evaluate.load_policy(state["members"][i]) reads it.  With a pool it has in addition "past", one dict per pool
+keys (Learner.state_dict()), so evaluate.load_policy(state["members"][i]) reads it; "league" is league.Table.state_dict().  With a pool it has in addition "past", one dict per pool
 member ("params", "optimizer" with the source's layout alone, "normaliser", "state", "taken": the update its snapshot was
 taken at), which evaluate.load_policy(state, past=i) reads, and "taken", the number of snapshots so far; the league table
 is over N.  After load_state_dict() the next collect() steps the simulator before its slot 0, as the Trainer's does.
@@ -71,10 +71,10 @@ is over N.  After load_state_dict() the next collect() steps the simulator befor
 import copy
 import dataclasses
 import math
-import time
 
 from . import advantages, league, optim, policy, policy_inputs, rollout, trainer
-from ._request import _run, on_current_stream
+from ._request import on_current_stream
+from .episodes import step_trackers
 from .policy_inputs import ObsNormaliser
 
 
@@ -171,37 +171,16 @@ def explore(value, base, scales, explore_range, rng):
     return min(max(float(value) * scale, float(base) * lo), float(base) * hi)
 
 
-class _Member(trainer.Trainer):
-    """One policy of a population as the Trainer's update sees it: its net, optimiser, normaliser, permutation generator,
-    statistics and config (with its own lr and entropy_coef), on the SHARED rollout, of which it owns the column block
-    [first, first + rows).  collect() is the population's."""
+class _Member(trainer.Learner):
+    """One policy of a population: a trainer.Learner (policy `index` seeded cfg.seed + index, its own copy of the config,
+    whose lr and entropy_coef change under exploration) on the SHARED rollout, of which it owns the column block
+    [first, first + rows); its adv_moments and clear are views of the population's, its normaliser's table is `table`."""
 
     def __init__(self, pop, index, net, table):
-        import torch
-        sim, cfg, dev = pop.sim, pop.cfg, pop.device
-        self.sim, self.fused, self.index = sim, pop.fused, index
-        self.cfg = dataclasses.replace(cfg)               # lr and entropy_coef change under exploration
-        self.rows, self.first, self.total_rows = pop.block, index * pop.block, pop.rows
-        self.dtype, self.device = pop.dtype, dev
-        if net is None:
-            net = policy.make_policy(self.dtype, generator=torch.Generator().manual_seed(cfg.seed + index))
-        self.net = net.to(dev).set_fused(self.fused)
-        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm,
-                              loss_scale=trainer.make_loss_scale(cfg, dev))
-        self.normaliser = ObsNormaliser(sim.gpu_id, table=table) if cfg.normalise_obs else None
-        self.rollout = pop.rollout
-        self.state = self.net.init_state(self.rows, dev, self.dtype)
-        self.clear = pop.clear[self.first:self.first + self.rows]
-        self.adv_moments = pop.adv_moments[index]
-        self.generator = torch.Generator(device=dev).manual_seed(cfg.seed + index)
-        self.update_index, self.counter, self.stepped = 0, 0, False
-        self._mb, self.phases, self.episodes = None, None, None
-        E = cfg.num_epochs
-        self.ppo_stats = torch.zeros(E, trainer.PPO_STATS, dtype=torch.float64, device=dev)
-        self.value_stats = torch.zeros(E, trainer.VALUE_STATS, dtype=torch.float64, device=dev)
-        self.adam_stats = torch.zeros(3, dtype=torch.float64, device=dev)
-        self._ppo_out = torch.zeros(trainer.PPO_STATS, dtype=torch.float64, device=dev)
-        self._value_out = torch.zeros(trainer.VALUE_STATS, dtype=torch.float64, device=dev)
+        m = pop.block
+        self.index, self.first, self.total_rows = index, index * m, pop.rows
+        super().__init__(pop.sim, dataclasses.replace(pop.cfg), net, pop.cfg.seed + index, m, pop.device, pop.dtype, pop.rollout,
+                         pop.adv_moments[index], pop.clear[index * m:(index + 1) * m], table=table, fused=pop.fused)
 
     lr = property(lambda self: self.opt.param_groups[0]["lr"])
     entropy_coef = property(lambda self: self.cfg.entropy_coef)
@@ -218,9 +197,6 @@ class _Member(trainer.Trainer):
         if m == R:
             return perm
         return torch.div(perm, m, rounding_mode="floor") * R + (self.first + perm % m)
-
-    def collect(self):
-        raise NotImplementedError("a member's rollout is Population.collect()'s")
 
 
 class _Past:
@@ -290,26 +266,11 @@ class Population:
         self.dtype = torch.float32 if cfg.dtype is None else cfg.dtype
         self.device = dev = torch.device("cuda", sim.gpu_id)
         T = cfg.steps_per_update
-        i32 = dict(dtype=torch.int32, device=dev)
-        # the league's state, as League holds it: counts | elo | the malformed worlds of all calls in one buffer
-        self.slot, self.row_of_slot, self.clear_slot = (torch.zeros(R, **i32) for _ in range(3))
-        self.bad = torch.zeros(1, **i32)
-        self.world = league.new_state(sim.num_worlds, dev)
-        n = P * P * league.OUTCOMES
-        self._table = torch.zeros(n + P + 1, dtype=torch.int64, device=dev)
-        self.counts = self._table[:n].view(P, P, league.OUTCOMES)
-        self.elo = self._table[n:n + P].view(torch.float64)
-        self.bad_total = self._table[n + P:]
-        self.elo.fill_(league.INITIAL_ELO)
-        if Q:
-            sim.set_league_schedule(self.schedule, P)
-        self._league_fn = "hs_league_step_scheduled" if Q else "hs_league_step"
-        self._league_req = league.request(sim.num_worlds, sim.agents_per_world, sim.gpu_id, P, cfg.team_size, self.world, self.counts, self.elo, cfg.k_factor,
-                                          slot=self.slot, row_of_slot=self.row_of_slot, clear_slot=self.clear_slot, bad=self.bad,
-                                          group=len(self.schedule) if Q else None)[1]
+        # with a pool, under its schedule, which it sets; here as slot, row_of_slot, clear_slot, bad, world, _table, counts, elo, bad_total
+        self.league_table = league.Table(sim, P, cfg.team_size, cfg.k_factor, self.schedule).bind(self)
         self.tables = torch.zeros(P, policy_inputs.NORM_TABLE, dtype=torch.float32, device=dev)
         self.tables[:, policy_inputs.ROW:] = 1.0
-        self.clear = torch.zeros(R, **i32)                # clear_slot of a rollout's closing step: clear[0] of the next
+        self.clear = torch.zeros(R, dtype=torch.int32, device=dev)       # clear_slot of a rollout's closing step: clear[0] of the next
         self.adv_moments = torch.zeros(P, advantages.MOMENTS, dtype=torch.float64, device=dev)
         nets = [None] * cfg.num_policies if nets is None else list(nets)
         if nets[0] is None:                               # the rollout needs the hidden width before the members need the rollout
@@ -339,18 +300,14 @@ class Population:
     lr = property(lambda self: [mb.lr for mb in self.members])
     entropy_coef = property(lambda self: [mb.entropy_coef for mb in self.members])
 
-    def _phase(self, name):
-        return trainer._NoSpan() if self.phases is None else self.phases(name)
+    _phase = trainer.Learner._phase
 
     def _export(self, name):
         return getattr(self.sim, name + "_tensor")().to_torch()
 
     def league_step(self):
-        """hs_league_step (with a pool, hs_league_step_scheduled) on the simulator's exports as they stand: once after
-        every sim.step()."""
-        with on_current_stream():
-            _run(self.sim, self._league_fn, self._league_req, None)
-        self.bad_total.add_(self.bad)
+        """league.Table.step() on the simulator's exports as they stand: once after every sim.step()."""
+        self.league_table.step()
 
     # ---- the rollout ----
     def _close_slot(self, t):
@@ -361,21 +318,15 @@ class Population:
                                   chunks=1, chunk_steps=1, rows=R)
 
     def _zero_carried(self, clear):
-        zero = (clear != 0).unsqueeze(1)
-        m = self.block
+        zero, m = clear != 0, self.block
         for p, mb in enumerate(self.members):
-            for x in (t for s in mb.state for t in s):
-                x.masked_fill_(zero[p * m:(p + 1) * m], 0)
+            rollout.zero_where(zero[p * m:(p + 1) * m], *(t for s in mb.state for t in s))
         for pm in self.past:
-            for x in pm.state:
-                x.masked_fill_(zero[pm.index * m:(pm.index + 1) * m], 0)
+            rollout.zero_where(zero[pm.index * m:(pm.index + 1) * m], *pm.state)
 
     def _after_step(self, t):
-        """What follows every sim.step(): the tracker, the close of slot `t` (None: there is none), the league step."""
-        if self.episodes is not None:
-            self.episodes.step()
-        if self.behaviour is not None:
-            self.behaviour.step()
+        """What follows every sim.step(): the trackers, the close of slot `t` (None: there is none), the league step."""
+        step_trackers(self.episodes, self.behaviour)
         if t is not None:
             self._close_slot(t)
         self.league_step()
@@ -404,20 +355,15 @@ class Population:
                 with self._phase("pack"):
                     sim.pack_policy_inputs_routed(self.row_of_slot, P, actor=buf.actor[t], critic=buf.critic[t], moments=self.moments[:, t], tables=tables)
                 if t % L == 0:
-                    k = t // L
                     for p, mb in enumerate(self.members):
-                        cols = slice(p * m, (p + 1) * m)
-                        for dst, src in ((buf.actor_h, mb.state[0][0]), (buf.actor_c, mb.state[0][1]), (buf.critic_h, mb.state[1][0]), (buf.critic_c, mb.state[1][1])):
-                            dst[k, cols].copy_(src)
+                        buf.snapshot_state(t // L, mb.state, slice(p * m, (p + 1) * m))
                 with self._phase("rollout_forward"):
                     for p, mb in enumerate(self.members):
                         cols = slice(p * m, (p + 1) * m)
                         self.logits[cols], self.critic_logits[cols], mb.state = mb.net(sim, buf.actor[t, cols], buf.critic[t, cols], mb.state, None)
                     for pm in self.past:                  # frozen: the actor and its head alone, as League.act runs them
                         cols = slice(pm.index * m, (pm.index + 1) * m)
-                        y, pm.state = pm.net.actor(sim, buf.actor[t, cols], pm.state, None)
-                        head = pm.net.actor_head
-                        self.logits[cols] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype))
+                        self.logits[cols], pm.state = pm.net.actor_logits(sim, buf.actor[t, cols], pm.state, None)
                     sim.value_head(self.critic_logits, value=buf.value[t])
                     sim.sample_actions_routed(self.logits, self.row_of_slot, buckets=self.buckets, seed=(cfg.seed, 0), counter=self.counter,
                                               action=buf.action[t], log_prob=buf.log_prob[t])
@@ -447,9 +393,7 @@ class Population:
             sim.pack_policy_inputs_routed(self.row_of_slot, self.num_all, critic=self.boot_rows, tables=self.tables if self.cfg.normalise_obs else None)
             for p, mb in enumerate(self.members):
                 cols = slice(p * m, (p + 1) * m)
-                y, _ = mb.net.critic(sim, self.boot_rows[cols], mb.state[1], None)
-                head = mb.net.critic_head
-                self.critic_logits[cols] = torch.nn.functional.linear(y, head.weight.to(y.dtype), head.bias.to(y.dtype))
+                self.critic_logits[cols], _ = mb.net.critic_logits(sim, self.boot_rows[cols], mb.state[1], None)
             sim.value_head(self.critic_logits, value=self.bootstrap)
         return self.bootstrap
 
@@ -489,15 +433,7 @@ class Population:
             policies.append(d)
         return {"policies": policies, "elo": host[P * per:P * per + N], "games": int(host[-2]), "bad": int(host[-1]), "update": self.update_index}
 
-    def update_iter(self):
-        """collect() then update(): the metrics, with "fps" = rows * steps_per_update / the wall time of both."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        t0 = time.perf_counter()
-        self.collect()
-        out = self.update()
-        out["fps"] = self.rows * self.cfg.steps_per_update / (time.perf_counter() - t0)
-        return out
+    update_iter = trainer.Trainer.update_iter             # collect() then update(): the metrics, with "fps"; the same text serves both
 
     # ---- the pool ----
     def snapshot(self, elo_train):
@@ -548,7 +484,7 @@ class Population:
         for mb in self.members:
             mb.update_index, mb.counter = self.update_index, self.counter
         d = {"members": [mb.state_dict() for mb in self.members],
-             "league": {"world": {k: t.clone() for k, t in self.world.items()}, "table": self._table.clone()},
+             "league": self.league_table.state_dict(),
              "hyper": {"lr": self.lr, "entropy_coef": self.entropy_coef, "rng": self.rng.bit_generator.state},
              "update_index": self.update_index, "counter": self.counter}
         if self.past:
@@ -557,7 +493,6 @@ class Population:
 
     def load_state_dict(self, d):
         """Load what state_dict() returned into a population of the same policies, config and simulator shape."""
-        import torch
         if len(d["members"]) != self.num_policies:
             raise ValueError(f"the state has {len(d['members'])} members: expected {self.num_policies}")
         if len(d.get("past", ())) != self.num_past:
@@ -571,10 +506,7 @@ class Population:
         for pm, pd in zip(self.past, d.get("past", ())):
             pm.load_state_dict(pd)
         self.taken = int(d.get("taken", 0))
-        with torch.no_grad():
-            self._table.copy_(d["league"]["table"])
-            for k, t in self.world.items():
-                t.copy_(d["league"]["world"][k])
+        self.league_table.load_state_dict(d["league"])
         self.rng.bit_generator.state = d["hyper"]["rng"]
         self.update_index, self.counter = int(d["update_index"]), int(d["counter"])
         self.stepped = False

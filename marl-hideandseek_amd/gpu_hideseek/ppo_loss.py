@@ -25,6 +25,7 @@ from ._request import (_DTYPES, _OUTPUT, _above_zero, _dtype_arg, _finite, _loss
                        _vector, _wanted)
 
 STATS = 7             # HS_PPO_STATS: sum pg, sum vl, sum ent, sum kl, policy-clipped, value-clipped, count
+STAT_COUNT = 6        # where the count of active samples lies in the statistics
 ROWS_PER_BLOCK = 32   # kPpoRows: samples a workgroup takes at a time
 MAX_GRID = 2048       # kPpoMaxGrid: workgroups of a call at the most
 DEFAULT_CLIP = 0.2
@@ -144,7 +145,7 @@ def stats_to_metrics(stats, entropy_coef=DEFAULT_ENTROPY_COEF, value_loss_coef=D
     s = stats.to(torch.float64)
     if s.shape != (STATS,):
         raise ValueError(f"stats have shape ({STATS},), got {tuple(s.shape)}")
-    count = s[6]
+    count = s[STAT_COUNT]
     n = torch.clamp(count, min=1.0)
     pg, vl, ent = s[0] / n, s[1] / n, s[2] / n
     return {"loss": grad_scale * (pg - entropy_coef * ent + value_loss_coef * vl), "policy_loss": pg, "value_loss": vl,

@@ -92,6 +92,13 @@ def state_zero_into(clear, mask, mask_before):
     return (clear != 0) | (mask == 0) | (mask_before == 0)
 
 
+def zero_where(zero, *tensors):
+    """Zero, in place, the rows of every [n, ...] tensor of `tensors` (carried LSTM states) where `zero` [n] (bool) is set."""
+    zero = zero.unsqueeze(1)
+    for x in tensors:
+        x.masked_fill_(zero, 0)
+
+
 def chunk_clears(clear, mask):
     """The `clear` [L, m] int32 that the recurrent core takes over a chunk of L slots whose per-slot fields are `clear`
     and `mask` [L, m]: the core zeroes the state carried OUT of a step, so step t < L - 1 takes state_zero_into() of slot
@@ -247,6 +254,12 @@ class Rollout:
         self.moments = torch.zeros(T, MOMENTS, dtype=torch.float64, device=dev)
         self.actor_h, self.critic_h = (torch.zeros(K, n, H, dtype=dtype, device=dev) for _ in range(2))
         self.actor_c, self.critic_c = (torch.zeros(K, n, H, dtype=f32, device=dev) for _ in range(2))
+
+    def snapshot_state(self, k, state, cols=slice(None)):
+        """The carried LSTM states `state` = ((h, c) of the actor, (h, c) of the critic), as the forward of chunk k's first
+        slot receives them, into actor_h, actor_c, critic_h and critic_c [k] (with `cols`, into that block of columns)."""
+        for dst, src in zip((self.actor_h, self.actor_c, self.critic_h, self.critic_c), (t for s in state for t in s)):
+            dst[k, cols].copy_(src)
 
     def tensors(self):
         """{name: tensor} of every buffer."""

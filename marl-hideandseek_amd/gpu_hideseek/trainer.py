@@ -8,8 +8,9 @@ defaults are jax_train.py's, the order of the calls below is the project's.
         metrics = tr.update_iter()          # collect() then update(); one read of the device at its end
 
 Composition only: every kernel is another module's (policy_inputs, policy, action_sampling, value_head, advantages,
-rollout, ppo_loss, optim).  Trainer is the single-device loop; ShardedTrainer (at the end of this module) is the same loop
-over the shards of a ShardedSimulator, one replica per shard, their gradients reduced by optim.reduce_gradients.
+rollout, ppo_loss, optim).  Learner is what an update needs (a population.Population's members are Learners); Trainer, a
+Learner that fills its own rollout, is the single-device loop; ShardedTrainer (at the end of this module) is the same loop
+over the shards of a ShardedSimulator, one Trainer per shard, their gradients reduced by optim.reduce_gradients.
 
 collect() fills the rollout (rollout.py states what slot t holds).  Per slot: sim.step() -> the done and self_mask exports
 into clear[t] and mask[t] -> the carried LSTM states zeroed in the rows whose episode starts with this observation or which
@@ -21,7 +22,7 @@ that grows by one per slot over the whole run) into the simulator's action tenso
 step's reward and done exports go into the slot it closes.
 The bootstrap.  After slot T - 1 the simulator is stepped once more, which closes slot T - 1 and leaves the observation
 o_T in the exports; the carried states are zeroed by the same rule.  Its value comes from a CRITIC-ONLY forward (the
-critic's rows packed without moments, the critic backbone and head on the carried critic state) whose new state is
+critic's rows packed without moments, the policy's critic_logits on the carried critic state) whose new state is
 dropped: the carried state is not advanced, the actor is not run.  The next collect() does not step before its slot 0: it packs the same exports with the normaliser as
 updated since, and runs the full forward with the policy as updated since, so log_prob[0] and value[0] belong to the
 policy that update() starts from, and every observation adds its moments once.  Then compute_advantages (moments=True)
@@ -51,6 +52,7 @@ import time
 
 from . import advantages, optim, policy, ppo_loss, rollout, value_head
 from ._request import on_current_stream
+from .episodes import step_trackers
 from .policy_inputs import ObsNormaliser
 
 
@@ -154,160 +156,36 @@ def make_loss_scale(cfg, device):
     return None if s is None else optim.LossScale(device, **s)
 
 
-class Trainer:
-    """The policy (policy.make_policy, seeded with cfg.seed, unless `net` is given), optim.Adam over its parameters, an
-    ObsNormaliser, the Rollout, the carried LSTM state and the sampling counter of one simulator (after sim.init())."""
+class Learner:
+    """What an update needs, and what a Trainer and a member of a population.Population share: the policy (`net`, or with
+    None policy.make_policy seeded with `seed`), optim.Adam, an ObsNormaliser (on `table`, a row of the caller's tables, if given),
+    the carried LSTM state of `rows` agent rows, the permutation generator (seeded with `seed`), the statistics and the
+    two counters.  `buf` (the Rollout it reads), `adv_moments` and `clear` are the caller's, kept as given: of a
+    population they are shared, or views into shared tensors."""
 
-    def __init__(self, sim, cfg=None, net=None, fused=True):
+    def __init__(self, sim, cfg, net, seed, rows, device, dtype, buf, adv_moments, clear, table=None, fused=True):
         import torch
-        self.sim, self.cfg, self.fused = sim, TrainConfig() if cfg is None else cfg, bool(fused)
-        cfg = self.cfg
-        self.rows = n = sim.num_worlds * sim.agents_per_world
-        check_config(cfg, n)
-        self.dtype = torch.float32 if cfg.dtype is None else cfg.dtype
-        self.device = dev = torch.device("cuda", sim.gpu_id)
+        self.sim, self.cfg, self.fused = sim, cfg, bool(fused)
+        self.rows, self.device, self.dtype = rows, device, dtype
         if net is None:
-            net = policy.make_policy(self.dtype, generator=torch.Generator().manual_seed(cfg.seed))
-        self.net = net.to(dev).set_fused(self.fused)
-        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm, loss_scale=make_loss_scale(cfg, dev))
-        self.normaliser = ObsNormaliser(sim.gpu_id) if cfg.normalise_obs else None
-        self.rollout = rollout.Rollout(sim, cfg.steps_per_update, cfg.num_bptt_chunks, self.dtype, hidden=self.net.actor.core.hidden)
-        self.state = self.net.init_state(n, dev, self.dtype)
-        self.clear = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.bootstrap = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.adv_moments = torch.zeros(advantages.MOMENTS, dtype=torch.float64, device=dev)
-        self.boot_rows = torch.zeros(n, rollout.ROW, dtype=self.dtype, device=dev)
-        self.generator = torch.Generator(device=dev).manual_seed(cfg.seed)
+            net = policy.make_policy(dtype, generator=torch.Generator().manual_seed(seed))
+        self.net = net.to(device).set_fused(self.fused)
+        self.opt = optim.Adam(sim, self.net.named_parameters(), lr=cfg.lr, max_grad_norm=cfg.max_grad_norm, loss_scale=make_loss_scale(cfg, device))
+        self.normaliser = ObsNormaliser(sim.gpu_id, table=table) if cfg.normalise_obs else None
+        self.rollout, self.adv_moments, self.clear = buf, adv_moments, clear
+        self.state = self.net.init_state(rows, device, dtype)
+        self.generator = torch.Generator(device=device).manual_seed(seed)
         self.update_index, self.counter = 0, 0
-        self.stepped = False              # the simulator has been stepped past the last slot: its exports are the next o_0
         self._mb = None
         self.phases = None                # a PhaseTimer, or None: no events
-        self.episodes = None              # an episodes.EpisodeStats, or None: collect() calls its step() after every sim.step()
-        self.behaviour = None             # a behaviour.BehaviourStats, or None: likewise
-        E = cfg.num_epochs
-        self.ppo_stats = torch.zeros(E, PPO_STATS, dtype=torch.float64, device=dev)
-        self.value_stats = torch.zeros(E, VALUE_STATS, dtype=torch.float64, device=dev)
-        self.adam_stats = torch.zeros(3, dtype=torch.float64, device=dev)         # sum of norms, skipped steps, t
-        self._ppo_out = torch.zeros(PPO_STATS, dtype=torch.float64, device=dev)
-        self._value_out = torch.zeros(VALUE_STATS, dtype=torch.float64, device=dev)
+        self.ppo_stats = torch.zeros(cfg.num_epochs, PPO_STATS, dtype=torch.float64, device=device)
+        self.value_stats = torch.zeros(cfg.num_epochs, VALUE_STATS, dtype=torch.float64, device=device)
+        self.adam_stats = torch.zeros(3, dtype=torch.float64, device=device)      # sum of norms, skipped steps, t
+        self._ppo_out = torch.zeros(PPO_STATS, dtype=torch.float64, device=device)
+        self._value_out = torch.zeros(VALUE_STATS, dtype=torch.float64, device=device)
 
     def _phase(self, name):
         return _NoSpan() if self.phases is None else self.phases(name)
-
-    # ---- the rollout ----
-    def _export(self, name):
-        return getattr(self.sim, name + "_tensor")().to_torch().reshape(self.rows, -1)
-
-    def _close_slot(self, t):
-        """The reward and done exports of the step just taken belong to slot t, whose action it consumed."""
-        self.rollout.reward[t].copy_(self._export("reward")[:, 0])
-        self.rollout.done[t].copy_(self._export("done")[:, 0])
-
-    def _zero_carried(self, clear, mask, mask_before):
-        """After a sim.step(): zero the carried LSTM state in the rows that rollout.state_zero_into() names, given the done
-        and self_mask exports of that step and the self_mask of the slot before."""
-        zero = rollout.state_zero_into(clear, mask, mask_before).unsqueeze(1)
-        for x in (t for s in self.state for t in s):
-            x.masked_fill_(zero, 0)
-
-    # collect() in the pieces a slot is made of (ShardedTrainer runs them slot by slot over its members).  All of them are
-    # called under on_current_stream() and torch.no_grad().
-    def _after_step(self, t):
-        """After the sim.step() that leads to slot t: close slot t - 1, take clear[t] and mask[t], zero the carried states."""
-        buf = self.rollout
-        if t > 0:
-            self._close_slot(t - 1)
-        buf.clear[t].copy_(self._export("done")[:, 0])
-        buf.mask[t].copy_(self._export("self_mask")[:, 0])
-        with self._phase("rollout_forward"):
-            self._zero_carried(buf.clear[t], buf.mask[t], buf.mask[t - 1] if t > 0 else buf.mask[t])
-
-    def _resume_slot(self):
-        """Slot 0 without a step: the closing step of the last collect() led here, and zeroed."""
-        buf = self.rollout
-        buf.clear[0].copy_(self.clear)
-        buf.mask[0].copy_(self._export("self_mask")[:, 0])
-
-    def _slot(self, t):
-        """Slot t from the exports: pack, at a chunk's first slot the snapshot of the carried states, forward, value, actions."""
-        sim, buf, net, cfg = self.sim, self.rollout, self.net, self.cfg
-        L = buf.chunk_steps
-        self.stepped = False
-        with self._phase("pack"):
-            sim.pack_policy_inputs(actor=buf.actor[t], critic=buf.critic[t], moments=buf.moments[t], normaliser=self.normaliser)
-        if t % L == 0:
-            k = t // L
-            for dst, src in ((buf.actor_h, self.state[0][0]), (buf.actor_c, self.state[0][1]), (buf.critic_h, self.state[1][0]), (buf.critic_c, self.state[1][1])):
-                dst[k].copy_(src)
-        with self._phase("rollout_forward"):
-            logits, critic_logits, self.state = net(sim, buf.actor[t], buf.critic[t], self.state, None)
-            sim.value_head(critic_logits, value=buf.value[t])
-            out = sim.sample_actions(logits, buckets=net.buckets, seed=(cfg.seed, 0), counter=self.counter, log_prob=buf.log_prob[t])
-            buf.action[t].copy_(out["action"].reshape(self.rows, -1))
-        self.counter += 1
-
-    def _after_closing_step(self):
-        """After the sim.step() past the last slot: close slot T - 1, keep its done as the next clear[0], zero the carried states."""
-        buf = self.rollout
-        T = buf.steps
-        self.stepped = True
-        self._close_slot(T - 1)
-        self.clear.copy_(buf.done[T - 1])
-        with self._phase("rollout_forward"):
-            self._zero_carried(self.clear, self._export("self_mask")[:, 0], buf.mask[T - 1])
-
-    def _gae(self):
-        """The bootstrap value, then advantages, returns and their moments over the rollout."""
-        buf, cfg = self.rollout, self.cfg
-        self.bootstrap_value()
-        self.sim.compute_advantages(buf.reward, buf.done, buf.value, self.bootstrap, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, mask=buf.mask,
-                                    advantages=buf.advantage, returns=buf.returns, moments=self.adv_moments)
-
-    def _fold_moments(self, moments):
-        """One batch of slot moments [K, 593] into the normaliser."""
-        if self.normaliser is not None:
-            self.normaliser.update(self.sim, moments)
-
-    def _step_trackers(self):
-        if self.episodes is not None:
-            self.episodes.step()
-        if self.behaviour is not None:
-            self.behaviour.step()
-
-    def collect(self):
-        """Fill the rollout with steps_per_update slots, the bootstrap value, the advantages and returns, and fold the
-        slots' moments into the normaliser."""
-        import torch
-        sim, buf = self.sim, self.rollout
-        with on_current_stream(), torch.no_grad():
-            for t in range(buf.steps):
-                if t > 0 or not self.stepped:
-                    with self._phase("sim"):
-                        sim.step()
-                    self._step_trackers()
-                    self._after_step(t)
-                else:
-                    self._resume_slot()
-                self._slot(t)
-            with self._phase("sim"):
-                sim.step()
-            self._step_trackers()
-            self._after_closing_step()
-            with self._phase("gae"):                     # the bootstrap's critic-only forward included
-                self._gae()
-                self._fold_moments(buf.moments)
-
-    def bootstrap_value(self):
-        """The critic's value of the observation in the simulator's exports into self.bootstrap, by a critic-only forward
-        on the carried critic state, which stays as it is."""
-        import torch
-        net = self.net
-        with on_current_stream(), torch.no_grad():
-            self.sim.pack_policy_inputs(critic=self.boot_rows, normaliser=self.normaliser)
-            y, _ = net.critic(self.sim, self.boot_rows, self.state[1], None)
-            critic_logits = torch.nn.functional.linear(y, net.critic_head.weight.to(y.dtype), net.critic_head.bias.to(y.dtype))
-            self.sim.value_head(critic_logits, value=self.bootstrap)
-        return self.bootstrap
 
     # ---- the update ----
     def minibatch(self, index):
@@ -358,8 +236,8 @@ class Trainer:
         return torch.randperm(self.rollout.sequences, generator=self.generator, device=self.device, dtype=torch.int32)
 
     def run_epochs(self):
-        """num_epochs epochs of num_minibatches minibatches over the rollout collect() filled: update() without the read
-        of the metrics (gpu_hideseek.population runs several policies' epochs before its one read)."""
+        """num_epochs epochs of num_minibatches minibatches over the rollout: an update without the read of the metrics
+        (gpu_hideseek.population runs several policies' epochs before its one read)."""
         cfg = self.cfg
         self.ppo_stats.zero_()
         self.value_stats.zero_()
@@ -374,11 +252,6 @@ class Trainer:
                     self.adam_stats[:2] += stats[::2]            # the norm and whether the step was skipped
                     self.adam_stats[2] = stats[3]
         self.update_index += 1
-
-    def update(self):
-        """run_epochs(), then the metrics (the one read of the device)."""
-        self.run_epochs()
-        return self.metrics()
 
     METRIC_NAMES = ("policy_loss", "entropy", "approx_kl", "clip_fraction", "value_loss", "explained_variance", "mean_value", "advantage_mean",
                     "advantage_std", "returns_mean", "returns_std", "grad_norm", "skipped", "adam_step")
@@ -411,19 +284,9 @@ class Trainer:
         return out
 
     def metrics(self):
-        """The statistics of the last update() as Python numbers: one copy to the host, which waits for the device."""
+        """The statistics of the last update as Python numbers: one copy to the host, which waits for the device."""
         import torch
         return self.metrics_from(torch.stack(self.metric_tensors()).cpu().tolist())
-
-    def update_iter(self):
-        """collect() then update(): the metrics, with "fps" = rows * steps_per_update / the wall time of both."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        t0 = time.perf_counter()
-        self.collect()
-        out = self.update()                      # ends with the read of the metrics: the device is idle
-        out["fps"] = self.rows * self.cfg.steps_per_update / (time.perf_counter() - t0)
-        return out
 
     # ---- checkpoints ----
     def state_dict(self):
@@ -435,7 +298,7 @@ class Trainer:
                 "update_index": self.update_index, "counter": self.counter}
 
     def load_state_dict(self, d):
-        """Load what state_dict() returned into a trainer of the same policy, config and row count."""
+        """Load what state_dict() returned into a learner of the same policy, config and row count."""
         import torch
         if tuple(d["params"].shape) != tuple(self.opt.flat.params.shape):
             raise ValueError(f"the state's parameters have shape {tuple(d['params'].shape)}: expected {tuple(self.opt.flat.params.shape)}")
@@ -453,6 +316,152 @@ class Trainer:
             self.normaliser.load_state_dict(d["normaliser"])
         self.generator.set_state(d["generator"].cpu())      # a state loaded with map_location is on the device
         self.update_index, self.counter = int(d["update_index"]), int(d["counter"])
+
+
+class Trainer(Learner):
+    """A Learner (the policy seeded with cfg.seed, unless `net` is given) with the Rollout it fills, the bootstrap value
+    and the sampling of one simulator (after sim.init()): collect(), update() and update_iter()."""
+
+    def __init__(self, sim, cfg=None, net=None, fused=True):
+        import torch
+        cfg = TrainConfig() if cfg is None else cfg
+        n = sim.num_worlds * sim.agents_per_world
+        check_config(cfg, n)
+        dtype = torch.float32 if cfg.dtype is None else cfg.dtype
+        dev = torch.device("cuda", sim.gpu_id)
+        if net is None:                   # the rollout needs the hidden width
+            net = policy.make_policy(dtype, generator=torch.Generator().manual_seed(cfg.seed))
+        buf = rollout.Rollout(sim, cfg.steps_per_update, cfg.num_bptt_chunks, dtype, hidden=net.actor.core.hidden)
+        super().__init__(sim, cfg, net, cfg.seed, n, dev, dtype, buf, torch.zeros(advantages.MOMENTS, dtype=torch.float64, device=dev),
+                         torch.zeros(n, dtype=torch.int32, device=dev), fused=fused)
+        self.bootstrap = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.boot_rows = torch.zeros(n, rollout.ROW, dtype=dtype, device=dev)
+        self.stepped = False              # the simulator has been stepped past the last slot: its exports are the next o_0
+        self.episodes = None              # an episodes.EpisodeStats, or None: collect() calls its step() after every sim.step()
+        self.behaviour = None             # a behaviour.BehaviourStats, or None: likewise
+
+    # ---- the rollout ----
+    def _export(self, name):
+        return getattr(self.sim, name + "_tensor")().to_torch().reshape(self.rows, -1)
+
+    def _close_slot(self, t):
+        """The reward and done exports of the step just taken belong to slot t, whose action it consumed."""
+        self.rollout.reward[t].copy_(self._export("reward")[:, 0])
+        self.rollout.done[t].copy_(self._export("done")[:, 0])
+
+    def _zero_carried(self, clear, mask, mask_before):
+        """After a sim.step(): zero the carried LSTM state in the rows that rollout.state_zero_into() names, given the done
+        and self_mask exports of that step and the self_mask of the slot before."""
+        rollout.zero_where(rollout.state_zero_into(clear, mask, mask_before), *self.state[0], *self.state[1])
+
+    # collect() in the pieces a slot is made of (ShardedTrainer runs them slot by slot over its members).  All of them are
+    # called under on_current_stream() and torch.no_grad().
+    def _after_step(self, t):
+        """After the sim.step() that leads to slot t: close slot t - 1, take clear[t] and mask[t], zero the carried states."""
+        buf = self.rollout
+        if t > 0:
+            self._close_slot(t - 1)
+        buf.clear[t].copy_(self._export("done")[:, 0])
+        buf.mask[t].copy_(self._export("self_mask")[:, 0])
+        with self._phase("rollout_forward"):
+            self._zero_carried(buf.clear[t], buf.mask[t], buf.mask[t - 1] if t > 0 else buf.mask[t])
+
+    def _resume_slot(self):
+        """Slot 0 without a step: the closing step of the last collect() led here, and zeroed."""
+        buf = self.rollout
+        buf.clear[0].copy_(self.clear)
+        buf.mask[0].copy_(self._export("self_mask")[:, 0])
+
+    def _slot(self, t):
+        """Slot t from the exports: pack, at a chunk's first slot the snapshot of the carried states, forward, value, actions."""
+        sim, buf, net, cfg = self.sim, self.rollout, self.net, self.cfg
+        L = buf.chunk_steps
+        self.stepped = False
+        with self._phase("pack"):
+            sim.pack_policy_inputs(actor=buf.actor[t], critic=buf.critic[t], moments=buf.moments[t], normaliser=self.normaliser)
+        if t % L == 0:
+            buf.snapshot_state(t // L, self.state)
+        with self._phase("rollout_forward"):
+            logits, critic_logits, self.state = net(sim, buf.actor[t], buf.critic[t], self.state, None)
+            sim.value_head(critic_logits, value=buf.value[t])
+            out = sim.sample_actions(logits, buckets=net.buckets, seed=(cfg.seed, 0), counter=self.counter, log_prob=buf.log_prob[t])
+            buf.action[t].copy_(out["action"].reshape(self.rows, -1))
+        self.counter += 1
+
+    def _after_closing_step(self):
+        """After the sim.step() past the last slot: close slot T - 1, keep its done as the next clear[0], zero the carried states."""
+        buf = self.rollout
+        T = buf.steps
+        self.stepped = True
+        self._close_slot(T - 1)
+        self.clear.copy_(buf.done[T - 1])
+        with self._phase("rollout_forward"):
+            self._zero_carried(self.clear, self._export("self_mask")[:, 0], buf.mask[T - 1])
+
+    def _gae(self):
+        """The bootstrap value, then advantages, returns and their moments over the rollout."""
+        buf, cfg = self.rollout, self.cfg
+        self.bootstrap_value()
+        self.sim.compute_advantages(buf.reward, buf.done, buf.value, self.bootstrap, gamma=cfg.gamma, gae_lambda=cfg.gae_lambda, mask=buf.mask,
+                                    advantages=buf.advantage, returns=buf.returns, moments=self.adv_moments)
+
+    def _fold_moments(self, moments):
+        """One batch of slot moments [K, 593] into the normaliser."""
+        if self.normaliser is not None:
+            self.normaliser.update(self.sim, moments)
+
+    def collect(self):
+        """Fill the rollout with steps_per_update slots, the bootstrap value, the advantages and returns, and fold the
+        slots' moments into the normaliser."""
+        import torch
+        sim, buf = self.sim, self.rollout
+        with on_current_stream(), torch.no_grad():
+            for t in range(buf.steps):
+                if t > 0 or not self.stepped:
+                    with self._phase("sim"):
+                        sim.step()
+                    step_trackers(self.episodes, self.behaviour)
+                    self._after_step(t)
+                else:
+                    self._resume_slot()
+                self._slot(t)
+            with self._phase("sim"):
+                sim.step()
+            step_trackers(self.episodes, self.behaviour)
+            self._after_closing_step()
+            with self._phase("gae"):                     # the bootstrap's critic-only forward included
+                self._gae()
+                self._fold_moments(buf.moments)
+
+    def bootstrap_value(self):
+        """The critic's value of the observation in the simulator's exports into self.bootstrap, by a critic-only forward
+        on the carried critic state, which stays as it is."""
+        import torch
+        with on_current_stream(), torch.no_grad():
+            self.sim.pack_policy_inputs(critic=self.boot_rows, normaliser=self.normaliser)
+            critic_logits, _ = self.net.critic_logits(self.sim, self.boot_rows, self.state[1], None)
+            self.sim.value_head(critic_logits, value=self.bootstrap)
+        return self.bootstrap
+
+    # ---- the update ----
+    def update(self):
+        """run_epochs() over the rollout collect() filled, then the metrics (the one read of the device)."""
+        self.run_epochs()
+        return self.metrics()
+
+    def update_iter(self):
+        """collect() then update(): the metrics, with "fps" = rows * steps_per_update / the wall time of both."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        self.collect()
+        out = self.update()                      # ends with the read of the metrics: the device is idle
+        out["fps"] = self.rows * self.cfg.steps_per_update / (time.perf_counter() - t0)
+        return out
+
+    def load_state_dict(self, d):
+        """Learner.load_state_dict(); the next collect() then steps the simulator before its slot 0."""
+        super().load_state_dict(d)
         self.stepped = False
 
 
@@ -476,7 +485,7 @@ class ShardedTrainer:
     run_epochs(): per epoch every member draws its own permutation (member g's generator is seeded cfg.seed + g); per
     minibatch part every member runs forward_backward on its own part; then every copy is enqueued before any reduction
     (for every device d and shard g != d, member g's gradient buffer into row g of d's staging buffer [G, n] and its
-    count of active samples, _ppo_out[6], into d's count vector; torch orders a copy between devices on both devices'
+    count of active samples, _ppo_out[ppo_loss.STAT_COUNT], into d's count vector; torch orders a copy between devices on both devices'
     current streams, and no host wait is added); then every member reduces in place into its own gradient buffer, its own
     row read where it lies; then every member's own opt.step().  Both losses divide by a shard's count c_g, so
     sum (c_g / C) grad_g is the gradient of the mean over all C active samples.  The loss scale is the same S on every
@@ -538,8 +547,7 @@ class ShardedTrainer:
         for m in self.members:
             m.phases = timer
 
-    def _phase(self, name):
-        return _NoSpan() if self._phases is None else self._phases(name)
+    _phase = Learner._phase
 
     def _each(self):
         """(g, member) with the member's device as torch's current one."""
@@ -551,9 +559,7 @@ class ShardedTrainer:
     def _step(self):
         with self._phase("sim"):
             self.ssim.step()
-        for hook in (self.episodes, self.behaviour):
-            for tracker in ([] if hook is None else hook if isinstance(hook, (list, tuple)) else [hook]):
-                tracker.step()
+        step_trackers(self.episodes, self.behaviour)
 
     # ---- the rollout ----
     def collect(self):
@@ -601,7 +607,7 @@ class ShardedTrainer:
             for g, mg in enumerate(self.members):
                 if g != d:
                     self.stage[d][g].copy_(mg.opt.flat.grads)
-                self.counts[d][g:g + 1].copy_(mg._ppo_out[6:7])
+                self.counts[d][g:g + 1].copy_(mg._ppo_out[ppo_loss.STAT_COUNT:ppo_loss.STAT_COUNT + 1])
 
     def reduce_gradients(self):
         """Every member's gradient buffer becomes the mean over all shards' active samples (after exchange_gradients())."""
@@ -634,10 +640,7 @@ class ShardedTrainer:
         for m in self.members:
             m.update_index += 1
 
-    def update(self):
-        """run_epochs(), then the metrics (the one read of the device)."""
-        self.run_epochs()
-        return self.metrics()
+    update = Trainer.update
 
     def metrics(self):
         """The statistics of the last update() over all shards as Python numbers: Trainer's keys, "shards" and "count".

@@ -277,8 +277,8 @@ def test_without_a_pool_no_schedule_is_set_and_the_scheduled_step_is_never_calle
     sim = TP._sim(WORLDS, NT)
     try:
         called = []
-        run = population._run
-        monkeypatch.setattr(population, "_run", lambda s, fn, *a: (called.append(fn), run(s, fn, *a))[1])
+        run = G._run                                                                   # the league's step runs from league.Table
+        monkeypatch.setattr(G, "_run", lambda s, fn, *a: (called.append(fn), run(s, fn, *a))[1])
         monkeypatch.setattr(type(sim), "set_league_schedule", lambda *a: pytest.fail("a schedule was set"))
         pop = population.Population(sim, TP._cfg(NT), nets=TP._policies(NT))
         pop.collect()
