@@ -1411,6 +1411,82 @@ int32_t hs_entity_attend_async(hs_sim *sim, void *hip_stream, const hs_entity_at
 int32_t hs_entity_attend_backward(hs_sim *sim, const hs_entity_attend_backward_request *req);
 int32_t hs_entity_attend_backward_async(hs_sim *sim, void *hip_stream, const hs_entity_attend_backward_request *req);
 
+/* The SimHash encoder: the reference's HashNet (scripts/jax_policy.py:170-218, the network make_policy selects with
+ * use_hash=True) over rows of hs_pack_policy_inputs.  HashNet concatenates self, agents, boxes and ramps, which is the
+ * row's column order, projects the HS_PACK_ROW columns onto HS_HASH_BITS directions, takes the sign bits as a bin number
+ * 0 .. HS_HASH_BINS - 1, looks the bin up in a table of HS_HASH_FEATURES channels and LayerNorms the looked-up row.  The
+ * reference's hash_power = 8 and feature_dim = 32 are fixed.  One kernel (csrc/hs_k_hash.h) reads a row once and writes
+ * its bin and its 32 channels; n is free, as for hs_ppo_loss.
+ * params is one array of HS_HASH_PARAMS f32: proj [8][296] (direction major), table [256][32], then the LayerNorm's
+ * scale (gamma) [32] and shift (beta) [32].
+ * The arithmetic is the contract.  Narrow rows are widened to f32 exactly; everything is IEEE f32, unfused except where
+ * fmaf is written, in exactly this order.  For a row x_0 .. x_295 and bit i < 8, with 64 lanes l:
+ *   p_l = +0;   p_l = fmaf(x_k, proj[i][k], p_l)   for k = l, l + 64, l + 128, l + 192 and, where l < 40, l + 256
+ *   y_i = the butterfly over the 64 lanes: for m = 1, 2, 4, 8, 16, 32 every lane replaces s_l by s_l + s_{l xor m}
+ *         (every lane ends with the same bits; it is hs_entity_encode's sum_c with L = 64)
+ *   bit_i = y_i > 0    (a NaN or an exact zero gives 0, so an all-zero row lands in bin 0);   bin = sum_i bit_i << i
+ * The order depends on nothing but the row: not on n, on the row's index, on the grid or on rows_dtype.
+ *   LayerNorm of table row b (hs_entity_encode's expression with E = 32 and its sum_c with L = 32):
+ *   mu = sum_c(t_c) / 32.0f;   d_c = t_c - mu;   var = sum_c(d_c * d_c) / 32.0f;   rstd = 1.0f / sqrtf(var + eps)
+ *   that_c = d_c * rstd;   T[b][c] = fmaf(that_c, gamma_c, beta_c)
+ *   features[row][c] = T[bin][c], rounded once to features_dtype, to nearest even
+ * A workgroup normalises the 256 table rows once, into LDS, and every row it takes is one gather: T depends on params and
+ * eps alone, so every workgroup holds the same bits.  eps = 1e-6 is flax's default; the reference's LayerNorm comes from
+ * madrona_learn, which is not part of its tree, so the constant is not pinned by it.
+ * hs_hash_encode_backward takes the forward's bin, the upstream grad_features [n][32] and params, and writes grad_params
+ * [HS_HASH_PARAMS] f32 in the layout of params.  The hash is a step function and the reference puts stop_gradient on it:
+ * there is no gradient with respect to proj or the rows, and the whole proj range of grad_params is written +0.  The
+ * LayerNorm's backward is linear in the incoming gradient, so the gradients are summed per bin first:
+ *   G[b][c] = the sum of grad_features[r][c] (widened exactly) over the rows r with bin_r = b, in this order, which depends
+ *     on n alone: with R = HS_HASH_ROWS_PER_ROUND rows per round and W = min(ceil(n / R), HS_HASH_MAX_GRID_BWD)
+ *     workgroups, workgroup w takes rounds w, w + W, ...; wave v of it the rows round * R + 2 v + s (s = 0, 1) and adds
+ *     them onto a slice [256][32] of its own that starts as +0, in round order and s = 0 before s = 1; the waves' slices
+ *     are added as ((v0 + v1) + v2) + v3; the workgroups' sums go to a workspace of the handle, where HS_HASH_SUM_SEGS
+ *     segments of ceil(W / segs) consecutive workgroups are each added in ascending order onto +0 and the segments then
+ *     in ascending order (the kernel that does so is hs_entity_encode_backward's)
+ *   h_c = gamma_c * G[b][c];   mh = sum_c(h_c) / 32.0f;   mhz = sum_c(h_c * that_c) / 32.0f
+ *   d table[b][c] = rstd * ((h_c - mh) - that_c * mhz), and +0 for a bin whose G[b] is 0 in every channel: a bin without
+ *     rows gets +0 by bit pattern
+ *   d gamma_c: HS_HASH_SUM_SEGS segments of 32 consecutive bins each start from +0 and take s = fmaf(G[b][c], that_c, s)
+ *     in ascending b; the segments are added in ascending order.  d beta_c the same with s = s + G[b][c].
+ * No atomics: the same inputs give the same bits on every call, and a row's bin and features do not depend on its
+ * position or on n.  grad_features all zero gives grad_params all +0.
+ * Rows may hold anything (a NaN in a column only clears bits); params and grad_features must be finite: nothing checks
+ * that on the device.  Two backward calls on one handle must not overlap (the workspace); forward calls may.  Everything
+ * is validated before anything is launched (HS_ERR_INVALID_ARG, nothing written, hs_last_error says which): a null
+ * request, null rows, params or features (backward: a null bin, grad_features, params or grad_params); an unknown dtype;
+ * n < 1 or n * 296 >= 2^31; eps not finite or <= 0; rows not 16-byte aligned, features or grad_features not aligned to
+ * their element size, params or grad_params not 4-byte aligned; an output range that overlaps an input range or another
+ * output; a call before hs_init or inside an open step.  The calls read no export and write no simulator state.  The
+ * blocking forms are ordered after the device's legacy default stream; the _async forms enqueue on the caller's
+ * hipStream_t without synchronising. */
+enum { HS_HASH_BITS = 8, HS_HASH_BINS = 256, HS_HASH_FEATURES = 32, HS_HASH_PARAMS = 8 * 296 + 256 * 32 + 32 + 32,
+       HS_HASH_ROWS_PER_ROUND = 8, HS_HASH_MAX_GRID_BWD = 256, HS_HASH_SUM_SEGS = 8 };
+typedef struct hs_hash_encode_request {
+    const void    *rows;          /* [n][HS_PACK_ROW] of rows_dtype, contiguous, 16-byte aligned */
+    const float   *params;        /* [HS_HASH_PARAMS] f32 */
+    int32_t n;                    /* rows, n >= 1 */
+    int32_t rows_dtype;           /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    int32_t features_dtype;       /* of features */
+    float eps;                    /* finite, > 0; 1e-6 */
+    void    *features;            /* [n][HS_HASH_FEATURES] of features_dtype */
+    uint8_t *bin;                 /* [n], or null */
+} hs_hash_encode_request;         /* 48 bytes */
+typedef struct hs_hash_encode_backward_request {
+    const uint8_t *bin;           /* [n], what the forward call wrote */
+    const void    *grad_features; /* [n][HS_HASH_FEATURES] of grad_dtype */
+    const float   *params;        /* as in the forward call */
+    int32_t n;
+    int32_t grad_dtype;           /* HS_DTYPE_F32 | HS_DTYPE_BF16 | HS_DTYPE_F16 */
+    float eps;
+    int32_t reserved;             /* ignored */
+    float   *grad_params;         /* [HS_HASH_PARAMS] f32 */
+} hs_hash_encode_backward_request;  /* 48 bytes */
+int32_t hs_hash_encode(hs_sim *sim, const hs_hash_encode_request *req);
+int32_t hs_hash_encode_async(hs_sim *sim, void *hip_stream, const hs_hash_encode_request *req);
+int32_t hs_hash_encode_backward(hs_sim *sim, const hs_hash_encode_backward_request *req);
+int32_t hs_hash_encode_backward_async(hs_sim *sim, void *hip_stream, const hs_hash_encode_backward_request *req);
+
 /* The XLA-callable entry points behind `sim.jax()` (src/bindings.cpp:97-118): enqueue on the caller's
  * hipStream_t, device buffers in the reference's order, no synchronisation except hs_jax_init.
  *   obs block (JAXIOObservations, mgr.cpp:168-201): prep_counter, self_data, self_type, self_mask, lidar,

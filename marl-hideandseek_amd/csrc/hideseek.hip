@@ -41,6 +41,7 @@
 #include "hs_k_sample_routed.h"           // likewise: emitted where launch_sample_routed (after launch_pack_routed) names it
 #include "hs_k_attend.h"                  // likewise: emitted where launch_attend (after launch_gae_grouped) names them
 #include "hs_k_reduce.h"                  // likewise: emitted where launch_reduce (at the end of this file) names it; it includes hs_k_adam.h itself
+#include "hs_k_hash.h"                    // likewise: emitted where launch_hash and launch_hash_bwd (at the end of this file, after launch_reduce) name them
 #include "hs_k_loss_scale.h"              // likewise: emitted where launch_adam_scaled (after launch_behaviour) names them; it includes hs_k_adam.h itself
 #include "hs_k_adam.h"
 #include "hs_core_probe.h"                // after every kernel header: the scalar core's probe table, read by k_core_eval alone
@@ -110,6 +111,7 @@ struct hs_sim {
     int32_t *twohot_counts = nullptr;      // hs_twohot_value: its own counts of k_ppo_count, [kPpoCountGrid]
     float *embed_partials = nullptr;       // hs_entity_encode_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_EMBED_PARAM_ROWS * kEmbMaxE]
     float *lstm_partials = nullptr;        // hs_lstm_cell_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_LSTM_PARAM_ROWS * kLstmMaxH]
+    float *hash_partials = nullptr;        // hs_hash_encode_backward: the bins' sums of each workgroup, then their sum, [kHashMaxGridBwd + 1][kHashBins * kHashFeat]
     float *dense_partials = nullptr;       // hs_dense_norm_act_backward: the sums of each workgroup, [kRowsMaxGridBwd][HS_DENSE_PARAM_ROWS * kDenseMaxC]
     double *adam_workspace = nullptr;      // hs_adam_step: the sum of squares of each workgroup and the snapshot of the state, [kAdamWorkspace]; hs_adam_step_scaled: then the snapshot of the loss-scale state, [kLossScaleWorkspace]
     double *episode_partials = nullptr;    // hs_episode_stats: the sums of each workgroup, [episode_grid][HS_EPISODE_STATS]
@@ -1761,6 +1763,69 @@ int check_reduce(hs_sim *s, const hs_grad_reduce_request *r) {
 int launch_reduce(hs_sim *s, hipStream_t strm, const hs_grad_reduce_request *r);
 }  // namespace
 
+// ---- the SimHash encoder (hs_k_hash.h) ----
+namespace {
+static_assert(HS_HASH_BITS == hs::kHashBits && HS_HASH_BINS == hs::kHashBins && HS_HASH_FEATURES == hs::kHashFeat && HS_HASH_PARAMS == hs::kHashParams &&
+              HS_HASH_ROWS_PER_ROUND == hs::kHashRows && HS_HASH_MAX_GRID_BWD == hs::kHashMaxGridBwd && HS_HASH_SUM_SEGS == hs::kRowsSumSegs &&
+              HS_HASH_SUM_SEGS == hs::kHashHalves && HS_HASH_SUM_SEGS == HS_EMBED_SUM_SEGS, "hs_hash_encode_request and k_hash agree");
+static_assert(sizeof(hs_hash_encode_request) == 48 && offsetof(hs_hash_encode_request, n) == 16 && offsetof(hs_hash_encode_request, features_dtype) == 24 &&
+              offsetof(hs_hash_encode_request, eps) == 28 && offsetof(hs_hash_encode_request, features) == 32 && offsetof(hs_hash_encode_request, bin) == 40,
+              "hs_hash_encode_request layout (gpu_hideseek/hash_encoder.py mirrors it)");
+static_assert(sizeof(hs_hash_encode_backward_request) == 48 && offsetof(hs_hash_encode_backward_request, grad_features) == 8 &&
+              offsetof(hs_hash_encode_backward_request, params) == 16 && offsetof(hs_hash_encode_backward_request, n) == 24 &&
+              offsetof(hs_hash_encode_backward_request, eps) == 32 && offsetof(hs_hash_encode_backward_request, grad_params) == 40,
+              "hs_hash_encode_backward_request layout (gpu_hideseek/hash_encoder.py mirrors it)");
+
+// What the two calls share.
+int check_hash_common(const Check &c, const float *params, int32_t n, float eps) {
+    if (!params) return c.bad("null params");
+    if (!count_ok(n, {HS_PACK_ROW})) return c.bad("n must be at least 1 and n * 296 below 2^31");
+    if (!std::isfinite(eps) || !(eps > 0.f)) return c.bad("eps must be finite and > 0");
+    return HS_OK;
+}
+
+int check_hash(hs_sim *s, const hs_hash_encode_request *r) {
+    const Check c{"hs_hash_encode"};
+    if (!r) return c.bad("null request");
+    if (!r->rows) return c.bad("null rows");
+    HS_TRY(check_hash_common(c, r->params, r->n, r->eps));
+    if (!r->features) return c.bad("null features");
+    HS_TRY(c.dtype(r->rows_dtype, "rows"));
+    HS_TRY(c.dtype(r->features_dtype, "features"));
+    const uintptr_t rsize = elem_size(r->rows_dtype), fsize = elem_size(r->features_dtype);
+    if (!aligned(16, {r->rows})) return c.bad("rows must be 16-byte aligned");
+    if (!aligned(4, {r->params})) return c.bad("params must be 4-byte aligned");
+    if (!aligned(fsize, {r->features})) return c.bad("features must be aligned to its element size");
+    const uintptr_t n = (uintptr_t)r->n;
+    HS_TRY(c.disjoint({range("rows", r->rows, n * HS_PACK_ROW * rsize), range("params", r->params, HS_HASH_PARAMS * 4)},
+                      {range("features", r->features, n * HS_HASH_FEATURES * fsize), range("bin", r->bin, n)}));
+    return c.handle_ready(s);
+}
+
+int check_hash_bwd(hs_sim *s, const hs_hash_encode_backward_request *r) {
+    const Check c{"hs_hash_encode_backward"};
+    if (!r) return c.bad("null request");
+    if (!r->bin) return c.bad("null bin");
+    if (!r->grad_features) return c.bad("null grad_features");
+    HS_TRY(check_hash_common(c, r->params, r->n, r->eps));
+    if (!r->grad_params) return c.bad("null grad_params");
+    HS_TRY(c.dtype(r->grad_dtype, "grad"));
+    const uintptr_t gsize = elem_size(r->grad_dtype);
+    if (!aligned(4, {r->params, r->grad_params})) return c.bad("params and grad_params must be 4-byte aligned");
+    if (!aligned(gsize, {r->grad_features})) return c.bad("grad_features must be aligned to its element size");
+    const uintptr_t n = (uintptr_t)r->n;
+    HS_TRY(c.disjoint({range("bin", r->bin, n), range("grad_features", r->grad_features, n * HS_HASH_FEATURES * gsize),
+                       range("params", r->params, HS_HASH_PARAMS * 4)},
+                      {range("grad_params", r->grad_params, HS_HASH_PARAMS * 4)}));
+    return c.handle_ready(s);
+}
+
+// Defined at the end of the file, after launch_reduce: the kernels are templates, emitted where their launches name them,
+// and behind every kernel that was there before them.
+int launch_hash(hs_sim *s, hipStream_t strm, const hs_hash_encode_request *r);
+int launch_hash_bwd(hs_sim *s, hipStream_t strm, const hs_hash_encode_backward_request *r);
+}  // namespace
+
 namespace {
 // Host copy of a tiled column (hs_state.h Col): element (row, world) at ((w / 8) * ROWS + row) * 8 + w % 8.
 template <typename T, int ROWS>
@@ -1909,6 +1974,7 @@ int32_t hs_create(const hs_config *cfg, hs_sim **out) {
     HS_ALLOC(s->embed_partials, (size_t)hs::kRowsMaxGridBwd * hs::kEmbParamRows * hs::kEmbMaxE);
     HS_ALLOC(s->lstm_partials, (size_t)hs::kRowsMaxGridBwd * hs::kLstmParamRows * hs::kLstmMaxH);
     HS_ALLOC(s->dense_partials, (size_t)hs::kRowsMaxGridBwd * hs::kDenseParamRows * hs::kDenseMaxC);
+    HS_ALLOC(s->hash_partials, (size_t)(hs::kHashMaxGridBwd + 1) * hs::kHashSlice);
     HS_ALLOC(s->adam_workspace, hs::kLossScaleWorkspace);
     HS_ALLOC(s->episode_partials, (size_t)hs::episode_grid((int)N, A) * hs::kEpiStats);
     HS_ALLOC(s->behaviour_partials, (size_t)hs::behaviour_grid((int)N) * hs::kBehStats);
@@ -2296,6 +2362,12 @@ int32_t hs_entity_attend(hs_sim *s, const hs_entity_attend_request *req) { retur
 int32_t hs_entity_attend_async(hs_sim *s, void *hip_stream, const hs_entity_attend_request *req) { return call_async(s, hip_stream, check_attend, launch_attend, req); }
 int32_t hs_entity_attend_backward(hs_sim *s, const hs_entity_attend_backward_request *req) { return call_blocking(s, check_attend_bwd, launch_attend_bwd, req); }
 int32_t hs_entity_attend_backward_async(hs_sim *s, void *hip_stream, const hs_entity_attend_backward_request *req) { return call_async(s, hip_stream, check_attend_bwd, launch_attend_bwd, req); }
+int32_t hs_hash_encode(hs_sim *s, const hs_hash_encode_request *req) { return call_blocking(s, check_hash, launch_hash, req); }
+int32_t hs_hash_encode_async(hs_sim *s, void *hip_stream, const hs_hash_encode_request *req) { return call_async(s, hip_stream, check_hash, launch_hash, req); }
+int32_t hs_hash_encode_backward(hs_sim *s, const hs_hash_encode_backward_request *req) { return call_blocking(s, check_hash_bwd, launch_hash_bwd, req); }
+int32_t hs_hash_encode_backward_async(hs_sim *s, void *hip_stream, const hs_hash_encode_backward_request *req) {
+    return call_async(s, hip_stream, check_hash_bwd, launch_hash_bwd, req);
+}
 int32_t hs_obs_norm_update(hs_sim *s, const hs_obs_norm_request *req) { return call_blocking(s, check_norm_update, launch_norm_update, req); }
 int32_t hs_obs_norm_update_async(hs_sim *s, void *hip_stream, const hs_obs_norm_request *req) { return call_async(s, hip_stream, check_norm_update, launch_norm_update, req); }
 int32_t hs_pack_policy_inputs_normalized(hs_sim *s, const hs_pack_request *req, const float *table) {
@@ -2552,6 +2624,34 @@ int launch_reduce(hs_sim *, hipStream_t strm, const hs_grad_reduce_request *r) {
     for (int g = 0; g < r->shards; ++g) a.src[g] = r->src[g];
     a.count = r->count; a.dst = r->dst; a.total = r->total; a.n = (int)r->n; a.shards = r->shards;
     hipLaunchKernelGGL(hs::k_reduce<>, dim3(hs::adam_grid(a.n, hs::kAdamStepMaxGrid)), dim3(hs::kAdamThreads), 0, strm, a);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+}  // namespace
+
+// ---- the SimHash encoder (hs_k_hash.h): its launches, after every kernel the file named before ----
+namespace {
+// One k_hash_fwd over the rows (the request has passed check_hash).
+int launch_hash(hs_sim *, hipStream_t strm, const hs_hash_encode_request *r) {
+    hs::HashArgs a = {};
+    a.rows = r->rows; a.params = r->params; a.features = r->features; a.bin = r->bin;
+    a.n = r->n; a.rowsType = elem_code(r->rows_dtype); a.featType = elem_code(r->features_dtype); a.eps = r->eps;
+    hipLaunchKernelGGL(hs::k_hash_fwd<>, dim3(hs::rows_grid(a.n, hs::kHashRows, hs::kHashMaxGrid)), dim3(hs::kRowsThreads), 0, strm, a);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+// k_hash_bwd_bins into the workspace's slices, their fixed-order sum into its last slice, and k_hash_bwd_table from there
+// (the request has passed check_hash_bwd).
+int launch_hash_bwd(hs_sim *s, hipStream_t strm, const hs_hash_encode_backward_request *r) {
+    hs::HashBwdArgs a = {};
+    a.bin = r->bin; a.gradFeatures = r->grad_features; a.params = r->params; a.workspace = s->hash_partials; a.gradParams = r->grad_params;
+    a.n = r->n; a.gradType = elem_code(r->grad_dtype); a.eps = r->eps;
+    const int nparts = hs::rows_grid(a.n, hs::kHashRows, hs::kHashMaxGridBwd);
+    float *G = s->hash_partials + (size_t)hs::kHashMaxGridBwd * hs::kHashSlice;
+    hipLaunchKernelGGL(hs::k_hash_bwd_bins<>, dim3(nparts), dim3(hs::kRowsThreads), 0, strm, a);
+    launch_partials_sum<float, hs::kRowsSumCols, hs::kRowsSumSegs>(strm, s->hash_partials, nparts, hs::kHashSlice, G);
+    hipLaunchKernelGGL(hs::k_hash_bwd_table<>, dim3(1), dim3(hs::kRowsThreads), 0, strm, a, (const float *)G);
     HS_HIP(hipGetLastError());
     return HS_OK;
 }

@@ -289,6 +289,28 @@ class HideAndSeekSimulator:
         from . import entity_encoder as _enc
         return _enc.compute_backward(self, rows, params, grad_features, argmax, stream, embed_dim=embed_dim, eps=eps, slope=slope, grad_params=grad_params)
 
+    def hash_encode(self, rows, params, *, eps=1e-6, features=True, bin=None, dtype=None, stream=None):
+        """The SimHash encoder in one kernel (gpu_hideseek.hash_encoder; hs_hash_encode, whose header comment states the
+        arithmetic: IEEE f32 in a fixed order).  `rows` [n, 296] (float32, bfloat16 or float16, contiguous, 16-byte
+        aligned) are rows of pack_policy_inputs; `params` the flat float32 tensor of 10624 elements
+        (hash_encoder.param_layout: proj [8, 296], table [256, 32], scale, shift).  A row's 8 projections give its bin
+        (bit i set where projection i is above 0), and its features are the LayerNorm (`eps`) of the bin's table row.
+        features [n, 32] in `dtype` (by default the rows') is True (allocated) or a preallocated tensor (a slot buf[t] of a
+        [T, rows, 32] buffer will do); bin [n] uint8 (what the backward call needs) is True, a tensor or None.
+        stream=None blocks; a torch.cuda.Stream or raw handle enqueues there without synchronising.  Returns
+        {name: tensor} of what was written."""
+        from . import hash_encoder as _hash
+        return _hash.compute(self, rows, params, stream, eps=eps, features=features, bin=bin, dtype=dtype)
+
+    def hash_encode_backward(self, bin, grad_features, params, *, eps=1e-6, grad_params=True, stream=None):
+        """The gradient of the SimHash encoder's parameters (hs_hash_encode_backward): the upstream `grad_features` [n, 32]
+        (float32, bfloat16 or float16) is summed per bin of the forward's `bin` [n] in a fixed order, and the 256 sums go
+        through the LayerNorm's backward.  grad_params (True or a float32 tensor of 10624 elements) has the layout of
+        params; its proj range and the table rows of bins without rows are +0.  The same inputs give the same bits on
+        every call.  Returns {"grad_params": tensor}."""
+        from . import hash_encoder as _hash
+        return _hash.compute_backward(self, bin, grad_features, params, stream, eps=eps, grad_params=grad_params)
+
     def lstm_cell(self, gates, c_prev, cell_params, *, clear=None, hidden=None, eps=1e-6, y=True, h_next=True, c_next=True, y_dtype=None, stream=None):
         """The recurrent core after its gate GEMMs in one kernel (gpu_hideseek.recurrent; hs_lstm_cell, whose header
         comment states the arithmetic: IEEE f32 in a fixed order).  `gates` [n, 4 H] (float32, bfloat16 or float16,

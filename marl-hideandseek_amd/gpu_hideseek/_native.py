@@ -96,7 +96,7 @@ def load():
                       ("hs_dense_norm_act", []), ("hs_dense_norm_act_backward", []), ("hs_adam_step", []), ("hs_reduce_gradients", []), ("hs_gather_sequences", []),
                       ("hs_episode_stats", []), ("hs_behaviour_stats", []), ("hs_league_step", []), ("hs_league_step_scheduled", []), ("hs_pack_policy_inputs_routed", []),
                       ("hs_sample_actions_routed", []), ("hs_compute_gae_grouped", []), ("hs_entity_attend", []),
-                      ("hs_entity_attend_backward", []), ("hs_ppo_loss_scaled", [C.c_void_p]), ("hs_twohot_value_scaled", [C.c_void_p]),
+                      ("hs_entity_attend_backward", []), ("hs_hash_encode", []), ("hs_hash_encode_backward", []), ("hs_ppo_loss_scaled", [C.c_void_p]), ("hs_twohot_value_scaled", [C.c_void_p]),
                       ("hs_adam_step_scaled", [C.c_void_p])):
         getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p] + extra
         getattr(L, fn).restype = C.c_int32

@@ -63,7 +63,7 @@ def load_policy(path_or_dict, dtype=None, device=None, member=None, encoder=None
             flat = optim.flatten(net.named_parameters(), device)
             break
     if net is None or theirs != flat.layout():
-        raise ValueError("the state's parameters are not laid out as policy.make_policy's")
+        raise ValueError("the state's parameters are not laid out as policy.make_policy's" + ("" if encoder is None else f" with encoder {encoder!r}"))
     with torch.no_grad():
         flat.params.copy_(d["params"])
     net._flat = flat                      # the parameters are views of this buffer

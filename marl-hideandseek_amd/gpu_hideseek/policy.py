@@ -20,10 +20,10 @@ Composition only: this file contains no kernel call of its own.  Every piece run
 In a chunk the encoder and the MLP do not depend on time: sequence() runs them once over the T * n flattened rows and
 only the LSTM step by step.
 """
-from . import entity_attention, entity_encoder, mlp, recurrent
+from . import entity_attention, entity_encoder, hash_encoder, mlp, recurrent
 from ._request import _module_base
 
-ENCODERS = ("simple", "attention")      # the reference's SimpleNet and its EntitySelfAttentionNet
+ENCODERS = ("simple", "attention", "hash")      # the reference's SimpleNet, its EntitySelfAttentionNet and its HashNet
 BUCKETS = (5, 5, 5, 2, 2)     # the reference's action heads: move amount, move angle, rotate, grab, lock
 BINS = 255                    # the two-hot critic's bins (value_head)
 
@@ -34,7 +34,11 @@ class Backbone(_module_base()):
     With encoder="attention" the backbone is entity_attention.AttentionEncoder(embed, channels) -> LSTMCore(channels,
     hidden) with no MLP in between: the reference's EntitySelfAttentionNet stands in place of all of SimpleNet, and its
     output channels feed the LSTM.  `masked` says whether the rows' entity tables carry their visibility masks (the
-    actor's do, the critic's do not): the attention encoder leaves the masked-out entities out."""
+    actor's do, the critic's do not): the attention encoder leaves the masked-out entities out.
+    With encoder="hash" it is hash_encoder.HashEncoder() -> LSTMCore(32, hidden), again with no MLP: the reference's
+    HashNet stands in place of all of SimpleNet and its 32 channels feed the LSTM.  `channels`, the width that feeds the
+    LSTM, must then be hash_encoder.FEATURES = 32 (make_policy passes it; the default of 256 is refused, not silently
+    replaced); `embed` and `layers` are not used."""
 
     def __init__(self, embed=64, channels=256, layers=3, hidden=256, fused=True, generator=None, encoder="simple", masked=False):
         super().__init__()
@@ -43,6 +47,11 @@ class Backbone(_module_base()):
         self.fused, self.kind, self.masked = bool(fused), encoder, bool(masked)
         if encoder == "attention":
             self.encoder = entity_attention.AttentionEncoder(embed, channels, fused=fused, generator=generator)
+        elif encoder == "hash":
+            if channels != hash_encoder.FEATURES:
+                raise ValueError(f"encoder 'hash' feeds the LSTM {hash_encoder.FEATURES} channels (hash_encoder.FEATURES): channels must be "
+                                 f"{hash_encoder.FEATURES}, got {channels}")
+            self.encoder = hash_encoder.HashEncoder(generator=generator)
         else:
             self.encoder = entity_encoder.EntityEncoder(embed, generator=generator)
             self.mlp = mlp.MLP(4 * embed, channels, layers, fused=fused, generator=generator)
@@ -53,7 +62,7 @@ class Backbone(_module_base()):
         self.fused = bool(fused)
         if self.kind == "attention":
             self.encoder.fused = self.fused
-        else:
+        elif self.kind == "simple":
             self.mlp.fused = self.fused
         return self
 
@@ -65,6 +74,10 @@ class Backbone(_module_base()):
         """The encoder and the MLP over rows [n, W]: [n, channels] in `dtype`.  They carry no state."""
         if self.kind == "attention":
             return self.encoder(sim, rows, dtype, self.masked)
+        if self.kind == "hash":
+            if self.fused:
+                return self.encoder(sim, rows, dtype)
+            return hash_encoder.eager(rows, self.encoder.params, self.encoder.eps).to(dtype)
         if self.fused:
             feats = self.encoder(sim, rows, dtype)
         else:
@@ -162,7 +175,12 @@ def make_policy(dtype=None, fused=True, generator=None, encoder="simple"):
     """An ActorCritic of the reference's sizes: embed 64, three layers of 256 channels, 256 hidden channels, heads of
     5 + 5 + 5 + 2 + 2 logits and 255 bins.  `dtype` (float32 by default) is the compute dtype the state's h carries.
     encoder="attention" builds the reference's other network instead, EntitySelfAttentionNet(num_embed_channels=128,
-    num_out_channels=256, num_heads=4), in front of the same LSTM and heads."""
+    num_out_channels=256, num_heads=4), in front of the same LSTM and heads; encoder="hash" its HashNet (hash_power 8,
+    feature_dim 32), whose 32 channels feed the LSTM."""
+    if encoder not in ENCODERS:
+        raise ValueError(f"encoder must be one of {ENCODERS}, got {encoder!r}")
     if encoder == "attention":
         return ActorCritic(BUCKETS, BINS, dtype=dtype, generator=generator, embed=128, channels=256, hidden=256, fused=fused, encoder="attention")
+    if encoder == "hash":
+        return ActorCritic(BUCKETS, BINS, dtype=dtype, generator=generator, channels=hash_encoder.FEATURES, hidden=256, fused=fused, encoder="hash")
     return ActorCritic(BUCKETS, BINS, dtype=dtype, generator=generator, embed=64, channels=256, layers=3, hidden=256, fused=fused)

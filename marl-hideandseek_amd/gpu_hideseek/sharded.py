@@ -225,6 +225,18 @@ class ShardedSimulator:
         return _enc.compute_backward_sharded(self, rows, params, grad_features, argmax, stream, grad_params=grad_params, embed_dim=embed_dim,
                                              eps=eps, slope=slope)
 
+    def hash_encode(self, rows, params, *, eps=1e-6, features=True, bin=None, dtype=None, stream=None):
+        """HideAndSeekSimulator.hash_encode per shard: `rows` has one tensor per shard, on the shard's device; `params` is
+        one tensor for all shards or a list; a list of the shards' results (hash_encoder.compute_sharded)."""
+        from . import hash_encoder as _hash
+        return _hash.compute_sharded(self, rows, params, stream, features=features, bin=bin, eps=eps, dtype=dtype)
+
+    def hash_encode_backward(self, bin, grad_features, params, *, eps=1e-6, grad_params=True, stream=None):
+        """HideAndSeekSimulator.hash_encode_backward per shard: every shard's grad_params is the sum over its own rows
+        (hash_encoder.compute_backward_sharded)."""
+        from . import hash_encoder as _hash
+        return _hash.compute_backward_sharded(self, bin, grad_features, params, stream, grad_params=grad_params, eps=eps)
+
     def lstm_cell(self, gates, c_prev, cell_params, *, clear=None, hidden=None, eps=1e-6, y=True, h_next=True, c_next=True, y_dtype=None, stream=None):
         """HideAndSeekSimulator.lstm_cell per shard: `gates`, `c_prev` (and `clear`) have one tensor per shard, on the
         shard's device; `cell_params` is one tensor for all shards or a list; a list of the shards' results

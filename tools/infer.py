@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import behaviour, evaluate  # noqa: E402
+from gpu_hideseek import behaviour, evaluate, policy  # noqa: E402
 
 
 def parse(argv=None):
@@ -43,7 +43,7 @@ def parse(argv=None):
     ap.add_argument("--greedy", action="store_true", help="every head's most likely action instead of a draw")
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--behaviour-stats", action="store_true", help="track object movement, locks, travel and grabs on the device and print them")
-    ap.add_argument("--encoder", choices=("simple", "attention"), help="the policy's network (tools/train.py --encoder); by default read from the checkpoint")
+    ap.add_argument("--encoder", choices=policy.ENCODERS, help="the policy's network (tools/train.py --encoder); by default read from the checkpoint")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")

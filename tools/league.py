@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "marl-hideandseek_amd"))
 import torch  # noqa: E402
 import gpu_hideseek  # noqa: E402
-from gpu_hideseek import behaviour, evaluate, league  # noqa: E402
+from gpu_hideseek import behaviour, evaluate, league, policy  # noqa: E402
 
 
 def parse(argv=None):
@@ -43,7 +43,7 @@ def parse(argv=None):
     ap.add_argument("--k-factor", type=float, default=league.DEFAULT_K_FACTOR)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--behaviour-stats", action="store_true", help="track object movement, locks, travel and grabs on the device and print them")
-    ap.add_argument("--encoder", choices=("simple", "attention"), help="every policy's network (tools/train.py --encoder); by default read from each checkpoint")
+    ap.add_argument("--encoder", choices=policy.ENCODERS, help="every policy's network (tools/train.py --encoder); by default read from each checkpoint")
     args = ap.parse_args(argv)
     if args.fp16 and args.bf16:
         ap.error("--fp16 and --bf16 exclude each other")
